@@ -15,7 +15,13 @@ partial frames), no
 collective on the data path; ``value`` = scene pixels / max-over-ranks time; per-rank times and the imbalance
 are reported.  ``--scaling weak`` instead gives every rank its own scene (seed + rank).
 
-Also reported (rank 0):
+A plain run (``--gpus 1 --steps N --warmup W``) does what the headline needs and nothing else: set-up (scene, plan,
+the settle executes), W warmup steps, the N timed steps, ``--dump-outputs DIR`` if asked (the last timed step's
+stream table and a fixed sample of its frame bytes as .npy, see ``dump_outputs``), and the result line (``value``,
+``ms_per_step``, ``config``, ``per_rank``, ``analysis_instance``).
+
+Every other leg runs only with ``--full`` (rank 0; each still has its ``--no-*`` switch), and adds to the line:
+* ``analysis_instance.ms_per_step_forced_17bit``: the same steps forced onto the 17-bit k_analyze_w instance;
 * ``roofline`` of the dominant kernel: HIP events on the plan's stream; algorithmic bytes = input raster
   bytes + emitted frame bytes of the units one launch processes; ``traffic`` / ``valu_issue_frac`` from
   in-run rocprofv3 PMC passes of this same build (``--no-pmc`` falls back to the committed profile
@@ -23,7 +29,10 @@ Also reported (rank 0):
 * ``cpu_baseline``: the CPU oracle (oracle/, C port of the path, 1 thread) on a bounded sample of the
   same scene, bytes checked against the GPU's; ``cpu_baseline_mp``: the same port fanned over the
   host's core share (BASELINE.md B-mp);
-* ``e2e``: the PCIe-inclusive path (host raster -> pipelined H2D / kernels / D2H -> host frames).
+* ``e2e``: the PCIe-inclusive path (host raster -> pipelined H2D / kernels / D2H -> host frames);
+* ``size_ratio_vs_libflac_c2``, ``pyflac_shim_c2``: the C2 raster's size against libFLAC's and the shim's latency;
+* ``kernel_stats``: a rocprofv3 kernel trace of a child run of the same steps.
+A ``--shard R/N`` projection line is made of the per-kernel times, so it runs that leg without ``--full``.
 """
 
 from __future__ import annotations
@@ -91,6 +100,47 @@ def sources_sha():
             h.update(p.name.encode())
             h.update(p.read_bytes())
     return h.hexdigest()[:16]
+
+
+# ------------------------------------------------------------------------------------- --dump-outputs
+DUMP_SAMPLE_BYTES = 8 << 20  # frame bytes kept in frames_sample.npy (as float32: 32 MiB of the 64 MB allowed)
+
+
+def dump_outputs(out_dir, ctx, plan, prefix=""):
+    """What a caller of the timed path holds after the last timed execute -- the stream table of ``plan.result()``
+    and the frame bytes in the plan's device output -- as float .npy files, so two builds can be compared:
+
+    * ``streams.npy``  float64 (nstreams, 8): offset, frame_bytes, data_min, data_max, sample_rate, bps, channels,
+      nframes of every stream (the integers are exact in float64);
+    * ``frames_sample.npy``  float32 (nstreams, chunk), chunk = DUMP_SAMPLE_BYTES // nstreams: ``chunk`` consecutive
+      frame bytes of EVERY stream, starting at a position inside the stream drawn by a generator seeded with SEED
+      (the whole stream, zero padded, when it is shorter than ``chunk``) -- the frames themselves are 0.5-22 GB;
+    * ``frames_sample_start.npy``  float64 (nstreams,): that position, in bytes from the stream's first byte.
+    """
+    out_dir.mkdir(parents=True, exist_ok=True)
+    infos, total = plan.result()
+    dev_out, _ = plan.device_output()
+    n = len(infos)
+    table = np.array([[s.offset, s.frame_bytes, s.data_min, s.data_max, s.sample_rate, s.bps, s.channels, s.nframes]
+                      for s in infos], dtype=np.float64).reshape(n, 8)
+    chunk = max(1, DUMP_SAMPLE_BYTES // max(1, n))
+    u = np.random.default_rng(SEED).random(n)
+    start = np.zeros(n, np.float64)
+    sample = np.zeros((n, chunk), np.float32)
+    for i, s in enumerate(infos):
+        size = int(s.frame_bytes)
+        take = min(size, chunk)
+        first = int(u[i] * (size - take + 1))
+        if s.offset + first + take > total:
+            raise RuntimeError(f"stream {i}: offset {s.offset} + {size} bytes exceeds the output's {total}")
+        buf = np.empty(max(1, take), np.uint8)
+        if take:
+            ctx.d2h(buf[:take], dev_out + int(s.offset) + first)
+        sample[i, :take] = buf[:take]
+        start[i] = first
+    np.save(out_dir / f"{prefix}streams.npy", table)
+    np.save(out_dir / f"{prefix}frames_sample.npy", sample)
+    np.save(out_dir / f"{prefix}frames_sample_start.npy", start)
 
 
 # ------------------------------------------------------------------------------------- CPU baselines
@@ -471,6 +521,14 @@ def main():
     ap.add_argument("--no-trace", action="store_true", help="skip the in-run rocprofv3 kernel-trace pass")
     ap.add_argument("--prof-dir", default=os.environ.get("FRA_PROF_DIR", str(ROOT / "gpurun_out" / "bench_prof")),
                     help="where the timed-launch kernel-stats CSV of the in-run trace pass is copied")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (forced-17-bit steps, per-kernel times and "
+                         "roofline, CPU baselines, e2e, C2 size ratio and shim latency, rocprofv3 trace and counter "
+                         "passes; each still subject to its --no-* switch).  Without it the run is set-up, warmup, "
+                         "the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (stream table, sampled frame bytes) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # PMC child: steps only
     ap.add_argument("--child-serial", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-mp-child", nargs=2, type=int, metavar=("PROCS", "TILES"), help=argparse.SUPPRESS)
@@ -600,10 +658,14 @@ def main():
     barrier()
     dt_s = t1 - t0
     inst = [17 if f else 16 for f in inst] if wave_plan else None
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), ctx, plan, f"rank{rank}_" if world > 1 else "")
+    # the legs below re-run the steps: only under --full (and for a --shard projection line, which is made of them)
+    extra = args.full or shard_of is not None
     # the same pipelined steps forced onto the 17-bit instance (what a plan runs before its count arrives, and on
     # data where more than 1/32 of the waves need bit 16): the adaptive pick's worth, reported beside ms_per_step
     k17_ms = None
-    if wave_plan and os.environ.get("FRA_KEEP17") is None:
+    if extra and wave_plan and os.environ.get("FRA_KEEP17") is None:
         os.environ["FRA_KEEP17"] = "1"  # read by every execute (getenv)
         try:
             plan.execute()
@@ -618,12 +680,14 @@ def main():
         finally:
             del os.environ["FRA_KEEP17"]
     # per-kernel launch times (roofline): the same steps again, serial, HIP events between kernels
-    plan.enable_timing(True)
-    for _ in range(args.steps):
-        plan.execute()
-    plan.sync()
-    kms, nexec = plan.timing()
-    plan.enable_timing(False)
+    kms, nexec = [0.0] * 4, 0
+    if extra:
+        plan.enable_timing(True)
+        for _ in range(args.steps):
+            plan.execute()
+        plan.sync()
+        kms, nexec = plan.timing()
+        plan.enable_timing(False)
     infos, total = plan.result()
     # the k_analyze_w instance the plan settled on (FRA_PLAN_KEEP17: kept residuals up to 17 bits, else 16)
     k17_plan = bool(plan.flags() & 8)
@@ -640,9 +704,11 @@ def main():
     dom = 1 if per_launch_ms[1] >= per_launch_ms[3] else 3
     dom_name = {1: "k_analyze", 3: "k_assemble"}[dom]
     alg_bytes = my_in_bytes + total
-    achieved = alg_bytes / (per_launch_ms[dom] * 1e-3) / 1e9
     step_ms_local = sum(per_launch_ms)
-    path_gbps = alg_bytes / (step_ms_local * 1e-3) / 1e9
+    achieved = path_gbps = None  # (no per-kernel times without the serial leg above)
+    if extra:
+        achieved = alg_bytes / (per_launch_ms[dom] * 1e-3) / 1e9
+        path_gbps = alg_bytes / (step_ms_local * 1e-3) / 1e9
 
     if shard_of is not None:  # projection line: this rank's share only, not a job throughput
         sh = {"shard": f"{shard_of[0]}/{shard_of[1]}", "config": cfg["workload"], "tiles": len(my_wins),
@@ -667,7 +733,7 @@ def main():
         job_px = scene_px * (world if weak else 1)
         value = job_px * args.steps / T / 1e6
         cpu = cpu_mp = None
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             gi = {i: infos[j] for j, i in enumerate(mine)}
             dev_out, _ = plan.device_output()
 
@@ -703,7 +769,7 @@ def main():
                 cpu_mp = {"value": None, "error": type(e).__name__}
         # PCIe-inclusive end-to-end (not `value`): host raster -> pipelined H2D / kernels / D2H -> host frames
         e2e = None
-        if not args.no_e2e and world == 1:
+        if args.full and not args.no_e2e and world == 1:
             if raster_bytes <= (8 << 30):
                 e2e = measure_e2e(N, ctx, cfg, dt, B, H, W, my_wins, my_px, dev_raster, plan)
             else:  # the whole raster is never page-locked: the bounded ring path (fra_plan_encode_ring)
@@ -713,51 +779,56 @@ def main():
                     e2e = {"value": None, "error": f"{type(e).__name__}: {e}"}
         # size vs libFLAC: only pinned for C2 (sample_rgb, 178,857 frame bytes at -c 5)
         size_c2 = None
-        try:
-            from flac_raster.tiff import read_geotiff
-            rgb, _ = read_geotiff(ROOT / "tests" / "golden" / "sample_rgb.tif")
-            _, fr = N.encode_windows(rgb, [(0, 0, 256, 256)], level=5, norm=16, device=ctx.device)
-            size_c2 = round(len(fr) / 178857.0, 5)
-        except Exception:
-            size_c2 = None
+        if args.full:
+            try:
+                from flac_raster.tiff import read_geotiff
+                rgb, _ = read_geotiff(ROOT / "tests" / "golden" / "sample_rgb.tif")
+                _, fr = N.encode_windows(rgb, [(0, 0, 256, 256)], level=5, norm=16, device=ctx.device)
+                size_c2 = round(len(fr) / 178857.0, 5)
+            except Exception:
+                size_c2 = None
         # pyflac-shim latency per stream on C2 (sample_rgb, 65,536 x 3 int16 samples; the reference's
         # per-tile call shape: StreamEncoder(...).process(audio); finish())
         shim = None
-        try:
-            shim = measure_shim_c2(N)
-        except Exception as e:  # reported, never fatal for the headline line
-            shim = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            try:
+                shim = measure_shim_c2(N)
+            except Exception as e:  # reported, never fatal for the headline line
+                shim = {"error": f"{type(e).__name__}: {e}"}
         # counters of the dominant kernel: in-run passes (this build), else the committed file if current.
         # The passes run in a child process: release this process's device buffers first.
         plan.close()
         ctx.free(dev_raster)
         plan = dev_raster = None
         kstats = None
-        if not args.no_trace and world == 1:
+        if args.full and not args.no_trace and world == 1:
             kstats = inrun_kernel_stats(args, args.prof_dir)
         pm = None
-        if not args.no_pmc and world == 1:
+        if args.full and not args.no_pmc and world == 1:
             pm = inrun_pmc(args, dom_name)
             if "traffic" not in pm and "valu_insts" not in pm:
                 pm = None
-        if pm is None:
-            pm = committed_profile(args, cfg, dom_name)
-        # the kernel the analysis phase's HIP events time: k_analyze_w (+ the partial-frame k_analyze list beside
-        # it) on 16-bit LUT plans at levels 3-6, k_analyze otherwise -- from the config, so lines without in-run
-        # counters (N > 1) name it too
-        dom_label = dom_name
-        codegen = codegen_stats(dom_name)
-        if dom_name == "k_analyze":
-            dom_label, prefix = analysis_kernel(cfg, dt, wave_plan, k17_plan)
-            codegen = codegen_stats(prefix.split("ILb")[0].split("ILi")[0].rsplit("fra", 1)[1].lstrip("0123456789"),
-                                    prefix)
-        hbm_frac = achieved / HBM_PEAK_GBPS
-        valu_frac = None
-        if pm.get("valu_insts") and pm.get("busy_cycles_per_xcd"):
-            valu_frac = pm["valu_insts"] * VALU_CYC / (SIMDS * pm["busy_cycles_per_xcd"])
-        bound = "hbm" if valu_frac is None or hbm_frac >= valu_frac else "valu"
-        per_rank = [{"rank": k, "ms_per_step": round(r[0] / args.steps * 1e3, 4), "analyze_ms": round(r[1], 4),
-                     "serial_ms": round(r[2], 4), "tiles": int(r[3]), "pixels": int(r[4]),
+        # roofline of the dominant kernel (--full: it needs the per-kernel times and the counters)
+        if args.full:
+            if pm is None:
+                pm = committed_profile(args, cfg, dom_name)
+            # the kernel the analysis phase's HIP events time: k_analyze_w (+ the partial-frame k_analyze list beside
+            # it) on 16-bit LUT plans at levels 3-6, k_analyze otherwise -- from the config, so lines without in-run
+            # counters (N > 1) name it too
+            dom_label = dom_name
+            codegen = codegen_stats(dom_name)
+            if dom_name == "k_analyze":
+                dom_label, prefix = analysis_kernel(cfg, dt, wave_plan, k17_plan)
+                codegen = codegen_stats(prefix.split("ILb")[0].split("ILi")[0].rsplit("fra", 1)[1].lstrip("0123456789"),
+                                        prefix)
+            hbm_frac = achieved / HBM_PEAK_GBPS
+            valu_frac = None
+            if pm.get("valu_insts") and pm.get("busy_cycles_per_xcd"):
+                valu_frac = pm["valu_insts"] * VALU_CYC / (SIMDS * pm["busy_cycles_per_xcd"])
+            bound = "hbm" if valu_frac is None or hbm_frac >= valu_frac else "valu"
+        per_rank = [{"rank": k, "ms_per_step": round(r[0] / args.steps * 1e3, 4),
+                     "analyze_ms": round(r[1], 4) if args.full else None,
+                     "serial_ms": round(r[2], 4) if args.full else None, "tiles": int(r[3]), "pixels": int(r[4]),
                      "frame_bytes": int(r[5])} for k, r in enumerate(ranks)]
         mean_t = sum(r[0] for r in ranks) / len(ranks)
         result = {
@@ -787,7 +858,7 @@ def main():
                                                       "tiles in strided order",
                                            "lpt": "whole tiles by LPT on pixel count"}[args.split])),
                        "split": args.split,
-                       "serial_ms_per_step": round(step_ms_local, 4)},
+                       "serial_ms_per_step": round(step_ms_local, 4) if args.full else None},
             "per_rank": per_rank,
             "imbalance": round(T / mean_t, 4) if mean_t > 0 else None,
             "analysis_instance": ({
@@ -799,37 +870,41 @@ def main():
                         "the same scene, so they run the instance the settle execute's count chose; bytes are equal "
                         "either way. first_execute_ms is the plan's first (17-bit, cold) execute, synced alone"}
                 if inst is not None else None),
-            "roofline": {"bound": bound, "kernel": dom_label, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": round(hbm_frac, 5), "traffic": pm.get("traffic"),
-                         "valu_issue_frac": round(valu_frac, 4) if valu_frac is not None else None,
-                         # whole path: algorithmic bytes of the step over the TIMED (pipelined) step, and over the
-                         # serial sum of the kernels (each alone, HIP events)
-                         "whole_path_frac": round(out_bytes_all / max(1e-12, T / args.steps) / 1e9 / HBM_PEAK_GBPS
-                                                  + raster_bytes * (world if weak else 1) / max(1e-12, T / args.steps)
-                                                  / 1e9 / HBM_PEAK_GBPS, 5),
-                         "whole_path_frac_serial": round(path_gbps / HBM_PEAK_GBPS, 5),
-                         "whole_path_gbps_serial": round(path_gbps, 2),
-                         "codegen": codegen,
-                         "alg_bytes_per_launch": int(alg_bytes),
-                         "kernel_ms_per_launch": {"minmax": round(per_launch_ms[0], 4),
-                                                  "analyze": round(per_launch_ms[1], 4),
-                                                  "frame_scan": round(per_launch_ms[2], 4),
-                                                  "pack": round(per_launch_ms[3], 4)},
-                         "counters": pm,
-                         "valu_note": f"valu_issue_frac = SQ_INSTS_VALU x {VALU_CYC} cyc / ({SIMDS} SIMDs x "
-                                      "GRBM_GUI_ACTIVE/8) of the same launch"},
-            "kernel_stats": ({"source": "rocprofv3 --kernel-trace --stats over bench.py --child --child-serial "
-                                        f"(the plan's {args.warmup}+{args.steps} executes only, serial as the "
-                                        "roofline's HIP events, no parity launches), CSV "
-                                        f"{args.config}_n1_{sources_sha()}_timed_kernel_stats.csv",
-                              "sources_sha": sources_sha(), "kernels": kstats} if kstats else None),
-            "reference_cpu": reference_cpu_probe(),
-            "cpu_baseline": cpu,
-            "cpu_baseline_mp": cpu_mp,
-            "size_ratio_vs_libflac_c2": size_c2,
-            "pyflac_shim_c2": shim,
-            "e2e": e2e,
         }
+        if args.full:
+            result.update({
+                "roofline": {"bound": bound, "kernel": dom_label, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
+                             "unit": "GB/s", "frac": round(hbm_frac, 5), "traffic": pm.get("traffic"),
+                             "valu_issue_frac": round(valu_frac, 4) if valu_frac is not None else None,
+                             # whole path: algorithmic bytes of the step over the TIMED (pipelined) step, and over the
+                             # serial sum of the kernels (each alone, HIP events)
+                             "whole_path_frac": round(
+                                 out_bytes_all / max(1e-12, T / args.steps) / 1e9 / HBM_PEAK_GBPS
+                                 + raster_bytes * (world if weak else 1) / max(1e-12, T / args.steps)
+                                 / 1e9 / HBM_PEAK_GBPS, 5),
+                             "whole_path_frac_serial": round(path_gbps / HBM_PEAK_GBPS, 5),
+                             "whole_path_gbps_serial": round(path_gbps, 2),
+                             "codegen": codegen,
+                             "alg_bytes_per_launch": int(alg_bytes),
+                             "kernel_ms_per_launch": {"minmax": round(per_launch_ms[0], 4),
+                                                      "analyze": round(per_launch_ms[1], 4),
+                                                      "frame_scan": round(per_launch_ms[2], 4),
+                                                      "pack": round(per_launch_ms[3], 4)},
+                             "counters": pm,
+                             "valu_note": f"valu_issue_frac = SQ_INSTS_VALU x {VALU_CYC} cyc / ({SIMDS} SIMDs x "
+                                          "GRBM_GUI_ACTIVE/8) of the same launch"},
+                "kernel_stats": ({"source": "rocprofv3 --kernel-trace --stats over bench.py --child --child-serial "
+                                            f"(the plan's {args.warmup}+{args.steps} executes only, serial as the "
+                                            "roofline's HIP events, no parity launches), CSV "
+                                            f"{args.config}_n1_{sources_sha()}_timed_kernel_stats.csv",
+                                  "sources_sha": sources_sha(), "kernels": kstats} if kstats else None),
+                "reference_cpu": reference_cpu_probe(),
+                "cpu_baseline": cpu,
+                "cpu_baseline_mp": cpu_mp,
+                "size_ratio_vs_libflac_c2": size_c2,
+                "pyflac_shim_c2": shim,
+                "e2e": e2e,
+            })
         print(json.dumps(result), flush=True)
     if plan is not None:
         plan.close()

@@ -3,7 +3,8 @@
 
 C1 sample_dem.tif 512^2 int16 and C2 sample_rgb.tif 256^2x3 uint8 (standard format, one stream):
 device-resident raster -> frames, K repeats timed (launch-latency bound at this size).
-C3/C4/C5: `bench.py --config cN --no-cpu --no-e2e` (synthetic rasters of the named shapes).
+C3/C4/C5: `bench.py --config cN --full --no-cpu --no-e2e` (synthetic rasters of the named shapes; --full for the
+per-kernel times and the roofline fraction).
 Writes one JSON object per config to stdout (and --out FILE)."""
 import argparse
 import json
@@ -45,7 +46,7 @@ def small(name, tif, level=5, reps=200):
 
 
 def big(cfg, steps):
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--no-cpu", "--no-e2e",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--full", "--no-cpu", "--no-e2e",
                         "--steps", str(steps), "--warmup", "1"], capture_output=True, text=True, timeout=900)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One round's measurement set (run on the GPU box from the repo root):
 #   bash tools/profile_round.sh <tag>        e.g. r01_c4_n1_v8
-# 1. python bench.py (default C4 line, CPU baseline + e2e)              -> gpurun_out/<tag>/bench.json
+# 1. python bench.py --full (C4 line with CPU baseline, e2e, counters)   -> <out>/<tag>/bench.json
 # 2. rocprofv3 --kernel-trace --stats on bench.py (kernels only)          -> gpurun_out/<tag>/stats/
 # 3. rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE (separate passes) -> gpurun_out/<tag>/pmc_{fetch,write}/
 # Then on the CPU side: python tools/traffic_summary.py gpurun_out/<tag> <tag>
@@ -9,7 +9,7 @@ set -e
 TAG=$1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
-timeout -k 10 300 python $GRAFT_REPO_ROOT/bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python "$(dirname "$0")/../bench.py" --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- \
