@@ -321,6 +321,12 @@ int fra_internal_set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+// device and stream of a context, for the translation units that do not see fra_ctx (fra_decode_dev.hip)
+void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream) {
+  *device = ctx->device;
+  *stream = ctx->stream;
+}
+
 const char* fra_last_error(void) { return g_err.c_str(); }
 int fra_abi_version(void) { return FRA_ABI_VERSION; }
 void fra_free(void* p) { free(p); }

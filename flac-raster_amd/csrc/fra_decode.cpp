@@ -26,19 +26,16 @@
 #include <vector>
 
 #include "../../include/flac_raster_amd.h"
+#include "fra_frame_header.h"
 
 extern "C" int fra_internal_set_error(int code, const char* fmt, ...);
 
 namespace {
 
-uint8_t g_crc8[256];
 uint16_t g_crc16[256];
 struct CrcInit {
   CrcInit() {
     for (int v = 0; v < 256; v++) {
-      uint32_t c = (uint32_t)v;
-      for (int b = 0; b < 8; b++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) : (c << 1);
-      g_crc8[v] = (uint8_t)c;
       uint32_t d = (uint32_t)v << 8;
       for (int b = 0; b < 8; b++) d = (d & 0x8000u) ? ((d << 1) ^ 0x8005u) : (d << 1);
       g_crc16[v] = (uint16_t)d;
@@ -110,66 +107,12 @@ struct Bits {
   void align() { pos = (pos + 7) & ~7ull; }
 };
 
-struct StreamParams {
-  int sample_rate = 0, channels = 0, bps = 0, min_bs = 0, max_bs = 0;
-  uint64_t total_samples = 0;
-};
+using fra_dec::FrameHdr;
+using fra_dec::StreamParams;
+using fra_dec::parse_metadata;
 
-struct FrameHdr {
-  int blocksize = 0, sample_rate = 0, chan_assign = 0, channels = 0, bps = 0;
-  uint64_t number = 0;  // frame number (fixed) or first sample (variable)
-  bool variable = false;
-  int hdr_len = 0;
-};
-
-// RFC 9639 9.1; 0 values of sample rate / bps (code 0) take the STREAMINFO ones.
-bool parse_header(const uint8_t* p, const uint8_t* end, const StreamParams& sp, FrameHdr& h) {
-  if (end - p < 6) return false;
-  if (p[0] != 0xFF || (p[1] & 0xFE) != 0xF8) return false;
-  h.variable = p[1] & 1;
-  const int bsc = p[2] >> 4, src = p[2] & 15, ca = p[3] >> 4, bpc = (p[3] >> 1) & 7;
-  if ((p[3] & 1) || bsc == 0 || src == 15 || ca > 10 || bpc == 3) return false;
-  const uint8_t* q = p + 4;
-  // UTF-8-like coded number
-  uint64_t v = *q++;
-  int extra = 0;
-  if (!(v & 0x80)) extra = 0;
-  else if ((v & 0xE0) == 0xC0) { v &= 0x1F; extra = 1; }
-  else if ((v & 0xF0) == 0xE0) { v &= 0x0F; extra = 2; }
-  else if ((v & 0xF8) == 0xF0) { v &= 0x07; extra = 3; }
-  else if ((v & 0xFC) == 0xF8) { v &= 0x03; extra = 4; }
-  else if ((v & 0xFE) == 0xFC) { v &= 0x01; extra = 5; }
-  else if (v == 0xFE) { v = 0; extra = 6; }
-  else return false;
-  if (!h.variable && extra > 5) return false;
-  if (end - q < extra + 1) return false;
-  for (int i = 0; i < extra; i++) {
-    if ((*q & 0xC0) != 0x80) return false;
-    v = (v << 6) | (*q++ & 0x3F);
-  }
-  h.number = v;
-  if (bsc == 1) h.blocksize = 192;
-  else if (bsc <= 5) h.blocksize = 576 << (bsc - 2);
-  else if (bsc == 6) { if (end - q < 2) return false; h.blocksize = *q++ + 1; }
-  else if (bsc == 7) { if (end - q < 3) return false; h.blocksize = ((q[0] << 8) | q[1]) + 1; q += 2; }
-  else h.blocksize = 256 << (bsc - 8);
-  static const int kRates[12] = {0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000};
-  if (src == 0) h.sample_rate = sp.sample_rate;
-  else if (src < 12) h.sample_rate = kRates[src];
-  else if (src == 12) { if (end - q < 2) return false; h.sample_rate = *q++ * 1000; }
-  else if (src == 13) { if (end - q < 3) return false; h.sample_rate = (q[0] << 8) | q[1]; q += 2; }
-  else { if (end - q < 3) return false; h.sample_rate = ((q[0] << 8) | q[1]) * 10; q += 2; }
-  static const int kBps[8] = {0, 8, 12, 0, 16, 20, 24, 32};
-  h.bps = bpc == 0 ? sp.bps : kBps[bpc];
-  if (h.bps < 4 || h.bps > 32) return false;
-  h.chan_assign = ca;
-  h.channels = ca < 8 ? ca + 1 : 2;
-  if (end - q < 1) return false;
-  uint32_t c8 = 0;
-  for (const uint8_t* r = p; r < q; r++) c8 = g_crc8[c8 ^ *r];
-  if (c8 != *q) return false;
-  h.hdr_len = (int)(q - p) + 1;
-  return true;
+inline bool parse_header(const uint8_t* p, const uint8_t* end, const StreamParams& sp, FrameHdr& h) {
+  return fra_dec::parse_header(p, end, sp.sample_rate, sp.bps, h);
 }
 
 // residual (RFC 9639 9.2.7) for a subframe of n samples with `order` warm-up samples
@@ -320,36 +263,6 @@ size_t decode_frame(const uint8_t* p, const uint8_t* end, const StreamParams& sp
       for (int c = 0; c < out_channels; c++) out[(size_t)i * out_channels + c] = (int32_t)sc.ch[c][i];
   }
   return flen;
-}
-
-// "fLaC" + metadata blocks; returns the offset of the first audio byte (0 on error)
-size_t parse_metadata(const uint8_t* d, size_t len, size_t at, StreamParams& sp) {
-  if (at > len || len - at < 8 || memcmp(d + at, "fLaC", 4) != 0) return 0;
-  size_t q = at + 4;
-  bool have_si = false;
-  for (;;) {
-    if (len - q < 4) return 0;
-    const bool last = d[q] & 0x80;
-    const int type = d[q] & 0x7F;
-    const size_t bl = ((size_t)d[q + 1] << 16) | ((size_t)d[q + 2] << 8) | d[q + 3];
-    q += 4;
-    if (len - q < bl) return 0;
-    if (type == 0) {
-      if (bl < 34) return 0;
-      const uint8_t* s = d + q;
-      sp.min_bs = (s[0] << 8) | s[1];
-      sp.max_bs = (s[2] << 8) | s[3];
-      sp.sample_rate = (s[10] << 12) | (s[11] << 4) | (s[12] >> 4);
-      sp.channels = ((s[12] >> 1) & 7) + 1;
-      sp.bps = (((s[12] & 1) << 4) | (s[13] >> 4)) + 1;
-      sp.total_samples = ((uint64_t)(s[13] & 15) << 32) | ((uint64_t)s[14] << 24) | ((uint64_t)s[15] << 16) |
-                         ((uint64_t)s[16] << 8) | s[17];
-      have_si = true;
-    }
-    q += bl;
-    if (last) break;
-  }
-  return have_si ? q : 0;
 }
 
 struct Cand {

@@ -1,0 +1,805 @@
+// fra_decode_dev.hip -- batched FLAC decode on the GPU: tile streams -> raster (fra_decode_device).
+//
+// FLAC gives a decoder three serial chains (a frame's end is known only after decoding it, subframe c+1 starts
+// where c ends, every sample depends on the previous `order` ones), so there is no parallelism inside a
+// subframe; a scene has 10^4..10^5 frames and that is where the parallelism lies:
+//
+//   host        candidates = the caller's frame offsets, or every sync position 0xFFF8/9 whose header parses and
+//               whose CRC-8 holds (threads over byte ranges, at most 16; no speculative decode on the host)
+//   k_dec_parse one lane per candidate: walks the frame's bits (subframe headers, warm-up, LPC parameters,
+//               partitioned Rice/Rice2 residual with escapes, VERBATIM, CONSTANT) through a three-word bit window,
+//               writes residuals / verbatim samples as int32 into scratch laid out in groups of 64 frames
+//               ((c * blocksize + i) * 64 + lane inside a group: a wave's stores of sample i are one 256-byte run),
+//               a descriptor per subframe, and per frame its byte length, sample count and status after the
+//               CRC-16 from the frame's start to its decoded end.  Every read is bounded by the stream's end and
+//               every loop by the block size and the unary cap, so a false candidate ends as "not a frame"
+//   host        frame table D2H, chain start -> end exactly as fra_decode (fLaC at a break = next stream)
+//   k_dec_restore one lane per chained (frame, channel): inverts FIXED 0-4 (registers) and LPC 1-32 (coefficients
+//               and a 32-entry history ring per lane in LDS) in place with 64-bit sums, checks every sample
+//               against the subframe's width
+//   k_dec_scatter per (group, 64 samples): wasted-bits shift, stereo undo, optional denormalisation, an LDS
+//               transpose so that scratch reads (lane-major) and raster writes (sample-major) are both contiguous
+//
+// Not covered (refused, never decoded differently): 33-bit samples (side channel of a 32-bps stream).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "../../include/flac_raster_amd.h"
+#include "fra_decode_host.h"
+
+extern "C" int fra_internal_set_error(int code, const char* fmt, ...);
+extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
+
+namespace {
+
+using fra_dec::FrameHdr;
+using fra_dec::HostCand;
+using fra_dec::StreamParams;
+using fra_dec::ST_NONE;
+using fra_dec::ST_OK;
+using fra_dec::ST_UNSUPPORTED;
+
+constexpr int kLanes = 64;  // frames per group = lanes of a wave
+constexpr uint64_t kNoFrame = ~0ull;
+constexpr uint32_t kMaxUnary = 1u << 28;
+enum : uint32_t { SF_CONSTANT = 0, SF_VERBATIM = 1, SF_FIXED = 2, SF_LPC = 3 };
+
+struct DecItem {
+  uint64_t end;  // absolute byte end of the item: no read goes past it
+  int32_t channels, bps, sample_rate, bs_stride;
+  int32_t row_off, col_off, width, height;
+  double dmin, span;
+};
+struct DecGroup {
+  uint64_t base;  // first scratch element of the group
+  int32_t item, count;
+};
+using FrameOut = fra_dec::FrameRec;
+struct DecArgs {
+  const uint8_t* data;
+  const DecItem* items;
+  const DecGroup* groups;
+  const uint64_t* starts;  // [ngroups * 64] absolute byte of every candidate (kNoFrame: empty slot)
+  FrameOut* fout;          // [ngroups * 64]
+  uint32_t* sdesc;         // [ngroups * 64 * 8]: kind | order << 8 | wasted << 16 | shift << 24
+  int32_t* coefs;          // [ngroups * 64 * 8 * 32]
+  int32_t* scratch;
+  const int64_t* samp0;    // [ngroups * 64]: item-relative first sample of a chained frame, -1 otherwise
+  uint32_t* fail;          // [ngroups * 64]: a reconstructed sample left the subframe's width
+  void* dst;
+  int64_t band_stride, row_stride, col_stride;
+  int32_t dst_dtype, denorm;
+};
+
+// ------------------------------------------------------------------------------------------ device bit reader
+// MSB-first over data[.., end); bits past `end` read as zeros and set `bad` (as the host's Bits)
+struct DBits {
+  const uint8_t* d;
+  uint64_t end;  // absolute byte bound
+  // a three-word window over bytes [cb, cb + 24): cw and nw are in use, fw was requested one refill ahead so that its
+  // load latency is covered by the ~64 bits of work in between; the read position is bit `o` (< 64) of cw
+  uint64_t cb, cw, nw, fw;
+  uint32_t o;
+  bool bad;  // the window moved past `end` (the frame cannot be one: its end is checked against `end` as well)
+  __device__ uint64_t ld(uint64_t byte) const {
+    if (byte + 8 <= end) {
+      uint64_t w;
+      __builtin_memcpy(&w, d + byte, 8);
+      return __builtin_bswap64(w);
+    }
+    uint64_t w = 0;
+    for (uint64_t i = 0; i < 8; i++) w = (w << 8) | (byte + i < end ? (uint64_t)d[byte + i] : 0ull);
+    return w;
+  }
+  __device__ void init(const uint8_t* data, uint64_t e, uint64_t byte) {
+    d = data; end = e; cb = byte; o = 0; bad = false;
+    cw = ld(byte); nw = ld(byte + 8); fw = ld(byte + 16);
+  }
+  __device__ uint64_t pos() const { return cb * 8 + o; }  // absolute bit position
+  __device__ uint64_t peek() const { return o ? (cw << o) | (nw >> (64 - o)) : cw; }
+  __device__ void skip(uint32_t n) {  // n <= 64
+    o += n;
+    if (o >= 64) {
+      o -= 64;
+      cb += 8;
+      cw = nw;
+      nw = fw;
+      fw = ld(cb + 16);
+      if (cb > end) bad = true;
+    }
+  }
+  __device__ uint32_t get(int n) {  // n <= 32
+    if (n == 0) return 0;
+    const uint32_t v = (uint32_t)(peek() >> (64 - n));
+    skip((uint32_t)n);
+    return v;
+  }
+  __device__ int32_t sget(int n) {
+    if (n == 0) return 0;
+    const uint32_t v = get(n);
+    return n == 32 ? (int32_t)v : (int32_t)(v << (32 - n)) >> (32 - n);
+  }
+  __device__ uint32_t unary() {  // zeros before a one; a run that reaches the end or the cap is bad
+    uint32_t z = 0;
+    for (;;) {
+      const uint64_t w = peek();
+      if (w) {
+        const int lz = __builtin_clzll(w);
+        skip((uint32_t)lz + 1);
+        return z + (uint32_t)lz;
+      }
+      skip(64);
+      z += 64;
+      if (bad || z > kMaxUnary + 64) { bad = true; return z; }
+    }
+  }
+};
+
+__device__ inline bool side_channel(int assign, int c) {
+  return (assign == 8 && c == 1) || (assign == 9 && c == 0) || (assign == 10 && c == 1);
+}
+
+// one candidate frame; returns its status
+__device__ int parse_frame(const DecArgs& a, const DecItem& it, const DecGroup& grp, int slot, int lane, uint64_t st,
+                           const uint16_t* crct, FrameOut& fo) {
+  FrameHdr h;
+  if (st >= it.end || !fra_dec::parse_header(a.data + st, a.data + it.end, it.sample_rate, it.bps, h)) return ST_NONE;
+  if (h.channels != it.channels || h.blocksize > it.bs_stride) return ST_NONE;
+  DBits br;
+  br.init(a.data, it.end, st + (uint64_t)h.hdr_len);
+  const int n = h.blocksize;
+  for (int c = 0; c < h.channels; c++) {
+    const int bps = h.bps + (side_channel(h.chan_assign, c) ? 1 : 0);
+    if (br.get(1) != 0) return ST_NONE;
+    const int type = (int)br.get(6);
+    int wasted = 0;
+    if (br.get(1)) wasted = (int)br.unary() + 1;
+    if (br.bad || wasted >= bps) return ST_NONE;
+    const int eb = bps - wasted;
+    uint32_t kind;
+    int order = 0;
+    if (type == 0) kind = SF_CONSTANT;
+    else if (type == 1) kind = SF_VERBATIM;
+    else if (type >= 8 && type <= 12) { kind = SF_FIXED; order = type - 8; }
+    else if (type >= 32) { kind = SF_LPC; order = type - 31; }
+    else return ST_NONE;
+    if (order > n) return ST_NONE;
+    if (eb > 32) return ST_UNSUPPORTED;  // 33-bit side channel of a 32-bps stream
+    int32_t* out = a.scratch + grp.base + (uint64_t)c * (uint64_t)it.bs_stride * kLanes + lane;
+    int shift = 0;
+    // CONSTANT keeps its value at sample 0; VERBATIM and the warm-up are eb-bit samples
+    const int plain = kind == SF_CONSTANT ? 1 : (kind == SF_VERBATIM ? n : order);
+    for (int i = 0; i < plain; i++) {
+      out[(uint64_t)i * kLanes] = br.sget(eb);
+      if (br.bad) return ST_NONE;
+    }
+    if (kind == SF_LPC) {
+      const int prec = (int)br.get(4) + 1;
+      if (prec == 16) return ST_NONE;
+      shift = br.sget(5);
+      if (shift < 0) return ST_NONE;
+      int32_t* cf = a.coefs + ((uint64_t)slot * 8 + c) * 32;
+      for (int j = 0; j < order; j++) cf[j] = br.sget(prec);
+    }
+    if (kind >= SF_FIXED) {
+      const uint32_t method = br.get(2);
+      if (method > 1) return ST_NONE;
+      const int pbits = method == 0 ? 4 : 5;
+      const uint32_t esc = method == 0 ? 15u : 31u;
+      const int porder = (int)br.get(4);
+      if (n & ((1 << porder) - 1)) return ST_NONE;
+      const int psz = n >> porder;
+      if (psz < order) return ST_NONE;
+      uint32_t k = br.get(pbits);
+      int raw = k == esc ? (int)br.get(5) : -1;
+      int left = psz - order;
+      for (int i = order; i < n; i++) {
+        if (left == 0) {  // next partition (psz >= 1: at most one per sample)
+          k = br.get(pbits);
+          raw = k == esc ? (int)br.get(5) : -1;
+          left = psz;
+        }
+        left--;
+        int32_t v;
+        if (raw >= 0) {
+          v = br.sget(raw);
+        } else {
+          const uint32_t q = br.unary();
+          if (br.bad || q > kMaxUnary) return ST_NONE;
+          const uint64_t u = ((uint64_t)q << k) | (k ? (uint64_t)br.get((int)k) : 0ull);
+          const int64_t w = (int64_t)(u >> 1) ^ -(int64_t)(u & 1);
+          if (w < INT32_MIN || w > INT32_MAX) return ST_NONE;
+          v = (int32_t)w;
+        }
+        if (br.bad) return ST_NONE;
+        out[(uint64_t)i * kLanes] = v;
+      }
+    }
+    if (br.bad) return ST_NONE;
+    a.sdesc[(uint64_t)slot * 8 + c] = kind | ((uint32_t)order << 8) | ((uint32_t)wasted << 16) | ((uint32_t)shift << 24);
+  }
+  const uint64_t body_end = (br.pos() + 7) >> 3;  // absolute byte after the padded subframes
+  if (body_end + 2 > it.end) return ST_NONE;
+  uint32_t crc = 0;
+  uint64_t p = st;
+  for (; p + 8 <= body_end; p += 8) {
+    uint64_t w;
+    __builtin_memcpy(&w, a.data + p, 8);
+    w = __builtin_bswap64(w);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+      crc = ((crc << 8) ^ crct[((crc >> 8) ^ (uint32_t)(w >> 56)) & 0xFF]) & 0xFFFF;
+      w <<= 8;
+    }
+  }
+  for (; p < body_end; p++) crc = ((crc << 8) ^ crct[((crc >> 8) ^ a.data[p]) & 0xFF]) & 0xFFFF;
+  if (crc != (((uint32_t)a.data[body_end] << 8) | a.data[body_end + 1])) return ST_NONE;
+  fo.len = (uint32_t)(body_end + 2 - st);
+  fo.n = n;
+  fo.assign = (uint8_t)h.chan_assign;
+  fo.bps = (uint8_t)h.bps;
+  return ST_OK;
+}
+
+__global__ __launch_bounds__(kLanes) void k_dec_parse(DecArgs a) {
+  __shared__ uint16_t crct[256];
+  for (int v = threadIdx.x; v < 256; v += kLanes) {
+    uint32_t d = (uint32_t)v << 8;
+    for (int b = 0; b < 8; b++) d = (d & 0x8000u) ? ((d << 1) ^ 0x8005u) : (d << 1);
+    crct[v] = (uint16_t)d;
+  }
+  __syncthreads();
+  const int g = blockIdx.x, lane = threadIdx.x, slot = g * kLanes + lane;
+  const DecGroup grp = a.groups[g];
+  const DecItem it = a.items[grp.item];
+  FrameOut fo{0, 0, 0, 0, 0, 0};
+  const uint64_t st = lane < grp.count ? a.starts[slot] : kNoFrame;
+  if (st != kNoFrame) fo.status = (uint8_t)parse_frame(a, it, grp, slot, lane, st, crct, fo);
+  a.fout[slot] = fo;
+}
+
+// ------------------------------------------------------------------------------------------ restore
+__global__ __launch_bounds__(kLanes) void k_dec_restore(DecArgs a) {
+  __shared__ int32_t s_coef[32 * kLanes];  // [j][lane]: a lane's column, conflict-free
+  __shared__ int32_t s_hist[32 * kLanes];  // history ring, sample i at row i & 31
+  const int g = blockIdx.x, c = blockIdx.y, lane = threadIdx.x, slot = g * kLanes + lane;
+  const DecGroup grp = a.groups[g];
+  const DecItem it = a.items[grp.item];
+  if (c >= it.channels || lane >= grp.count || a.samp0[slot] < 0) return;
+  const FrameOut fo = a.fout[slot];
+  const uint32_t d = a.sdesc[(uint64_t)slot * 8 + c];
+  const uint32_t kind = d & 0xFF;
+  const int order = (int)((d >> 8) & 0xFF), wasted = (int)((d >> 16) & 0xFF), shift = (int)(d >> 24);
+  if (kind < SF_FIXED) return;
+  const int n = fo.n;
+  const int eb = (int)fo.bps + (side_channel(fo.assign, c) ? 1 : 0) - wasted;  // <= 32 (parse refused 33)
+  // samples within eb bits keep every predictor sum below 2^53: no int64 overflow (as the host decoder)
+  const int64_t lo = -((int64_t)1 << (eb - 1)), hi = ((int64_t)1 << (eb - 1)) - 1;
+  int32_t* s = a.scratch + grp.base + (uint64_t)c * (uint64_t)it.bs_stride * kLanes + lane;
+  bool bad = false;
+  if (kind == SF_FIXED) {
+    int64_t s1 = 0, s2 = 0, s3 = 0, s4 = 0;  // s[i-1] .. s[i-4]
+    for (int i = 0; i < order; i++) { s4 = s3; s3 = s2; s2 = s1; s1 = s[(uint64_t)i * kLanes]; }
+    for (int i0 = order; i0 < n; i0 += 8) {
+      int32_t r[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) r[u] = i0 + u < n ? s[(uint64_t)(i0 + u) * kLanes] : 0;
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        if (i0 + u < n) {
+          int64_t p = 0;
+          switch (order) {
+            case 1: p = s1; break;
+            case 2: p = 2 * s1 - s2; break;
+            case 3: p = 3 * s1 - 3 * s2 + s3; break;
+            case 4: p = 4 * s1 - 6 * s2 + 4 * s3 - s4; break;
+          }
+          const int64_t v = p + r[u];
+          if (v < lo || v > hi) bad = true;
+          s[(uint64_t)(i0 + u) * kLanes] = (int32_t)v;
+          s4 = s3; s3 = s2; s2 = s1; s1 = (int32_t)v;
+        }
+      }
+      if (bad) break;
+    }
+  } else {
+    const int32_t* cf = a.coefs + ((uint64_t)slot * 8 + c) * 32;
+    for (int j = 0; j < order; j++) s_coef[j * kLanes + lane] = cf[j];
+    for (int i = 0; i < order; i++) s_hist[(i & 31) * kLanes + lane] = s[(uint64_t)i * kLanes];
+    for (int i0 = order; i0 < n; i0 += 8) {
+      int32_t r[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) r[u] = i0 + u < n ? s[(uint64_t)(i0 + u) * kLanes] : 0;
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        const int i = i0 + u;
+        if (i < n) {
+          int64_t acc = 0;
+          for (int j = 0; j < order; j++)
+            acc += (int64_t)s_coef[j * kLanes + lane] * (int64_t)s_hist[((i - 1 - j) & 31) * kLanes + lane];
+          const int64_t v = (acc >> shift) + r[u];
+          if (v < lo || v > hi) bad = true;
+          s_hist[(i & 31) * kLanes + lane] = (int32_t)v;
+          s[(uint64_t)i * kLanes] = (int32_t)v;
+        }
+      }
+      if (bad) break;
+    }
+  }
+  if (bad) a.fail[slot] = 1;
+}
+
+// ------------------------------------------------------------------------------------------ scatter
+__device__ inline double sat(double x, double lo, double hi) {
+  return x != x ? 0.0 : (x < lo ? lo : (x > hi ? hi : x));
+}
+
+// one decoded sample -> the destination element (every f64 operation separate, in normalization.py's order)
+__device__ inline void put_sample(const DecArgs& a, const DecItem& it, int64_t e, int32_t s) {
+  if (a.denorm == FRA_DENORM_NONE) {
+    if (a.dst_dtype == FRA_I16) ((int16_t*)a.dst)[e] = (int16_t)s;
+    else ((int32_t*)a.dst)[e] = s;
+    return;
+  }
+  double y;
+  if (a.denorm == FRA_DENORM_INT) y = (double)s / (it.bps <= 16 ? 32767.0 : 8388607.0);
+  else y = (double)(it.bps <= 16 ? s : (s >> 16)) / 32768.0;
+  double x = y + 1.0;
+  x = x / 2.0;
+  x = x * it.span;
+  x = x + it.dmin;
+  switch (a.dst_dtype) {
+    case FRA_U8: ((uint8_t*)a.dst)[e] = (uint8_t)sat(rint(x), 0.0, 255.0); break;
+    case FRA_I8: ((int8_t*)a.dst)[e] = (int8_t)sat(rint(x), -128.0, 127.0); break;
+    case FRA_U16: ((uint16_t*)a.dst)[e] = (uint16_t)sat(rint(x), 0.0, 65535.0); break;
+    case FRA_I16: ((int16_t*)a.dst)[e] = (int16_t)sat(rint(x), -32768.0, 32767.0); break;
+    case FRA_U32: ((uint32_t*)a.dst)[e] = (uint32_t)sat(rint(x), 0.0, 4294967295.0); break;
+    case FRA_I32: ((int32_t*)a.dst)[e] = (int32_t)sat(rint(x), -2147483648.0, 2147483647.0); break;
+    case FRA_F32: ((float*)a.dst)[e] = (float)x; break;
+    default: ((double*)a.dst)[e] = x; break;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dec_scatter(DecArgs a) {
+  __shared__ int32_t tile[kLanes][kLanes + 1];
+  const int g = blockIdx.x, i0 = blockIdx.y * kLanes, t = threadIdx.x;
+  const DecGroup grp = a.groups[g];
+  const DecItem it = a.items[grp.item];
+  if (i0 >= it.bs_stride) return;
+  const int lane = t & 63, q = t >> 6;
+  const int slot = g * kLanes + lane;
+  const bool live = lane < grp.count && a.samp0[slot] >= 0;
+  FrameOut fo{0, 0, 0, 0, 0, 0};
+  if (live) fo = a.fout[slot];
+  const uint32_t d0 = live ? a.sdesc[(uint64_t)slot * 8] : 0u;
+  const uint32_t d1 = live && it.channels > 1 ? a.sdesc[(uint64_t)slot * 8 + 1] : 0u;
+  const int32_t* sc = a.scratch + grp.base + lane;
+  const uint64_t cstride = (uint64_t)it.bs_stride * kLanes;
+  const uint32_t nsamp = (uint32_t)it.width * (uint32_t)it.height;
+  for (int c = 0; c < it.channels; c++) {
+    __syncthreads();
+    if (live) {
+      const uint32_t dc = c == 0 ? d0 : (c == 1 ? d1 : a.sdesc[(uint64_t)slot * 8 + c]);
+      for (int k = 0; k < 16; k++) {
+        const int i = i0 + q + 4 * k;
+        if (i >= fo.n) break;
+        int32_t v;
+        if (fo.assign >= 8 && c < 2) {
+          const int64_t x0 = (int64_t)((uint64_t)(int64_t)sc[(uint64_t)((d0 & 0xFF) ? i : 0) * kLanes] << ((d0 >> 16) & 0xFF));
+          const int64_t x1 =
+              (int64_t)((uint64_t)(int64_t)sc[cstride + (uint64_t)((d1 & 0xFF) ? i : 0) * kLanes] << ((d1 >> 16) & 0xFF));
+          int64_t l, r;
+          if (fo.assign == 8) { l = x0; r = x0 - x1; }        // L/S
+          else if (fo.assign == 9) { l = x0 + x1; r = x1; }   // S/R
+          else {                                              // M/S
+            const int64_t m = (x0 * 2) | (x1 & 1);
+            l = (m + x1) >> 1;
+            r = (m - x1) >> 1;
+          }
+          v = (int32_t)(c == 0 ? l : r);
+        } else {
+          const int64_t x = (int64_t)sc[(uint64_t)c * cstride + (uint64_t)((dc & 0xFF) ? i : 0) * kLanes];
+          v = (int32_t)(int64_t)((uint64_t)x << ((dc >> 16) & 0xFF));
+        }
+        tile[lane][i - i0] = v;
+      }
+    }
+    __syncthreads();
+    for (int k = 0; k < 16; k++) {
+      const int f = q + 4 * k;  // frame of the group; lane = sample within the 64-sample run
+      if (f >= grp.count) break;
+      const int fs = g * kLanes + f;
+      const int64_t s0 = a.samp0[fs];
+      if (s0 < 0) continue;
+      const int i = i0 + lane;
+      if (i >= a.fout[fs].n) continue;
+      const uint64_t p = (uint64_t)s0 + (uint64_t)i;
+      if (p >= nsamp) continue;  // (the host checked the chain's sample count against the window)
+      const uint32_t row = (uint32_t)p / (uint32_t)it.width, col = (uint32_t)p % (uint32_t)it.width;
+      const int64_t e = (int64_t)c * a.band_stride + ((int64_t)it.row_off + row) * a.row_stride +
+                        ((int64_t)it.col_off + col) * a.col_stride;
+      put_sample(a, it, e, tile[f][lane]);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ host side
+int elem_size(int dt) {
+  switch (dt) {
+    case FRA_U8: case FRA_I8: return 1;
+    case FRA_U16: case FRA_I16: return 2;
+    case FRA_F64: return 8;
+    default: return 4;
+  }
+}
+
+struct ItemPlan {
+  bool search = false;
+  StreamParams sp;
+  uint64_t audio = 0;           // item-relative first audio byte (search path)
+  std::vector<HostCand> cand;   // sorted by start
+  int32_t first_group = 0, ngroups = 0;
+};
+
+// device buffers and events of one call, released on every path
+struct Scratch {
+  std::vector<void*> dev;
+  std::vector<void*> pinned;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~Scratch() {
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : pinned) (void)hipHostFree(p);
+    for (auto e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t alloc(void** p, size_t bytes) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+    if (e == hipSuccess) dev.push_back(*p);
+    return e;
+  }
+};
+
+thread_local float g_last_ms[4] = {0, 0, 0, 0};
+
+#define DCHK(x)                                                                                              \
+  do {                                                                                                       \
+    hipError_t _e = (x);                                                                                     \
+    if (_e != hipSuccess)                                                                                    \
+      return fra_internal_set_error(_e == hipErrorOutOfMemory ? FRA_E_NOMEM : FRA_E_HIP, "%s: %s (%s:%d)", #x, \
+                                    hipGetErrorString(_e), __FILE__, __LINE__);                              \
+  } while (0)
+
+const char kUnsupported[] = "33-bit samples (side channel of a 32-bps stream) are not supported on the device";
+
+}  // namespace
+
+extern "C" {
+
+FRA_API int fra_decode_device_timing(float* ms4) {
+  if (!ms4) return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  memcpy(ms4, g_last_ms, sizeof(g_last_ms));
+  return FRA_OK;
+}
+
+FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decoded* infos) {
+  if (!ctx || !job || !infos) return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  const int ni = job->nitems;
+  if (ni < 0 || (ni && !job->items) || (!job->data && job->len) || !job->dst)
+    return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  if (job->dst_dtype < FRA_U8 || job->dst_dtype > FRA_F64)
+    return fra_internal_set_error(FRA_E_INVALID, "bad dst_dtype %d", job->dst_dtype);
+  if (job->denorm < FRA_DENORM_NONE || job->denorm > FRA_DENORM_PCM16)
+    return fra_internal_set_error(FRA_E_INVALID, "bad denorm %d", job->denorm);
+  if (job->denorm == FRA_DENORM_NONE && job->dst_dtype != FRA_I16 && job->dst_dtype != FRA_I32)
+    return fra_internal_set_error(FRA_E_INVALID, "FRA_DENORM_NONE needs dst_dtype FRA_I16 or FRA_I32");
+  if (job->channels < 1 || job->channels > 8 || job->band_stride < 0 || job->row_stride < 0 || job->col_stride < 0)
+    return fra_internal_set_error(FRA_E_INVALID, "bad destination layout (channels %d)", job->channels);
+  memset(infos, 0, sizeof(fra_decoded) * (size_t)ni);
+  if (ni == 0) return FRA_OK;
+
+  bool any_search = false;
+  int64_t extent = 0;  // elements of dst addressed, from element 0
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    if (it.offset > job->len || it.bytes > job->len - it.offset)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d lies outside the data", i);
+    const fra_window& w = it.window;
+    if (w.row_off < 0 || w.col_off < 0 || w.width < 0 || (w.height < 0 && w.width != 1) || w.height == INT32_MIN)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: bad window", i);
+    if ((int64_t)std::abs(w.height) * w.width > INT32_MAX)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: a window of more than 2^31 - 1 samples is not supported "
+                                                   "on the device", i);
+    if (it.frame_offsets) {
+      if (it.nframes < 0 || it.channels < 1 || it.channels > 8 || it.bps < 4 || it.bps > 32 || it.blocksize < 1 ||
+          it.blocksize > 65536)
+        return fra_internal_set_error(FRA_E_INVALID, "item %d: bad stream parameters", i);
+      for (int f = 0; f < it.nframes; f++)
+        if (it.frame_offsets[f + 1] < it.frame_offsets[f])
+          return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets are not ascending", i);
+      if (it.frame_offsets[it.nframes] > it.bytes)
+        return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets run past the item", i);
+    } else {
+      any_search = true;
+    }
+    if (w.height != 0 && w.width > 0)
+      extent = std::max<int64_t>(extent, (int64_t)(job->channels - 1) * job->band_stride +
+                                             ((int64_t)w.row_off + std::abs(w.height) - 1) * job->row_stride +
+                                             ((int64_t)w.col_off + w.width - 1) * job->col_stride + 1);
+  }
+
+  int device = 0;
+  hipStream_t s = nullptr;
+  fra_internal_ctx_stream(ctx, &device, &s);
+  (void)hipSetDevice(device);
+  Scratch sc;
+
+  // ---- the input on both sides where needed
+  const uint8_t* hdata = job->data_on_device ? nullptr : job->data;
+  std::unique_ptr<uint8_t[]> hcopy;
+  if (any_search && job->data_on_device) {  // the candidate search and the chain read the bytes on the host
+    hcopy.reset(new (std::nothrow) uint8_t[(size_t)job->len + 1]);
+    if (!hcopy) return fra_internal_set_error(FRA_E_NOMEM, "out of host memory");
+    if (job->len) DCHK(hipMemcpy(hcopy.get(), job->data, (size_t)job->len, hipMemcpyDeviceToHost));
+    hdata = hcopy.get();
+  }
+  const uint8_t* ddata = job->data;
+  if (!job->data_on_device) {
+    void* p = nullptr;
+    DCHK(sc.alloc(&p, (size_t)job->len));
+    if (job->len) DCHK(hipMemcpyAsync(p, job->data, (size_t)job->len, hipMemcpyHostToDevice, s));
+    ddata = (const uint8_t*)p;
+  }
+
+  // ---- candidates
+  std::vector<ItemPlan> plan((size_t)ni);
+  std::vector<fra_dec::ScanUnit> units;
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    ItemPlan& ip = plan[(size_t)i];
+    if (it.frame_offsets) {
+      ip.sp.sample_rate = 0;
+      ip.sp.channels = it.channels;
+      ip.sp.bps = it.bps;
+      ip.sp.max_bs = it.blocksize;
+      ip.cand.reserve((size_t)it.nframes);
+      for (int f = 0; f < it.nframes; f++) ip.cand.push_back({it.frame_offsets[f], it.blocksize});
+      continue;
+    }
+    ip.search = true;
+    const uint8_t* d = hdata + it.offset;
+    const size_t at = fra_dec::skip_id3(d, (size_t)it.bytes);
+    if (at == SIZE_MAX) return fra_internal_set_error(FRA_E_INVALID, "item %d: ID3v2 tag runs past the end of the data", i);
+    ip.audio = fra_dec::parse_metadata(d, (size_t)it.bytes, at, ip.sp);
+    if (!ip.audio) return fra_internal_set_error(FRA_E_INVALID, "item %d: not a FLAC stream (bad fLaC/STREAMINFO)", i);
+    if (ip.sp.channels < 1 || ip.sp.channels > 8 || ip.sp.bps < 4 || ip.sp.bps > 32)
+      return fra_internal_set_error(FRA_E_INVALID, "unsupported STREAMINFO (channels %d, bps %d)", ip.sp.channels,
+                                    ip.sp.bps);
+    for (uint64_t b = ip.audio; b < it.bytes; b += (1u << 20))
+      units.push_back({i, d, it.bytes, b, std::min<uint64_t>(it.bytes, b + (1u << 20)), &ip.sp, {}});
+  }
+  if (!units.empty()) {
+    fra_dec::scan_units(units);
+    for (auto& u : units) {
+      auto& c = plan[(size_t)u.item].cand;
+      c.insert(c.end(), u.found.begin(), u.found.end());  // units are in byte order
+    }
+  }
+
+  // ---- groups of 64 candidate frames (a group never spans items), scratch layout
+  std::vector<DecItem> h_items((size_t)ni);
+  std::vector<DecGroup> h_groups;
+  uint64_t scratch_elems = 0;
+  int bs_max = 1;
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    ItemPlan& ip = plan[(size_t)i];
+    if (ip.sp.channels != job->channels)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d has %d channels, the destination %d", i, ip.sp.channels,
+                                    job->channels);
+    if (job->denorm == FRA_DENORM_NONE && job->dst_dtype == FRA_I16 && ip.sp.bps > 16)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: a %d-bps stream needs dst_dtype FRA_I32", i, ip.sp.bps);
+    int stride = 1;
+    for (const HostCand& c : ip.cand) stride = std::max(stride, c.bs);
+    bs_max = std::max(bs_max, stride);
+    DecItem& di = h_items[(size_t)i];
+    di.end = it.offset + it.bytes;
+    di.channels = ip.sp.channels;
+    di.bps = ip.sp.bps;
+    di.sample_rate = ip.sp.sample_rate;
+    di.bs_stride = stride;
+    di.row_off = it.window.row_off;
+    di.col_off = it.window.col_off;
+    di.width = it.window.width;
+    di.height = std::abs(it.window.height);  // (< 0: a capacity in rows of one sample)
+    di.dmin = it.data_min;
+    di.span = it.data_max - it.data_min;
+    ip.first_group = (int32_t)h_groups.size();
+    ip.ngroups = (int32_t)((ip.cand.size() + kLanes - 1) / kLanes);
+    for (int g = 0; g < ip.ngroups; g++) {
+      const int cnt = (int)std::min<size_t>(kLanes, ip.cand.size() - (size_t)g * kLanes);
+      h_groups.push_back({scratch_elems, i, cnt});
+      scratch_elems += (uint64_t)ip.sp.channels * (uint64_t)stride * kLanes;
+    }
+  }
+  const size_t ng = h_groups.size();
+  if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "too many candidate frames");
+  const size_t nslots = ng * kLanes;
+  std::vector<uint64_t> h_starts(std::max<size_t>(1, nslots), kNoFrame);
+  for (int i = 0; i < ni; i++) {
+    const ItemPlan& ip = plan[(size_t)i];
+    for (size_t k = 0; k < ip.cand.size(); k++)
+      h_starts[(size_t)ip.first_group * kLanes + k] = job->items[i].offset + ip.cand[k].start;
+  }
+
+  DecArgs a{};
+  a.data = ddata;
+  a.band_stride = job->band_stride;
+  a.row_stride = job->row_stride;
+  a.col_stride = job->col_stride;
+  a.dst_dtype = job->dst_dtype;
+  a.denorm = job->denorm;
+  void *d_items, *d_groups, *d_starts, *d_fout, *d_sdesc, *d_coefs, *d_scratch, *d_samp0, *d_fail, *d_dst = nullptr;
+  DCHK(sc.alloc(&d_items, sizeof(DecItem) * (size_t)ni));
+  DCHK(sc.alloc(&d_groups, sizeof(DecGroup) * ng));
+  DCHK(sc.alloc(&d_starts, sizeof(uint64_t) * nslots));
+  DCHK(sc.alloc(&d_fout, sizeof(FrameOut) * nslots));
+  DCHK(sc.alloc(&d_sdesc, sizeof(uint32_t) * nslots * 8));
+  DCHK(sc.alloc(&d_coefs, sizeof(int32_t) * nslots * 8 * 32));
+  DCHK(sc.alloc(&d_scratch, sizeof(int32_t) * (size_t)scratch_elems));
+  DCHK(sc.alloc(&d_samp0, sizeof(int64_t) * nslots));
+  DCHK(sc.alloc(&d_fail, sizeof(uint32_t) * nslots));
+  const size_t dst_bytes = (size_t)extent * (size_t)elem_size(job->dst_dtype);
+  // a host destination with contiguous rows comes back window by window; any other layout is staged whole, so
+  // that elements between the windows keep the caller's values either way
+  const bool by_window = !job->dst_on_device && job->col_stride == 1;
+  if (job->dst_on_device) {
+    d_dst = job->dst;
+  } else {
+    DCHK(sc.alloc(&d_dst, dst_bytes));
+    if (dst_bytes && !by_window) DCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
+  }
+  a.items = (const DecItem*)d_items;
+  a.groups = (const DecGroup*)d_groups;
+  a.starts = (const uint64_t*)d_starts;
+  a.fout = (FrameOut*)d_fout;
+  a.sdesc = (uint32_t*)d_sdesc;
+  a.coefs = (int32_t*)d_coefs;
+  a.scratch = (int32_t*)d_scratch;
+  a.samp0 = (const int64_t*)d_samp0;
+  a.fail = (uint32_t*)d_fail;
+  a.dst = d_dst;
+  for (auto& e : sc.ev) DCHK(hipEventCreate(&e));
+  DCHK(hipMemcpyAsync(d_items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
+  if (ng) {
+    DCHK(hipMemcpyAsync(d_groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
+    DCHK(hipMemcpyAsync(d_starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
+    DCHK(hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * nslots, s));
+  }
+
+  // ---- parse every candidate
+  std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
+  DCHK(hipEventRecord(sc.ev[0], s));
+  if (ng) {
+    hipLaunchKernelGGL(k_dec_parse, dim3((unsigned)ng), dim3(kLanes), 0, s, a);
+    DCHK(hipGetLastError());
+  }
+  DCHK(hipEventRecord(sc.ev[1], s));
+  if (ng) DCHK(hipMemcpyAsync(h_fout.data(), d_fout, sizeof(FrameOut) * nslots, hipMemcpyDeviceToHost, s));
+  DCHK(hipStreamSynchronize(s));
+
+  // ---- chain (item-relative byte positions, the host decoder's wording)
+  std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    const ItemPlan& ip = plan[(size_t)i];
+    const size_t s0 = (size_t)ip.first_group * kLanes;
+    uint64_t nsamp = 0;
+    int64_t nframes = 0;
+    int nstreams = 1;
+    if (!ip.search) {
+      for (size_t k = 0; k < ip.cand.size(); k++) {
+        const FrameOut& fo = h_fout[s0 + k];
+        if (fo.status == ST_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
+        if (fo.status != ST_OK || fo.len != it.frame_offsets[k + 1] - it.frame_offsets[k])
+          return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
+                                        (unsigned long long)it.frame_offsets[k]);
+        h_samp0[s0 + k] = (int64_t)nsamp;
+        nsamp += (uint64_t)fo.n;
+        nframes++;
+      }
+    } else {
+      const fra_dec::ChainResult cr = fra_dec::chain_stream(hdata + it.offset, it.bytes, ip.audio, ip.sp,
+                                                            (job->flags & FRA_DECODE_CONCAT) != 0, ip.cand,
+                                                            h_fout.data() + s0, h_samp0.data() + s0);
+      if (cr.code == fra_dec::CHAIN_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
+      if (cr.code == fra_dec::CHAIN_CONCAT_FORMAT)
+        return fra_internal_set_error(FRA_E_INVALID, "concatenated stream at byte %llu has a different format",
+                                      (unsigned long long)cr.byte);
+      if (cr.code == fra_dec::CHAIN_LOST_SYNC)
+        return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
+                                      (unsigned long long)cr.byte);
+      nsamp = cr.nsamp;
+      nframes = cr.nframes;
+      nstreams = cr.nstreams;
+    }
+    if (it.window.height < 0) {
+      if (nsamp > (uint64_t)(-(int64_t)it.window.height)) {
+        infos[i].channels = ip.sp.channels;
+        infos[i].bps = ip.sp.bps;
+        infos[i].nsamples = nsamp;
+        return fra_internal_set_error(FRA_E_SPACE, "item %d: the stream has %llu samples per channel, room for %lld", i,
+                                      (unsigned long long)nsamp, -(long long)it.window.height);
+      }
+    } else if (nsamp != (uint64_t)it.window.height * (uint64_t)it.window.width)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream has %llu samples per channel, its window %d x %d",
+                                    i, (unsigned long long)nsamp, it.window.height, it.window.width);
+    fra_decoded& inf = infos[i];
+    inf.sample_rate = ip.sp.sample_rate;
+    inf.channels = ip.sp.channels;
+    inf.bps = ip.sp.bps;
+    inf.blocksize = ip.sp.max_bs;
+    inf.nframes = nframes;
+    inf.nsamples = nsamp;
+    inf.nstreams = nstreams;
+    inf.audio_offset = ip.audio;
+  }
+
+  // ---- restore and scatter the chained frames
+  std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
+  if (ng) {
+    DCHK(hipMemcpyAsync(d_samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
+    DCHK(hipEventRecord(sc.ev[2], s));
+    hipLaunchKernelGGL(k_dec_restore, dim3((unsigned)ng, (unsigned)job->channels), dim3(kLanes), 0, s, a);
+    DCHK(hipGetLastError());
+  }
+  else DCHK(hipEventRecord(sc.ev[2], s));
+  DCHK(hipEventRecord(sc.ev[3], s));
+  if (ng) {
+    hipLaunchKernelGGL(k_dec_scatter, dim3((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes)), dim3(256), 0, s, a);
+    DCHK(hipGetLastError());
+  }
+  DCHK(hipEventRecord(sc.ev[4], s));
+  if (ng) DCHK(hipMemcpyAsync(h_fail.data(), d_fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
+  if (by_window) {
+    const size_t es = (size_t)elem_size(job->dst_dtype);
+    for (int i = 0; i < ni; i++) {
+      const fra_window& w = job->items[i].window;
+      const int64_t rows = w.height < 0 ? (int64_t)infos[i].nsamples : w.height;
+      if (rows <= 0 || w.width <= 0) continue;
+      for (int c = 0; c < job->channels; c++) {
+        const size_t off = ((size_t)c * (size_t)job->band_stride + (size_t)w.row_off * (size_t)job->row_stride +
+                            (size_t)w.col_off) * es;
+        if (job->row_stride == 0 || rows == 1)
+          DCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)d_dst + off, (size_t)w.width * es,
+                              hipMemcpyDeviceToHost, s));
+        else
+          DCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)d_dst + off,
+                                (size_t)job->row_stride * es, (size_t)w.width * es, (size_t)rows,
+                                hipMemcpyDeviceToHost, s));
+      }
+    }
+  } else if (!job->dst_on_device && dst_bytes) {
+    DCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
+  }
+  DCHK(hipStreamSynchronize(s));
+  for (size_t k = 0; k < nslots; k++)
+    if (h_fail[k])
+      return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
+                                                   "(frame at byte %llu)", (unsigned long long)h_starts[k]);
+  float ms[4] = {0, 0, 0, 0};
+  (void)hipEventElapsedTime(&ms[0], sc.ev[0], sc.ev[1]);
+  (void)hipEventElapsedTime(&ms[1], sc.ev[2], sc.ev[3]);
+  (void)hipEventElapsedTime(&ms[2], sc.ev[3], sc.ev[4]);
+  (void)hipEventElapsedTime(&ms[3], sc.ev[0], sc.ev[4]);
+  memcpy(g_last_ms, ms, sizeof(ms));
+  return FRA_OK;
+}
+
+}  // extern "C"

@@ -70,6 +70,24 @@ class Decoded(C.Structure):
 
 DECODE_CONCAT = 1
 E_SPACE = -6
+DENORM_NONE, DENORM_INT, DENORM_PCM16 = 0, 1, 2
+
+
+class DecodeItem(C.Structure):
+    _fields_ = [
+        ("offset", C.c_uint64), ("bytes", C.c_uint64), ("window", Window), ("data_min", C.c_double),
+        ("data_max", C.c_double), ("frame_offsets", C.POINTER(C.c_uint64)), ("nframes", C.c_int32),
+        ("channels", C.c_int32), ("bps", C.c_int32), ("blocksize", C.c_int32),
+    ]
+
+
+class DecodeJob(C.Structure):
+    _fields_ = [
+        ("data", C.c_void_p), ("len", C.c_uint64), ("data_on_device", C.c_int32), ("items", C.POINTER(DecodeItem)),
+        ("nitems", C.c_int32), ("flags", C.c_int32), ("dst", C.c_void_p), ("dst_on_device", C.c_int32),
+        ("dst_dtype", C.c_int32), ("denorm", C.c_int32), ("channels", C.c_int32), ("band_stride", C.c_int64),
+        ("row_stride", C.c_int64), ("col_stride", C.c_int64),
+    ]
 
 
 class TiffChunk(C.Structure):
@@ -93,7 +111,8 @@ EXPORTS = [
     "fra_decode", "fra_plan_encode_host", "fra_plan_capacity", "fra_host_alloc", "fra_host_free",
     "fra_host_register", "fra_host_unregister", "fra_tiff_decode", "fra_plan_set_first_frame",
     "fra_plan_flags", "fra_plan_encode_host_progress", "fra_tiff_compress_bound", "fra_tiff_compress",
-    "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged",
+    "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
+    "fra_decode_device_timing",
 ]
 
 
@@ -155,6 +174,8 @@ def load():
         if hasattr(L, "fra_plan_encode_ring"):
             L.fra_plan_encode_ring.argtypes = [vp, vp, C.c_int64, vp, u64, C.POINTER(u64), vp, vp]
             L.fra_plan_host_band_rows.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.fra_decode_device.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Decoded)]
+        L.fra_decode_device_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -319,6 +340,64 @@ class Context:
                                     omax, out.ctypes.data_as(C.c_void_p), C.byref(mn), C.byref(mx)))
         return out, mn.value, mx.value
 
+    def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
+                      denorm: int = DENORM_NONE, concat: bool = False) -> List[Decoded]:
+        """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
+
+        ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
+        length)``.  ``items``: one dict per stream with ``offset``, ``bytes``, ``window`` (row_off, col_off, height,
+        width) and optionally ``data_min`` / ``data_max`` (denormalisation) and ``frame_offsets`` (uint64 array of
+        nframes + 1 offsets relative to ``offset``; then also ``channels``, ``bps``, ``blocksize``: nothing is
+        searched).  ``dst``: a numpy array (copied to the device and back, so elements outside the windows keep
+        their values) or a device pointer (int); sample p of channel c of a stream lands at element
+        ``c * strides[0] + (row_off + p // width) * strides[1] + (col_off + p % width) * strides[2]``.
+        Returns the per-stream :class:`Decoded` infos.  Anything the device path does not cover raises
+        :class:`NativeError`; there is no fallback to the host decoder."""
+        keep = []
+        job = DecodeJob()
+        if isinstance(data, tuple):
+            job.data, job.len, job.data_on_device = C.c_void_p(int(data[0])), int(data[1]), 1
+        else:
+            buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+            if buf.dtype != np.uint8 or not buf.flags.c_contiguous:
+                raise TypeError("data must be contiguous uint8")
+            keep.append(buf)
+            job.data, job.len, job.data_on_device = C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, 0
+        arr = (DecodeItem * max(1, len(items)))()
+        for it, d in zip(arr, items):
+            it.offset, it.bytes = int(d["offset"]), int(d["bytes"])
+            it.window = Window(*[int(v) for v in d["window"]])
+            it.data_min, it.data_max = float(d.get("data_min", 0.0)), float(d.get("data_max", 0.0))
+            fo = d.get("frame_offsets")
+            if fo is not None:
+                fo = np.ascontiguousarray(fo, dtype=np.uint64)
+                keep.append(fo)
+                it.frame_offsets = fo.ctypes.data_as(C.POINTER(C.c_uint64))
+                it.nframes = fo.size - 1
+                it.channels, it.bps, it.blocksize = int(d["channels"]), int(d["bps"]), int(d["blocksize"])
+        job.items, job.nitems = arr, len(items)
+        job.flags = DECODE_CONCAT if concat else 0
+        if isinstance(dst, np.ndarray):
+            job.dst, job.dst_on_device = C.c_void_p(dst.ctypes.data), 0
+        else:
+            job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
+        job.dst_dtype = DTYPE_CODES[np.dtype(dst_dtype)]
+        job.denorm = denorm
+        job.channels = channels
+        job.band_stride, job.row_stride, job.col_stride = (int(v) for v in strides)
+        infos = (Decoded * max(1, len(items)))()
+        rc = load().fra_decode_device(self.h, C.byref(job), infos)
+        if rc == E_SPACE:
+            raise OutputTooSmall(max(int(i.nsamples) for i in infos))
+        _check(rc)
+        return list(infos)[: len(items)]
+
+    def decode_timing(self) -> List[float]:
+        """HIP-event ms of this thread's last ``decode_device``: parse, restore, scatter, first kernel to last."""
+        ms = (C.c_float * 4)()
+        _check(load().fra_decode_device_timing(ms))
+        return list(ms)
+
     def synth(self, kind: int, seed: int, bands: int, height: int, width: int, dev_out: int):
         _check(load().fra_synth_raster(self.h, kind, seed, bands, height, width, C.c_void_p(dev_out)))
 
@@ -336,6 +415,9 @@ class Plan:
         L = load()
         self.ctx = ctx
         self.nwin = len(windows)
+        self.windows = [tuple(int(v) for v in w) for w in windows]
+        self.strides = tuple(int(v) for v in strides)
+        self.blocksize = blocksize
         self._wins = (Window * max(1, self.nwin))(*[Window(*w) for w in windows])
         self._keep = keepalive
         job = Job()
@@ -717,6 +799,39 @@ def decode(data: bytes, concat: bool = False) -> Tuple[np.ndarray, Decoded]:
     finally:
         L.fra_free(ptr)
     return out.reshape(-1, info.channels), info
+
+
+def decode_on_device(data: bytes, concat: bool = False, device: int = 0) -> Tuple[np.ndarray, Decoded]:
+    """:func:`decode` on the GPU (``fra_decode_device``, ``FRA_DENORM_NONE``) -> ((N, C) int16 for streams of
+    <= 16 bps / int32 otherwise, info).  The sample count is only known after the frames are parsed: the call is made
+    with room for STREAMINFO's total (or a guess from the size) and repeated once with the count the library reports
+    when that was too small."""
+    from . import flac_meta
+
+    data = bytes(data)
+    at = 0
+    if data[:3] == b"ID3" and len(data) >= 10:
+        at = 10 + ((data[6] & 0x7F) << 21 | (data[7] & 0x7F) << 14 | (data[8] & 0x7F) << 7 | (data[9] & 0x7F))
+    try:
+        f = flac_meta.FLACFile(data[at:])
+    except Exception as e:  # (damaged metadata: the same verdict as the decoders')
+        raise NativeError(f"not a FLAC stream: {e}") from e
+    ch, bps = f.channels, f.bits_per_sample
+    dt = np.dtype(np.int16 if bps <= 16 else np.int32)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    ctx = default_context(device)
+    room = int(f.total_samples) if f.total_samples and not concat else max(4096, min(1 << 24, 2 * len(data) // ch))
+    for attempt in (0, 1):
+        out = np.zeros((room, ch), dtype=dt)
+        job_items = [{"offset": 0, "bytes": buf.size, "window": (0, 0, -room, 1)}]
+        try:
+            info = ctx.decode_device(buf, job_items, out, dt, ch, (1, ch, 0), DENORM_NONE, concat)[0]
+            return out[:info.nsamples], info
+        except OutputTooSmall as e:
+            if attempt:
+                raise
+            room = e.needed
+    raise AssertionError("unreachable")
 
 
 def tiff_compress(compression: int, chunks: np.ndarray, level: int = 6, threads: int = 0):

@@ -44,6 +44,15 @@ def _devices(spec: Optional[str]) -> Optional[List[int]]:
     return [int(x) for x in spec.split(",") if x.strip()]
 
 
+def _gpu_present() -> bool:
+    from . import _native
+
+    try:
+        return _native.device_count() > 0
+    except Exception:
+        return False
+
+
 @app.command()
 def convert(
     input_file: str = typer.Argument(..., help="Input file (TIFF or FLAC)"),
@@ -86,6 +95,15 @@ def convert(
             console.print(f"[green]Created streaming FLAC: {output_file} ({len(idx['frames'])} tiles, "
                           f"{output_file.stat().st_size / 1024 / 1024:.2f} MB)[/green]")
             return
+        if direction == "flac_to_tiff":
+            from .streaming import is_streaming_container, streaming_to_tiff
+
+            if is_streaming_container(src):
+                # first of --devices, else device 0 when a GPU is present, else the host decoder
+                dev = devs[0] if devs else (0 if _gpu_present() else None)
+                idx = streaming_to_tiff(src, output_file, device=dev)
+                console.print(f"[green]SUCCESS: Converted {len(idx['frames'])} tiles to TIFF: {output_file}[/green]")
+                return
         conv = RasterFLACConverter(devices=devs)
         if direction == "tiff_to_flac":
             res = conv.tiff_to_flac(src, output_file, compression_level, spatial, tile_size)

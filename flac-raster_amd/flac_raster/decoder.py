@@ -12,15 +12,21 @@ upper 16 bits (``x >> 16``), so 32-bps streams come back truncated (F8) -- repro
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Tuple, Union
+from typing import Optional, Tuple, Union
 
 import numpy as np
 
 from . import _native
 
 
-def decode_flac(data: bytes, concat: bool = False) -> Tuple[np.ndarray, int, int]:
-    """Exact decode -> ((N, C) int16 for 16-bps / int32 otherwise, sample_rate, bps)."""
+def decode_flac(data: bytes, concat: bool = False, device: Optional[int] = None) -> Tuple[np.ndarray, int, int]:
+    """Exact decode -> ((N, C) int16 for 16-bps / int32 otherwise, sample_rate, bps).
+
+    ``device=None``: the host decoder (``fra_decode``).  An integer: that GPU (``fra_decode_device``); a stream the
+    device path does not cover raises ``NativeError`` -- it is not decoded on the host instead."""
+    if device is not None:
+        samples, info = _native.decode_on_device(bytes(data), concat=concat, device=int(device))
+        return samples, info.sample_rate, info.bps
     samples, info = _native.decode(bytes(data), concat=concat)
     if info.bps <= 16:
         samples = samples.astype(np.int16)

@@ -236,3 +236,80 @@ def read_tile_bytes(path: Path, frame: Dict, header_size: int) -> bytes:
     with open(path, "rb") as f:
         f.seek(header_size + frame["byte_offset"])
         return f.read(frame["byte_size"])
+
+
+# ------------------------------------------------------------------------------------------ container -> raster
+def _container_bytes(src) -> bytes:
+    return bytes(src) if isinstance(src, (bytes, bytearray, memoryview)) else Path(src).read_bytes()
+
+
+def is_streaming_container(path: Path) -> bool:
+    """A ``.flac`` file that starts with neither ``fLaC`` nor an ID3v2 tag: the ``--streaming`` container."""
+    with open(path, "rb") as f:
+        head = f.read(4)
+    return head[:4] != b"fLaC" and head[:3] != b"ID3"
+
+
+def _tile_items(data: bytes):
+    """The index and, per tile, the ``decode_device`` item: byte range, window and the tile's own min / max tags."""
+    index, hs = read_index_bytes(data)
+    items = []
+    for fr in index["frames"]:
+        a = hs + fr["byte_offset"]
+        b = a + fr["byte_size"]
+        if b > len(data):
+            raise ValueError(f"tile {fr['frame_id']} runs past the end of the container")
+        tags = flac_meta.FLACFile(data[a:b]).tags
+        w = fr["window"]
+        items.append({"offset": a, "bytes": b - a, "window": (w["row_off"], w["col_off"], w["height"], w["width"]),
+                      "data_min": float(tags["GEOSPATIAL_DATA_MIN"][0]), "data_max": float(tags["GEOSPATIAL_DATA_MAX"][0])})
+    return index, items
+
+
+def streaming_to_raster(src, device: Optional[int] = None, semantics: str = "pcm16"):
+    """Streaming container (path or bytes) -> ``(raster (B, H, W) in the index's dtype, index)``.
+
+    Every tile is denormalised with its own ``GEOSPATIAL_DATA_MIN`` / ``_MAX`` tags into its window of the index.
+    ``semantics="pcm16"`` gives what ``flac_to_tiff`` / ``extract`` give per tile (PCM_16 floats),
+    ``"int"`` denormalises the exact integer samples.  ``device=None`` is the host implementation (``fra_decode`` per
+    tile + ``denormalize_from_audio``, no GPU needed); an integer runs one ``fra_decode_device`` call over all tiles
+    on that GPU."""
+    from . import _native
+    from .decoder import decode_flac, pcm16_float
+    from .normalization import NormalizationParams, denormalize_from_audio
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    data = _container_bytes(src)
+    index, items = _tile_items(data)
+    dt = np.dtype(index["dtype"])
+    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
+    out = np.zeros((B, H, W), dtype=dt)
+    if device is not None:
+        ctx = _native.default_context(int(device))
+        ctx.decode_device(np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (H * W, W, 1),
+                          _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, index
+    for it in items:
+        r, c, h, w = it["window"]
+        samples, _, bps = decode_flac(data[it["offset"]:it["offset"] + it["bytes"]])
+        if samples.shape != (h * w, B):
+            raise ValueError(f"tile at ({r}, {c}) decodes to {samples.shape}, expected {(h * w, B)}")
+        params = NormalizationParams(it["data_min"], it["data_max"], str(dt), 16 if bps <= 16 else 24,
+                                     32767 if bps <= 16 else 8388607)
+        audio = pcm16_float(samples) if semantics == "pcm16" else samples
+        out[:, r:r + h, c:c + w] = denormalize_from_audio(audio, params).reshape(h, w, B).transpose(2, 0, 1)
+    return out, index
+
+
+def streaming_to_tiff(path: Path, tiff_path: Path, device: Optional[int] = None) -> Dict:
+    """Streaming container -> GeoTIFF with the index's transform and CRS (``flac_to_tiff`` semantics per tile);
+    returns the index."""
+    from .tiff import write_geotiff
+
+    raster, index = streaming_to_raster(Path(path), device=device)
+    t = index.get("transform")
+    crs = index.get("crs")
+    write_geotiff(Path(tiff_path), raster, transform=tuple(t[:6]) if t else None,
+                  crs=crs if crs and crs != "None" else None)
+    return index

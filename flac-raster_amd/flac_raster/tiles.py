@@ -261,3 +261,28 @@ def encode_tiles(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]],
     if errors:
         raise errors[0]
     return [ts for grp in out for ts in grp]
+
+
+def verify_on_device(plan: "_native.Plan", raster_ptr: int,
+                     strides: Optional[Tuple[int, int, int]] = None) -> bool:
+    """Decode an executed plan's device output on its GPU into ``raster_ptr`` (a device buffer of int16 for 16-bps
+    plans / int32 otherwise, laid out like the plan's raster, or with other element ``strides``) without copying the
+    frames to the host: the frames are addressed through ``fra_plan_frame_offsets``, nothing is searched.  Returns True
+    when every frame parsed with a matching CRC-16 (a corrupt frame raises ``NativeError``).  The library offers the
+    decode; comparing the samples with the expectation stays with the caller."""
+    infos, total = plan.result()
+    nfr = sum(i.nframes for i in infos)
+    off = plan.frame_offsets(nfr)
+    ptr, _ = plan.device_output()
+    items, f0 = [], 0
+    for inf, w in zip(infos, plan.windows):
+        fo = off[f0:f0 + inf.nframes + 1] - np.uint64(inf.offset)
+        items.append({"offset": inf.offset, "bytes": inf.frame_bytes, "window": w, "frame_offsets": fo,
+                      "channels": inf.channels, "bps": inf.bps, "blocksize": plan.blocksize})
+        f0 += inf.nframes
+    if not items:
+        return True
+    dt = np.int16 if all(i.bps <= 16 for i in infos) else np.int32
+    out = plan.ctx.decode_device((ptr, total), items, int(raster_ptr), dt, infos[0].channels,
+                                 strides or plan.strides)
+    return all(o.nframes == i.nframes for o, i in zip(out, infos))

@@ -223,6 +223,58 @@ typedef struct {
 } fra_decoded;
 FRA_API int fra_decode(const uint8_t *data, uint64_t len, int32_t flags, fra_decoded *info, int32_t **samples);
 
+/* Batched FLAC decode on the GPU: tile streams -> raster (the inverse of the fused normalise + encode path).
+ * Every item is one FLAC stream inside `data` whose samples fill one window of the destination: sample p of
+ * channel c lands at element c*band_stride + (row_off + p / width)*row_stride + (col_off + p % width)*col_stride
+ * of dst.  Without frame_offsets the host lists the sync candidates (header CRC-8) of each stream and the GPU
+ * decodes and CRC-16-checks every candidate (k_dec_parse); the frames are chained exactly as in fra_decode.
+ * With frame_offsets (a plan's own output: fra_plan_frame_offsets + fra_plan_device_output) nothing is searched
+ * and the input may stay on the device.  The frames are then restored (k_dec_restore) and scattered
+ * (k_dec_scatter: wasted bits, stereo undo, optional denormalisation, placement).
+ *   FRA_DENORM_NONE   dst_dtype FRA_I16 (streams of <= 16 bps only) or FRA_I32: the integers fra_decode returns.
+ *   FRA_DENORM_INT    denormalize_from_audio on the exact integers (normalization.py:205-253): y = s / scale
+ *                     (32767 for <= 16 bps, else 8388607), x = (y + 1.0) / 2.0 * (data_max - data_min) + data_min,
+ *                     integer dst: round half even, float dst: cast; every step a separate IEEE f64 operation.
+ *   FRA_DENORM_PCM16  flac_to_tiff's result (F8): y = s / 32768.0 (<= 16 bps) or (s >> 16) / 32768.0, same map.
+ * Float -> integer conversions outside the destination type's range saturate (NaN -> 0); numpy leaves them
+ * undefined.  What the device path does not cover -- a side channel of a 32-bps stream (33-bit samples), a
+ * window of more than 2^31 - 1 samples -- fails with FRA_E_INVALID and a message saying it is not supported on
+ * the device; it is never decoded differently from fra_decode.  A corrupt or truncated frame fails with
+ * FRA_E_INVALID ("lost sync / corrupt frame at byte N", N relative to the item).  Scratch is allocated per call
+ * and freed on every path; on failure dst may be partly written.  dst on the host is copied back before return
+ * and must then be one allocation spanning every addressed element from element 0. */
+#define FRA_DENORM_NONE 0
+#define FRA_DENORM_INT 1
+#define FRA_DENORM_PCM16 2
+typedef struct {
+  uint64_t offset, bytes;        /* one FLAC stream (fLaC ... last frame; ID3v2 prefix allowed) inside data */
+  fra_window window;             /* destination of its samples; height*width == samples per channel.  A caller
+                                    that does not know the count passes width 1 and height = -capacity: up to
+                                    capacity samples are written one per row and infos[i].nsamples reports the
+                                    count; more than capacity fails with FRA_E_SPACE before anything is written,
+                                    with the needed count in infos[i].nsamples */
+  double data_min, data_max;     /* for denormalisation; ignored when denorm == FRA_DENORM_NONE */
+  const uint64_t *frame_offsets; /* optional: nframes+1 offsets relative to `offset`, frames only (no header):
+                                    skips candidate search and chain; sample_rate/bps/channels/blocksize
+                                    then come from the fields below */
+  int32_t nframes, channels, bps, blocksize;
+} fra_decode_item;
+
+typedef struct {
+  const uint8_t *data; uint64_t len; int32_t data_on_device;
+  const fra_decode_item *items; int32_t nitems;
+  int32_t flags;                 /* FRA_DECODE_CONCAT */
+  void *dst; int32_t dst_on_device;
+  int32_t dst_dtype;             /* fra_dtype */
+  int32_t denorm;                /* FRA_DENORM_NONE | FRA_DENORM_INT | FRA_DENORM_PCM16 */
+  int32_t channels; int64_t band_stride, row_stride, col_stride;
+} fra_decode_job;
+
+FRA_API int fra_decode_device(fra_ctx *ctx, const fra_decode_job *job, fra_decoded *infos /* nitems */);
+/* HIP-event times of the calling thread's last successful fra_decode_device: 0 k_dec_parse, 1 k_dec_restore,
+ * 2 k_dec_scatter, 3 first kernel to last (includes the frame-table copy and the host chain) */
+FRA_API int fra_decode_device_timing(float *ms4);
+
 /* Synthetic rasters, generated on the device with integer-exact hashes so a
  * host numpy mirror reproduces any window bit for bit.  kind: 3 = C3 DEM int16, 4 = C4 S2-like
  * uint16 (4 bands), 5 = C5 reflectance float32.  dev_out: device buffer (bands, height, width). */

@@ -1,0 +1,188 @@
+#!/usr/bin/env python3
+"""Decode benchmark: the device decoder (``fra_decode_device``) against the host decoder (``fra_decode``).
+
+A synthetic C4-like scene (``fra_synth_raster`` kind 4: 10980 x 10980 x 4 uint16, tile 1024, level 5) is encoded
+once by a plan on the GPU; ``--tiles N`` keeps the first N tiles (default: all 121).  Per step, over ``--warmup`` +
+``--steps`` steps, one JSON line reports:
+
+  host_decode_ms    fra_decode on every tile's stream, one tile after the other; each call uses at most 16 threads
+                    (the library caps its pool at 16, it is not sized by the machine's core count)
+  device_ms         HIP events, first decode kernel to last: the plan's frames resident on the device, frame offsets
+                    supplied (no candidate search), samples into a device raster
+  device_search_ms  wall time of the same decode without offsets: complete streams in page-locked host memory, so it
+                    includes their H2D copy, the candidate search, the frame-table copy and the chain
+  e2e_ms            wall time, host container bytes -> host raster (``streaming_to_raster(device=0)``)
+  samples_per_s     of each of the above, and each kernel's share of device_ms (``kernels``)
+
+    python tools/bench_decode.py --tiles 121 --steps 3 --warmup 1
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "flac-raster_amd"))
+
+from flac_raster import _native as N  # noqa: E402
+from flac_raster.geo import Affine  # noqa: E402
+from flac_raster.streaming import assemble_streaming, streaming_to_raster  # noqa: E402
+from flac_raster.tiles import calculate_tiles, streams_from  # noqa: E402
+
+SEED = 20240607
+B, H, W, TILE, LEVEL = 4, 10980, 10980, 1024, 5
+
+
+def host_decode_all(streams) -> int:
+    """fra_decode on every stream (no copy of the samples into numpy); returns the samples decoded."""
+    L = N.load()
+    total = 0
+    for s in streams:
+        buf = np.frombuffer(s, dtype=np.uint8)
+        info = N.Decoded()
+        ptr = C.POINTER(C.c_int32)()
+        N._check(L.fra_decode(buf.ctypes.data_as(C.c_void_p), buf.size, 0, C.byref(info), C.byref(ptr)))
+        total += info.nsamples * info.channels
+        L.fra_free(ptr)
+    return total
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--tiles", type=int, default=0, help="first N tiles of the scene (0: all 121)")
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--host-steps", type=int, default=1, help="timed passes of the host decoder (it is slow)")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the container leg")
+    args = ap.parse_args()
+
+    ctx = N.Context(0)
+    dt = np.dtype(np.uint16)
+    dev_raster = ctx.alloc(B * H * W * dt.itemsize)
+    ctx.synth(4, SEED, B, H, W, dev_raster)
+    wins = calculate_tiles(H, W, TILE)
+    if args.tiles:
+        wins = wins[: args.tiles]
+    plan = N.Plan(ctx, dev_raster, True, dt, B, (H * W, W, 1), wins, LEVEL, 4096, 16)
+    plan.execute()
+    plan.sync()
+    infos, total = plan.result()
+    nfr = sum(i.nframes for i in infos)
+    off = plan.frame_offsets(nfr)
+    frames_ptr, _ = plan.device_output()
+    samples = sum(w[2] * w[3] for w in wins) * B
+    dev_out = ctx.alloc(B * H * W * 2)  # int16 samples, laid out like the raster
+
+    # ---- device, offsets supplied, everything resident
+    items, f0 = [], 0
+    for inf, w in zip(infos, wins):
+        items.append({"offset": inf.offset, "bytes": inf.frame_bytes, "window": w,
+                      "frame_offsets": off[f0:f0 + inf.nframes + 1] - np.uint64(inf.offset),
+                      "channels": inf.channels, "bps": inf.bps, "blocksize": 4096})
+        f0 += inf.nframes
+    dev_ms, dev_wall, kern = [], [], []
+    for k in range(args.warmup + args.steps):
+        t0 = time.perf_counter()
+        ctx.decode_device((frames_ptr, total), items, dev_out, np.int16, B, (H * W, W, 1))
+        t1 = time.perf_counter()
+        if k >= args.warmup:
+            ms = ctx.decode_timing()
+            dev_ms.append(ms[3])
+            kern.append(ms[:3])
+            dev_wall.append((t1 - t0) * 1e3)
+
+    _, frames = plan.download()
+    streams = streams_from(infos, frames)
+
+    def verify() -> int:
+        """The device raster against the host decoder on the first, middle and last tile; then cleared."""
+        got = np.empty((B, H, W), np.int16)
+        ctx.d2h(got, dev_out)
+        picks = sorted({0, len(wins) // 2, len(wins) - 1})
+        for i in picks:
+            r, c, h, w = wins[i]
+            x, _ = N.decode(streams[i].data)
+            if not np.array_equal(got[:, r:r + h, c:c + w], x.reshape(h, w, B).transpose(2, 0, 1)):
+                raise SystemExit(f"device decode of tile {i} differs from the host decoder")
+        got[:] = 0
+        ctx.h2d(dev_out, got)
+        return len(picks)
+
+    verified = verify()
+
+    # ---- device, search path: complete streams in page-locked host memory
+    blob_len = sum(len(ts) for ts in streams)
+    blob = N.pinned_empty(blob_len, np.uint8)
+    sitems, p = [], 0
+    for ts, w in zip(streams, wins):
+        d = ts.data
+        blob[p:p + len(d)] = np.frombuffer(d, np.uint8)
+        sitems.append({"offset": p, "bytes": len(d), "window": w})
+        p += len(d)
+    search_ms, search_ev = [], []
+    for k in range(args.warmup + args.steps):
+        t0 = time.perf_counter()
+        ctx.decode_device(blob, sitems, dev_out, np.int16, B, (H * W, W, 1))
+        t1 = time.perf_counter()
+        if k >= args.warmup:
+            search_ms.append((t1 - t0) * 1e3)
+            search_ev.append(ctx.decode_timing()[3])
+
+    verified += verify()
+
+    # ---- host decoder, tile by tile
+    tile_streams = [ts.data for ts in streams]
+    host_decode_all(tile_streams[:1])
+    host_ms = []
+    for _ in range(max(1, args.host_steps)):
+        t0 = time.perf_counter()
+        n = host_decode_all(tile_streams)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+        assert n == samples
+
+    # ---- host container bytes -> host raster
+    e2e_ms = []
+    if not args.no_e2e:
+        data = assemble_streaming(wins, streams, (B, H, W), dt, Affine(10.0, 0.0, 0.0, 0.0, -10.0, 0.0), "EPSG:32633",
+                                  TILE)
+        for k in range(min(1, args.warmup) + min(2, args.steps)):
+            t0 = time.perf_counter()
+            streaming_to_raster(data, device=0)
+            if k >= min(1, args.warmup):
+                e2e_ms.append((time.perf_counter() - t0) * 1e3)
+
+    med = statistics.median
+    d_ms, s_ms, h_ms = med(dev_ms), med(search_ms), med(host_ms)
+    kmed = [med([k[i] for k in kern]) for i in range(3)]
+    res = {
+        "workload": f"decode C4-like {W}x{H}x{B} uint16, tile {TILE}, level {LEVEL}, {len(wins)} tiles",
+        "tiles": len(wins), "frames": nfr, "samples": samples, "frame_bytes": total,
+        "steps": args.steps, "warmup": args.warmup, "tiles_verified_against_host_decoder": verified,
+        "host_decode_ms": round(h_ms, 3), "device_ms": round(d_ms, 3), "device_wall_ms": round(med(dev_wall), 3),
+        "device_search_ms": round(s_ms, 3), "device_search_event_ms": round(med(search_ev), 3),
+        "e2e_ms": round(med(e2e_ms), 3) if e2e_ms else None,
+        "samples_per_s": {"host": round(samples / h_ms * 1e3), "device": round(samples / d_ms * 1e3),
+                          "device_search": round(samples / s_ms * 1e3),
+                          "e2e": round(samples / med(e2e_ms) * 1e3) if e2e_ms else None},
+        "kernels": {"k_dec_parse_ms": round(kmed[0], 3), "k_dec_restore_ms": round(kmed[1], 3),
+                    "k_dec_scatter_ms": round(kmed[2], 3),
+                    "share": [round(v / d_ms, 3) for v in kmed]},
+        "host_over_device": round(h_ms / d_ms, 2), "host_over_device_search": round(h_ms / s_ms, 2),
+        "all_ms": {"host": [round(v, 2) for v in host_ms], "device": [round(v, 3) for v in dev_ms],
+                   "device_search": [round(v, 2) for v in search_ms], "e2e": [round(v, 2) for v in e2e_ms]},
+    }
+    print(json.dumps(res), flush=True)
+    plan.close()
+    ctx.free(dev_out)
+    ctx.free(dev_raster)
+
+
+if __name__ == "__main__":
+    main()
