@@ -33,8 +33,8 @@
 
 #include "../../include/flac_raster_amd.h"
 #include "fra_decode_host.h"
+#include "fra_host.h"
 
-extern "C" int fra_internal_set_error(int code, const char* fmt, ...);
 extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
 
 namespace {
@@ -431,15 +431,6 @@ __global__ __launch_bounds__(256) void k_dec_scatter(DecArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ host side
-int elem_size(int dt) {
-  switch (dt) {
-    case FRA_U8: case FRA_I8: return 1;
-    case FRA_U16: case FRA_I16: return 2;
-    case FRA_F64: return 8;
-    default: return 4;
-  }
-}
-
 struct ItemPlan {
   bool search = false;
   StreamParams sp;
@@ -448,33 +439,7 @@ struct ItemPlan {
   int32_t first_group = 0, ngroups = 0;
 };
 
-// device buffers and events of one call, released on every path
-struct Scratch {
-  std::vector<void*> dev;
-  std::vector<void*> pinned;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~Scratch() {
-    for (void* p : dev) (void)hipFree(p);
-    for (void* p : pinned) (void)hipHostFree(p);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  hipError_t alloc(void** p, size_t bytes) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e == hipSuccess) dev.push_back(*p);
-    return e;
-  }
-};
-
 thread_local float g_last_ms[4] = {0, 0, 0, 0};
-
-#define DCHK(x)                                                                                              \
-  do {                                                                                                       \
-    hipError_t _e = (x);                                                                                     \
-    if (_e != hipSuccess)                                                                                    \
-      return fra_internal_set_error(_e == hipErrorOutOfMemory ? FRA_E_NOMEM : FRA_E_HIP, "%s: %s (%s:%d)", #x, \
-                                    hipGetErrorString(_e), __FILE__, __LINE__);                              \
-  } while (0)
 
 const char kUnsupported[] = "33-bit samples (side channel of a 32-bps stream) are not supported on the device";
 
@@ -538,7 +503,8 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   hipStream_t s = nullptr;
   fra_internal_ctx_stream(ctx, &device, &s);
   (void)hipSetDevice(device);
-  Scratch sc;
+  HipArena sc;  // device buffers and events of this call, released on every path
+  hipEvent_t ev[5] = {};
 
   // ---- the input on both sides where needed
   const uint8_t* hdata = job->data_on_device ? nullptr : job->data;
@@ -546,14 +512,14 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   if (any_search && job->data_on_device) {  // the candidate search and the chain read the bytes on the host
     hcopy.reset(new (std::nothrow) uint8_t[(size_t)job->len + 1]);
     if (!hcopy) return fra_internal_set_error(FRA_E_NOMEM, "out of host memory");
-    if (job->len) DCHK(hipMemcpy(hcopy.get(), job->data, (size_t)job->len, hipMemcpyDeviceToHost));
+    if (job->len) HIPCHK(hipMemcpy(hcopy.get(), job->data, (size_t)job->len, hipMemcpyDeviceToHost));
     hdata = hcopy.get();
   }
   const uint8_t* ddata = job->data;
   if (!job->data_on_device) {
     void* p = nullptr;
-    DCHK(sc.alloc(&p, (size_t)job->len));
-    if (job->len) DCHK(hipMemcpyAsync(p, job->data, (size_t)job->len, hipMemcpyHostToDevice, s));
+    HIPCHK(sc.alloc(&p, (size_t)job->len));
+    if (job->len) HIPCHK(hipMemcpyAsync(p, job->data, (size_t)job->len, hipMemcpyHostToDevice, s));
     ddata = (const uint8_t*)p;
   }
 
@@ -646,15 +612,15 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   a.dst_dtype = job->dst_dtype;
   a.denorm = job->denorm;
   void *d_items, *d_groups, *d_starts, *d_fout, *d_sdesc, *d_coefs, *d_scratch, *d_samp0, *d_fail, *d_dst = nullptr;
-  DCHK(sc.alloc(&d_items, sizeof(DecItem) * (size_t)ni));
-  DCHK(sc.alloc(&d_groups, sizeof(DecGroup) * ng));
-  DCHK(sc.alloc(&d_starts, sizeof(uint64_t) * nslots));
-  DCHK(sc.alloc(&d_fout, sizeof(FrameOut) * nslots));
-  DCHK(sc.alloc(&d_sdesc, sizeof(uint32_t) * nslots * 8));
-  DCHK(sc.alloc(&d_coefs, sizeof(int32_t) * nslots * 8 * 32));
-  DCHK(sc.alloc(&d_scratch, sizeof(int32_t) * (size_t)scratch_elems));
-  DCHK(sc.alloc(&d_samp0, sizeof(int64_t) * nslots));
-  DCHK(sc.alloc(&d_fail, sizeof(uint32_t) * nslots));
+  HIPCHK(sc.alloc(&d_items, sizeof(DecItem) * (size_t)ni));
+  HIPCHK(sc.alloc(&d_groups, sizeof(DecGroup) * ng));
+  HIPCHK(sc.alloc(&d_starts, sizeof(uint64_t) * nslots));
+  HIPCHK(sc.alloc(&d_fout, sizeof(FrameOut) * nslots));
+  HIPCHK(sc.alloc(&d_sdesc, sizeof(uint32_t) * nslots * 8));
+  HIPCHK(sc.alloc(&d_coefs, sizeof(int32_t) * nslots * 8 * 32));
+  HIPCHK(sc.alloc(&d_scratch, sizeof(int32_t) * (size_t)scratch_elems));
+  HIPCHK(sc.alloc(&d_samp0, sizeof(int64_t) * nslots));
+  HIPCHK(sc.alloc(&d_fail, sizeof(uint32_t) * nslots));
   const size_t dst_bytes = (size_t)extent * (size_t)elem_size(job->dst_dtype);
   // a host destination with contiguous rows comes back window by window; any other layout is staged whole, so
   // that elements between the windows keep the caller's values either way
@@ -662,8 +628,8 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   if (job->dst_on_device) {
     d_dst = job->dst;
   } else {
-    DCHK(sc.alloc(&d_dst, dst_bytes));
-    if (dst_bytes && !by_window) DCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(sc.alloc(&d_dst, dst_bytes));
+    if (dst_bytes && !by_window) HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
   }
   a.items = (const DecItem*)d_items;
   a.groups = (const DecGroup*)d_groups;
@@ -675,24 +641,24 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   a.samp0 = (const int64_t*)d_samp0;
   a.fail = (uint32_t*)d_fail;
   a.dst = d_dst;
-  for (auto& e : sc.ev) DCHK(hipEventCreate(&e));
-  DCHK(hipMemcpyAsync(d_items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
+  for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
+  HIPCHK(hipMemcpyAsync(d_items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
   if (ng) {
-    DCHK(hipMemcpyAsync(d_groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
-    DCHK(hipMemcpyAsync(d_starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
-    DCHK(hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * nslots, s));
+    HIPCHK(hipMemcpyAsync(d_groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * nslots, s));
   }
 
   // ---- parse every candidate
   std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
-  DCHK(hipEventRecord(sc.ev[0], s));
+  HIPCHK(hipEventRecord(ev[0], s));
   if (ng) {
     hipLaunchKernelGGL(k_dec_parse, dim3((unsigned)ng), dim3(kLanes), 0, s, a);
-    DCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  DCHK(hipEventRecord(sc.ev[1], s));
-  if (ng) DCHK(hipMemcpyAsync(h_fout.data(), d_fout, sizeof(FrameOut) * nslots, hipMemcpyDeviceToHost, s));
-  DCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventRecord(ev[1], s));
+  if (ng) HIPCHK(hipMemcpyAsync(h_fout.data(), d_fout, sizeof(FrameOut) * nslots, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
 
   // ---- chain (item-relative byte positions, the host decoder's wording)
   std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
@@ -754,19 +720,19 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   // ---- restore and scatter the chained frames
   std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
   if (ng) {
-    DCHK(hipMemcpyAsync(d_samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
-    DCHK(hipEventRecord(sc.ev[2], s));
+    HIPCHK(hipMemcpyAsync(d_samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev[2], s));
     hipLaunchKernelGGL(k_dec_restore, dim3((unsigned)ng, (unsigned)job->channels), dim3(kLanes), 0, s, a);
-    DCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  else DCHK(hipEventRecord(sc.ev[2], s));
-  DCHK(hipEventRecord(sc.ev[3], s));
+  else HIPCHK(hipEventRecord(ev[2], s));
+  HIPCHK(hipEventRecord(ev[3], s));
   if (ng) {
     hipLaunchKernelGGL(k_dec_scatter, dim3((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes)), dim3(256), 0, s, a);
-    DCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  DCHK(hipEventRecord(sc.ev[4], s));
-  if (ng) DCHK(hipMemcpyAsync(h_fail.data(), d_fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(ev[4], s));
+  if (ng) HIPCHK(hipMemcpyAsync(h_fail.data(), d_fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
   if (by_window) {
     const size_t es = (size_t)elem_size(job->dst_dtype);
     for (int i = 0; i < ni; i++) {
@@ -777,27 +743,27 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
         const size_t off = ((size_t)c * (size_t)job->band_stride + (size_t)w.row_off * (size_t)job->row_stride +
                             (size_t)w.col_off) * es;
         if (job->row_stride == 0 || rows == 1)
-          DCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)d_dst + off, (size_t)w.width * es,
+          HIPCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)d_dst + off, (size_t)w.width * es,
                               hipMemcpyDeviceToHost, s));
         else
-          DCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)d_dst + off,
+          HIPCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)d_dst + off,
                                 (size_t)job->row_stride * es, (size_t)w.width * es, (size_t)rows,
                                 hipMemcpyDeviceToHost, s));
       }
     }
   } else if (!job->dst_on_device && dst_bytes) {
-    DCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
   }
-  DCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   for (size_t k = 0; k < nslots; k++)
     if (h_fail[k])
       return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
                                                    "(frame at byte %llu)", (unsigned long long)h_starts[k]);
   float ms[4] = {0, 0, 0, 0};
-  (void)hipEventElapsedTime(&ms[0], sc.ev[0], sc.ev[1]);
-  (void)hipEventElapsedTime(&ms[1], sc.ev[2], sc.ev[3]);
-  (void)hipEventElapsedTime(&ms[2], sc.ev[3], sc.ev[4]);
-  (void)hipEventElapsedTime(&ms[3], sc.ev[0], sc.ev[4]);
+  (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
+  (void)hipEventElapsedTime(&ms[1], ev[2], ev[3]);
+  (void)hipEventElapsedTime(&ms[2], ev[3], ev[4]);
+  (void)hipEventElapsedTime(&ms[3], ev[0], ev[4]);
   memcpy(g_last_ms, ms, sizeof(ms));
   return FRA_OK;
 }

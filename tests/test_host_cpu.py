@@ -51,6 +51,19 @@ def test_abi_exports_every_declared_symbol():
     assert L.fra_abi_version() == 3
 
 
+def test_plan_layout_check_program(tmp_path):
+    """The plan layout (fra_layout.h: frames, capacity, window tables, groups, host bands, partial list) as a
+    stand-alone g++ program under AddressSanitizer + UBSan (make plancheck): every invariant holds, no GPU."""
+    import shutil
+    import subprocess
+    if not shutil.which("g++") or not shutil.which("make"):
+        pytest.skip("no g++ / make")
+    csrc = ROOT / "flac-raster_amd" / "csrc"
+    subprocess.run(["make", "-C", str(csrc), "plancheck"], check=True, capture_output=True)
+    run = subprocess.run([str(csrc / "build" / "plan_layout_check")], capture_output=True, text=True)
+    assert run.returncode == 0 and "plan layout ok" in run.stdout, run.stdout[-4000:] + run.stderr[-4000:]
+
+
 def test_abi_errors_without_device():
     if N.device_count() > 0:
         pytest.skip("a GPU is visible; this checks the no-device error path")
