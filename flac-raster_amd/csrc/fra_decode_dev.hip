@@ -20,7 +20,13 @@
 //   k_dec_scatter per (group, 64 samples): wasted-bits shift, stereo undo, optional denormalisation, an LDS
 //               transpose so that scratch reads (lane-major) and raster writes (sample-major) are both contiguous
 //
-// Not covered (refused, never decoded differently): 33-bit samples (side channel of a 32-bps stream).
+// fra_decode_device_window runs the same kernels over the frames that hold samples of a region of interest: the
+// host selects them by frame number (fixed-blocksize streams: frame f starts at sample f * blocksize), k_dec_parse
+// and k_dec_restore see only those, and k_dec_scatter clips to the region at the granularity of a frame's
+// 64-sample run.  Damage in a frame that was not selected is not detected: that frame is never read.
+//
+// Not covered (refused, never decoded differently): 33-bit samples (side channel of a 32-bps stream); by the
+// windowed read also FRA_DECODE_CONCAT, capacity windows and variable-blocksize streams.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,8 +60,14 @@ enum : uint32_t { SF_CONSTANT = 0, SF_VERBATIM = 1, SF_FIXED = 2, SF_LPC = 3 };
 struct DecItem {
   uint64_t end;  // absolute byte end of the item: no read goes past it
   int32_t channels, bps, sample_rate, bs_stride;
-  int32_t row_off, col_off, width, height;
+  int32_t row_off, col_off, width, height;  // the tile; row_off / col_off = destination position of its first pixel
+                                             // (windowed read: below zero when the region starts inside the tile)
   double dmin, span;
+};
+// per item of a windowed read (the kClip instances of k_dec_restore / k_dec_scatter)
+struct DecClip {
+  int32_t r0, r1, c0, c1;  // tile-relative rows / columns that are written
+  int64_t p_lo, p_hi;      // tile samples that are needed
 };
 struct DecGroup {
   uint64_t base;  // first scratch element of the group
@@ -76,6 +88,7 @@ struct DecArgs {
   void* dst;
   int64_t band_stride, row_stride, col_stride;
   int32_t dst_dtype, denorm;
+  const DecClip* clips;    // [nitems], windowed read only
 };
 
 // ------------------------------------------------------------------------------------------ device bit reader
@@ -266,6 +279,8 @@ __global__ __launch_bounds__(kLanes) void k_dec_parse(DecArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ restore
+// kClip: the windowed read, which stops at a frame's last needed sample
+template <bool kClip>
 __global__ __launch_bounds__(kLanes) void k_dec_restore(DecArgs a) {
   __shared__ int32_t s_coef[32 * kLanes];  // [j][lane]: a lane's column, conflict-free
   __shared__ int32_t s_hist[32 * kLanes];  // history ring, sample i at row i & 31
@@ -278,7 +293,7 @@ __global__ __launch_bounds__(kLanes) void k_dec_restore(DecArgs a) {
   const uint32_t kind = d & 0xFF;
   const int order = (int)((d >> 8) & 0xFF), wasted = (int)((d >> 16) & 0xFF), shift = (int)(d >> 24);
   if (kind < SF_FIXED) return;
-  const int n = fo.n;
+  const int n = kClip ? (int)std::min<int64_t>(fo.n, a.clips[grp.item].p_hi - a.samp0[slot]) : fo.n;
   const int eb = (int)fo.bps + (side_channel(fo.assign, c) ? 1 : 0) - wasted;  // <= 32 (parse refused 33)
   // samples within eb bits keep every predictor sum below 2^53: no int64 overflow (as the host decoder)
   const int64_t lo = -((int64_t)1 << (eb - 1)), hi = ((int64_t)1 << (eb - 1)) - 1;
@@ -367,6 +382,8 @@ __device__ inline void put_sample(const DecArgs& a, const DecItem& it, int64_t e
   }
 }
 
+// kClip: the windowed read, which writes only the item's clip rectangle and skips every 64-sample run outside it
+template <bool kClip>
 __global__ __launch_bounds__(256) void k_dec_scatter(DecArgs a) {
   __shared__ int32_t tile[kLanes][kLanes + 1];
   const int g = blockIdx.x, i0 = blockIdx.y * kLanes, t = threadIdx.x;
@@ -383,9 +400,29 @@ __global__ __launch_bounds__(256) void k_dec_scatter(DecArgs a) {
   const int32_t* sc = a.scratch + grp.base + lane;
   const uint64_t cstride = (uint64_t)it.bs_stride * kLanes;
   const uint32_t nsamp = (uint32_t)it.width * (uint32_t)it.height;
+  // does this frame's 64-sample run hold a sample inside the clip?  Runs that do not are neither loaded (phase 1)
+  // nor stored (phase 2); a block without any such run returns before touching scratch
+  __shared__ uint8_t s_need[kLanes];
+  bool need = live;
+  DecClip cl{};
+  if constexpr (kClip) {
+    cl = a.clips[grp.item];
+    need = false;
+    if (live && i0 < fo.n && it.width > 0) {
+      const int64_t s0 = a.samp0[slot];
+      const int64_t pa = std::max<int64_t>(s0 + i0, cl.p_lo), pb = std::min<int64_t>(s0 + std::min(fo.n, i0 + kLanes), cl.p_hi);
+      if (pa < pb) {
+        const int32_t col = (int32_t)(pa % it.width);
+        if (col >= cl.c0 && col < cl.c1) need = true;
+        else need = pa + (col < cl.c0 ? cl.c0 - col : it.width - col + cl.c0) < pb;
+      }
+    }
+    if (q == 0) s_need[lane] = need;
+    if (!__syncthreads_or(need)) return;
+  }
   for (int c = 0; c < it.channels; c++) {
     __syncthreads();
-    if (live) {
+    if (need) {
       const uint32_t dc = c == 0 ? d0 : (c == 1 ? d1 : a.sdesc[(uint64_t)slot * 8 + c]);
       for (int k = 0; k < 16; k++) {
         const int i = i0 + q + 4 * k;
@@ -417,12 +454,14 @@ __global__ __launch_bounds__(256) void k_dec_scatter(DecArgs a) {
       if (f >= grp.count) break;
       const int fs = g * kLanes + f;
       const int64_t s0 = a.samp0[fs];
-      if (s0 < 0) continue;
+      if (s0 < 0 || (kClip && !s_need[f])) continue;
       const int i = i0 + lane;
       if (i >= a.fout[fs].n) continue;
       const uint64_t p = (uint64_t)s0 + (uint64_t)i;
       if (p >= nsamp) continue;  // (the host checked the chain's sample count against the window)
       const uint32_t row = (uint32_t)p / (uint32_t)it.width, col = (uint32_t)p % (uint32_t)it.width;
+      if (kClip && ((int32_t)row < cl.r0 || (int32_t)row >= cl.r1 || (int32_t)col < cl.c0 || (int32_t)col >= cl.c1))
+        continue;
       const int64_t e = (int64_t)c * a.band_stride + ((int64_t)it.row_off + row) * a.row_stride +
                         ((int64_t)it.col_off + col) * a.col_stride;
       put_sample(a, it, e, tile[f][lane]);
@@ -443,17 +482,54 @@ thread_local float g_last_ms[4] = {0, 0, 0, 0};
 
 const char kUnsupported[] = "33-bit samples (side channel of a 32-bps stream) are not supported on the device";
 
-}  // namespace
+// the kernel times of a finished call (events: parse start / end, restore start, scatter start / end)
+void keep_times(const hipEvent_t* ev) {
+  float ms[4] = {0, 0, 0, 0};
+  (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
+  (void)hipEventElapsedTime(&ms[1], ev[2], ev[3]);
+  (void)hipEventElapsedTime(&ms[2], ev[3], ev[4]);
+  (void)hipEventElapsedTime(&ms[3], ev[0], ev[4]);
+  memcpy(g_last_ms, ms, sizeof(ms));
+}
 
-extern "C" {
-
-FRA_API int fra_decode_device_timing(float* ms4) {
-  if (!ms4) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  memcpy(ms4, g_last_ms, sizeof(g_last_ms));
+// k_dec_parse over every slot, the frame table back to the host (ev[0], ev[1] around the kernel); synchronises
+int parse_candidates(const DecArgs& a, size_t ng, FrameOut* h_fout, const hipEvent_t* ev, hipStream_t s) {
+  HIPCHK(hipEventRecord(ev[0], s));
+  if (ng) {
+    hipLaunchKernelGGL(k_dec_parse, dim3((unsigned)ng), dim3(kLanes), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(ev[1], s));
+  if (ng) HIPCHK(hipMemcpyAsync(h_fout, a.fout, sizeof(FrameOut) * ng * kLanes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return FRA_OK;
 }
 
-FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decoded* infos) {
+// the chain's first samples to the device, k_dec_restore and k_dec_scatter over the chained frames (ev[2..4]), the
+// failure flags back; enqueues only
+template <bool kClip>
+int restore_and_scatter(const DecArgs& a, size_t ng, int channels, int bs_max, const int64_t* h_samp0, uint32_t* h_fail,
+                        const hipEvent_t* ev, hipStream_t s) {
+  const size_t nslots = ng * kLanes;
+  if (ng) {
+    HIPCHK(hipMemcpyAsync((void*)a.samp0, h_samp0, sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev[2], s));
+    hipLaunchKernelGGL(k_dec_restore<kClip>, dim3((unsigned)ng, (unsigned)channels), dim3(kLanes), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  else HIPCHK(hipEventRecord(ev[2], s));
+  HIPCHK(hipEventRecord(ev[3], s));
+  if (ng) {
+    hipLaunchKernelGGL(k_dec_scatter<kClip>, dim3((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes)), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(ev[4], s));
+  if (ng) HIPCHK(hipMemcpyAsync(h_fail, a.fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
+  return FRA_OK;
+}
+
+// what both entries check of a job and of its items before any GPU work
+int check_job(const fra_ctx* ctx, const fra_decode_job* job, const fra_decoded* infos) {
   if (!ctx || !job || !infos) return fra_internal_set_error(FRA_E_INVALID, "null argument");
   const int ni = job->nitems;
   if (ni < 0 || (ni && !job->items) || (!job->data && job->len) || !job->dst)
@@ -466,33 +542,80 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
     return fra_internal_set_error(FRA_E_INVALID, "FRA_DENORM_NONE needs dst_dtype FRA_I16 or FRA_I32");
   if (job->channels < 1 || job->channels > 8 || job->band_stride < 0 || job->row_stride < 0 || job->col_stride < 0)
     return fra_internal_set_error(FRA_E_INVALID, "bad destination layout (channels %d)", job->channels);
+  return FRA_OK;
+}
+
+int check_item(const fra_decode_job* job, int i) {
+  const fra_decode_item& it = job->items[i];
+  if (it.offset > job->len || it.bytes > job->len - it.offset)
+    return fra_internal_set_error(FRA_E_INVALID, "item %d lies outside the data", i);
+  const fra_window& w = it.window;
+  if (w.row_off < 0 || w.col_off < 0 || w.width < 0 || (w.height < 0 && w.width != 1) || w.height == INT32_MIN)
+    return fra_internal_set_error(FRA_E_INVALID, "item %d: bad window", i);
+  if ((int64_t)std::abs(w.height) * w.width > INT32_MAX)
+    return fra_internal_set_error(FRA_E_INVALID, "item %d: a window of more than 2^31 - 1 samples is not supported "
+                                                 "on the device", i);
+  if (it.frame_offsets) {
+    if (it.nframes < 0 || it.channels < 1 || it.channels > 8 || it.bps < 4 || it.bps > 32 || it.blocksize < 1 ||
+        it.blocksize > 65536)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: bad stream parameters", i);
+    for (int f = 0; f < it.nframes; f++)
+      if (it.frame_offsets[f + 1] < it.frame_offsets[f])
+        return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets are not ascending", i);
+    if (it.frame_offsets[it.nframes] > it.bytes)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets run past the item", i);
+  }
+  return FRA_OK;
+}
+
+// the per-group and per-slot tables and the scratch of one call, owned by `sc`
+int alloc_tables(HipArena& sc, DecArgs& a, size_t ni, size_t ng, uint64_t scratch_elems) {
+  const size_t nslots = ng * kLanes;
+  void *d_items, *d_groups, *d_starts, *d_fout, *d_sdesc, *d_coefs, *d_scratch, *d_samp0, *d_fail;
+  HIPCHK(sc.alloc(&d_items, sizeof(DecItem) * ni));
+  HIPCHK(sc.alloc(&d_groups, sizeof(DecGroup) * ng));
+  HIPCHK(sc.alloc(&d_starts, sizeof(uint64_t) * nslots));
+  HIPCHK(sc.alloc(&d_fout, sizeof(FrameOut) * nslots));
+  HIPCHK(sc.alloc(&d_sdesc, sizeof(uint32_t) * nslots * 8));
+  HIPCHK(sc.alloc(&d_coefs, sizeof(int32_t) * nslots * 8 * 32));
+  HIPCHK(sc.alloc(&d_scratch, sizeof(int32_t) * (size_t)scratch_elems));
+  HIPCHK(sc.alloc(&d_samp0, sizeof(int64_t) * nslots));
+  HIPCHK(sc.alloc(&d_fail, sizeof(uint32_t) * nslots));
+  a.items = (const DecItem*)d_items;
+  a.groups = (const DecGroup*)d_groups;
+  a.starts = (const uint64_t*)d_starts;
+  a.fout = (FrameOut*)d_fout;
+  a.sdesc = (uint32_t*)d_sdesc;
+  a.coefs = (int32_t*)d_coefs;
+  a.scratch = (int32_t*)d_scratch;
+  a.samp0 = (const int64_t*)d_samp0;
+  a.fail = (uint32_t*)d_fail;
+  return FRA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+FRA_API int fra_decode_device_timing(float* ms4) {
+  if (!ms4) return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  memcpy(ms4, g_last_ms, sizeof(g_last_ms));
+  return FRA_OK;
+}
+
+FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decoded* infos) {
+  if (const int rc = check_job(ctx, job, infos)) return rc;
+  const int ni = job->nitems;
   memset(infos, 0, sizeof(fra_decoded) * (size_t)ni);
   if (ni == 0) return FRA_OK;
 
   bool any_search = false;
   int64_t extent = 0;  // elements of dst addressed, from element 0
   for (int i = 0; i < ni; i++) {
+    if (const int rc = check_item(job, i)) return rc;
     const fra_decode_item& it = job->items[i];
-    if (it.offset > job->len || it.bytes > job->len - it.offset)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d lies outside the data", i);
     const fra_window& w = it.window;
-    if (w.row_off < 0 || w.col_off < 0 || w.width < 0 || (w.height < 0 && w.width != 1) || w.height == INT32_MIN)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d: bad window", i);
-    if ((int64_t)std::abs(w.height) * w.width > INT32_MAX)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d: a window of more than 2^31 - 1 samples is not supported "
-                                                   "on the device", i);
-    if (it.frame_offsets) {
-      if (it.nframes < 0 || it.channels < 1 || it.channels > 8 || it.bps < 4 || it.bps > 32 || it.blocksize < 1 ||
-          it.blocksize > 65536)
-        return fra_internal_set_error(FRA_E_INVALID, "item %d: bad stream parameters", i);
-      for (int f = 0; f < it.nframes; f++)
-        if (it.frame_offsets[f + 1] < it.frame_offsets[f])
-          return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets are not ascending", i);
-      if (it.frame_offsets[it.nframes] > it.bytes)
-        return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets run past the item", i);
-    } else {
-      any_search = true;
-    }
+    if (!it.frame_offsets) any_search = true;
     if (w.height != 0 && w.width > 0)
       extent = std::max<int64_t>(extent, (int64_t)(job->channels - 1) * job->band_stride +
                                              ((int64_t)w.row_off + std::abs(w.height) - 1) * job->row_stride +
@@ -611,16 +734,9 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   a.col_stride = job->col_stride;
   a.dst_dtype = job->dst_dtype;
   a.denorm = job->denorm;
-  void *d_items, *d_groups, *d_starts, *d_fout, *d_sdesc, *d_coefs, *d_scratch, *d_samp0, *d_fail, *d_dst = nullptr;
-  HIPCHK(sc.alloc(&d_items, sizeof(DecItem) * (size_t)ni));
-  HIPCHK(sc.alloc(&d_groups, sizeof(DecGroup) * ng));
-  HIPCHK(sc.alloc(&d_starts, sizeof(uint64_t) * nslots));
-  HIPCHK(sc.alloc(&d_fout, sizeof(FrameOut) * nslots));
-  HIPCHK(sc.alloc(&d_sdesc, sizeof(uint32_t) * nslots * 8));
-  HIPCHK(sc.alloc(&d_coefs, sizeof(int32_t) * nslots * 8 * 32));
-  HIPCHK(sc.alloc(&d_scratch, sizeof(int32_t) * (size_t)scratch_elems));
-  HIPCHK(sc.alloc(&d_samp0, sizeof(int64_t) * nslots));
-  HIPCHK(sc.alloc(&d_fail, sizeof(uint32_t) * nslots));
+  void* d_dst = nullptr;
+  if (const int rc = alloc_tables(sc, a, (size_t)ni, ng, scratch_elems)) return rc;
+  void *d_items = (void*)a.items, *d_groups = (void*)a.groups, *d_starts = (void*)a.starts, *d_fail = a.fail;
   const size_t dst_bytes = (size_t)extent * (size_t)elem_size(job->dst_dtype);
   // a host destination with contiguous rows comes back window by window; any other layout is staged whole, so
   // that elements between the windows keep the caller's values either way
@@ -631,15 +747,6 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
     HIPCHK(sc.alloc(&d_dst, dst_bytes));
     if (dst_bytes && !by_window) HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
   }
-  a.items = (const DecItem*)d_items;
-  a.groups = (const DecGroup*)d_groups;
-  a.starts = (const uint64_t*)d_starts;
-  a.fout = (FrameOut*)d_fout;
-  a.sdesc = (uint32_t*)d_sdesc;
-  a.coefs = (int32_t*)d_coefs;
-  a.scratch = (int32_t*)d_scratch;
-  a.samp0 = (const int64_t*)d_samp0;
-  a.fail = (uint32_t*)d_fail;
   a.dst = d_dst;
   for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
   HIPCHK(hipMemcpyAsync(d_items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
@@ -651,14 +758,7 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
 
   // ---- parse every candidate
   std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
-  HIPCHK(hipEventRecord(ev[0], s));
-  if (ng) {
-    hipLaunchKernelGGL(k_dec_parse, dim3((unsigned)ng), dim3(kLanes), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(ev[1], s));
-  if (ng) HIPCHK(hipMemcpyAsync(h_fout.data(), d_fout, sizeof(FrameOut) * nslots, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if (const int rc = parse_candidates(a, ng, h_fout.data(), ev, s)) return rc;
 
   // ---- chain (item-relative byte positions, the host decoder's wording)
   std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
@@ -719,20 +819,8 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
 
   // ---- restore and scatter the chained frames
   std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
-  if (ng) {
-    HIPCHK(hipMemcpyAsync(d_samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(k_dec_restore, dim3((unsigned)ng, (unsigned)job->channels), dim3(kLanes), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  else HIPCHK(hipEventRecord(ev[2], s));
-  HIPCHK(hipEventRecord(ev[3], s));
-  if (ng) {
-    hipLaunchKernelGGL(k_dec_scatter, dim3((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes)), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(ev[4], s));
-  if (ng) HIPCHK(hipMemcpyAsync(h_fail.data(), d_fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
+  if (const int rc = restore_and_scatter<false>(a, ng, job->channels, bs_max, h_samp0.data(), h_fail.data(), ev, s))
+    return rc;
   if (by_window) {
     const size_t es = (size_t)elem_size(job->dst_dtype);
     for (int i = 0; i < ni; i++) {
@@ -759,12 +847,312 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
     if (h_fail[k])
       return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
                                                    "(frame at byte %llu)", (unsigned long long)h_starts[k]);
-  float ms[4] = {0, 0, 0, 0};
-  (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
-  (void)hipEventElapsedTime(&ms[1], ev[2], ev[3]);
-  (void)hipEventElapsedTime(&ms[2], ev[3], ev[4]);
-  (void)hipEventElapsedTime(&ms[3], ev[0], ev[4]);
-  memcpy(g_last_ms, ms, sizeof(ms));
+  keep_times(ev);
+  return FRA_OK;
+}
+
+// The windowed read: as fra_decode_device, for the frames that hold samples of `roi` only.  Tables, scratch and
+// the uploaded bytes follow the selection: an item outside the region costs nothing, an item inside it costs its
+// selected frames (the search path uploads a stream from its first selected candidate to its end, because a
+// frame's length is known only after k_dec_parse).
+FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi,
+                                     fra_decoded* infos) {
+  if (!roi) return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  if (const int rc = check_job(ctx, job, infos)) return rc;
+  if (roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0)
+    return fra_internal_set_error(FRA_E_INVALID, "the region of interest needs height > 0, width > 0 and an origin "
+                                                 ">= 0 (%d x %d at %d, %d)", roi->height, roi->width, roi->row_off,
+                                  roi->col_off);
+  if (job->flags & FRA_DECODE_CONCAT)
+    return fra_internal_set_error(FRA_E_INVALID, "FRA_DECODE_CONCAT is not supported by the windowed read");
+  const int ni = job->nitems;
+  memset(infos, 0, sizeof(fra_decoded) * (size_t)ni);
+  if (ni == 0) return FRA_OK;
+
+  std::vector<fra_dec::FrameSel> sel((size_t)ni);
+  bool any_search = false;
+  int64_t extent = 0;  // elements of dst addressed, from element 0 (= the region's first pixel)
+  for (int i = 0; i < ni; i++) {
+    if (const int rc = check_item(job, i)) return rc;
+    const fra_decode_item& it = job->items[i];
+    const fra_window& w = it.window;
+    if (w.height < 0)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: a capacity window (height < 0) is not supported by the "
+                                                   "windowed read", i);
+    fra_dec::FrameSel& sl = sel[(size_t)i];
+    sl = fra_dec::select_samples(w.row_off, w.col_off, w.height, w.width, roi->row_off, roi->col_off, roi->height,
+                                 roi->width);
+    if (!sl.hit) continue;
+    if (it.frame_offsets) sl.set_blocksize(it.blocksize);
+    else any_search = true;
+    extent = std::max<int64_t>(extent, (int64_t)(job->channels - 1) * job->band_stride +
+                                           ((int64_t)sl.rb - 1 - roi->row_off) * job->row_stride +
+                                           ((int64_t)sl.cb - 1 - roi->col_off) * job->col_stride + 1);
+  }
+
+  int device = 0;
+  hipStream_t s = nullptr;
+  fra_internal_ctx_stream(ctx, &device, &s);
+  (void)hipSetDevice(device);
+  HipArena sc;
+  hipEvent_t ev[5] = {};
+
+  // ---- the bytes of the intersecting search items on the host
+  const uint8_t* hdata = job->data_on_device ? nullptr : job->data;
+  std::unique_ptr<uint8_t[]> hcopy;
+  if (any_search && job->data_on_device) {
+    hcopy.reset(new (std::nothrow) uint8_t[(size_t)job->len + 1]);  // (only the ranges copied below are touched)
+    if (!hcopy) return fra_internal_set_error(FRA_E_NOMEM, "out of host memory");
+    for (int i = 0; i < ni; i++) {
+      const fra_decode_item& it = job->items[i];
+      if (sel[(size_t)i].hit && !it.frame_offsets && it.bytes)
+        HIPCHK(hipMemcpy(hcopy.get() + it.offset, job->data + it.offset, (size_t)it.bytes, hipMemcpyDeviceToHost));
+    }
+    hdata = hcopy.get();
+  }
+
+  // ---- candidates of the selected frames
+  std::vector<ItemPlan> plan((size_t)ni);
+  std::vector<std::vector<HostCand>> all((size_t)ni);  // search path: every candidate of the stream
+  std::vector<fra_dec::ScanUnit> units;
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    ItemPlan& ip = plan[(size_t)i];
+    fra_dec::FrameSel& sl = sel[(size_t)i];
+    if (!sl.hit) continue;
+    if (it.frame_offsets) {
+      ip.sp.sample_rate = 0;
+      ip.sp.channels = it.channels;
+      ip.sp.bps = it.bps;
+      ip.sp.max_bs = it.blocksize;
+      if (sl.f_hi >= it.nframes) return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
+      // frame f is entry f of the offsets and starts at sample f * blocksize (header numbers are not consulted)
+      for (int64_t f = sl.f_lo; f <= sl.f_hi; f++) ip.cand.push_back({it.frame_offsets[f], it.blocksize, 0, (uint64_t)f});
+      continue;
+    }
+    ip.search = true;
+    const uint8_t* d = hdata + it.offset;
+    const size_t at = fra_dec::skip_id3(d, (size_t)it.bytes);
+    if (at == SIZE_MAX) return fra_internal_set_error(FRA_E_INVALID, "item %d: ID3v2 tag runs past the end of the data", i);
+    ip.audio = fra_dec::parse_metadata(d, (size_t)it.bytes, at, ip.sp);
+    if (!ip.audio) return fra_internal_set_error(FRA_E_INVALID, "item %d: not a FLAC stream (bad fLaC/STREAMINFO)", i);
+    if (ip.sp.channels < 1 || ip.sp.channels > 8 || ip.sp.bps < 4 || ip.sp.bps > 32)
+      return fra_internal_set_error(FRA_E_INVALID, "unsupported STREAMINFO (channels %d, bps %d)", ip.sp.channels,
+                                    ip.sp.bps);
+    if (ip.sp.min_bs != ip.sp.max_bs || ip.sp.max_bs < 1)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: the windowed read needs a fixed-blocksize stream "
+                                                   "(STREAMINFO block sizes %d .. %d)", i, ip.sp.min_bs, ip.sp.max_bs);
+    sl.set_blocksize(ip.sp.max_bs);
+    if (ip.sp.total_samples && (uint64_t)sl.p_hi > ip.sp.total_samples)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
+    for (uint64_t b = ip.audio; b < it.bytes; b += (1u << 20))
+      units.push_back({i, d, it.bytes, b, std::min<uint64_t>(it.bytes, b + (1u << 20)), &ip.sp, {}});
+  }
+  if (!units.empty()) {
+    fra_dec::scan_units(units);
+    for (auto& u : units) {
+      auto& c = all[(size_t)u.item];
+      c.insert(c.end(), u.found.begin(), u.found.end());  // units are in byte order
+    }
+    for (int i = 0; i < ni; i++) {
+      ItemPlan& ip = plan[(size_t)i];
+      if (!ip.search) continue;
+      const auto& c = all[(size_t)i];
+      if (!c.empty() && c.front().start == ip.audio && c.front().variable)
+        return fra_internal_set_error(FRA_E_INVALID, "item %d: the windowed read needs a fixed-blocksize stream "
+                                                     "(variable-blocksize frame header)", i);
+      fra_dec::filter_candidates(c, sel[(size_t)i].f_lo, sel[(size_t)i].f_hi, ip.cand);
+    }
+  }
+
+  // ---- groups of 64 selected candidates, scratch layout, and where each item's bytes lie on the device: a host
+  //      input is uploaded as the spans that hold the selected frames, one after the other
+  std::vector<DecItem> h_items((size_t)ni);
+  std::vector<DecClip> h_clips((size_t)ni);
+  std::vector<DecGroup> h_groups;
+  std::vector<uint64_t> dev_base((size_t)ni, 0), span_a((size_t)ni, 0), span_b((size_t)ni, 0);
+  uint64_t scratch_elems = 0, upload = 0;
+  int bs_max = 1;
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    ItemPlan& ip = plan[(size_t)i];
+    const fra_dec::FrameSel& sl = sel[(size_t)i];
+    DecItem& di = h_items[(size_t)i];
+    memset(&di, 0, sizeof(di));
+    if (!sl.hit) continue;
+    if (ip.sp.channels != job->channels)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d has %d channels, the destination %d", i, ip.sp.channels,
+                                    job->channels);
+    if (job->denorm == FRA_DENORM_NONE && job->dst_dtype == FRA_I16 && ip.sp.bps > 16)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: a %d-bps stream needs dst_dtype FRA_I32", i, ip.sp.bps);
+    const int stride = ip.sp.max_bs;
+    bs_max = std::max(bs_max, stride);
+    if (!ip.cand.empty()) {
+      span_a[(size_t)i] = ip.cand.front().start;
+      span_b[(size_t)i] = ip.search ? it.bytes : it.frame_offsets[sl.f_hi + 1];
+    }
+    if (job->data_on_device) {
+      dev_base[(size_t)i] = it.offset;
+      span_b[(size_t)i] = it.bytes;
+    } else {
+      dev_base[(size_t)i] = upload - span_a[(size_t)i];  // (modulo 2^64; only dev_base + [span_a, span_b) is addressed)
+      upload += span_b[(size_t)i] - span_a[(size_t)i];
+    }
+    di.end = dev_base[(size_t)i] + span_b[(size_t)i];
+    di.channels = ip.sp.channels;
+    di.bps = ip.sp.bps;
+    di.sample_rate = ip.sp.sample_rate;
+    di.bs_stride = stride;
+    di.row_off = it.window.row_off - roi->row_off;
+    di.col_off = it.window.col_off - roi->col_off;
+    di.width = it.window.width;
+    di.height = it.window.height;
+    h_clips[(size_t)i] = {sl.ra - it.window.row_off, sl.rb - it.window.row_off, sl.ca - it.window.col_off,
+                          sl.cb - it.window.col_off, sl.p_lo, sl.p_hi};
+    di.dmin = it.data_min;
+    di.span = it.data_max - it.data_min;
+    ip.first_group = (int32_t)h_groups.size();
+    ip.ngroups = (int32_t)((ip.cand.size() + kLanes - 1) / kLanes);
+    for (int g = 0; g < ip.ngroups; g++) {
+      const int cnt = (int)std::min<size_t>(kLanes, ip.cand.size() - (size_t)g * kLanes);
+      h_groups.push_back({scratch_elems, i, cnt});
+      scratch_elems += (uint64_t)ip.sp.channels * (uint64_t)stride * kLanes;
+    }
+  }
+  const size_t ng = h_groups.size();
+  if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "too many candidate frames");
+  const size_t nslots = ng * kLanes;
+  std::vector<uint64_t> h_starts(std::max<size_t>(1, nslots), kNoFrame);
+  std::vector<uint64_t> h_rel(std::max<size_t>(1, nslots), 0);  // item-relative, for messages
+  for (int i = 0; i < ni; i++) {
+    const ItemPlan& ip = plan[(size_t)i];
+    for (size_t k = 0; k < ip.cand.size(); k++) {
+      h_starts[(size_t)ip.first_group * kLanes + k] = dev_base[(size_t)i] + ip.cand[k].start;
+      h_rel[(size_t)ip.first_group * kLanes + k] = ip.cand[k].start;
+    }
+  }
+
+  DecArgs a{};
+  a.band_stride = job->band_stride;
+  a.row_stride = job->row_stride;
+  a.col_stride = job->col_stride;
+  a.dst_dtype = job->dst_dtype;
+  a.denorm = job->denorm;
+  if (job->data_on_device) {
+    a.data = job->data;
+  } else {
+    void* p = nullptr;
+    HIPCHK(sc.alloc(&p, (size_t)upload));
+    for (int i = 0; i < ni; i++)
+      if (span_b[(size_t)i] > span_a[(size_t)i])
+        HIPCHK(hipMemcpyAsync((uint8_t*)p + (dev_base[(size_t)i] + span_a[(size_t)i]),
+                              job->data + job->items[i].offset + span_a[(size_t)i],
+                              (size_t)(span_b[(size_t)i] - span_a[(size_t)i]), hipMemcpyHostToDevice, s));
+    a.data = (const uint8_t*)p;
+  }
+  if (const int rc = alloc_tables(sc, a, (size_t)ni, ng, scratch_elems)) return rc;
+  void* d_clips = nullptr;
+  HIPCHK(sc.alloc(&d_clips, sizeof(DecClip) * (size_t)ni));
+  a.clips = (const DecClip*)d_clips;
+  void* d_dst = nullptr;
+  const size_t es = (size_t)elem_size(job->dst_dtype);
+  const size_t dst_bytes = (size_t)extent * es;
+  // as fra_decode_device: contiguous rows come back intersection by intersection, any other layout is staged whole
+  const bool by_window = !job->dst_on_device && job->col_stride == 1;
+  if (job->dst_on_device) {
+    d_dst = job->dst;
+  } else {
+    HIPCHK(sc.alloc(&d_dst, dst_bytes));
+    if (dst_bytes && !by_window) HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
+  }
+  a.dst = d_dst;
+  for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
+  HIPCHK(hipMemcpyAsync((void*)a.items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_clips, h_clips.data(), sizeof(DecClip) * (size_t)ni, hipMemcpyHostToDevice, s));
+  if (ng) {
+    HIPCHK(hipMemcpyAsync((void*)a.groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((void*)a.starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(a.fail, 0, sizeof(uint32_t) * nslots, s));
+  }
+
+  // ---- parse the selected candidates
+  std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
+  if (const int rc = parse_candidates(a, ng, h_fout.data(), ev, s)) return rc;
+
+  // ---- the selected frames: CRC-16 (status), byte-contiguous, full blocks, reaching the last needed sample
+  std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = job->items[i];
+    const ItemPlan& ip = plan[(size_t)i];
+    const fra_dec::FrameSel& sl = sel[(size_t)i];
+    if (!sl.hit) continue;
+    const size_t s0 = (size_t)ip.first_group * kLanes;
+    const int64_t bs = ip.sp.max_bs;
+    int64_t nframes = 0;
+    if (!ip.search) {
+      for (size_t k = 0; k < ip.cand.size(); k++) {
+        const FrameOut& fo = h_fout[s0 + k];
+        const int64_t f = sl.f_lo + (int64_t)k;
+        if (fo.status == ST_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
+        if (fo.status != ST_OK || fo.len != it.frame_offsets[f + 1] - it.frame_offsets[f] ||
+            (fo.n != bs && f != it.nframes - 1))
+          return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
+                                        (unsigned long long)it.frame_offsets[f]);
+        h_samp0[s0 + k] = f * bs;
+        nframes++;
+      }
+      if (sl.f_hi * bs + h_fout[s0 + ip.cand.size() - 1].n < sl.p_hi)
+        return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
+    } else {
+      const fra_dec::ChainResult cr = fra_dec::chain_window(it.bytes, ip.audio, bs, sl, all[(size_t)i], ip.cand,
+                                                            h_fout.data() + s0, h_samp0.data() + s0);
+      if (cr.code == fra_dec::CHAIN_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
+      if (cr.code == fra_dec::CHAIN_ENDS_EARLY)
+        return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
+      if (cr.code != fra_dec::CHAIN_OK)
+        return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
+                                      (unsigned long long)cr.byte);
+      nframes = cr.nframes;
+    }
+    fra_decoded& inf = infos[i];
+    inf.sample_rate = ip.sp.sample_rate;
+    inf.channels = ip.sp.channels;
+    inf.bps = ip.sp.bps;
+    inf.blocksize = ip.sp.max_bs;
+    inf.nframes = nframes;
+    inf.nsamples = (uint64_t)(sl.rb - sl.ra) * (uint64_t)(sl.cb - sl.ca);
+    inf.nstreams = 1;
+    inf.audio_offset = ip.audio;
+  }
+
+  // ---- restore and scatter
+  std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
+  if (const int rc = restore_and_scatter<true>(a, ng, job->channels, bs_max, h_samp0.data(), h_fail.data(), ev, s))
+    return rc;
+  if (by_window) {
+    for (int i = 0; i < ni; i++) {
+      const fra_dec::FrameSel& sl = sel[(size_t)i];
+      if (!sl.hit) continue;
+      const size_t rows = (size_t)(sl.rb - sl.ra), cols = (size_t)(sl.cb - sl.ca);
+      for (int c = 0; c < job->channels; c++) {
+        const size_t off = ((size_t)c * (size_t)job->band_stride +
+                            (size_t)(sl.ra - roi->row_off) * (size_t)job->row_stride + (size_t)(sl.ca - roi->col_off)) * es;
+        if (job->row_stride == 0 || rows == 1)
+          HIPCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)d_dst + off, cols * es, hipMemcpyDeviceToHost, s));
+        else
+          HIPCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)d_dst + off,
+                                  (size_t)job->row_stride * es, cols * es, rows, hipMemcpyDeviceToHost, s));
+      }
+    }
+  } else if (!job->dst_on_device && dst_bytes) {
+    HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  for (size_t k = 0; k < nslots; k++)
+    if (h_fail[k])
+      return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
+                                                   "(frame at byte %llu)", (unsigned long long)h_rel[k]);
+  keep_times(ev);
   return FRA_OK;
 }
 

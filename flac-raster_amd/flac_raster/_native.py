@@ -112,7 +112,7 @@ EXPORTS = [
     "fra_host_register", "fra_host_unregister", "fra_tiff_decode", "fra_plan_set_first_frame",
     "fra_plan_flags", "fra_plan_encode_host_progress", "fra_tiff_compress_bound", "fra_tiff_compress",
     "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
-    "fra_decode_device_timing",
+    "fra_decode_device_timing", "fra_decode_device_window",
 ]
 
 
@@ -176,6 +176,7 @@ def load():
             L.fra_plan_host_band_rows.argtypes = [vp, C.POINTER(C.c_int64)]
         L.fra_decode_device.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Decoded)]
         L.fra_decode_device_timing.argtypes = [C.POINTER(C.c_float)]
+        L.fra_decode_device_window.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(Decoded)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -341,7 +342,7 @@ class Context:
         return out, mn.value, mx.value
 
     def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
-                      denorm: int = DENORM_NONE, concat: bool = False) -> List[Decoded]:
+                      denorm: int = DENORM_NONE, concat: bool = False, roi=None) -> List[Decoded]:
         """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
 
         ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
@@ -352,7 +353,8 @@ class Context:
         their values) or a device pointer (int); sample p of channel c of a stream lands at element
         ``c * strides[0] + (row_off + p // width) * strides[1] + (col_off + p % width) * strides[2]``.
         Returns the per-stream :class:`Decoded` infos.  Anything the device path does not cover raises
-        :class:`NativeError`; there is no fallback to the host decoder."""
+        :class:`NativeError`; there is no fallback to the host decoder.  (``roi``: see
+        :meth:`decode_device_window`.)"""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -386,14 +388,31 @@ class Context:
         job.channels = channels
         job.band_stride, job.row_stride, job.col_stride = (int(v) for v in strides)
         infos = (Decoded * max(1, len(items)))()
-        rc = load().fra_decode_device(self.h, C.byref(job), infos)
+        if roi is not None:
+            rc = load().fra_decode_device_window(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), infos)
+        else:
+            rc = load().fra_decode_device(self.h, C.byref(job), infos)
         if rc == E_SPACE:
             raise OutputTooSmall(max(int(i.nsamples) for i in infos))
         _check(rc)
         return list(infos)[: len(items)]
 
+    def decode_device_window(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
+                             denorm: int = DENORM_NONE) -> List[Decoded]:
+        """The pixels of ``roi`` (row_off, col_off, height, width) only (``fra_decode_device_window``).
+
+        Arguments as :meth:`decode_device`, except that every item's ``window`` is its tile's window in source-raster
+        coordinates, ``roi`` is in the same coordinates, and ``dst`` is addressed relative to the region: raster pixel
+        (R, C) of channel c lands at ``c * strides[0] + (R - roi[0]) * strides[1] + (C - roi[1]) * strides[2]``.  Only
+        the frames that hold samples of the region are read and decoded; a tile outside it reports 0 frames.  The
+        result is bit-identical to cropping the full decode."""
+        if roi is None:
+            raise ValueError("roi is required")
+        return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi)
+
     def decode_timing(self) -> List[float]:
-        """HIP-event ms of this thread's last ``decode_device``: parse, restore, scatter, first kernel to last."""
+        """HIP-event ms of this thread's last ``decode_device`` / ``decode_device_window``: parse, restore, scatter,
+        first kernel to last."""
         ms = (C.c_float * 4)()
         _check(load().fra_decode_device_timing(ms))
         return list(ms)

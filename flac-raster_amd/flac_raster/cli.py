@@ -183,6 +183,37 @@ def extract(
 
 
 @app.command()
+def window(
+    flac_file: str = typer.Argument(..., help="Streaming FLAC file"),
+    output: Path = typer.Option(..., "--output", "-o", help="Output TIFF file path"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="Bounding box: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="Pixel window: 'row,col,height,width'"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Read a pixel window of a streaming FLAC file to GeoTIFF (only the tiles and frames it needs)."""
+    from .streaming import window_to_tiff
+
+    try:
+        if (bbox is None) == (pixels is None):
+            console.print("[red]Error: give exactly one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        path = _local(flac_file)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        # the given device, else device 0 when a GPU is present, else the host decoder (as convert)
+        dev = device if device is not None else (0 if _gpu_present() else None)
+        got, idx = window_to_tiff(path, output, window=win, bbox=box, device=dev)
+        console.print(f"[green]Saved rows {got[0]}..{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]} of "
+                      f"{idx['height']} x {idx['width']} to: {output}[/green]")
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Window read failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
+@app.command()
 def query(
     flac_file: str = typer.Argument(..., help="Spatial FLAC file"),
     bbox: str = typer.Option(..., "--bbox", "-b", help="Bounding box: 'xmin,ymin,xmax,ymax'"),

@@ -7,7 +7,9 @@ by one batched GPU plan per device (``tiles.encode_tiles``), and the per-tile ta
 same host byte assembly (``flac_meta``) with the values the temp GeoTIFF would have carried:
 the window transform (rasterio ``windows.transform`` arithmetic), no nodata, the source CRS.
 
-Reader = the index parse + byte-range slicing of ``cli.extract`` (``cli.py:238-313``).
+Reader = the index parse + byte-range slicing of ``cli.extract`` (``cli.py:238-313``); ``streaming_to_raster`` decodes
+the whole container, ``read_window`` a pixel window of it (only the byte ranges of the tiles it intersects are read,
+and on the GPU only the frames that hold its rows are decoded).
 """
 
 from __future__ import annotations
@@ -313,3 +315,126 @@ def streaming_to_tiff(path: Path, tiff_path: Path, device: Optional[int] = None)
     write_geotiff(Path(tiff_path), raster, transform=tuple(t[:6]) if t else None,
                   crs=crs if crs and crs != "None" else None)
     return index
+
+
+# ------------------------------------------------------------------------------------------ container -> window
+def resolve_window(index: Dict, window: Optional[Sequence[int]] = None,
+                   bbox: Optional[Sequence[float]] = None) -> Tuple[int, int, int, int]:
+    """The pixel window ``(row_off, col_off, height, width)`` of a request, clipped to the index's raster.
+
+    ``bbox`` = (xmin, ymin, xmax, ymax) in the index's CRS goes through the index's transform: floor of the minimum
+    pixel edge, ceil of the maximum.  A transform with rotation terms raises ``ValueError``, an empty result
+    ``LookupError``."""
+    if (window is None) == (bbox is None):
+        raise ValueError("Specify exactly one of window and bbox")
+    H, W = int(index["height"]), int(index["width"])
+    if bbox is not None:
+        if len(bbox) != 4:
+            raise ValueError("Bbox must have 4 coordinates")
+        t = index.get("transform")
+        if not t:
+            raise ValueError("the index has no transform")
+        a, b, c, d, e, f = (float(v) for v in t[:6])
+        if b != 0.0 or d != 0.0 or a == 0.0 or e == 0.0:
+            raise ValueError("a bbox needs an axis-aligned transform (no rotation terms)")
+        cols = sorted(((float(bbox[0]) - c) / a, (float(bbox[2]) - c) / a))
+        rows = sorted(((float(bbox[1]) - f) / e, (float(bbox[3]) - f) / e))
+        r0, r1 = int(np.floor(rows[0])), int(np.ceil(rows[1]))
+        c0, c1 = int(np.floor(cols[0])), int(np.ceil(cols[1]))
+    else:
+        if len(window) != 4:
+            raise ValueError("Window must be (row_off, col_off, height, width)")
+        r0, c0, h, w = (int(v) for v in window)
+        r1, c1 = r0 + h, c0 + w
+    r0, c0, r1, c1 = max(r0, 0), max(c0, 0), min(r1, H), min(c1, W)
+    if r1 <= r0 or c1 <= c0:
+        raise LookupError("The window does not intersect the raster")
+    return r0, c0, r1 - r0, c1 - c0
+
+
+def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                device: Optional[int] = None, semantics: str = "pcm16"):
+    """A pixel window of a streaming container (path or bytes) -> ``(raster (B, h, w) in the index's dtype, window,
+    index)``, bit-identical to cropping :func:`streaming_to_raster`.
+
+    ``window`` = (row_off, col_off, height, width) or ``bbox`` = (xmin, ymin, xmax, ymax), see :func:`resolve_window`;
+    the returned window is the clipped one.  Of a file only the index and the byte ranges of the intersecting tiles
+    are read (seek + read).  ``device=None`` decodes those tiles on the host and crops; an integer makes one
+    ``fra_decode_device_window`` call on that GPU, which decodes only the frames that hold the window's rows."""
+    from . import _native
+    from .decoder import decode_flac, pcm16_float
+    from .normalization import NormalizationParams, denormalize_from_audio
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data = memoryview(src)
+        index, hs = read_index_bytes(bytes(data[:4 + struct.unpack(">I", data[:4])[0]]))
+        size, fh = len(data), None
+    else:
+        sf = open_streaming(Path(src))
+        index, hs = sf.index, sf.header_size
+        size, fh = Path(src).stat().st_size, open(src, "rb")
+    try:
+        R, C_, h, w = win = resolve_window(index, window, bbox)
+        blob, items = bytearray(), []
+        for fr in index["frames"]:
+            fw = fr["window"]
+            if (fw["row_off"] >= R + h or fw["row_off"] + fw["height"] <= R or fw["col_off"] >= C_ + w
+                    or fw["col_off"] + fw["width"] <= C_):
+                continue
+            a = hs + fr["byte_offset"]
+            b = a + fr["byte_size"]
+            if b > size:
+                raise ValueError(f"tile {fr['frame_id']} runs past the end of the container")
+            if fh is None:
+                tile = bytes(data[a:b])
+            else:
+                fh.seek(a)
+                tile = fh.read(b - a)
+            tags = flac_meta.FLACFile(tile).tags  # the tile's own min / max, as _tile_items
+            items.append({"offset": len(blob), "bytes": b - a,
+                          "window": (fw["row_off"], fw["col_off"], fw["height"], fw["width"]),
+                          "data_min": float(tags["GEOSPATIAL_DATA_MIN"][0]),
+                          "data_max": float(tags["GEOSPATIAL_DATA_MAX"][0])})
+            blob += tile
+    finally:
+        if fh is not None:
+            fh.close()
+    if not items:
+        raise LookupError("No tiles intersect the window")
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    out = np.zeros((B, h, w), dtype=dt)
+    if device is not None:
+        ctx = _native.default_context(int(device))
+        ctx.decode_device_window(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (h * w, w, 1), win,
+                                 _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, win, index
+    for it in items:
+        r, c, th, tw = it["window"]
+        samples, _, bps = decode_flac(bytes(blob[it["offset"]:it["offset"] + it["bytes"]]))
+        if samples.shape != (th * tw, B):
+            raise ValueError(f"tile at ({r}, {c}) decodes to {samples.shape}, expected {(th * tw, B)}")
+        params = NormalizationParams(it["data_min"], it["data_max"], str(dt), 16 if bps <= 16 else 24,
+                                     32767 if bps <= 16 else 8388607)
+        audio = pcm16_float(samples) if semantics == "pcm16" else samples
+        tile = denormalize_from_audio(audio, params).reshape(th, tw, B).transpose(2, 0, 1)
+        ra, rb, ca, cb = max(r, R), min(r + th, R + h), max(c, C_), min(c + tw, C_ + w)
+        out[:, ra - R:rb - R, ca - C_:cb - C_] = tile[:, ra - r:rb - r, ca - c:cb - c]
+    return out, win, index
+
+
+def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] = None,
+                   bbox: Optional[Sequence[float]] = None, device: Optional[int] = None):
+    """A pixel window of a streaming container -> GeoTIFF with the index's CRS and the transform shifted to the
+    window's origin; returns ``(window, index)``."""
+    from .tiff import write_geotiff
+
+    raster, win, index = read_window(Path(path), window=window, bbox=bbox, device=device)
+    t = index.get("transform")
+    crs = index.get("crs")
+    write_geotiff(Path(tiff_path), raster,
+                  transform=tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None,
+                  crs=crs if crs and crs != "None" else None)
+    return win, index

@@ -263,13 +263,9 @@ def encode_tiles(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]],
     return [ts for grp in out for ts in grp]
 
 
-def verify_on_device(plan: "_native.Plan", raster_ptr: int,
-                     strides: Optional[Tuple[int, int, int]] = None) -> bool:
-    """Decode an executed plan's device output on its GPU into ``raster_ptr`` (a device buffer of int16 for 16-bps
-    plans / int32 otherwise, laid out like the plan's raster, or with other element ``strides``) without copying the
-    frames to the host: the frames are addressed through ``fra_plan_frame_offsets``, nothing is searched.  Returns True
-    when every frame parsed with a matching CRC-16 (a corrupt frame raises ``NativeError``).  The library offers the
-    decode; comparing the samples with the expectation stays with the caller."""
+def _plan_items(plan: "_native.Plan"):
+    """An executed plan's device output as ``decode_device`` input: (stream infos, (pointer, length), one item per
+    window addressed through the plan's frame offsets)."""
     infos, total = plan.result()
     nfr = sum(i.nframes for i in infos)
     off = plan.frame_offsets(nfr)
@@ -280,9 +276,37 @@ def verify_on_device(plan: "_native.Plan", raster_ptr: int,
         items.append({"offset": inf.offset, "bytes": inf.frame_bytes, "window": w, "frame_offsets": fo,
                       "channels": inf.channels, "bps": inf.bps, "blocksize": plan.blocksize})
         f0 += inf.nframes
+    return infos, (ptr, total), items
+
+
+def verify_on_device(plan: "_native.Plan", raster_ptr: int,
+                     strides: Optional[Tuple[int, int, int]] = None) -> bool:
+    """Decode an executed plan's device output on its GPU into ``raster_ptr`` (a device buffer of int16 for 16-bps
+    plans / int32 otherwise, laid out like the plan's raster, or with other element ``strides``) without copying the
+    frames to the host: the frames are addressed through ``fra_plan_frame_offsets``, nothing is searched.  Returns True
+    when every frame parsed with a matching CRC-16 (a corrupt frame raises ``NativeError``).  The library offers the
+    decode; comparing the samples with the expectation stays with the caller."""
+    infos, data, items = _plan_items(plan)
     if not items:
         return True
     dt = np.int16 if all(i.bps <= 16 for i in infos) else np.int32
-    out = plan.ctx.decode_device((ptr, total), items, int(raster_ptr), dt, infos[0].channels,
+    out = plan.ctx.decode_device(data, items, int(raster_ptr), dt, infos[0].channels,
                                  strides or plan.strides)
     return all(o.nframes == i.nframes for o, i in zip(out, infos))
+
+
+def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int], raster_ptr: int,
+                          strides: Optional[Tuple[int, int, int]] = None):
+    """The windowed counterpart of :func:`verify_on_device`: decode the pixels ``window`` (row_off, col_off, height,
+    width, in the plan's raster coordinates) of an executed plan's device output into ``raster_ptr``, a device buffer
+    of int16 (16-bps plans) / int32 whose element 0 is the window's first pixel (default ``strides``: band-planar
+    ``(height * width, width, 1)`` of the window).  Only the frames that hold samples of the window are parsed,
+    through ``fra_plan_frame_offsets``; nothing is searched and nothing is copied to the host.  Returns the per-tile
+    :class:`Decoded` infos (0 frames for a tile outside the window); a corrupt selected frame raises ``NativeError``."""
+    infos, data, items = _plan_items(plan)
+    if not items:
+        return []
+    _, _, h, w = (int(v) for v in window)
+    dt = np.int16 if all(i.bps <= 16 for i in infos) else np.int32
+    return plan.ctx.decode_device_window(data, items, int(raster_ptr), dt, infos[0].channels,
+                                         strides or (h * w, w, 1), window)

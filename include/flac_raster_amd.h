@@ -271,8 +271,34 @@ typedef struct {
 } fra_decode_job;
 
 FRA_API int fra_decode_device(fra_ctx *ctx, const fra_decode_job *job, fra_decoded *infos /* nitems */);
-/* HIP-event times of the calling thread's last successful fra_decode_device: 0 k_dec_parse, 1 k_dec_restore,
- * 2 k_dec_scatter, 3 first kernel to last (includes the frame-table copy and the host chain) */
+
+/* Windowed read: the pixels of `roi` only, bit-identical to cropping what fra_decode_device gives.  items[i].window
+ * is the tile's window in source-raster coordinates (as a streaming container's index gives it) and roi is in the
+ * same coordinates (height > 0, width > 0, origin >= 0).  dst is addressed relative to the region: raster pixel
+ * (R, C) of channel ch inside both roi and items[i].window lands at element ch*band_stride + (R - roi.row_off)*row_stride
+ * + (C - roi.col_off)*col_stride; no other element is written (a host dst keeps the caller's values there).
+ * Denormalisation, destination dtypes and saturation are those of fra_decode_device.
+ *   An item that does not intersect roi is validated (it must lie inside data) but its bytes are never read; its
+ * infos[i] has nframes == 0 and nsamples == 0.  For an intersecting item infos[i].nframes is the number of frames
+ * decoded and nsamples the number of pixels of the intersection.
+ *   For a tile (r0, c0, H, W) with intersection rows [ra, rb) and columns [ca, cb) the needed samples are
+ * [p_lo, p_hi), p_lo = (ra-r0)*W + (ca-c0), p_hi = (rb-1-r0)*W + (cb-c0), and the needed frames p_lo / blocksize
+ * through (p_hi-1) / blocksize: only those are parsed, restored and scattered, and scratch and every table are
+ * sized by them.  With frame_offsets, frame f is entry f and starts at sample f * blocksize (header numbers are not
+ * consulted).  Without, the host keeps the sync candidates whose header frame number lies in that range and chains
+ * them locally (from the first audio byte for frame 0, else from each candidate carrying the first number, in byte
+ * order; the first chain of consecutive numbers with valid CRC-16s wins).  Every selected frame must have a valid
+ * CRC-16, follow its predecessor byte for byte and, unless it is the stream's last, hold blocksize samples, and
+ * the last one must reach p_hi: otherwise FRA_E_INVALID ("lost sync / corrupt frame at byte N", N relative to the
+ * item, or "the stream ends before the window").
+ *   Accepted limitation: damage in a frame that was not selected is not detected -- the price of not reading it.
+ *   Refused with FRA_E_INVALID: FRA_DECODE_CONCAT, the capacity form height < 0, a stream whose STREAMINFO minimum
+ * and maximum block sizes differ or whose frames carry the variable-blocksize flag, and 33-bit samples. */
+FRA_API int fra_decode_device_window(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                     fra_decoded *infos /* nitems */);
+/* HIP-event times of the calling thread's last successful fra_decode_device or fra_decode_device_window:
+ * 0 k_dec_parse, 1 k_dec_restore, 2 k_dec_scatter, 3 first kernel to last (includes the frame-table copy and the
+ * host chain) */
 FRA_API int fra_decode_device_timing(float *ms4);
 
 /* Synthetic rasters, generated on the device with integer-exact hashes so a

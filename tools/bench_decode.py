@@ -15,6 +15,15 @@ once by a plan on the GPU; ``--tiles N`` keeps the first N tiles (default: all 1
   samples_per_s     of each of the above, and each kernel's share of device_ms (``kernels``)
 
     python tools/bench_decode.py --tiles 121 --steps 3 --warmup 1
+
+``--window [r,c,h,w]`` (default: 2048 x 2048 at the scene's centre) times a windowed read
+(``fra_decode_device_window``) against the full decode of the same run -- what a user of the full decode has to do to
+get the same pixels -- on both paths: frames resident with offsets (``window_ms`` against ``device_ms``, HIP events,
+and the wall times) and complete streams in page-locked host memory, searched (``window_search_ms`` against
+``device_search_ms``, wall).  The window's pixels must equal the crop of the full decode.  The host-decoder and
+container legs are skipped.
+
+    python tools/bench_decode.py --window --steps 5 --warmup 2
 """
 from __future__ import annotations
 
@@ -61,6 +70,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-steps", type=int, default=1, help="timed passes of the host decoder (it is slow)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the container leg")
+    ap.add_argument("--window", nargs="?", const="center", default=None, metavar="r,c,h,w",
+                    help="time a windowed read against the full decode (default window: 2048 x 2048 at the centre)")
     args = ap.parse_args()
 
     ctx = N.Context(0)
@@ -134,6 +145,66 @@ def main():
         if k >= args.warmup:
             search_ms.append((t1 - t0) * 1e3)
             search_ev.append(ctx.decode_timing()[3])
+
+    if args.window:
+        if args.window == "center":
+            win = ((H - 2048) // 2, (W - 2048) // 2, 2048, 2048)
+        else:
+            win = tuple(int(v) for v in args.window.split(","))
+        r, c, h, w = win
+        full = np.empty((B, H, W), np.int16)
+        ctx.d2h(full, dev_out)  # the full decode of the search leg
+        want = full[:, r:r + h, c:c + w].copy()
+        del full
+        dev_win = ctx.alloc(B * h * w * 2)
+        got = np.empty((B, h, w), np.int16)
+        legs = {}
+        for name, data, its in (("window", (frames_ptr, total), items), ("window_search", blob, sitems)):
+            wall, evt, ks = [], [], []
+            for k in range(args.warmup + args.steps):
+                t0 = time.perf_counter()
+                out = ctx.decode_device_window(data, its, dev_win, np.int16, B, (h * w, w, 1), win)
+                t1 = time.perf_counter()
+                if k >= args.warmup:
+                    ms = ctx.decode_timing()
+                    wall.append((t1 - t0) * 1e3)
+                    evt.append(ms[3])
+                    ks.append(ms[:3])
+            ctx.d2h(got, dev_win)
+            if not np.array_equal(got, want):
+                raise SystemExit(f"{name}: the window differs from the crop of the full decode")
+            ctx.h2d(dev_win, np.zeros_like(got))
+            legs[name] = (wall, evt, ks, sum(o.nframes for o in out), sum(1 for o in out if o.nframes))
+        ctx.free(dev_win)
+        med = statistics.median
+        kfull = [med([k[i] for k in kern]) for i in range(3)]
+        wwall, wevt, wks, wfr, wtiles = legs["window"]
+        swall, sevt, sks, _, _ = legs["window_search"]
+        names = ("k_dec_parse_ms", "k_dec_restore_ms", "k_dec_scatter_ms")
+        res = {
+            "workload": f"window {h}x{w} at ({r}, {c}) of C4-like {W}x{H}x{B} uint16, tile {TILE}, level {LEVEL}, "
+                        f"{len(wins)} tiles",
+            "window": list(win), "tiles": len(wins), "frames": nfr, "window_tiles": wtiles, "window_frames": wfr,
+            "steps": args.steps, "warmup": args.warmup, "window_equals_crop_of_full_decode": True,
+            "device_ms": round(med(dev_ms), 3), "device_wall_ms": round(med(dev_wall), 3),
+            "window_ms": round(med(wevt), 3), "window_wall_ms": round(med(wwall), 3),
+            "device_search_ms": round(med(search_ms), 3), "window_search_ms": round(med(swall), 3),
+            "window_search_event_ms": round(med(sevt), 3),
+            "full_over_window": {"events": round(med(dev_ms) / med(wevt), 2),
+                                 "wall": round(med(dev_wall) / med(wwall), 2),
+                                 "search_wall": round(med(search_ms) / med(swall), 2)},
+            "area_ratio": round(sum(x[2] * x[3] for x in wins) / (h * w), 2),
+            "kernels_full": {n: round(v, 3) for n, v in zip(names, kfull)},
+            "kernels_window": {n: round(med([k[i] for k in wks]), 3) for i, n in enumerate(names)},
+            "kernels_window_search": {n: round(med([k[i] for k in sks]), 3) for i, n in enumerate(names)},
+            "all_ms": {"window": [round(v, 3) for v in wevt], "window_wall": [round(v, 3) for v in wwall],
+                       "window_search": [round(v, 2) for v in swall]},
+        }
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
 
     verified += verify()
 

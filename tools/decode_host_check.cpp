@@ -4,7 +4,11 @@
 //     command line and over corrupted / truncated variants of them; the per-candidate frame lengths that k_dec_parse
 //     would report come from the host decoder's own validate-only frame decode, and the chain's verdict and sample
 //     count must agree with fra_decode on the same bytes;
-//   * the argument validation of fra_decode_device, which returns before any GPU work.
+//   * the windowed read's frame selection (select_samples / filter_candidates / chain_window): for a few frame
+//     ranges of every file (first frame only, a middle range, through the last frame) the selected frames and their
+//     first samples must equal what the full chain assigns to the same frames, and a bit-flipped variant must fail
+//     exactly when the flipped byte lies in a selected frame;
+//   * the argument validation of fra_decode_device and fra_decode_device_window, which returns before any GPU work.
 // usage: decode_host_check [--concat] file.flac ...
 #include <cstdarg>
 #include <cstdio>
@@ -62,6 +66,102 @@ static int search_and_chain(const std::vector<uint8_t>& v, bool concat, uint64_t
   return r.code == fra_dec::CHAIN_OK ? 0 : -1;
 }
 
+// every candidate of a stream with the frame records the host decoder gives them
+struct Scanned {
+  fra_dec::StreamParams sp;
+  size_t audio = 0;
+  std::vector<fra_dec::HostCand> cand;
+  std::vector<fra_dec::FrameRec> rec;
+};
+static bool scan_with_records(const std::vector<uint8_t>& v, Scanned& s) {
+  const uint8_t* d = v.data();
+  const size_t len = v.size();
+  const size_t at = fra_dec::skip_id3(d, len);
+  if (at == SIZE_MAX) return false;
+  s.audio = fra_dec::parse_metadata(d, len, at, s.sp);
+  if (!s.audio || s.sp.channels < 1 || s.sp.channels > 8 || s.sp.bps < 4 || s.sp.bps > 32) return false;
+  fra_dec::scan_range(d, len, s.audio, len, s.sp, s.cand);
+  s.rec.assign(s.cand.size() + 1, fra_dec::FrameRec{0, 0, 0, 0, 0, 0});
+  Scratch sc;
+  for (size_t k = 0; k < s.cand.size(); k++) {
+    FrameHdr h;
+    size_t fl = 0;
+    if (parse_header(d + s.cand[k].start, d + len, s.sp, h)) fl = decode_frame(d + s.cand[k].start, d + len, s.sp, h, nullptr, s.sp.channels, sc);
+    s.rec[k] = {(uint32_t)fl, h.blocksize, (uint8_t)(fl ? fra_dec::ST_OK : fra_dec::ST_NONE), (uint8_t)h.chan_assign, (uint8_t)h.bps, 0};
+  }
+  return true;
+}
+
+// the local chain of frames [f_lo, f_hi] of `v`; returns the chain's code and fills (start, first sample) pairs
+static fra_dec::ChainCode window_chain(const std::vector<uint8_t>& v, int64_t f_lo, int64_t f_hi, int64_t p_hi,
+                                       std::vector<std::pair<uint64_t, int64_t>>& got) {
+  Scanned s;
+  if (!scan_with_records(v, s) || s.sp.min_bs != s.sp.max_bs) return fra_dec::CHAIN_LOST_SYNC;
+  fra_dec::FrameSel sel;
+  sel.hit = true;
+  sel.f_lo = f_lo; sel.f_hi = f_hi;
+  sel.p_lo = f_lo * s.sp.max_bs; sel.p_hi = p_hi;
+  std::vector<fra_dec::HostCand> kept;
+  fra_dec::filter_candidates(s.cand, f_lo, f_hi, kept);
+  std::vector<fra_dec::FrameRec> rec(kept.size() + 1);
+  for (size_t k = 0, j = 0; k < kept.size(); k++) {  // both lists are in byte order
+    while (s.cand[j].start != kept[k].start) j++;
+    rec[k] = s.rec[j];
+  }
+  std::vector<int64_t> samp0(kept.size() + 1, -1);
+  const fra_dec::ChainResult r = fra_dec::chain_window(v.size(), s.audio, s.sp.max_bs, sel, s.cand, kept, rec.data(), samp0.data());
+  got.clear();
+  for (size_t k = 0; k < kept.size(); k++)
+    if (samp0[k] >= 0) got.push_back({kept[k].start, samp0[k]});
+  if (r.code == fra_dec::CHAIN_OK) EXPECT(r.nframes == (int64_t)got.size(), "chain_window counts %lld frames, marks %zu", (long long)r.nframes, got.size());
+  return r.code;
+}
+
+static void check_ranges(const char* what, const std::vector<uint8_t>& v) {
+  Scanned s;
+  if (!scan_with_records(v, s)) { EXPECT(false, "%s: not a stream", what); return; }
+  std::vector<int64_t> samp0(s.cand.size() + 1, -1);
+  const fra_dec::ChainResult full = fra_dec::chain_stream(v.data(), v.size(), s.audio, s.sp, false, s.cand, s.rec.data(), samp0.data());
+  EXPECT(full.code == fra_dec::CHAIN_OK && full.nframes > 0 && s.sp.min_bs == s.sp.max_bs, "%s: no fixed-blocksize chain", what);
+  if (g_fail) return;
+  struct Fr { uint64_t start, len; int64_t samp0; };
+  std::vector<Fr> fr;
+  for (size_t k = 0; k < s.cand.size(); k++)
+    if (samp0[k] >= 0) fr.push_back({s.cand[k].start, s.rec[k].len, samp0[k]});
+  const int64_t F = (int64_t)fr.size(), bs = s.sp.max_bs;
+  const int64_t ranges[3][2] = {{0, 0}, {F / 3, std::max(F / 3, 2 * F / 3 - 1)}, {std::max<int64_t>(0, F - 2), F - 1}};
+  for (auto& rg : ranges) {
+    const int64_t f_lo = rg[0], f_hi = rg[1];
+    const int64_t p_hi = std::min<int64_t>((f_hi + 1) * bs, (int64_t)full.nsamp);
+    std::vector<std::pair<uint64_t, int64_t>> got;
+    const fra_dec::ChainCode code = window_chain(v, f_lo, f_hi, p_hi, got);
+    bool same = code == fra_dec::CHAIN_OK && (int64_t)got.size() == f_hi - f_lo + 1;
+    for (int64_t f = f_lo; same && f <= f_hi; f++)
+      same = got[(size_t)(f - f_lo)].first == fr[(size_t)f].start && got[(size_t)(f - f_lo)].second == fr[(size_t)f].samp0;
+    EXPECT(same, "%s: frames %lld..%lld differ from the full chain (code %d)", what, (long long)f_lo, (long long)f_hi, (int)code);
+    EXPECT(window_chain(v, f_lo, f_hi, p_hi + 1, got) != fra_dec::CHAIN_OK || p_hi < (int64_t)full.nsamp,
+           "%s: a window past the last frame's samples accepted", what);
+    // bit flips before, inside and after the range
+    const uint64_t a = fr[(size_t)f_lo].start, b = fr[(size_t)f_hi].start + fr[(size_t)f_hi].len;
+    const uint64_t flips[] = {s.audio + 9, a > s.audio ? a - 1 : a, a, a + 5, (a + b) / 2, b - 1, b, b + 7, v.size() - 3};
+    for (uint64_t pos : flips) {
+      if (pos < s.audio || pos >= v.size()) continue;
+      std::vector<uint8_t> e(v);
+      e[(size_t)pos] ^= 0x04;
+      const bool inside = pos >= a && pos < b;
+      const bool ok = window_chain(e, f_lo, f_hi, p_hi, got) == fra_dec::CHAIN_OK;
+      EXPECT(ok == !inside, "%s: frames %lld..%lld (bytes %llu..%llu), bit flipped at %llu: chain %s", what, (long long)f_lo,
+             (long long)f_hi, (unsigned long long)a, (unsigned long long)b, (unsigned long long)pos, ok ? "succeeds" : "fails");
+      if (ok) {
+        bool eq = (int64_t)got.size() == f_hi - f_lo + 1;
+        for (int64_t f = f_lo; eq && f <= f_hi; f++) eq = got[(size_t)(f - f_lo)].first == fr[(size_t)f].start;
+        EXPECT(eq, "%s: frames %lld..%lld move under a flip at %llu", what, (long long)f_lo, (long long)f_hi, (unsigned long long)pos);
+      }
+    }
+  }
+  printf("%-40s %lld frames, 3 frame ranges checked\n", what, (long long)F);
+}
+
 static void check_bytes(const char* what, const std::vector<uint8_t>& v, bool concat) {
   fra_decoded info;
   int32_t* smp = nullptr;
@@ -97,6 +197,12 @@ int main(int argc, char** argv) {
     fclose(f);
     check_bytes(argv[i], v, concat);
     if (concat) check_bytes("  without the concat flag", v, false);
+    {  // the windowed read takes one stream: of a concatenated file, the first
+      std::vector<uint8_t> one(v);
+      uint64_t nsamp = 0, bad = 0; int64_t nfr = 0; int nst = 0;
+      if (concat && search_and_chain(v, false, &nsamp, &nfr, &nst, &bad) != 0 && bad < v.size()) one.resize((size_t)bad);
+      check_ranges("  frame ranges", one);
+    }
     const size_t flips[] = {200, 50000, v.size() - 3, v.size() / 2, v.size() / 3};
     for (size_t pos : flips) {
       if (pos >= v.size()) continue;
@@ -151,6 +257,23 @@ int main(int argc, char** argv) {
   fo[2] = 60;
   { auto x = it; x.frame_offsets = fo; x.nframes = 2; x.channels = 0; x.bps = 16; x.blocksize = 16; bad("0 channels", job, x); }
   { auto j = job; j.nitems = 0; EXPECT(fra_decode_device(ctx, &j, inf) == FRA_OK, "empty job refused"); }
+  // ... and of fra_decode_device_window
+  const fra_window roi{0, 0, 1, 8};
+  auto badw = [&](const char* what, fra_decode_job j, fra_decode_item x, const fra_window* r) {
+    j.items = &x;
+    EXPECT(fra_decode_device_window(ctx, &j, r, inf) == FRA_E_INVALID, "window read: %s accepted", what);
+  };
+  badw("null roi", job, it, nullptr);
+  EXPECT(fra_decode_device_window(nullptr, &job, &roi, inf) == FRA_E_INVALID, "window read: null ctx accepted");
+  { fra_window r = roi; r.height = 0; badw("zero-height roi", job, it, &r); }
+  { fra_window r = roi; r.width = 0; badw("zero-width roi", job, it, &r); }
+  { fra_window r = roi; r.width = -3; badw("negative-width roi", job, it, &r); }
+  { fra_window r = roi; r.row_off = -1; badw("negative roi origin", job, it, &r); }
+  { auto j = job; j.flags = FRA_DECODE_CONCAT; badw("FRA_DECODE_CONCAT", j, it, &roi); }
+  { auto x = it; x.window = {0, 0, -8, 1}; badw("capacity window", job, x, &roi); }
+  { auto j = job; j.dst_dtype = 9; badw("dtype 9", j, it, &roi); }
+  { auto x = it; x.offset = 60; x.bytes = 8; x.window = {100, 100, 1, 8}; badw("item past the data, outside the roi", job, x, &roi); }
+  { auto j = job; j.nitems = 0; EXPECT(fra_decode_device_window(ctx, &j, &roi, inf) == FRA_OK, "window read: empty job refused"); }
   printf("argument validation checked\n");
 #endif
   printf(g_fail ? "%d FAILED\n" : "host check ok\n", g_fail);
