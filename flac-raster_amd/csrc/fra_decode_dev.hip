@@ -25,6 +25,10 @@
 // and k_dec_restore see only those, and k_dec_scatter clips to the region at the granularity of a frame's
 // 64-sample run.  Damage in a frame that was not selected is not detected: that frame is never read.
 //
+// fra_internal_verify_device (fra_plan_verify) runs k_dec_parse and k_dec_restore over a plan's own frames and then
+// k_dec_verify in k_dec_scatter's place: same grid and transpose, but it loads the source raster element instead of
+// storing to it, normalises it anew and compares.  Nothing is written but a mismatch count and the first mismatch.
+//
 // Not covered (refused, never decoded differently): 33-bit samples (side channel of a 32-bps stream); by the
 // windowed read also FRA_DECODE_CONCAT, capacity windows and variable-blocksize streams.
 #include <hip/hip_runtime.h>
@@ -39,7 +43,9 @@
 
 #include "../../include/flac_raster_amd.h"
 #include "fra_decode_host.h"
+#include "fra_device.h"
 #include "fra_host.h"
+#include "fra_verify.h"
 
 extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
 
@@ -469,6 +475,104 @@ __global__ __launch_bounds__(256) void k_dec_scatter(DecArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------ verify
+struct VerArgs {
+  const void* src;           // the source raster; DecArgs' strides and the items' windows address it
+  const fra::NormDev* nd;    // [nitems] min / max keys of the encode
+  unsigned long long* res;   // [nitems][2]: mismatch count, smallest mismatching key (p << 3) | channel
+  int32_t* vals;             // [nitems][2]: expected and decoded sample at that key (pass 1)
+  int32_t norm, pass;
+};
+
+// k_dec_scatter<false>'s grid and phases, but phase 2 loads the source element the scatter would store to, normalises
+// it by the plain f64 sequence (no table) and compares.  Pass 0 counts the mismatches of the group's item and keeps
+// the smallest key; pass 1, launched only when an item has mismatches, writes both samples at that key.
+template <int SRC>
+__global__ __launch_bounds__(256) void k_dec_verify(DecArgs a, VerArgs v) {
+  __shared__ int32_t tile[kLanes][kLanes + 1];
+  const int g = blockIdx.x, i0 = blockIdx.y * kLanes, t = threadIdx.x;
+  const DecGroup grp = a.groups[g];
+  const DecItem it = a.items[grp.item];
+  if (i0 >= it.bs_stride) return;
+  unsigned long long* res = v.res + 2 * (size_t)grp.item;
+  unsigned long long first = 0;
+  if (v.pass) {  // (uniform over the block)
+    if (res[0] == 0) return;
+    first = res[1];
+  }
+  const int lane = t & 63, q = t >> 6;
+  const int slot = g * kLanes + lane;
+  const bool live = lane < grp.count && a.samp0[slot] >= 0;
+  FrameOut fo{0, 0, 0, 0, 0, 0};
+  if (live) fo = a.fout[slot];
+  const uint32_t d0 = live ? a.sdesc[(uint64_t)slot * 8] : 0u;
+  const uint32_t d1 = live && it.channels > 1 ? a.sdesc[(uint64_t)slot * 8 + 1] : 0u;
+  const int32_t* sc = a.scratch + grp.base + lane;
+  const uint64_t cstride = (uint64_t)it.bs_stride * kLanes;
+  const uint32_t nsamp = (uint32_t)it.width * (uint32_t)it.height;
+  const fra::NormParams np = fra::norm_params(v.norm, v.nd[grp.item]);
+  unsigned long long nbad = 0, kmin = ~0ull;
+  for (int c = 0; c < it.channels; c++) {
+    __syncthreads();
+    if (live) {
+      const uint32_t dc = c == 0 ? d0 : (c == 1 ? d1 : a.sdesc[(uint64_t)slot * 8 + c]);
+      for (int k = 0; k < 16; k++) {
+        const int i = i0 + q + 4 * k;
+        if (i >= fo.n) break;
+        int32_t s;
+        if (fo.assign >= 8 && c < 2) {
+          const int64_t x0 = (int64_t)((uint64_t)(int64_t)sc[(uint64_t)((d0 & 0xFF) ? i : 0) * kLanes] << ((d0 >> 16) & 0xFF));
+          const int64_t x1 =
+              (int64_t)((uint64_t)(int64_t)sc[cstride + (uint64_t)((d1 & 0xFF) ? i : 0) * kLanes] << ((d1 >> 16) & 0xFF));
+          int64_t l, r;
+          if (fo.assign == 8) { l = x0; r = x0 - x1; }        // L/S
+          else if (fo.assign == 9) { l = x0 + x1; r = x1; }   // S/R
+          else {                                              // M/S
+            const int64_t m = (x0 * 2) | (x1 & 1);
+            l = (m + x1) >> 1;
+            r = (m - x1) >> 1;
+          }
+          s = (int32_t)(c == 0 ? l : r);
+        } else {
+          const int64_t x = (int64_t)sc[(uint64_t)c * cstride + (uint64_t)((dc & 0xFF) ? i : 0) * kLanes];
+          s = (int32_t)(int64_t)((uint64_t)x << ((dc >> 16) & 0xFF));
+        }
+        tile[lane][i - i0] = s;
+      }
+    }
+    __syncthreads();
+    for (int k = 0; k < 16; k++) {
+      const int f = q + 4 * k;  // frame of the group; lane = sample within the 64-sample run
+      if (f >= grp.count) break;
+      const int fs = g * kLanes + f;
+      const int64_t s0 = a.samp0[fs];
+      if (s0 < 0) continue;
+      const int i = i0 + lane;
+      if (i >= a.fout[fs].n) continue;
+      const uint64_t p = (uint64_t)s0 + (uint64_t)i;
+      if (p >= nsamp) continue;  // (the host checked every frame's samples against the window)
+      const uint32_t row = (uint32_t)p / (uint32_t)it.width, col = (uint32_t)p % (uint32_t)it.width;
+      const int64_t e = (int64_t)c * a.band_stride + ((int64_t)it.row_off + row) * a.row_stride +
+                        ((int64_t)it.col_off + col) * a.col_stride;
+      const int32_t want = fra::fetch_sample<SRC>(v.src, e, np), got = tile[f][lane];
+      if (want != got) {
+        const unsigned long long key = (p << 3) | (unsigned)c;
+        if (!v.pass) {
+          nbad++;
+          kmin = key < kmin ? key : kmin;
+        } else if (key == first) {
+          v.vals[2 * (size_t)grp.item] = want;
+          v.vals[2 * (size_t)grp.item + 1] = got;
+        }
+      }
+    }
+  }
+  if (nbad) {
+    atomicAdd(&res[0], nbad);
+    atomicMin(&res[1], kmin);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ host side
 struct ItemPlan {
   bool search = false;
@@ -591,6 +695,23 @@ int alloc_tables(HipArena& sc, DecArgs& a, size_t ni, size_t ng, uint64_t scratc
   a.samp0 = (const int64_t*)d_samp0;
   a.fail = (uint32_t*)d_fail;
   return FRA_OK;
+}
+
+// k_dec_verify's instance of the source dtype, over k_dec_scatter's grid
+void launch_verify(int dtype, dim3 grid, hipStream_t s, const DecArgs& a, const VerArgs& v) {
+  switch (dtype) {
+#define FRA_VERIFY_CASE(DT, ST) \
+  case DT: hipLaunchKernelGGL(k_dec_verify<fra::ST>, grid, dim3(256), 0, s, a, v); break;
+    FRA_VERIFY_CASE(FRA_U8, ST_U8)
+    FRA_VERIFY_CASE(FRA_I8, ST_I8)
+    FRA_VERIFY_CASE(FRA_U16, ST_U16)
+    FRA_VERIFY_CASE(FRA_I16, ST_I16)
+    FRA_VERIFY_CASE(FRA_U32, ST_U32)
+    FRA_VERIFY_CASE(FRA_I32, ST_I32)
+    FRA_VERIFY_CASE(FRA_F32, ST_F32)
+    FRA_VERIFY_CASE(FRA_F64, ST_F64)
+#undef FRA_VERIFY_CASE
+  }
 }
 
 }  // namespace
@@ -1152,6 +1273,186 @@ FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, co
     if (h_fail[k])
       return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
                                                    "(frame at byte %llu)", (unsigned long long)h_rel[k]);
+  keep_times(ev);
+  return FRA_OK;
+}
+
+// The verify entry (fra_verify.h): fra_decode_device's offsets path up to k_dec_restore, then k_dec_verify against
+// the source raster.  Hidden: fra_plan_verify is the public way in.
+int fra_internal_verify_device(fra_ctx* ctx, const uint8_t* data, uint64_t len, const fra_decode_item* items,
+                               int32_t nitems, int32_t channels, const fra_verify_source* src,
+                               const int32_t* first_frames, fra_verify_report* reports, int32_t* bad_windows) {
+  if (!ctx || !src || !reports || !bad_windows || nitems < 0 || (nitems && !items) || (!data && len))
+    return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  if (nitems && (!src->raster || !src->norm_rows)) return fra_internal_set_error(FRA_E_INVALID, "null argument");
+  if (src->dtype < FRA_U8 || src->dtype > FRA_F64) return fra_internal_set_error(FRA_E_INVALID, "bad dtype %d", src->dtype);
+  if (src->norm != 0 && src->norm != 16 && src->norm != 24)
+    return fra_internal_set_error(FRA_E_INVALID, "norm must be 0, 16 or 24");
+  if (src->norm == 0 && src->dtype != FRA_I16 && src->dtype != FRA_I32)
+    return fra_internal_set_error(FRA_E_INVALID, "norm == 0 needs int16 or int32 samples");
+  if (channels < 1 || channels > 8 || src->band_stride < 0 || src->row_stride < 0 || src->col_stride < 0)
+    return fra_internal_set_error(FRA_E_INVALID, "bad source layout (channels %d)", channels);
+  const int ni = nitems;
+  fra_decode_job job{};  // (what check_item reads)
+  job.data = data;
+  job.len = len;
+  job.items = items;
+  job.nitems = ni;
+  for (int i = 0; i < ni; i++) {
+    if (const int rc = check_item(&job, i)) return rc;
+    const fra_decode_item& it = items[i];
+    if (!it.frame_offsets) return fra_internal_set_error(FRA_E_INVALID, "item %d: verify needs frame offsets", i);
+    if (it.window.height < 0) return fra_internal_set_error(FRA_E_INVALID, "item %d: bad window", i);
+    if (it.channels != channels)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d has %d channels, the source %d", i, it.channels, channels);
+    const int64_t nsamp = (int64_t)it.window.height * it.window.width;
+    const int64_t nfr_all = (nsamp + it.blocksize - 1) / it.blocksize;
+    const int64_t first = first_frames ? first_frames[i] : 0;
+    if (first < 0 || first > nfr_all || it.nframes > nfr_all - first)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: frames %lld + %d lie past the window's %lld frames", i,
+                                    (long long)first, it.nframes, (long long)nfr_all);
+    if (!first_frames && it.nframes != nfr_all)
+      return fra_internal_set_error(FRA_E_INVALID, "item %d: %d frames, its window %d x %d holds %lld", i, it.nframes,
+                                    it.window.height, it.window.width, (long long)nfr_all);
+  }
+  memset(reports, 0, sizeof(fra_verify_report) * (size_t)ni);
+  for (int i = 0; i < ni; i++) reports[i].first_sample = -1;
+  *bad_windows = 0;
+  if (ni == 0) return FRA_OK;
+
+  int device = 0;
+  hipStream_t s = nullptr;
+  fra_internal_ctx_stream(ctx, &device, &s);
+  (void)hipSetDevice(device);
+  HipArena sc;  // device buffers and events of this call, released on every path
+  hipEvent_t ev[5] = {};
+
+  // ---- groups of 64 frames (a group never spans items), scratch layout
+  std::vector<DecItem> h_items((size_t)ni);
+  std::vector<DecGroup> h_groups;
+  std::vector<int32_t> first_group((size_t)ni);
+  uint64_t scratch_elems = 0;
+  int bs_max = 1;
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = items[i];
+    bs_max = std::max(bs_max, it.blocksize);
+    DecItem& di = h_items[(size_t)i];
+    di.end = it.offset + it.bytes;
+    di.channels = it.channels;
+    di.bps = it.bps;
+    di.sample_rate = 0;
+    di.bs_stride = it.blocksize;
+    di.row_off = it.window.row_off;
+    di.col_off = it.window.col_off;
+    di.width = it.window.width;
+    di.height = it.window.height;
+    di.dmin = 0.0;
+    di.span = 0.0;
+    first_group[(size_t)i] = (int32_t)h_groups.size();
+    for (int f = 0; f < it.nframes; f += kLanes) {
+      h_groups.push_back({scratch_elems, i, std::min(kLanes, it.nframes - f)});
+      scratch_elems += (uint64_t)it.channels * (uint64_t)it.blocksize * kLanes;
+    }
+  }
+  const size_t ng = h_groups.size();
+  if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "too many frames");
+  const size_t nslots = ng * kLanes;
+  std::vector<uint64_t> h_starts(std::max<size_t>(1, nslots), kNoFrame);
+  for (int i = 0; i < ni; i++)
+    for (int f = 0; f < items[i].nframes; f++)
+      h_starts[(size_t)first_group[(size_t)i] * kLanes + (size_t)f] = items[i].offset + items[i].frame_offsets[f];
+
+  DecArgs a{};
+  a.data = data;
+  a.band_stride = src->band_stride;
+  a.row_stride = src->row_stride;
+  a.col_stride = src->col_stride;
+  if (const int rc = alloc_tables(sc, a, (size_t)ni, ng, scratch_elems)) return rc;
+  VerArgs v{};
+  v.src = src->raster;
+  v.nd = (const fra::NormDev*)src->norm_rows;
+  v.norm = src->norm;
+  HIPCHK(sc.alloc(&v.res, sizeof(unsigned long long) * 2 * (size_t)ni));
+  HIPCHK(sc.alloc(&v.vals, sizeof(int32_t) * 2 * (size_t)ni));
+  for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
+  std::vector<unsigned long long> h_res(2 * (size_t)ni);
+  for (int i = 0; i < ni; i++) {
+    h_res[2 * (size_t)i] = 0;
+    h_res[2 * (size_t)i + 1] = ~0ull;
+  }
+  HIPCHK(hipMemcpyAsync((void*)a.items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(v.res, h_res.data(), sizeof(unsigned long long) * 2 * (size_t)ni, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(v.vals, 0, sizeof(int32_t) * 2 * (size_t)ni, s));
+  if (ng) {
+    HIPCHK(hipMemcpyAsync((void*)a.groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((void*)a.starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(a.fail, 0, sizeof(uint32_t) * nslots, s));
+  }
+
+  // ---- parse every frame; each must be one, of its offsets' length and of its position's sample count
+  std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
+  if (const int rc = parse_candidates(a, ng, h_fout.data(), ev, s)) return rc;
+  std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
+  for (int i = 0; i < ni; i++) {
+    const fra_decode_item& it = items[i];
+    const size_t g0 = (size_t)first_group[(size_t)i] * kLanes;
+    const int64_t nsamp = (int64_t)it.window.height * it.window.width;
+    int64_t at = (int64_t)(first_frames ? first_frames[i] : 0) * it.blocksize;
+    for (int f = 0; f < it.nframes; f++) {
+      const FrameOut& fo = h_fout[g0 + (size_t)f];
+      if (fo.status == ST_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
+      if (fo.status != ST_OK || fo.len != it.frame_offsets[f + 1] - it.frame_offsets[f] ||
+          fo.n != std::min<int64_t>(it.blocksize, nsamp - at))
+        return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
+                                      (unsigned long long)it.frame_offsets[f]);
+      h_samp0[g0 + (size_t)f] = at;
+      at += fo.n;
+    }
+    reports[i].nframes = it.nframes;
+  }
+
+  // ---- restore, compare
+  std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
+  const dim3 grid((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes));
+  if (ng) {
+    HIPCHK(hipMemcpyAsync((void*)a.samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev[2], s));
+    hipLaunchKernelGGL(k_dec_restore<false>, dim3((unsigned)ng, (unsigned)channels), dim3(kLanes), 0, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[3], s));
+    launch_verify(src->dtype, grid, s, a, v);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[4], s));
+    HIPCHK(hipMemcpyAsync(h_fail.data(), a.fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_res.data(), v.res, sizeof(unsigned long long) * 2 * (size_t)ni, hipMemcpyDeviceToHost, s));
+  } else {
+    for (int k = 2; k < 5; k++) HIPCHK(hipEventRecord(ev[k], s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  for (size_t k = 0; k < nslots; k++)
+    if (h_fail[k])
+      return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
+                                                   "(frame at byte %llu)", (unsigned long long)h_starts[k]);
+  int bad = 0;
+  for (int i = 0; i < ni; i++) bad += h_res[2 * (size_t)i] != 0;
+  if (bad) {  // the rare path: both samples at every bad item's first mismatch
+    std::vector<int32_t> h_vals(2 * (size_t)ni);
+    v.pass = 1;
+    launch_verify(src->dtype, grid, s, a, v);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_vals.data(), v.vals, sizeof(int32_t) * 2 * (size_t)ni, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < ni; i++) {
+      if (!h_res[2 * (size_t)i]) continue;
+      fra_verify_report& r = reports[i];
+      r.mismatches = h_res[2 * (size_t)i];
+      r.first_sample = (int64_t)(h_res[2 * (size_t)i + 1] >> 3);
+      r.first_channel = (int32_t)(h_res[2 * (size_t)i + 1] & 7);
+      r.expected = h_vals[2 * (size_t)i];
+      r.got = h_vals[2 * (size_t)i + 1];
+    }
+  }
+  *bad_windows = bad;
   keep_times(ev);
   return FRA_OK;
 }

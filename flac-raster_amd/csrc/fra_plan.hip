@@ -8,6 +8,7 @@
 #include <new>
 
 #include "fra_plan.h"
+#include "fra_verify.h"
 
 namespace fra {
 int frame_scan_blocks(int nframes);
@@ -431,6 +432,46 @@ int fra_plan_device_output(fra_plan* p, const uint8_t** dev_ptr, uint64_t* capac
   *dev_ptr = p->d_out;
   *capacity = p->out_cap;
   return FRA_OK;
+}
+
+int fra_plan_verify(fra_plan* p, fra_verify_report* reports, int32_t* bad_windows) {
+  if (!p || !reports || !bad_windows) return set_err(FRA_E_INVALID, "null argument");
+  if (!p->executed) return set_err(FRA_E_STATE, "plan not executed");
+  (void)hipSetDevice(p->ctx->device);
+  if (int rc = plan_sync_all(p)) return rc;
+  // the last execute's frames: its slot set's offsets, relative to each window's first frame
+  const size_t nfr = (size_t)p->args.nframes_total, nst = p->streams.size();
+  std::vector<uint64_t> off(nfr + 1);
+  HIPCHK(hipMemcpy(off.data(), p->args.frame_off, sizeof(uint64_t) * (nfr + 1), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> rel(nfr + nst + 1);
+  std::vector<fra_decode_item> items(nst);
+  std::vector<int32_t> first(nst, 0);
+  for (size_t s = 0; s < nst; s++) {
+    const StreamDev& st = p->streams[s];
+    uint64_t* r = rel.data() + st.first_frame + s;
+    for (int f = 0; f <= st.nframes; f++) r[f] = off[(size_t)st.first_frame + f] - off[st.first_frame];
+    fra_decode_item& it = items[s];
+    it = fra_decode_item{};
+    it.offset = off[st.first_frame];
+    it.bytes = r[st.nframes];
+    it.window = p->windows[s];
+    it.frame_offsets = r;
+    it.nframes = st.nframes;
+    it.channels = st.channels;
+    it.bps = st.bps;
+    it.blocksize = p->job.blocksize;
+    if (st.nframes) first[s] = p->frames[st.first_frame].index;  // (a ranged plan's first frame of the stream)
+  }
+  fra_verify_source src{};
+  src.raster = p->d_raster;
+  src.dtype = p->job.dtype;
+  src.norm = p->job.norm;
+  src.band_stride = p->job.band_stride;
+  src.row_stride = p->job.row_stride;
+  src.col_stride = p->job.col_stride;
+  src.norm_rows = p->nset[p->curn].norm;  // the last execute's min / max keys, read on the device
+  return fra_internal_verify_device(p->ctx, p->d_out, off[nfr], items.data(), (int32_t)nst, p->job.channels, &src,
+                                    first.data(), reports, bad_windows);
 }
 
 int fra_plan_enable_timing(fra_plan* p, int32_t on) {

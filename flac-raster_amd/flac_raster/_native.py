@@ -41,6 +41,22 @@ class OutputTooSmall(NativeError):
         self.needed = needed
 
 
+class VerifyMismatch(NativeError):
+    """Verify found decoded samples that differ from the normalised input (``Plan.verify``, ``verify=True``).
+
+    ``tile``: index of the first bad window of the call; ``pixel``: ``(row, col, band)`` of its first mismatch in
+    raster coordinates; ``expected`` / ``got``: the normalised input sample and the decoded one there;
+    ``mismatches``: differing samples of that tile; ``bad_tiles``: tiles with mismatches."""
+
+    def __init__(self, tile: int, pixel: Tuple[int, int, int], expected: int, got: int, mismatches: int,
+                 bad_tiles: int = 1):
+        super().__init__(f"verify: tile {tile} differs from its input at pixel (row {pixel[0]}, col {pixel[1]}, "
+                         f"band {pixel[2]}): expected sample {expected}, decoded {got}; {mismatches} samples differ "
+                         f"in this tile, {bad_tiles} tile(s) differ")
+        self.tile, self.pixel, self.expected, self.got = tile, tuple(pixel), expected, got
+        self.mismatches, self.bad_tiles = mismatches, bad_tiles
+
+
 class Window(C.Structure):
     _fields_ = [("row_off", C.c_int32), ("col_off", C.c_int32), ("height", C.c_int32), ("width", C.c_int32)]
 
@@ -65,6 +81,13 @@ class Decoded(C.Structure):
     _fields_ = [
         ("sample_rate", C.c_int32), ("channels", C.c_int32), ("bps", C.c_int32), ("blocksize", C.c_int32),
         ("nframes", C.c_int64), ("nsamples", C.c_uint64), ("nstreams", C.c_int32), ("audio_offset", C.c_uint64),
+    ]
+
+
+class VerifyReport(C.Structure):
+    _fields_ = [
+        ("mismatches", C.c_uint64), ("first_sample", C.c_int64), ("first_channel", C.c_int32),
+        ("expected", C.c_int32), ("got", C.c_int32), ("nframes", C.c_int32),
     ]
 
 
@@ -112,7 +135,7 @@ EXPORTS = [
     "fra_host_register", "fra_host_unregister", "fra_tiff_decode", "fra_plan_set_first_frame",
     "fra_plan_flags", "fra_plan_encode_host_progress", "fra_tiff_compress_bound", "fra_tiff_compress",
     "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
-    "fra_decode_device_timing", "fra_decode_device_window",
+    "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify",
 ]
 
 
@@ -177,6 +200,8 @@ def load():
         L.fra_decode_device.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Decoded)]
         L.fra_decode_device_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_decode_device_window.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(Decoded)]
+        if hasattr(L, "fra_plan_verify"):  # (older builds load for same-box A/Bs)
+            L.fra_plan_verify.argtypes = [vp, C.POINTER(VerifyReport), C.POINTER(i32)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -566,6 +591,17 @@ class Plan:
         _check(load().fra_plan_device_output(self.h, C.byref(p), C.byref(cap)))
         return p.value, cap.value
 
+    def verify(self) -> List[VerifyReport]:
+        """libFLAC's verify mode for this plan (``fra_plan_verify``): decode the frames of the last execute /
+        ``encode_host`` / ``encode_ring`` on the GPU and compare every sample with the plan's current raster,
+        normalised anew.  One :class:`VerifyReport` per window (``mismatches == 0`` and ``first_sample == -1`` when
+        clean); a frame that does not parse or fails its CRC-16 raises :class:`NativeError`.  No second raster is
+        allocated.  :func:`raise_on_mismatch` turns the reports into :class:`VerifyMismatch`."""
+        reports = (VerifyReport * max(1, self.nwin))()
+        bad = C.c_int32()
+        _check(load().fra_plan_verify(self.h, reports, C.byref(bad)))
+        return list(reports)[: self.nwin]
+
     def enable_timing(self, on: bool = True):
         _check(load().fra_plan_enable_timing(self.h, 1 if on else 0))
 
@@ -585,6 +621,24 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+def mismatch_pixel(window, first_sample: int, first_channel: int) -> Tuple[int, int, int]:
+    """``(row, col, band)`` in raster coordinates of sample ``first_sample`` (window-relative pixel index, row-major)
+    of channel ``first_channel`` of ``window`` (row_off, col_off, height, width)."""
+    r0, c0, _, w = (int(v) for v in window)
+    return r0 + int(first_sample) // w, c0 + int(first_sample) % w, int(first_channel)
+
+
+def raise_on_mismatch(reports: Sequence[VerifyReport], windows):
+    """Raise :class:`VerifyMismatch` for the first report with mismatches (``windows``: the plan's windows)."""
+    bad = [k for k, r in enumerate(reports) if r.mismatches]
+    if not bad:
+        return
+    k = bad[0]
+    r = reports[k]
+    pixel = mismatch_pixel(windows[k], r.first_sample, r.first_channel)
+    raise VerifyMismatch(k, pixel, int(r.expected), int(r.got), int(r.mismatches), len(bad))
 
 
 _default_ctx = {}
@@ -640,7 +694,7 @@ def _element_strides(a: np.ndarray) -> Tuple[int, int, int]:
 
 def encode_windows_buffer(raster: np.ndarray, windows, level: int = 5, blocksize: int = 4096, norm: int = 16,
                           sample_rate: int = 0, device: int = 0, pinned: bool = True,
-                          rows_ready: Optional[np.ndarray] = None, frame_ranges=None):
+                          rows_ready: Optional[np.ndarray] = None, frame_ranges=None, verify: bool = False):
     """Encode windows of a band-planar host raster ``(B, H, W)`` (any non-negative strides, e.g. a row
     band view of a larger raster) through the pipelined host path (``fra_plan_encode_host``).
 
@@ -648,7 +702,8 @@ def encode_windows_buffer(raster: np.ndarray, windows, level: int = 5, blocksize
     every window's FLAC frames concatenated in window order; ``infos[i].offset/.frame_bytes`` slice it.
     ``rows_ready``: the raster is still being filled by a producer thread that publishes the rows done
     in ``rows_ready[0]`` (``fra_plan_encode_host_progress``).  ``frame_ranges``: (first frame, count) per
-    window (``fra_plan_create_ranged``).
+    window (``fra_plan_create_ranged``).  ``verify``: decode the plan's frames on the GPU and compare them with the
+    plan's copy of the raster before the plan is closed (:meth:`Plan.verify`); raises :class:`VerifyMismatch`.
     """
     a = np.asarray(raster)
     if a.ndim == 2:
@@ -665,6 +720,8 @@ def encode_windows_buffer(raster: np.ndarray, windows, level: int = 5, blocksize
         cap, _ = plan.capacity()
         out = pinned_empty(cap, np.uint8) if pinned else np.empty(cap, np.uint8)
         total = plan.encode_host(a, out) if rows_ready is None else plan.encode_host_progress(a, out, rows_ready)
+        if verify:
+            raise_on_mismatch(plan.verify(), plan.windows)
         infos, _ = plan.result()
         return infos, out[:total]
     finally:
@@ -681,13 +738,16 @@ def ring_rows_for(band_rows: int, step: int, height: int) -> int:
 
 
 def encode_windows_ring(shape, dtype, windows, fill, level: int = 5, blocksize: int = 4096, norm: int = 16,
-                        sample_rate: int = 0, device: int = 0, step: int = 0, ring_rows: int = 0):
+                        sample_rate: int = 0, device: int = 0, step: int = 0, ring_rows: int = 0,
+                        verify: bool = False):
     """Encode windows of a band-planar raster of ``shape`` ``(B, H, W)`` that never exists whole in host
     memory (``fra_plan_encode_ring``): a producer thread calls ``fill(dst, r0, r1)`` to write image rows
     ``[r0, r1)`` of every band into ``dst`` (a ``(B, r1 - r0, W)`` view of a page-locked ring), in steps of
     ``step`` rows (default: the tallest host band), top to bottom; each step waits until the encoder's H2D
     copies have released its ring rows.  Host memory: the ring (``ring_rows`` rows, default
     :func:`ring_rows_for`) + the frames (a lazily committed buffer: only the written bytes are resident).
+
+    ``verify``: as :func:`encode_windows_buffer` (the plan's device copy holds the whole raster after the pass).
 
     Returns ``(infos, frames, ring_rows)`` as :func:`encode_windows_buffer` (``frames`` not page-locked)."""
     B, H, W = shape
@@ -745,6 +805,8 @@ def encode_windows_ring(shape, dtype, windows, fill, level: int = 5, blocksize: 
         th.join()
         if errors:
             raise errors[0]
+        if verify:
+            raise_on_mismatch(plan.verify(), plan.windows)
         infos, _ = plan.result()
         return infos, out[:total], R
     finally:

@@ -18,6 +18,7 @@ from rich.console import Console
 from rich.logging import RichHandler
 from rich.table import Table
 
+from ._native import VerifyMismatch
 from .compare import compare_tiffs, display_comparison_table
 from .converter import RasterFLACConverter
 
@@ -64,6 +65,8 @@ def convert(
     force: bool = typer.Option(False, "--force", "-f", help="Overwrite existing output file"),
     verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose logging"),
     devices: Optional[str] = typer.Option(None, "--devices", help="GPU ids to split tiles over, e.g. 0,1,2,3"),
+    verify: bool = typer.Option(False, "--verify", help="TIFF to FLAC: decode every frame on the GPU and compare it "
+                                                        "with the input before the output is written"),
 ):
     """Convert between TIFF and FLAC formats."""
     if verbose:
@@ -88,10 +91,13 @@ def convert(
             console.print(f"[red]Error: Output exists: {output_file}[/red]")
             raise typer.Exit(1)
         devs = _devices(devices)
+        if verify and direction != "tiff_to_flac":
+            console.print("[red]Error: --verify applies to TIFF -> FLAC conversions[/red]")
+            raise typer.Exit(1)
         if streaming and direction == "tiff_to_flac":
             from .streaming import create_streaming_flac
 
-            idx = create_streaming_flac(src, output_file, tile_size, compression_level, devs)
+            idx = create_streaming_flac(src, output_file, tile_size, compression_level, devs, verify=verify)
             console.print(f"[green]Created streaming FLAC: {output_file} ({len(idx['frames'])} tiles, "
                           f"{output_file.stat().st_size / 1024 / 1024:.2f} MB)[/green]")
             return
@@ -106,13 +112,18 @@ def convert(
                 return
         conv = RasterFLACConverter(devices=devs)
         if direction == "tiff_to_flac":
-            res = conv.tiff_to_flac(src, output_file, compression_level, spatial, tile_size)
+            res = conv.tiff_to_flac(src, output_file, compression_level, spatial, tile_size, verify=verify)
             if spatial and res:
                 console.print(f"[green]Created {len(res.frames)} spatial tiles[/green]")
         else:
             conv.flac_to_tiff(src, output_file)
     except typer.Exit:
         raise
+    except VerifyMismatch as e:
+        console.print(f"[red]Verify failed: tile {e.tile}, pixel row {e.pixel[0]} col {e.pixel[1]} band {e.pixel[2]}: "
+                      f"expected sample {e.expected}, decoded {e.got} ({e.mismatches} samples differ in this tile, "
+                      f"{e.bad_tiles} tile(s) differ)[/red]")
+        raise typer.Exit(1)
     except Exception as e:
         logger.exception("Conversion failed")
         console.print(f"[red]Error: {e}[/red]")

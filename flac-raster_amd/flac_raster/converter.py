@@ -80,7 +80,9 @@ class RasterFLACConverter:
         self.devices = list(devices) if devices else None
 
     def tiff_to_flac(self, tiff_path: Path, flac_path: Path, compression_level: int = 5,
-                     spatial_tiling: bool = False, tile_size: int = 512):
+                     spatial_tiling: bool = False, tile_size: int = 512, verify: bool = False):
+        """``verify``: decode the encoded frames on the GPU and compare them with the raster before the file is
+        written (``tiles.encode_tiles``; raises ``VerifyMismatch``)."""
         tiff_path, flac_path = Path(tiff_path), Path(flac_path)
         self.logger.info(f"Starting TIFF to FLAC conversion: {tiff_path} -> {flac_path}")
         if spatial_tiling:
@@ -88,7 +90,7 @@ class RasterFLACConverter:
 
             console.print("[cyan]Using spatial tiling for HTTP range streaming[/cyan]")
             enc = SpatialFLACEncoder(tile_size=tile_size, devices=self.devices)
-            return enc.encode_spatial_flac(tiff_path, flac_path, compression_level)
+            return enc.encode_spatial_flac(tiff_path, flac_path, compression_level, verify=verify)
         console.print(f"[cyan]Reading TIFF file: {tiff_path}[/cyan]")
         g = GeoTIFF(tiff_path)
         data = g.read()
@@ -97,7 +99,7 @@ class RasterFLACConverter:
         console.print(f"[green]Raster info: {info.width}x{info.height}, {info.count} band(s), "
                       f"dtype: {info.dtype}[/green]")
         console.print(f"[yellow]Using sample rate: {sample_rate}Hz, bit depth: {bps}[/yellow]")
-        ts = encode_tiles(data, [(0, 0, info.height, info.width)], compression_level, self.devices)[0]
+        ts = encode_tiles(data, [(0, 0, info.height, info.width)], compression_level, self.devices, verify=verify)[0]
         assert ts.sample_rate == sample_rate
         meta = raster_metadata(info.width, info.height, info.count, data.dtype, info.crs, Affine(*info.transform),
                                ts.data_min, ts.data_max, info.nodata, 32767 if bps == 16 else 8388607)

@@ -177,18 +177,21 @@ def rank_items(tiles: Sequence[Tuple[int, int, int, int]], world: int, rank: int
 
 def encode_tiles_distributed(raster, tiles: Sequence[Tuple[int, int, int, int]], level: int = 5,
                              d: Optional[Dist] = None, encode_fn: EncodeFn = encode_tiles,
-                             dst: int = 0, split: str = "frames") -> Optional[List[TileStream]]:
+                             dst: int = 0, split: str = "frames", verify: bool = False) -> Optional[List[TileStream]]:
     """Each rank encodes its work items (``rank_items``) on its local GPU; ``dst`` receives every stream in
     tile order (other ranks get ``None``): the frames of a tile split over ranks are concatenated in frame
     order, which is exactly the tile's stream.  Bytes are identical for any world size and split.
     ``raster`` is an in-memory (bands, H, W) array, or a GeoTIFF path / ``GeoTIFF``: then every rank
     decodes only the windows of its own tiles (``read_rank_mosaic``), never the whole scene.  ``encode_fn``
-    takes ``frame_ranges=`` when a rank holds part of a tile."""
+    takes ``frame_ranges=`` when a rank holds part of a tile, and ``verify=`` when ``verify`` is set: every rank then
+    verifies its own (ranged) plan over its own frames (``tiles.encode_tiles``)."""
     d = d or Dist()
     items = rank_items(tiles, d.world, d.rank, split)
     mine = [i for i, _, _ in items]
     whole = all(f0 == 0 and n >= frames_of(tiles[i]) for i, f0, n in items)
     kw = {} if whole else {"frame_ranges": [(f0, n) for _, f0, n in items]}
+    if verify:
+        kw["verify"] = True
     if isinstance(raster, (str, os.PathLike)) or type(raster).__name__ == "GeoTIFF":
         mosaic, local = read_rank_mosaic(raster, [tiles[i] for i in mine], pinned=encode_fn is encode_tiles)
         streams = encode_fn(mosaic, local, level, [d.local_rank], **kw) if mine else []

@@ -25,6 +25,10 @@ Drop-in for the two reference call sites::
   not in this container; that timing rule is restated from the public libFLAC sources and is not
   pinned by a fixture here.  Bytes are independent of how the samples are split across calls.
 * GPU plans are cached per block count, so repeated calls of one size reuse their device workspace.
+* ``verify=True`` is libFLAC's verify mode: the frames of every ``process()`` / ``finish()`` are decoded on the GPU
+  and compared with their input samples (``Plan.verify``) before any of them reaches the write callback; a mismatch
+  sets ``VERIFY_MISMATCH_IN_AUDIO_DATA``, a frame that does not decode ``VERIFY_DECODER_ERROR``, and both raise
+  ``EncoderProcessException``.
 """
 
 from __future__ import annotations
@@ -196,11 +200,28 @@ class StreamEncoder:
         except _native.NativeError as e:
             self._state = EncoderState.MEMORY_ALLOCATION_ERROR
             raise EncoderProcessException(str(e)) from e
+        if self._verify:
+            self._verify_plan(plan)
         mv = memoryview(out)
         for i in range(nfr):
             a, b = int(offsets[i]), int(offsets[i + 1])
             self._emit(bytes(mv[a:b]), min(self._bs, n - i * self._bs), self._next_frame + i)
         self._next_frame += nfr
+
+    def _verify_plan(self, plan):
+        """libFLAC's verify mode: decode the frames just encoded on the GPU and compare them with the samples they
+        were made from (``Plan.verify``), before any of them reaches the write callback."""
+        try:
+            rep = plan.verify()[0]
+        except _native.NativeError as e:
+            self._state = EncoderState.VERIFY_DECODER_ERROR
+            raise EncoderProcessException(f"{self._state}: {e}") from e
+        if rep.mismatches:
+            self._state = EncoderState.VERIFY_MISMATCH_IN_AUDIO_DATA
+            at = self._next_frame * self._bs + int(rep.first_sample)
+            raise EncoderProcessException(
+                f"{self._state}: sample {at} (frame {at // self._bs}), channel {rep.first_channel}: expected "
+                f"{rep.expected}, got {rep.got}; {rep.mismatches} samples of this call differ")
 
     def close(self):
         """Hand this encoder's GPU plans back to the process-wide pool (the next encoder of the same

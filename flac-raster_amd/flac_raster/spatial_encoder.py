@@ -126,14 +126,15 @@ class SpatialFLACEncoder:
         return tile_bbox(transform, row_off, col_off, height, width)
 
     def encode_spatial_flac(self, tiff_path: Path, flac_path: Path, compression_level: int = 5,
-                            enable_streaming: bool = True) -> SpatialIndex:
+                            enable_streaming: bool = True, verify: bool = False) -> SpatialIndex:
+        """``verify``: as ``tiles.encode_tiles`` (raises ``VerifyMismatch`` before the file is written)."""
         g = GeoTIFF(tiff_path)
         raster = g.read()
         info = g.info
         transform = Affine(*info.transform)
         crs = CRS(info.crs) if info.crs else None
         tiles = self._calculate_tiles(info.height, info.width)
-        streams = encode_tiles(raster, tiles, compression_level, self.devices)
+        streams = encode_tiles(raster, tiles, compression_level, self.devices, verify=verify)
         self.frames, self.bytes_written = [], 0
         for i, ((r, c, h, w), ts) in enumerate(zip(tiles, streams)):
             fr = SpatialFrame(i, self._tile_to_bbox(r, c, h, w, transform), Window(c, r, w, h), self.bytes_written,

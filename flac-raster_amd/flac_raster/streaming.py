@@ -79,11 +79,13 @@ def assemble_streaming(tiles: Sequence[Tuple[int, int, int, int]], streams: Sequ
 
 
 def build_streaming(raster: np.ndarray, transform: Affine, crs: Optional[str], tile_size: int,
-                    compression_level: int = 5, devices: Optional[Sequence[int]] = None) -> bytes:
-    """Container bytes for a band-planar ``(B, H, W)`` raster (all tiles on the GPU(s))."""
+                    compression_level: int = 5, devices: Optional[Sequence[int]] = None,
+                    verify: bool = False) -> bytes:
+    """Container bytes for a band-planar ``(B, H, W)`` raster (all tiles on the GPU(s)); ``verify`` as
+    ``tiles.encode_tiles``."""
     a = raster if raster.ndim == 3 else raster[None]
     tiles = calculate_tiles(a.shape[1], a.shape[2], tile_size)
-    streams = encode_tiles(a, tiles, compression_level, devices)
+    streams = encode_tiles(a, tiles, compression_level, devices, verify=verify)
     return assemble_streaming(tiles, streams, a.shape, a.dtype, transform, crs, tile_size)
 
 
@@ -125,7 +127,7 @@ def decode_step(g: GeoTIFF, tile_size: int) -> int:
 
 
 def encode_geotiff_ring(g: GeoTIFF, tiles, compression_level: int = 5, device: int = 0, tile_size: int = 512,
-                        ring_rows: int = 0):
+                        ring_rows: int = 0, verify: bool = False):
     """GeoTIFF -> tile streams with bounded host memory: the file's row bands are decoded into a
     page-locked ring (``tiles.encode_tiles_ring``) that the pipelined encoder copies from and recycles, so
     the raster is never held whole -- as the reference, which reads one tile window at a time
@@ -136,11 +138,11 @@ def encode_geotiff_ring(g: GeoTIFF, tiles, compression_level: int = 5, device: i
         g.read_window_into(dst, r0, 0, r1 - r0, info.width)
 
     return encode_tiles_ring((info.count, info.height, info.width), info.dtype, tiles, fill, compression_level,
-                             device, step=decode_step(g, tile_size), ring_rows=ring_rows)
+                             device, step=decode_step(g, tile_size), ring_rows=ring_rows, verify=verify)
 
 
 def encode_geotiff_streaming(input_path: Path, tile_size: int = 512, compression_level: int = 5,
-                             devices: Optional[Sequence[int]] = None, ring: bool = True):
+                             devices: Optional[Sequence[int]] = None, ring: bool = True, verify: bool = False):
     """GeoTIFF file -> (tiles, streams, raster info): decode and encode overlapped.  One device: through
     the bounded ring (``encode_geotiff_ring``); several: the whole raster is decoded into page-locked
     memory (``decode_while_encoding``) and split over the devices."""
@@ -149,7 +151,8 @@ def encode_geotiff_streaming(input_path: Path, tile_size: int = 512, compression
         try:
             info = g.info
             tiles = calculate_tiles(info.height, info.width, tile_size)
-            streams, _ = encode_geotiff_ring(g, tiles, compression_level, devices[0] if devices else 0, tile_size)
+            streams, _ = encode_geotiff_ring(g, tiles, compression_level, devices[0] if devices else 0, tile_size,
+                                             verify=verify)
             return tiles, streams, (info.count, info.height, info.width), np.dtype(info.dtype), info
         finally:
             g.close()
@@ -157,7 +160,8 @@ def encode_geotiff_streaming(input_path: Path, tile_size: int = 512, compression
     try:
         tiles = calculate_tiles(raster.shape[1], raster.shape[2], tile_size)
         try:
-            streams = encode_tiles(raster, tiles, compression_level, devices, rows_ready=rows_ready, producer=th)
+            streams = encode_tiles(raster, tiles, compression_level, devices, rows_ready=rows_ready, producer=th,
+                                   verify=verify)
         finally:
             th.join()
         if th.errors:  # type: ignore[attr-defined]
@@ -168,13 +172,16 @@ def encode_geotiff_streaming(input_path: Path, tile_size: int = 512, compression
 
 
 def create_streaming_flac(input_path: Path, output_path: Path, tile_size: int = 512, compression_level: int = 5,
-                          devices: Optional[Sequence[int]] = None) -> Dict:
+                          devices: Optional[Sequence[int]] = None, verify: bool = False) -> Dict:
     """Write the streaming container for a GeoTIFF; returns the index.
 
     The raster is decoded into page-locked memory by a producer thread, row band by row band, while the
     pipelined host path encodes the bands already decoded (H2D, kernels and D2H of band b overlap the
-    decode of band b+1); the container is written from zero-copy views of the page-locked frames."""
-    tiles, streams, shape, dtype, info = encode_geotiff_streaming(input_path, tile_size, compression_level, devices)
+    decode of band b+1); the container is written from zero-copy views of the page-locked frames.  ``verify``:
+    every plan's frames are decoded on the GPU and compared with the raster before anything is written
+    (``tiles.encode_tiles``; raises ``VerifyMismatch``)."""
+    tiles, streams, shape, dtype, info = encode_geotiff_streaming(input_path, tile_size, compression_level, devices,
+                                                                  verify=verify)
     parts = streaming_parts(tiles, streams, shape, dtype, Affine(*info.transform), info.crs, tile_size)
     with open(output_path, "wb") as f:
         for p in parts:

@@ -171,8 +171,17 @@ def norm_bits(dtype) -> int:
     return 16 if np.dtype(dtype) in (np.uint8, np.int8, np.uint16, np.int16) else 24
 
 
+def mismatch_pixel(window: Tuple[int, int, int, int], first_sample: int, first_channel: int) -> Tuple[int, int, int]:
+    """``(row, col, band)`` in raster coordinates of a verify report's first mismatch: ``first_sample`` is the
+    window-relative pixel index (row-major over the window's own width, ragged edge tiles included) and
+    ``first_channel`` the band; ``window`` is (row_off, col_off, height, width)."""
+    return _native.mismatch_pixel(window, first_sample, first_channel)
+
+
 def _encode_group(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]], level: int, device: int,
-                  norm: int, out: list, errors: list, slot: int, rows_ready=None, frame_ranges=None):
+                  norm: int, out: list, errors: list, slot: int, rows_ready=None, frame_ranges=None,
+                  verify: bool = False, tile0: int = 0):
+    r0 = 0
     try:
         r0 = min(t[0] for t in tiles)
         r1 = max(t[0] + t[2] for t in tiles)
@@ -182,8 +191,11 @@ def _encode_group(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]]
             raise ValueError("rows_ready needs the group to start at raster row 0")
         infos, frames = _native.encode_windows_buffer(sub, wins, level=level, blocksize=BLOCKSIZE, norm=norm,
                                                       device=device, rows_ready=rows_ready,
-                                                      frame_ranges=frame_ranges)
+                                                      frame_ranges=frame_ranges, verify=verify)
         out[slot] = streams_from(infos, frames)
+    except _native.VerifyMismatch as e:  # from the group's rows and tiles to the raster's
+        errors.append(_native.VerifyMismatch(tile0 + e.tile, (e.pixel[0] + r0, e.pixel[1], e.pixel[2]), e.expected,
+                                             e.got, e.mismatches, e.bad_tiles))
     except BaseException as e:  # re-raised on the calling thread
         errors.append(e)
 
@@ -200,22 +212,24 @@ def streams_from(infos, frames) -> List[TileStream]:
 
 
 def encode_tiles_ring(shape, dtype, tiles: Sequence[Tuple[int, int, int, int]], fill, level: int = 5,
-                      device: int = 0, step: int = 0, ring_rows: int = 0) -> Tuple[List[TileStream], int]:
+                      device: int = 0, step: int = 0, ring_rows: int = 0,
+                      verify: bool = False) -> Tuple[List[TileStream], int]:
     """:func:`encode_tiles` for a raster that is produced row band by row band and never held whole
     (``_native.encode_windows_ring``): ``fill(dst, r0, r1)`` writes image rows ``[r0, r1)`` of every band
-    into ``dst``.  The reference reads each tile's window the same way (``cli.py:553-559``).  Returns the
-    streams and the ring's height in rows."""
+    into ``dst``.  The reference reads each tile's window the same way (``cli.py:553-559``).  ``verify``: as
+    :func:`encode_tiles`.  Returns the streams and the ring's height in rows."""
     if not tiles:
         return [], 0
     infos, frames, R = _native.encode_windows_ring(shape, dtype, tiles, fill, level=level, blocksize=BLOCKSIZE,
                                                    norm=norm_bits(dtype), device=device, step=step,
-                                                   ring_rows=ring_rows)
+                                                   ring_rows=ring_rows, verify=verify)
     return streams_from(infos, frames), R
 
 
 def encode_tiles(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]], level: int = 5,
                  devices: Optional[Sequence[int]] = None, rows_ready=None,
-                 producer: Optional[threading.Thread] = None, frame_ranges=None) -> List[TileStream]:
+                 producer: Optional[threading.Thread] = None, frame_ranges=None,
+                 verify: bool = False) -> List[TileStream]:
     """Encode every tile of a band-planar ``(B, H, W)`` raster as its own FLAC stream on the GPU(s).
 
     Each stream equals what ``normalize_to_audio`` + ``pyflac.StreamEncoder(blocksize=4096)``
@@ -224,6 +238,9 @@ def encode_tiles(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]],
     rows done in ``rows_ready[0]``; one device encodes as the rows land, several wait for the producer.
     ``frame_ranges``: (first frame, count) per tile -- only those frames of each stream (one device; the
     multi-GPU work items of ``frame_split``); the TileStream's body then holds just those frames.
+    ``verify``: libFLAC's verify mode -- every plan's frames are decoded on its GPU and compared with its copy of the
+    raster, normalised anew, before the plan is closed (``_native.Plan.verify``); a difference raises
+    ``_native.VerifyMismatch`` with the tile, the pixel and both samples, a frame that does not decode ``NativeError``.
     """
     a = np.asarray(raster)
     if a.ndim == 2:
@@ -248,11 +265,12 @@ def encode_tiles(raster: np.ndarray, tiles: Sequence[Tuple[int, int, int, int]],
     if frame_ranges is not None:
         if len(devs) != 1:
             raise ValueError("frame_ranges: one device per call (one rank per GPU)")
-        _encode_group(a, tiles, level, devs[0], norm, out, errors, 0, rows_ready, frame_ranges)
+        _encode_group(a, tiles, level, devs[0], norm, out, errors, 0, rows_ready, frame_ranges, verify)
     elif len(runs) == 1:
-        _encode_group(a, tiles, level, devs[0], norm, out, errors, 0, rows_ready)
+        _encode_group(a, tiles, level, devs[0], norm, out, errors, 0, rows_ready, None, verify)
     else:
-        th = [threading.Thread(target=_encode_group, args=(a, tiles[s:e], level, devs[k], norm, out, errors, k))
+        th = [threading.Thread(target=_encode_group,
+                               args=(a, tiles[s:e], level, devs[k], norm, out, errors, k, None, None, verify, s))
               for k, (s, e) in enumerate(runs)]
         for t in th:
             t.start()
@@ -285,7 +303,9 @@ def verify_on_device(plan: "_native.Plan", raster_ptr: int,
     plans / int32 otherwise, laid out like the plan's raster, or with other element ``strides``) without copying the
     frames to the host: the frames are addressed through ``fra_plan_frame_offsets``, nothing is searched.  Returns True
     when every frame parsed with a matching CRC-16 (a corrupt frame raises ``NativeError``).  The library offers the
-    decode; comparing the samples with the expectation stays with the caller."""
+    decode; comparing the samples with the expectation stays with the caller -- or with ``Plan.verify``
+    (``fra_plan_verify``), which decodes the same way and compares on the GPU with the plan's own raster, without a
+    destination buffer."""
     infos, data, items = _plan_items(plan)
     if not items:
         return True

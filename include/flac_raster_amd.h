@@ -301,6 +301,30 @@ FRA_API int fra_decode_device_window(fra_ctx *ctx, const fra_decode_job *job, co
  * host chain) */
 FRA_API int fra_decode_device_timing(float *ms4);
 
+/* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
+ * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
+ * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the
+ * plan's own copy of a host raster) normalised anew by the plain f64 operation sequence with the min / max of the last
+ * execute, read on the device (k_dec_verify; norm == 0: the raw int16 / int32).  No second raster is allocated and
+ * nothing is written back; scratch is that of fra_decode_device, allocated per call and freed on every path.
+ *   Returns FRA_OK whether or not samples differ: a mismatch is a result.  reports[w] describes window w and
+ * *bad_windows counts the windows with mismatches > 0.  first_sample / first_channel name the first mismatch in the
+ * stream's sample order (pixel, then channel); first_sample is the window-relative pixel index (row = first_sample /
+ * width, column = first_sample % width of the window), also for a ranged plan (fra_plan_create_ranged), which is
+ * verified over its own frames only.  A raster the caller has overwritten since the execute simply reports mismatches.
+ *   FRA_E_INVALID for a null argument (before the plan is looked at) and, with the decoder's message ("lost sync /
+ * corrupt frame at byte N", N relative to the window's first frame), for a frame that does not parse or whose CRC-16
+ * fails; FRA_E_STATE before the first execute.  Synchronous.  Afterwards fra_decode_device_timing reports k_dec_parse,
+ * k_dec_restore and, in slot 2, k_dec_verify. */
+typedef struct {
+  uint64_t mismatches;    /* samples (counted per channel) that differ from the normalised input */
+  int64_t  first_sample;  /* window-relative pixel index of the first mismatch in (pixel, channel) order; -1: none */
+  int32_t  first_channel;
+  int32_t  expected, got; /* normalised input sample / decoded sample there (0 when none) */
+  int32_t  nframes;       /* frames decoded, each with a valid CRC-16 */
+} fra_verify_report;      /* 32 bytes */
+FRA_API int fra_plan_verify(fra_plan *plan, fra_verify_report *reports /* nwindows */, int32_t *bad_windows);
+
 /* Synthetic rasters, generated on the device with integer-exact hashes so a
  * host numpy mirror reproduces any window bit for bit.  kind: 3 = C3 DEM int16, 4 = C4 S2-like
  * uint16 (4 bands), 5 = C5 reflectance float32.  dev_out: device buffer (bands, height, width). */

@@ -24,6 +24,14 @@ and the wall times) and complete streams in page-locked host memory, searched (`
 container legs are skipped.
 
     python tools/bench_decode.py --window --steps 5 --warmup 2
+
+``--verify`` times verify mode (``fra_plan_verify``: the plan's frames decoded and compared with its raster on the
+GPU, nothing stored) beside the plain decode of the same frames in the same run: ``verify_wall_ms`` / ``verify_ms``
+(HIP events, first kernel to last) and its three kernel times against ``device_wall_ms`` / ``device_ms`` and the
+decode's.  The plan's encode time (``encode_ms``, wall, one execute + sync) is reported for scale.  A pixel of the
+raster is then overwritten and must be the one reported.  The other legs are skipped.
+
+    python tools/bench_decode.py --verify --steps 5 --warmup 2
 """
 from __future__ import annotations
 
@@ -72,6 +80,7 @@ def main():
     ap.add_argument("--no-e2e", action="store_true", help="skip the container leg")
     ap.add_argument("--window", nargs="?", const="center", default=None, metavar="r,c,h,w",
                     help="time a windowed read against the full decode (default window: 2048 x 2048 at the centre)")
+    ap.add_argument("--verify", action="store_true", help="time fra_plan_verify against the plain decode")
     args = ap.parse_args()
 
     ctx = N.Context(0)
@@ -108,6 +117,60 @@ def main():
             dev_ms.append(ms[3])
             kern.append(ms[:3])
             dev_wall.append((t1 - t0) * 1e3)
+
+    if args.verify:
+        ver_wall, ver_ms, ver_kern = [], [], []
+        for k in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            reports = plan.verify()
+            t1 = time.perf_counter()
+            if any(r.mismatches for r in reports) or sum(r.nframes for r in reports) != nfr:
+                raise SystemExit("verify: the plan's frames differ from its raster")
+            if k >= args.warmup:
+                ms = ctx.decode_timing()
+                ver_wall.append((t1 - t0) * 1e3)
+                ver_ms.append(ms[3])
+                ver_kern.append(ms[:3])
+        enc_ms = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            plan.execute()
+            plan.sync()
+            enc_ms.append((time.perf_counter() - t0) * 1e3)
+        # one changed pixel (tile 60, band 2) is the one mismatch reported
+        t = min(60, len(wins) - 1)
+        r0, c0, _, tw = wins[t]
+        px = np.empty(1, dt)
+        at = dev_raster + ((2 * H + r0 + 5) * W + c0 + 7) * dt.itemsize
+        ctx.d2h(px, at)
+        ctx.h2d(at, px ^ 0x10)
+        reports = plan.verify()
+        bad = [(i, r.mismatches, r.first_sample, r.first_channel) for i, r in enumerate(reports) if r.mismatches]
+        if bad != [(t, 1, 5 * tw + 7, 2)]:
+            raise SystemExit(f"verify: changed pixel of tile {t} reported as {bad}")
+        med = statistics.median
+        names = ("k_dec_parse_ms", "k_dec_restore_ms")
+        res = {
+            "workload": f"verify C4-like {W}x{H}x{B} uint16, tile {TILE}, level {LEVEL}, {len(wins)} tiles",
+            "tiles": len(wins), "frames": nfr, "samples": samples, "frame_bytes": total,
+            "steps": args.steps, "warmup": args.warmup, "changed_pixel_found": True,
+            "encode_ms": round(med(enc_ms), 3),
+            "device_ms": round(med(dev_ms), 3), "device_wall_ms": round(med(dev_wall), 3),
+            "verify_ms": round(med(ver_ms), 3), "verify_wall_ms": round(med(ver_wall), 3),
+            "kernels_decode": dict({n: round(med([k[i] for k in kern]), 3) for i, n in enumerate(names)},
+                                   k_dec_scatter_ms=round(med([k[2] for k in kern]), 3)),
+            "kernels_verify": dict({n: round(med([k[i] for k in ver_kern]), 3) for i, n in enumerate(names)},
+                                   k_dec_verify_ms=round(med([k[2] for k in ver_kern]), 3)),
+            "all_ms": {"device": [round(v, 3) for v in dev_ms], "verify": [round(v, 3) for v in ver_ms],
+                       "verify_wall": [round(v, 3) for v in ver_wall],
+                       "k_dec_scatter": [round(k[2], 3) for k in kern],
+                       "k_dec_verify": [round(k[2], 3) for k in ver_kern]},
+        }
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
 
     _, frames = plan.download()
     streams = streams_from(infos, frames)

@@ -8,7 +8,9 @@
 //     ranges of every file (first frame only, a middle range, through the last frame) the selected frames and their
 //     first samples must equal what the full chain assigns to the same frames, and a bit-flipped variant must fail
 //     exactly when the flipped byte lies in a selected frame;
-//   * the argument validation of fra_decode_device and fra_decode_device_window, which returns before any GPU work.
+//   * the argument validation of fra_decode_device, fra_decode_device_window and the verify entry behind
+//     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), which returns
+//     before any GPU work.
 // usage: decode_host_check [--concat] file.flac ...
 #include <cstdarg>
 #include <cstdio>
@@ -29,6 +31,7 @@ extern "C" int fra_internal_set_error(int code, const char* fmt, ...) {
   return code;
 }
 #ifdef WITH_DEVICE_ENTRY
+#include "../flac-raster_amd/csrc/fra_verify.h"
 typedef struct ihipStream_t* hipStream_t;
 extern "C" void fra_internal_ctx_stream(fra_ctx*, int* device, hipStream_t* stream) { *device = 0; *stream = nullptr; }
 #endif
@@ -274,6 +277,48 @@ int main(int argc, char** argv) {
   { auto j = job; j.dst_dtype = 9; badw("dtype 9", j, it, &roi); }
   { auto x = it; x.offset = 60; x.bytes = 8; x.window = {100, 100, 1, 8}; badw("item past the data, outside the roi", job, x, &roi); }
   { auto j = job; j.nitems = 0; EXPECT(fra_decode_device_window(ctx, &j, &roi, inf) == FRA_OK, "window read: empty job refused"); }
+  // ... and of the verify entry (fra_plan_verify's driver): an item over frame offsets, a source raster, reports
+  {
+    uint64_t vo[3] = {0, 30, 64};  // two frames of 16 samples: an 8 x 4 window
+    fra_decode_item vi{};
+    vi.offset = 0; vi.bytes = 64; vi.window = {0, 0, 8, 4};
+    vi.frame_offsets = vo; vi.nframes = 2; vi.channels = 1; vi.bps = 16; vi.blocksize = 16;
+    int16_t raster[32] = {0};
+    double rows[5] = {0};  // stands in for one device NormDev; never read on these paths
+    fra_verify_source vs{};
+    vs.raster = raster; vs.dtype = FRA_I16; vs.norm = 16; vs.band_stride = 32; vs.row_stride = 4; vs.col_stride = 1;
+    vs.norm_rows = rows;
+    fra_verify_report rep[1];
+    int32_t nbad = 0, ff = 0;
+    auto ver = [&](fra_ctx* c, const uint8_t* d, const fra_decode_item* x, int n, int ch, const fra_verify_source* sr,
+                   const int32_t* f0, fra_verify_report* r, int32_t* b) {
+      return fra_internal_verify_device(c, d, 64, x, n, ch, sr, f0, r, b);
+    };
+    EXPECT(ver(nullptr, data, &vi, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: null ctx accepted");
+    EXPECT(ver(ctx, nullptr, &vi, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: null data accepted");
+    EXPECT(ver(ctx, data, nullptr, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: null items accepted");
+    EXPECT(ver(ctx, data, &vi, 1, 1, nullptr, &ff, rep, &nbad) == FRA_E_INVALID, "verify: null source accepted");
+    EXPECT(ver(ctx, data, &vi, 1, 1, &vs, &ff, nullptr, &nbad) == FRA_E_INVALID, "verify: null reports accepted");
+    EXPECT(ver(ctx, data, &vi, 1, 1, &vs, &ff, rep, nullptr) == FRA_E_INVALID, "verify: null bad_windows accepted");
+    { auto s2 = vs; s2.raster = nullptr; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID, "verify: null raster accepted"); }
+    { auto s2 = vs; s2.norm_rows = nullptr; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID, "verify: null norm rows accepted"); }
+    { auto s2 = vs; s2.dtype = 8; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID, "verify: dtype 8 accepted"); }
+    { auto s2 = vs; s2.norm = 8; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID, "verify: norm 8 accepted"); }
+    { auto s2 = vs; s2.dtype = FRA_U16; s2.norm = 0; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID, "verify: norm 0 of uint16 accepted"); }
+    { auto s2 = vs; s2.col_stride = -1; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID, "verify: negative stride accepted"); }
+    EXPECT(ver(ctx, data, &vi, 1, 2, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: channel count unlike the item's accepted");
+    EXPECT(ver(ctx, data, &vi, -1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: negative item count accepted");
+    { auto x = vi; x.frame_offsets = nullptr; EXPECT(ver(ctx, data, &x, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: item without frame offsets accepted"); }
+    { auto x = vi; x.bytes = 60; EXPECT(ver(ctx, data, &x, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: offsets past the item accepted"); }
+    { auto x = vi; x.offset = 8; EXPECT(ver(ctx, data, &x, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: item past the data accepted"); }
+    { auto x = vi; x.window = {0, 0, -32, 1}; EXPECT(ver(ctx, data, &x, 1, 1, &vs, &ff, rep, &nbad) == FRA_E_INVALID, "verify: capacity window accepted"); }
+    // a per-item first frame: the window has 2 frames, so (1, 2 frames), (2, 1 frame), 3 and -1 lie past the stream
+    for (int32_t f0 : {1, 3, -1}) EXPECT(ver(ctx, data, &vi, 1, 1, &vs, &f0, rep, &nbad) == FRA_E_INVALID, "verify: first frame %d accepted", f0);
+    { auto x = vi; x.nframes = 1; x.bytes = 30; int32_t f0 = 2; EXPECT(ver(ctx, data, &x, 1, 1, &vs, &f0, rep, &nbad) == FRA_E_INVALID, "verify: one frame from frame 2 of 2 accepted"); }
+    { auto x = vi; x.nframes = 1; x.bytes = 30; EXPECT(ver(ctx, data, &x, 1, 1, &vs, nullptr, rep, &nbad) == FRA_E_INVALID, "verify: 1 of 2 frames without a first frame accepted"); }
+    nbad = 7;
+    EXPECT(ver(ctx, data, &vi, 0, 1, &vs, &ff, rep, &nbad) == FRA_OK && nbad == 0, "verify: empty job refused");
+  }
   printf("argument validation checked\n");
 #endif
   printf(g_fail ? "%d FAILED\n" : "host check ok\n", g_fail);
