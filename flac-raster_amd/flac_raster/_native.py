@@ -91,7 +91,18 @@ class VerifyReport(C.Structure):
     ]
 
 
+class DecimateJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("src_band_stride", C.c_int64), ("src_row_stride", C.c_int64),
+        ("src_col_stride", C.c_int64), ("factor", C.c_int32), ("resampling", C.c_int32), ("dst", C.c_void_p),
+        ("dst_on_device", C.c_int32), ("dst_band_stride", C.c_int64), ("dst_row_stride", C.c_int64),
+        ("dst_col_stride", C.c_int64),
+    ]
+
+
 DECODE_CONCAT = 1
+RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
 E_SPACE = -6
 DENORM_NONE, DENORM_INT, DENORM_PCM16 = 0, 1, 2
 
@@ -135,7 +146,8 @@ EXPORTS = [
     "fra_host_register", "fra_host_unregister", "fra_tiff_decode", "fra_plan_set_first_frame",
     "fra_plan_flags", "fra_plan_encode_host_progress", "fra_tiff_compress_bound", "fra_tiff_compress",
     "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
-    "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify",
+    "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify", "fra_decimate",
+    "fra_decode_device_decimated", "fra_decimate_timing",
 ]
 
 
@@ -202,6 +214,11 @@ def load():
         L.fra_decode_device_window.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(Decoded)]
         if hasattr(L, "fra_plan_verify"):  # (older builds load for same-box A/Bs)
             L.fra_plan_verify.argtypes = [vp, C.POINTER(VerifyReport), C.POINTER(i32)]
+        if hasattr(L, "fra_decimate"):
+            L.fra_decimate.argtypes = [vp, C.POINTER(DecimateJob)]
+            L.fra_decode_device_decimated.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32,
+                                                      C.POINTER(Decoded)]
+            L.fra_decimate_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -367,7 +384,7 @@ class Context:
         return out, mn.value, mx.value
 
     def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
-                      denorm: int = DENORM_NONE, concat: bool = False, roi=None) -> List[Decoded]:
+                      denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None) -> List[Decoded]:
         """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
 
         ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
@@ -379,7 +396,8 @@ class Context:
         ``c * strides[0] + (row_off + p // width) * strides[1] + (col_off + p % width) * strides[2]``.
         Returns the per-stream :class:`Decoded` infos.  Anything the device path does not cover raises
         :class:`NativeError`; there is no fallback to the host decoder.  (``roi``: see
-        :meth:`decode_device_window`.)"""
+        :meth:`decode_device_window`; ``decimate`` = (factor, resampling code): see
+        :meth:`decode_device_decimated`.)"""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -413,7 +431,10 @@ class Context:
         job.channels = channels
         job.band_stride, job.row_stride, job.col_stride = (int(v) for v in strides)
         infos = (Decoded * max(1, len(items)))()
-        if roi is not None:
+        if decimate is not None:
+            rc = load().fra_decode_device_decimated(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
+                                                    int(decimate[0]), int(decimate[1]), infos)
+        elif roi is not None:
             rc = load().fra_decode_device_window(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), infos)
         else:
             rc = load().fra_decode_device(self.h, C.byref(job), infos)
@@ -434,6 +455,76 @@ class Context:
         if roi is None:
             raise ValueError("roi is required")
         return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi)
+
+    def decode_device_decimated(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
+                                factor: int, resampling: str = "nearest", denorm: int = DENORM_NONE) -> List[Decoded]:
+        """``roi`` at ``1 / factor`` resolution (``fra_decode_device_decimated``): exactly
+        ``resample.decimate`` of what :meth:`decode_device_window` would have written, without the full-resolution
+        region leaving the GPU.
+
+        Arguments as :meth:`decode_device_window`, except that ``dst`` and ``strides`` address the
+        ``resample.decimated_shape(roi[2], roi[3], factor)`` output.  ``factor``: 2, 4, 8, 16, 32 or 64; ``resampling``:
+        ``"nearest"`` or ``"average"``.  The items must cover the region."""
+        from .resample import check_factor, resampling_code
+
+        if roi is None:
+            raise ValueError("roi is required")
+        return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi,
+                                  (check_factor(factor), resampling_code(resampling)))
+
+    def decimate(self, src, factor: int, resampling: str = "nearest", dst=None, *, dtype=None, shape=None,
+                 strides=None, dst_strides=None):
+        """A raster at ``1 / factor`` resolution on this context's GPU (``fra_decimate``, the rule of
+        ``flac_raster.resample``).
+
+        ``src``: a numpy array ``(B, h, w)`` / ``(h, w)`` of one of the eight raster dtypes with any non-negative
+        strides (a view is fine: it is copied to the device from its first element to its last), or a device pointer
+        (int) with ``dtype``, ``shape`` = (B, h, w) and element ``strides`` (default band-planar).  ``dst``: ``None``
+        (a new array is returned), a numpy array view ``(B, oh, ow)`` (the elements between its outputs keep their
+        values), or a device pointer with element ``dst_strides`` (default band-planar).  Returns ``dst``."""
+        from .resample import check_factor, decimated_shape, resampling_code
+
+        k, mode = check_factor(factor), resampling_code(resampling)
+        job = DecimateJob()
+        if isinstance(src, np.ndarray):
+            a = src if src.ndim == 3 else src[None]
+            if a.ndim != 3:
+                raise ValueError("src must be (B, h, w) or (h, w)")
+            dt, (B, h, w), sst = a.dtype, a.shape, _element_strides(a)
+            job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
+        else:
+            dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
+            sst = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
+            job.src, job.src_on_device = C.c_void_p(int(src)), 1
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"unsupported dtype {dt}")
+        oh, ow = decimated_shape(h, w, k)
+        ret = dst
+        if dst is None:
+            ret = dst = np.zeros((B, oh, ow), dtype=dt)
+            if isinstance(src, np.ndarray) and src.ndim == 2:
+                ret = dst[0]
+        if isinstance(dst, np.ndarray):
+            d = dst if dst.ndim == 3 else dst[None]
+            if d.shape != (B, oh, ow) or d.dtype != dt:
+                raise ValueError(f"dst must be {(B, oh, ow)} of {dt}, got {d.shape} of {d.dtype}")
+            dstr = _element_strides(d)
+            job.dst, job.dst_on_device = C.c_void_p(d.ctypes.data), 0
+        else:
+            dstr = tuple(int(v) for v in dst_strides) if dst_strides is not None else (oh * ow, ow, 1)
+            job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
+        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
+        job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
+        job.factor, job.resampling = k, mode
+        job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
+        _check(load().fra_decimate(self.h, C.byref(job)))
+        return ret
+
+    def decimate_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_decimate`` (:meth:`decimate` / :meth:`decode_device_decimated`)."""
+        ms = C.c_float()
+        _check(load().fra_decimate_timing(C.byref(ms)))
+        return ms.value
 
     def decode_timing(self) -> List[float]:
         """HIP-event ms of this thread's last ``decode_device`` / ``decode_device_window``: parse, restore, scatter,

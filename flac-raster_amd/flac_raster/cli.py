@@ -200,6 +200,8 @@ def window(
     bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="Bounding box: 'xmin,ymin,xmax,ymax'"),
     pixels: Optional[str] = typer.Option(None, "--window", "-w", help="Pixel window: 'row,col,height,width'"),
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+    decimate: int = typer.Option(1, "--decimate", help="Write the window at 1/K resolution: K = 2, 4, 8, 16, 32 or 64"),
+    resampling: str = typer.Option("nearest", "--resampling", help="With --decimate: nearest or average"),
 ):
     """Read a pixel window of a streaming FLAC file to GeoTIFF (only the tiles and frames it needs)."""
     from .streaming import window_to_tiff
@@ -213,13 +215,40 @@ def window(
         win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
         # the given device, else device 0 when a GPU is present, else the host decoder (as convert)
         dev = device if device is not None else (0 if _gpu_present() else None)
-        got, idx = window_to_tiff(path, output, window=win, bbox=box, device=dev)
+        got, idx = window_to_tiff(path, output, window=win, bbox=box, device=dev, decimate=decimate,
+                                  resampling=resampling)
+        scale = f" at 1/{decimate} resolution ({resampling})" if decimate != 1 else ""
         console.print(f"[green]Saved rows {got[0]}..{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]} of "
-                      f"{idx['height']} x {idx['width']} to: {output}[/green]")
+                      f"{idx['height']} x {idx['width']}{scale} to: {output}[/green]")
     except typer.Exit:
         raise
     except Exception as e:
         logger.exception("Window read failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
+@app.command()
+def overview(
+    flac_file: str = typer.Argument(..., help="Streaming FLAC file"),
+    output: Path = typer.Option(..., "--output", "-o", help="Output TIFF file path"),
+    factor: int = typer.Option(..., "--factor", help="Write the raster at 1/K resolution: K = 2, 4, 8, 16, 32 or 64"),
+    resampling: str = typer.Option("average", "--resampling", help="nearest or average"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Write a reduced-resolution preview of a whole streaming FLAC file to GeoTIFF."""
+    from .streaming import overview_to_tiff
+
+    try:
+        path = _local(flac_file)
+        dev = device if device is not None else (0 if _gpu_present() else None)
+        shape, idx = overview_to_tiff(path, output, factor, resampling, device=dev)
+        console.print(f"[green]Saved {idx['height']} x {idx['width']} at 1/{factor} resolution ({resampling}) as "
+                      f"{shape[1]} x {shape[2]} to: {output}[/green]")
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Overview failed")
         console.print(f"[red]Error: {e}[/red]")
         raise typer.Exit(1)
 

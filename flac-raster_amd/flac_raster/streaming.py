@@ -9,7 +9,8 @@ the window transform (rasterio ``windows.transform`` arithmetic), no nodata, the
 
 Reader = the index parse + byte-range slicing of ``cli.extract`` (``cli.py:238-313``); ``streaming_to_raster`` decodes
 the whole container, ``read_window`` a pixel window of it (only the byte ranges of the tiles it intersects are read,
-and on the GPU only the frames that hold its rows are decoded).
+and on the GPU only the frames that hold its rows are decoded), at full resolution or decimated by 2 .. 64
+(``decimate=``), and ``read_overview`` the whole raster decimated (``resample`` states the rule).
 """
 
 from __future__ import annotations
@@ -23,7 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import flac_meta
+from . import flac_meta, resample
 from .converter import raster_metadata, raster_tags
 from .geo import Affine, window_transform
 from .tiff import GeoTIFF
@@ -360,9 +361,16 @@ def resolve_window(index: Dict, window: Optional[Sequence[int]] = None,
 
 
 def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
-                device: Optional[int] = None, semantics: str = "pcm16"):
+                device: Optional[int] = None, semantics: str = "pcm16", decimate: int = 1,
+                resampling: str = "nearest"):
     """A pixel window of a streaming container (path or bytes) -> ``(raster (B, h, w) in the index's dtype, window,
     index)``, bit-identical to cropping :func:`streaming_to_raster`.
+
+    ``decimate`` = 2, 4, 8, 16, 32 or 64 returns the window at that fraction of the resolution instead:
+    ``resample.decimate(window's raster, decimate, resampling)``, shape ``(B, ceil(h / k), ceil(w / k))``; the returned
+    window is still the clipped full-resolution one (``resample.decimated_transform`` gives the result's transform).
+    On the host the window is read as below and decimated with numpy; on a GPU one ``fra_decode_device_decimated``
+    call decodes and decimates it there and only the small result comes back.
 
     ``window`` = (row_off, col_off, height, width) or ``bbox`` = (xmin, ymin, xmax, ymax), see :func:`resolve_window`;
     the returned window is the clipped one.  Of a file only the index and the byte ranges of the intersecting tiles
@@ -374,6 +382,10 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
 
     if semantics not in ("pcm16", "int"):
         raise ValueError("semantics must be 'pcm16' or 'int'")
+    k = 1
+    if decimate != 1:
+        k = resample.check_factor(decimate)
+        resample.resampling_code(resampling)
     if isinstance(src, (bytes, bytearray, memoryview)):
         data = memoryview(src)
         index, hs = read_index_bytes(bytes(data[:4 + struct.unpack(">I", data[:4])[0]]))
@@ -412,6 +424,13 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
         raise LookupError("No tiles intersect the window")
     dt = np.dtype(index["dtype"])
     B = int(index["bands"])
+    if device is not None and k > 1:
+        oh, ow = resample.decimated_shape(h, w, k)
+        out = np.zeros((B, oh, ow), dtype=dt)
+        ctx = _native.default_context(int(device))
+        ctx.decode_device_decimated(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win, k,
+                                    resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, win, index
     out = np.zeros((B, h, w), dtype=dt)
     if device is not None:
         ctx = _native.default_context(int(device))
@@ -429,19 +448,74 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
         tile = denormalize_from_audio(audio, params).reshape(th, tw, B).transpose(2, 0, 1)
         ra, rb, ca, cb = max(r, R), min(r + th, R + h), max(c, C_), min(c + tw, C_ + w)
         out[:, ra - R:rb - R, ca - C_:cb - C_] = tile[:, ra - r:rb - r, ca - c:cb - c]
+    if k > 1:
+        out = resample.decimate(out, k, resampling)
     return out, win, index
 
 
+def read_overview(src, factor: int, resampling: str = "average", device: Optional[int] = None,
+                  semantics: str = "pcm16"):
+    """The whole raster of a streaming container (path or bytes) at ``1 / factor`` resolution -> ``(raster (B,
+    ceil(H / k), ceil(W / k)) in the index's dtype, index)``: ``resample.decimate(streaming_to_raster(src)[0], factor,
+    resampling)``.  ``device=None`` reads the raster on the host and decimates it with numpy; an integer makes one
+    ``fra_decode_device_decimated`` call on that GPU: the full-resolution raster exists only in device memory and the
+    overview alone is copied back (the container's bytes go to the device as they are, as in
+    :func:`streaming_to_raster`)."""
+    from . import _native
+
+    k = resample.check_factor(factor)
+    resample.resampling_code(resampling)
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    if device is None:
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            index, _ = read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))
+        else:
+            index = open_streaming(Path(src)).index
+        out, _, index = read_window(src, window=(0, 0, int(index["height"]), int(index["width"])), device=None,
+                                    semantics=semantics, decimate=k, resampling=resampling)
+        return out, index
+    data = _container_bytes(src)
+    index, items = _tile_items(data)
+    dt = np.dtype(index["dtype"])
+    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
+    oh, ow = resample.decimated_shape(H, W, k)
+    out = np.zeros((B, oh, ow), dtype=dt)
+    ctx = _native.default_context(int(device))
+    ctx.decode_device_decimated(np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), (0, 0, H, W),
+                                k, resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+    return out, index
+
+
 def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] = None,
-                   bbox: Optional[Sequence[float]] = None, device: Optional[int] = None):
+                   bbox: Optional[Sequence[float]] = None, device: Optional[int] = None, decimate: int = 1,
+                   resampling: str = "nearest"):
     """A pixel window of a streaming container -> GeoTIFF with the index's CRS and the transform shifted to the
-    window's origin; returns ``(window, index)``."""
+    window's origin (``decimate`` > 1: the window at that fraction of the resolution, pixel size scaled to match);
+    returns ``(window, index)``."""
     from .tiff import write_geotiff
 
-    raster, win, index = read_window(Path(path), window=window, bbox=bbox, device=device)
+    raster, win, index = read_window(Path(path), window=window, bbox=bbox, device=device, decimate=decimate,
+                                     resampling=resampling)
     t = index.get("transform")
     crs = index.get("crs")
-    write_geotiff(Path(tiff_path), raster,
-                  transform=tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None,
-                  crs=crs if crs and crs != "None" else None)
+    if t and decimate != 1:
+        transform = resample.decimated_transform(t, win, decimate)
+    else:
+        transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
+    write_geotiff(Path(tiff_path), raster, transform=transform, crs=crs if crs and crs != "None" else None)
     return win, index
+
+
+def overview_to_tiff(path: Path, tiff_path: Path, factor: int, resampling: str = "average",
+                     device: Optional[int] = None):
+    """The whole raster of a streaming container at ``1 / factor`` resolution -> GeoTIFF with the index's CRS and the
+    pixel size scaled by ``factor``; returns ``(raster shape, index)``."""
+    from .tiff import write_geotiff
+
+    raster, index = read_overview(Path(path), factor, resampling, device=device)
+    t = index.get("transform")
+    crs = index.get("crs")
+    write_geotiff(Path(tiff_path), raster, transform=resample.decimated_transform(t, (0, 0), factor) if t else None,
+                  crs=crs if crs and crs != "None" else None)
+    return raster.shape, index

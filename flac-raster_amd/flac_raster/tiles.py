@@ -316,17 +316,28 @@ def verify_on_device(plan: "_native.Plan", raster_ptr: int,
 
 
 def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int], raster_ptr: int,
-                          strides: Optional[Tuple[int, int, int]] = None):
+                          strides: Optional[Tuple[int, int, int]] = None, decimate: int = 1,
+                          resampling: str = "nearest"):
     """The windowed counterpart of :func:`verify_on_device`: decode the pixels ``window`` (row_off, col_off, height,
     width, in the plan's raster coordinates) of an executed plan's device output into ``raster_ptr``, a device buffer
     of int16 (16-bps plans) / int32 whose element 0 is the window's first pixel (default ``strides``: band-planar
     ``(height * width, width, 1)`` of the window).  Only the frames that hold samples of the window are parsed,
     through ``fra_plan_frame_offsets``; nothing is searched and nothing is copied to the host.  Returns the per-tile
-    :class:`Decoded` infos (0 frames for a tile outside the window); a corrupt selected frame raises ``NativeError``."""
+    :class:`Decoded` infos (0 frames for a tile outside the window); a corrupt selected frame raises ``NativeError``.
+
+    ``decimate`` = 2 .. 64: the window at that fraction of the resolution (``resample.decimate`` of the above with
+    ``resampling``, ``fra_decode_device_decimated``); ``raster_ptr`` and the default ``strides`` then address the
+    ``resample.decimated_shape(height, width, decimate)`` output, and the plan's tiles must cover the window."""
     infos, data, items = _plan_items(plan)
     if not items:
         return []
     _, _, h, w = (int(v) for v in window)
     dt = np.int16 if all(i.bps <= 16 for i in infos) else np.int32
+    if decimate != 1:
+        from .resample import decimated_shape
+
+        oh, ow = decimated_shape(h, w, decimate)
+        return plan.ctx.decode_device_decimated(data, items, int(raster_ptr), dt, infos[0].channels,
+                                                strides or (oh * ow, ow, 1), window, decimate, resampling)
     return plan.ctx.decode_device_window(data, items, int(raster_ptr), dt, infos[0].channels,
                                          strides or (h * w, w, 1), window)

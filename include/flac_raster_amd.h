@@ -301,6 +301,54 @@ FRA_API int fra_decode_device_window(fra_ctx *ctx, const fra_decode_job *job, co
  * host chain) */
 FRA_API int fra_decode_device_timing(float *ms4);
 
+/* Decimated reads: a raster, or a region of a set of tile streams, at 1/factor resolution, factor one of 2, 4, 8, 16,
+ * 32, 64 (k below).  The h x w input is cut into k x k blocks anchored at its origin: block (R, C) covers rows
+ * [R k, min(R k + k, h)) and columns [C k, min(C k + k, w)) and holds n = rows x columns pixels (edge blocks are
+ * smaller).  The output is (channels, oh, ow), oh = ceil(h / k), ow = ceil(w / k), in the input's dtype.
+ *   FRA_RESAMPLE_NEAREST  out[b, R, C] = in[b, min(R k + k/2, h - 1), min(C k + k/2, w - 1)]
+ *   FRA_RESAMPLE_AVERAGE  integer dtypes: S = the exact integer sum of the block (|S| < 2^44),
+ *                         out = rint((double)S / (double)n), round half to even; no summation order is implied.
+ *                         f32 / f64: every element is converted to f64; each block row is padded with +0.0 to k elements
+ *                         and summed by the adjacent-pair tree ((x0 + x1), (x2 + x3), ... then pairs of those, log2 k
+ *                         levels); the row sums are accumulated top to bottom (acc = row 0; acc += row 1; ...; rows the
+ *                         block does not have are not added); out = (T)(acc / (double)n).  Plain IEEE arithmetic: NaN
+ *                         and +-inf propagate, nothing is skipped.
+ * With a geotransform (a, b, c, d, e, f) and the input's origin at (row, col) the output's transform is
+ * (a k, b k, c + col a + row b, d k, e k, f + col d + row e). */
+#define FRA_RESAMPLE_NEAREST 0
+#define FRA_RESAMPLE_AVERAGE 1
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype, of src and dst */
+  int32_t channels, height, width;          /* >= 1 */
+  int64_t src_band_stride, src_row_stride, src_col_stride;  /* elements, >= 0 */
+  int32_t factor, resampling;
+  void *dst; int32_t dst_on_device;         /* (channels, oh, ow) through the strides below */
+  int64_t dst_band_stride, dst_row_stride, dst_col_stride;
+} fra_decimate_job;
+/* k_decimate alone, over a host or device raster of any dtype.  Synchronous.  Host buffers are staged as the decoder
+ * stages them: each must be one allocation spanning every addressed element from element 0; the elements of dst that
+ * are not outputs keep the caller's values.  Rows are read with 16-byte loads when src_col_stride == 1 and src, the row
+ * stride and the band stride are multiples of 16 bytes, element by element otherwise (any layout, e.g. pixel-interleaved).
+ * FRA_E_INVALID, before any GPU work, for a null argument, a factor outside the six values, an unknown resampling code,
+ * a bad dtype or layout. */
+FRA_API int fra_decimate(fra_ctx *ctx, const fra_decimate_job *job);
+/* The windowed read at 1/factor resolution: exactly the decimation (rule above) of what fra_decode_device_window would
+ * have written for `roi`, in dst_dtype, after its denormalisation and saturation.  roi, the items and infos mean what
+ * they mean there; the job's dst and strides address the oh x ow output (h = roi->height, w = roi->width), and no other
+ * element is written.  The call runs fra_decode_device_window into a per-call device buffer of the region (band-planar,
+ * rows padded to 16 bytes), so every refusal and message of the windowed read is this call's as well; then k_decimate on
+ * the context's stream; then, for a host dst, the copy back.  The region buffer is released on every path.  Device
+ * memory: the windowed read's scratch beside the region buffer, then the region buffer beside a staged host dst.
+ *   FRA_E_INVALID before any GPU work: a null argument, a factor outside the six values, an unknown resampling code, and
+ * items whose intersections with roi do not add up to roi's area ("the items do not cover the region"): every pixel of
+ * the region must be decoded, since an average reads all of them.  Overlapping items remain the caller's contract.
+ *   Afterwards fra_decode_device_timing reports the inner windowed read and fra_decimate_timing the decimation. */
+FRA_API int fra_decode_device_decimated(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi, int32_t factor,
+                                        int32_t resampling, fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last k_decimate (fra_decimate or fra_decode_device_decimated) */
+FRA_API int fra_decimate_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -32,6 +32,17 @@ decode's.  The plan's encode time (``encode_ms``, wall, one execute + sync) is r
 raster is then overwritten and must be the one reported.  The other legs are skipped.
 
     python tools/bench_decode.py --verify --steps 5 --warmup 2
+
+``--decimate K`` (``--resampling`` nearest | average, default average) times the decimated read of the whole raster
+(``fra_decode_device_decimated``) in three legs: the full decode to a device destination as above (``device_ms``); the
+decimated decode of the same resident frames (``kernels_decimated``: parse, restore, scatter and ``k_decimate`` by HIP
+events, ``decimated_wall_ms``; ``k_decimate_TBps`` = (bytes read + written) / its event time;
+``peak_device_bytes_of_call`` = the drop of free device memory sampled beside one call); and container bytes -> host
+raster, ``read_overview(device=0)`` against ``streaming_to_raster(device=0)`` alternating in this process
+(``e2e_overview_ms`` / ``e2e_full_ms``).  The result must equal ``resample.decimate`` of the full decode on the rows
+checked.  The other legs are skipped.
+
+    python tools/bench_decode.py --decimate 8 --steps 5 --warmup 2
 """
 from __future__ import annotations
 
@@ -40,6 +51,7 @@ import ctypes as C
 import json
 import statistics
 import sys
+import threading
 import time
 from pathlib import Path
 
@@ -50,7 +62,8 @@ sys.path.insert(0, str(ROOT / "flac-raster_amd"))
 
 from flac_raster import _native as N  # noqa: E402
 from flac_raster.geo import Affine  # noqa: E402
-from flac_raster.streaming import assemble_streaming, streaming_to_raster  # noqa: E402
+from flac_raster.resample import FACTORS, decimate, decimated_shape  # noqa: E402
+from flac_raster.streaming import assemble_streaming, read_overview, streaming_to_raster  # noqa: E402
 from flac_raster.tiles import calculate_tiles, streams_from  # noqa: E402
 
 SEED = 20240607
@@ -81,6 +94,9 @@ def main():
     ap.add_argument("--window", nargs="?", const="center", default=None, metavar="r,c,h,w",
                     help="time a windowed read against the full decode (default window: 2048 x 2048 at the centre)")
     ap.add_argument("--verify", action="store_true", help="time fra_plan_verify against the plain decode")
+    ap.add_argument("--decimate", type=int, default=0, metavar="K", choices=(0,) + FACTORS,
+                    help="time the decimated read of the whole raster at 1/K against the full decode")
+    ap.add_argument("--resampling", default="average", choices=("nearest", "average"), help="with --decimate")
     args = ap.parse_args()
 
     ctx = N.Context(0)
@@ -174,6 +190,99 @@ def main():
 
     _, frames = plan.download()
     streams = streams_from(infos, frames)
+
+    if args.decimate:
+        k, mode = args.decimate, args.resampling
+        oh, ow = decimated_shape(H, W, k)
+        roi = (0, 0, H, W)
+        dev_small = ctx.alloc(B * oh * ow * 2)
+        dec_wall, dec_kern, dec_k = [], [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ctx.decode_device_decimated((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi, k,
+                                        mode)
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                dec_wall.append((t1 - t0) * 1e3)
+                dec_kern.append(ctx.decode_timing())
+                dec_k.append(ctx.decimate_timing())
+        # one more call with the free device memory sampled beside it: the peak of the call
+        hip = C.CDLL("libamdhip64.so")
+        free, tot = C.c_size_t(), C.c_size_t()
+        hip.hipMemGetInfo(C.byref(free), C.byref(tot))
+        base, low, stop = free.value, [free.value], threading.Event()
+
+        def sample():
+            f, t = C.c_size_t(), C.c_size_t()
+            while not stop.is_set():
+                if hip.hipMemGetInfo(C.byref(f), C.byref(t)) == 0:
+                    low[0] = min(low[0], f.value)
+                time.sleep(0.0005)
+
+        th = threading.Thread(target=sample, daemon=True)
+        th.start()
+        ctx.decode_device_decimated((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi, k, mode)
+        stop.set()
+        th.join()
+        # the result against the numpy rule over the full decode: the top 2048 rows and the ragged bottom blocks
+        got = np.empty((B, oh, ow), np.int16)
+        ctx.d2h(got, dev_small)
+        full = np.empty((B, H, W), np.int16)
+        ctx.d2h(full, dev_out)
+        top = 2048 // k
+        tail = oh - 4
+        if not (np.array_equal(got[:, :top], decimate(full[:, :2048], k, mode))
+                and np.array_equal(got[:, tail:], decimate(full[:, tail * k:], k, mode))):
+            raise SystemExit("the decimated decode differs from resample.decimate of the full decode")
+        del full
+        ctx.free(dev_small)
+        # container bytes -> host raster, both ways, alternating
+        data = assemble_streaming(wins, streams, (B, H, W), dt, Affine(10.0, 0.0, 0.0, 0.0, -10.0, 0.0), "EPSG:32633",
+                                  TILE)
+        ov_ms, full_ms = [], []
+        n_e2e = min(1, args.warmup) + min(3, args.steps)
+        for s in range(n_e2e):
+            t0 = time.perf_counter()
+            small, _ = read_overview(data, k, mode, device=0)
+            t1 = time.perf_counter()
+            big, _ = streaming_to_raster(data, device=0)
+            t2 = time.perf_counter()
+            if s == 0 and not np.array_equal(small[:, :top], decimate(big[:, :2048], k, mode)):
+                raise SystemExit("read_overview differs from resample.decimate of streaming_to_raster")
+            del big
+            if s >= min(1, args.warmup):
+                ov_ms.append((t1 - t0) * 1e3)
+                full_ms.append((t2 - t1) * 1e3)
+        med = statistics.median
+        kd = med(dec_k)
+        # average reads the region once and writes the output; nearest reads one element per output
+        moved = (B * H * W * 2 if mode == "average" else B * oh * ow * 2) + B * oh * ow * 2
+        names = ("k_dec_parse_ms", "k_dec_restore_ms", "k_dec_scatter_ms")
+        res = {
+            "workload": f"decimate {k} ({mode}) of C4-like {W}x{H}x{B} uint16, tile {TILE}, level {LEVEL}, "
+                        f"{len(wins)} tiles, whole raster",
+            "factor": k, "resampling": mode, "output": [B, oh, ow], "tiles": len(wins), "frames": nfr,
+            "steps": args.steps, "warmup": args.warmup, "equals_numpy_rule_on_checked_rows": True,
+            "device_ms": round(med(dev_ms), 3), "device_wall_ms": round(med(dev_wall), 3),
+            "kernels_full": {n: round(med([q[i] for q in kern]), 3) for i, n in enumerate(names)},
+            "decimated_wall_ms": round(med(dec_wall), 3),
+            "decimated_events_ms": round(med([q[3] for q in dec_kern]) + kd, 3),
+            "kernels_decimated": dict({n: round(med([q[i] for q in dec_kern]), 3) for i, n in enumerate(names)},
+                                      k_decimate_ms=round(kd, 4)),
+            "k_decimate_bytes": moved, "k_decimate_TBps": round(moved / (kd * 1e-3) / 1e12, 3),
+            "peak_device_bytes_of_call": base - low[0],
+            "region_buffer_bytes": B * H * (-(-W // 8) * 8) * 2, "output_bytes": B * oh * ow * 2,
+            "e2e_overview_ms": round(med(ov_ms), 2), "e2e_full_ms": round(med(full_ms), 2),
+            "e2e_full_over_overview": round(med(full_ms) / med(ov_ms), 2),
+            "all_ms": {"k_decimate": [round(v, 4) for v in dec_k], "decimated_wall": [round(v, 2) for v in dec_wall],
+                       "device": [round(v, 3) for v in dev_ms], "e2e_overview": [round(v, 2) for v in ov_ms],
+                       "e2e_full": [round(v, 2) for v in full_ms]},
+        }
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
 
     def verify() -> int:
         """The device raster against the host decoder on the first, middle and last tile; then cleared."""

@@ -319,6 +319,47 @@ int main(int argc, char** argv) {
     nbad = 7;
     EXPECT(ver(ctx, data, &vi, 0, 1, &vs, &ff, rep, &nbad) == FRA_OK && nbad == 0, "verify: empty job refused");
   }
+  // ... and of the decimated reads (fra_decimate.hip): refused before any GPU work
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;
+    dj.items = &di;
+    const fra_window r48{0, 0, 4, 8};
+    auto dec = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, int k, int mode, fra_decoded* o) {
+      return fra_decode_device_decimated(c, j, r, k, mode, o);
+    };
+    EXPECT(dec(nullptr, &dj, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: null ctx accepted");
+    EXPECT(dec(ctx, nullptr, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: null job accepted");
+    EXPECT(dec(ctx, &dj, nullptr, 2, 1, inf) == FRA_E_INVALID, "decimated read: null roi accepted");
+    EXPECT(dec(ctx, &dj, &r48, 2, 1, nullptr) == FRA_E_INVALID, "decimated read: null infos accepted");
+    for (int k : {0, 1, 3, 128, -2}) EXPECT(dec(ctx, &dj, &r48, k, 1, inf) == FRA_E_INVALID, "decimated read: factor %d accepted", k);
+    for (int m : {2, -1}) EXPECT(dec(ctx, &dj, &r48, 2, m, inf) == FRA_E_INVALID, "decimated read: resampling %d accepted", m);
+    { fra_window r = r48; r.height = 5; EXPECT(dec(ctx, &dj, &r, 2, 1, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "decimated read: uncovered row accepted"); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(dec(ctx, &j, &r48, 2, 1, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "decimated read: uncovered column accepted"); }
+    { auto j = dj; j.nitems = 0; EXPECT(dec(ctx, &j, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(dec(ctx, &dj, &r, 2, 1, inf) == FRA_E_INVALID && g_msg.find("region of interest") != std::string::npos, "decimated read: zero-width roi accepted"); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(dec(ctx, &j, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst = nullptr; EXPECT(dec(ctx, &j, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: null dst accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(dec(ctx, &j, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: dtype 9 accepted"); }
+    { auto x = di; x.window = {0, 0, -8, 1}; auto j = dj; j.items = &x; EXPECT(dec(ctx, &j, &r48, 2, 1, inf) == FRA_E_INVALID, "decimated read: capacity window accepted"); }
+    int32_t out[16];
+    fra_decimate_job mj{};
+    mj.src = dst; mj.dtype = FRA_I32; mj.channels = 1; mj.height = 8; mj.width = 8;
+    mj.src_band_stride = 64; mj.src_row_stride = 8; mj.src_col_stride = 1;
+    mj.factor = 2; mj.resampling = FRA_RESAMPLE_AVERAGE;
+    mj.dst = out; mj.dst_band_stride = 16; mj.dst_row_stride = 4; mj.dst_col_stride = 1;
+    EXPECT(fra_decimate(nullptr, &mj) == FRA_E_INVALID, "decimate: null ctx accepted");
+    EXPECT(fra_decimate(ctx, nullptr) == FRA_E_INVALID, "decimate: null job accepted");
+    { auto j = mj; j.src = nullptr; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: null src accepted"); }
+    { auto j = mj; j.dst = nullptr; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: null dst accepted"); }
+    for (int k : {0, 1, 3, 128}) { auto j = mj; j.factor = k; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: factor %d accepted", k); }
+    { auto j = mj; j.resampling = 2; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: resampling 2 accepted"); }
+    { auto j = mj; j.dtype = 8; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: dtype 8 accepted"); }
+    { auto j = mj; j.height = 0; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: zero height accepted"); }
+    { auto j = mj; j.dst_row_stride = -1; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: negative stride accepted"); }
+    EXPECT(fra_decimate_timing(nullptr) == FRA_E_INVALID, "decimate timing: null accepted");
+  }
   printf("argument validation checked\n");
 #endif
   printf(g_fail ? "%d FAILED\n" : "host check ok\n", g_fail);
