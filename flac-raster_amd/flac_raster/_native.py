@@ -101,6 +101,26 @@ class DecimateJob(C.Structure):
     ]
 
 
+class CompareBand(C.Structure):
+    """One band's report of ``fra_compare`` / ``fra_decode_device_compare`` (128 bytes; the rule: ``compare.py``)."""
+
+    _fields_ = [
+        ("count", C.c_uint64), ("differing", C.c_uint64), ("unordered", C.c_uint64), ("first_row", C.c_int64),
+        ("first_col", C.c_int64), ("sum_abs", C.c_uint64), ("sum_sq_lo", C.c_uint64), ("sum_sq_hi", C.c_uint64),
+        ("max_abs", C.c_double), ("fsum_abs", C.c_double), ("fsum_sq", C.c_double), ("a_min", C.c_double),
+        ("a_max", C.c_double), ("b_min", C.c_double), ("b_max", C.c_double), ("reserved", C.c_uint64),
+    ]
+
+
+class CompareJob(C.Structure):
+    _fields_ = [
+        ("a", C.c_void_p), ("a_on_device", C.c_int32), ("a_band_stride", C.c_int64), ("a_row_stride", C.c_int64),
+        ("a_col_stride", C.c_int64), ("b", C.c_void_p), ("b_on_device", C.c_int32), ("b_band_stride", C.c_int64),
+        ("b_row_stride", C.c_int64), ("b_col_stride", C.c_int64), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32),
+    ]
+
+
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
 E_SPACE = -6
@@ -147,7 +167,8 @@ EXPORTS = [
     "fra_plan_flags", "fra_plan_encode_host_progress", "fra_tiff_compress_bound", "fra_tiff_compress",
     "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
     "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify", "fra_decimate",
-    "fra_decode_device_decimated", "fra_decimate_timing",
+    "fra_decode_device_decimated", "fra_decimate_timing", "fra_compare", "fra_decode_device_compare",
+    "fra_compare_timing",
 ]
 
 
@@ -219,6 +240,11 @@ def load():
             L.fra_decode_device_decimated.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32,
                                                       C.POINTER(Decoded)]
             L.fra_decimate_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_compare"):
+            L.fra_compare.argtypes = [vp, C.POINTER(CompareJob), C.POINTER(CompareBand)]
+            L.fra_decode_device_compare.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), vp, i32, C.c_int64,
+                                                    C.c_int64, C.c_int64, C.POINTER(CompareBand), C.POINTER(Decoded)]
+            L.fra_compare_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -384,7 +410,8 @@ class Context:
         return out, mn.value, mx.value
 
     def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
-                      denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None) -> List[Decoded]:
+                      denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None,
+                      compare=None) -> List[Decoded]:
         """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
 
         ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
@@ -397,7 +424,8 @@ class Context:
         Returns the per-stream :class:`Decoded` infos.  Anything the device path does not cover raises
         :class:`NativeError`; there is no fallback to the host decoder.  (``roi``: see
         :meth:`decode_device_window`; ``decimate`` = (factor, resampling code): see
-        :meth:`decode_device_decimated`.)"""
+        :meth:`decode_device_decimated`; ``compare`` = (ref pointer, on device, element strides, reports array): see
+        :meth:`decode_device_compare`, ``dst`` is then ``None``.)"""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -422,7 +450,9 @@ class Context:
                 it.channels, it.bps, it.blocksize = int(d["channels"]), int(d["bps"]), int(d["blocksize"])
         job.items, job.nitems = arr, len(items)
         job.flags = DECODE_CONCAT if concat else 0
-        if isinstance(dst, np.ndarray):
+        if dst is None:
+            job.dst, job.dst_on_device = None, 0
+        elif isinstance(dst, np.ndarray):
             job.dst, job.dst_on_device = C.c_void_p(dst.ctypes.data), 0
         else:
             job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
@@ -431,7 +461,12 @@ class Context:
         job.channels = channels
         job.band_stride, job.row_stride, job.col_stride = (int(v) for v in strides)
         infos = (Decoded * max(1, len(items)))()
-        if decimate is not None:
+        if compare is not None:
+            ref, ref_on_device, rst, bands = compare
+            rc = load().fra_decode_device_compare(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
+                                                  C.c_void_p(int(ref)), 1 if ref_on_device else 0, int(rst[0]),
+                                                  int(rst[1]), int(rst[2]), bands, infos)
+        elif decimate is not None:
             rc = load().fra_decode_device_decimated(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                     int(decimate[0]), int(decimate[1]), infos)
         elif roi is not None:
@@ -524,6 +559,76 @@ class Context:
         """HIP-event ms of this thread's last ``k_decimate`` (:meth:`decimate` / :meth:`decode_device_decimated`)."""
         ms = C.c_float()
         _check(load().fra_decimate_timing(C.byref(ms)))
+        return ms.value
+
+    def decode_device_compare(self, data, items, ref, dst_dtype, channels: int, roi, denorm: int = DENORM_NONE,
+                              ref_strides=None) -> Tuple[List[CompareBand], List[Decoded]]:
+        """``roi`` of the tile streams compared with a reference raster (``fra_decode_device_compare``): the reports of
+        ``compare.compare_arrays(what decode_device_window would have written, ref)``, one per band, without the
+        decoded region leaving the GPU.
+
+        ``data``, ``items``, ``roi``, ``denorm`` as :meth:`decode_device_window`.  ``ref``: a numpy array ``(channels, h,
+        w)`` of ``dst_dtype`` addressed relative to the region (a view with any non-negative strides is fine: it is
+        copied to the device from its first element to its last), or a device pointer (int) with element
+        ``ref_strides`` (default band-planar).  The items must cover the region.  Returns ``(reports, infos)``;
+        ``first_row`` / ``first_col`` are relative to the region."""
+        if roi is None:
+            raise ValueError("roi is required")
+        dt = np.dtype(dst_dtype)
+        h, w = int(roi[2]), int(roi[3])
+        if isinstance(ref, np.ndarray):
+            if ref.shape != (channels, h, w) or ref.dtype != dt:
+                raise ValueError(f"ref must be {(channels, h, w)} of {dt}, got {ref.shape} of {ref.dtype}")
+            where = (ref.ctypes.data, False, _element_strides(ref))
+        else:
+            where = (int(ref), True, tuple(int(v) for v in ref_strides) if ref_strides is not None else (h * w, w, 1))
+        bands = (CompareBand * max(1, channels))()
+        infos = self.decode_device(data, items, None, dt, channels, (0, 0, 0), denorm, False, roi,
+                                   compare=where + (bands,))
+        return list(bands)[:channels], infos
+
+    def compare(self, a, b, *, dtype=None, shape=None, a_strides=None, b_strides=None) -> List[CompareBand]:
+        """Two rasters compared on this context's GPU (``fra_compare``, the rule of ``flac_raster.compare``): one
+        :class:`CompareBand` per band.
+
+        ``a``, ``b``: numpy arrays ``(B, h, w)`` / ``(h, w)`` of one of the eight raster dtypes with any non-negative
+        strides (views are fine: each is copied to the device from its first element to its last), or device pointers
+        (int) with ``dtype``, ``shape`` = (B, h, w) and element strides (default band-planar).  Neither is written."""
+        job = CompareJob()
+        shp, dt = None, None
+        sides = []
+        for x, st in ((a, a_strides), (b, b_strides)):
+            if isinstance(x, np.ndarray):
+                v = x if x.ndim == 3 else x[None]
+                if v.ndim != 3:
+                    raise ValueError("rasters must be (B, h, w) or (h, w)")
+                if (shp is not None and v.shape != shp) or (dt is not None and v.dtype != dt):
+                    raise ValueError(f"the rasters differ in shape or dtype: {shp} of {dt}, {v.shape} of {v.dtype}")
+                shp, dt = tuple(v.shape), v.dtype
+                sides.append((v.ctypes.data, 0, _element_strides(v), v))
+            else:
+                sides.append((int(x), 1, st, None))
+        if shp is None:
+            shp, dt = tuple(int(v) for v in shape), np.dtype(dtype)
+        elif (shape is not None and tuple(shape) != shp) or (dtype is not None and np.dtype(dtype) != dt):
+            raise ValueError("shape / dtype disagree with the array given")
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"unsupported dtype {dt}")
+        B, h, w = shp
+        sides = [(p, dev, tuple(int(v) for v in st) if st is not None else (h * w, w, 1), keep)
+                 for p, dev, st, keep in sides]
+        (job.a, job.a_on_device, ast, _), (job.b, job.b_on_device, bst, _) = sides
+        job.a_band_stride, job.a_row_stride, job.a_col_stride = ast
+        job.b_band_stride, job.b_row_stride, job.b_col_stride = bst
+        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
+        bands = (CompareBand * max(1, B))()
+        _check(load().fra_compare(self.h, C.byref(job), bands))
+        return list(bands)[:B]
+
+    def compare_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_compare`` + fold (:meth:`compare` / :meth:`decode_device_compare`)."""
+        ms = C.c_float()
+        _check(load().fra_compare_timing(C.byref(ms)))
         return ms.value
 
     def decode_timing(self) -> List[float]:

@@ -309,6 +309,60 @@ def compare(
         export_json.write_text(json.dumps(res, indent=2, default=list))
 
 
+@app.command()
+def check(
+    source: Path = typer.Argument(..., help="Source TIFF file"),
+    flac_file: str = typer.Argument(..., help="Streaming FLAC file made from it"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="Compare this bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="Compare this pixel window only: 'row,col,height,width'"),
+    semantics: str = typer.Option("pcm16", "--semantics", help="pcm16 (what convert back to TIFF gives) or int"),
+    max_diff: Optional[float] = typer.Option(None, "--max-diff", help="Accept differences up to this absolute value"),
+    export_json: Optional[Path] = typer.Option(None, "--export", "-e", help="Export the comparison to JSON"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Does a streaming FLAC file give its source TIFF back, and if not, by how much (exit 0: it does)."""
+    from .compare import display_first_differences
+    from .streaming import check_against_tiff
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        if not source.exists():
+            console.print(f"[red]File not found: {source}[/red]")
+            raise typer.Exit(1)
+        path = _local(flac_file)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        dev = device if device is not None else (0 if _gpu_present() else None)
+        res, got, _ = check_against_tiff(path, source, window=win, bbox=box, device=dev, semantics=semantics,
+                                         count_one_sided_nans=max_diff is not None)
+        display_comparison_table(res)
+        display_first_differences(res)
+        if max_diff is None:
+            ok = res["arrays_equal"]
+        else:  # a pixel with a NaN on one side only differs by no number: it is never within a tolerance
+            ok = res["max_difference"] <= max_diff and res["one_sided_nan"] == 0
+        res["max_diff_allowed"], res["passed"] = max_diff, bool(ok)
+        if export_json:
+            export_json.write_text(json.dumps(res, indent=2, default=list))
+        where = f"rows {got[0]}..{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]}"
+        if ok:
+            console.print(f"[green]{path.name} gives {source.name} back ({where}, {semantics}"
+                          + (f", differences up to {res['max_difference']:g} <= {max_diff:g}" if max_diff is not None
+                             and not res["arrays_equal"] else "") + ")[/green]")
+        else:
+            console.print(f"[red]{path.name} differs from {source.name} in {res['differing']} pixel values ({where}, "
+                          f"{semantics}, largest difference {res['max_difference']:g})[/red]")
+            raise typer.Exit(1)
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Check failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
 def _show_tiff_info(path: Path):
     from .tiff import GeoTIFF
 

@@ -377,8 +377,6 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     are read (seek + read).  ``device=None`` decodes those tiles on the host and crops; an integer makes one
     ``fra_decode_device_window`` call on that GPU, which decodes only the frames that hold the window's rows."""
     from . import _native
-    from .decoder import decode_flac, pcm16_float
-    from .normalization import NormalizationParams, denormalize_from_audio
 
     if semantics not in ("pcm16", "int"):
         raise ValueError("semantics must be 'pcm16' or 'int'")
@@ -386,6 +384,32 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     if decimate != 1:
         k = resample.check_factor(decimate)
         resample.resampling_code(resampling)
+    index, win, blob, items = _window_items(src, window, bbox)
+    R, C_, h, w = win
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    if device is not None and k > 1:
+        oh, ow = resample.decimated_shape(h, w, k)
+        out = np.zeros((B, oh, ow), dtype=dt)
+        ctx = _native.default_context(int(device))
+        ctx.decode_device_decimated(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win, k,
+                                    resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, win, index
+    out = np.zeros((B, h, w), dtype=dt)
+    if device is not None:
+        ctx = _native.default_context(int(device))
+        ctx.decode_device_window(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (h * w, w, 1), win,
+                                 _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, win, index
+    _decode_window_on_host(blob, items, win, out, semantics)
+    if k > 1:
+        out = resample.decimate(out, k, resampling)
+    return out, win, index
+
+
+def _window_items(src, window, bbox):
+    """The index of a container (path or bytes), the clipped window of a request, and the bytes and ``decode_device``
+    items of the tiles that intersect it (of a file only the index and those byte ranges are read)."""
     if isinstance(src, (bytes, bytearray, memoryview)):
         data = memoryview(src)
         index, hs = read_index_bytes(bytes(data[:4 + struct.unpack(">I", data[:4])[0]]))
@@ -422,21 +446,16 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
             fh.close()
     if not items:
         raise LookupError("No tiles intersect the window")
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
-    if device is not None and k > 1:
-        oh, ow = resample.decimated_shape(h, w, k)
-        out = np.zeros((B, oh, ow), dtype=dt)
-        ctx = _native.default_context(int(device))
-        ctx.decode_device_decimated(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win, k,
-                                    resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
-        return out, win, index
-    out = np.zeros((B, h, w), dtype=dt)
-    if device is not None:
-        ctx = _native.default_context(int(device))
-        ctx.decode_device_window(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (h * w, w, 1), win,
-                                 _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
-        return out, win, index
+    return index, win, blob, items
+
+
+def _decode_window_on_host(blob, items, win, out: np.ndarray, semantics: str):
+    """The tiles of ``_window_items`` decoded on the host, denormalised and cropped into ``out`` (B, h, w)."""
+    from .decoder import decode_flac, pcm16_float
+    from .normalization import NormalizationParams, denormalize_from_audio
+
+    R, C_, h, w = win
+    B, dt = out.shape[0], out.dtype
     for it in items:
         r, c, th, tw = it["window"]
         samples, _, bps = decode_flac(bytes(blob[it["offset"]:it["offset"] + it["bytes"]]))
@@ -448,9 +467,114 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
         tile = denormalize_from_audio(audio, params).reshape(th, tw, B).transpose(2, 0, 1)
         ra, rb, ca, cb = max(r, R), min(r + th, R + h), max(c, C_), min(c + tw, C_ + w)
         out[:, ra - R:rb - R, ca - C_:cb - C_] = tile[:, ra - r:rb - r, ca - c:cb - c]
-    if k > 1:
-        out = resample.decimate(out, k, resampling)
-    return out, win, index
+
+
+# ------------------------------------------------------------------------------------------ container against raster
+def _compare_window(win, blob, items, ref: np.ndarray, device: Optional[int], semantics: str,
+                    count_one_sided_nans: bool = False) -> Dict:
+    """The window ``win`` of the tiles of ``_window_items`` against ``ref`` (B, h, w): on the host the window is
+    decoded and compared with numpy; on a GPU one ``fra_decode_device_compare`` call returns the reports."""
+    from . import _native
+    from .compare import compare_arrays, report_from_bands
+
+    B, dt = ref.shape[0], ref.dtype
+    r, c, h, w = win
+    if device is None:
+        out = np.zeros((B, h, w), dtype=dt)
+        _decode_window_on_host(blob, items, win, out, semantics)
+        report = compare_arrays(out, ref)
+    else:
+        ctx = _native.default_context(int(device))
+        data = np.frombuffer(blob, dtype=np.uint8)
+        denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+        bands, _ = ctx.decode_device_compare(data, items, ref, dt, B, win, denorm)
+        report = report_from_bands(bands, dt)
+        if count_one_sided_nans and report["one_sided_nan"] is None:
+            out = np.zeros((B, h, w), dtype=dt)
+            ctx.decode_device_window(data, items, out, dt, B, (h * w, w, 1), win, denorm)
+            for i, band in enumerate(report["bands"]):
+                band["one_sided_nan"] = int(np.count_nonzero(np.isnan(out[i]) != np.isnan(ref[i])))
+            report["one_sided_nan"] = sum(band["one_sided_nan"] for band in report["bands"])
+    report["origin"] = [r, c]
+    return report
+
+
+def compare_with_raster(src, raster: np.ndarray, window: Optional[Sequence[int]] = None,
+                        bbox: Optional[Sequence[float]] = None, device: Optional[int] = None,
+                        semantics: str = "pcm16"):
+    """Does this container (path or bytes) give ``raster`` back, and if not, by how much -> ``(report, window,
+    index)``: ``compare.compare_arrays(read_window(src, ...)[0], raster cropped to the window)``, the container's
+    pixels being ``file1`` / ``a`` and the raster's ``file2`` / ``b``.
+
+    ``raster`` is the whole source raster ``(B, H, W)`` of the index's dtype and shape (``ValueError`` otherwise);
+    ``window`` / ``bbox`` restrict the comparison as in :func:`read_window` (default: the whole raster); the positions
+    in the report are relative to the returned (clipped) window, whose origin is ``report["origin"]``.
+    ``device=None`` reads the window on the host and compares with numpy; an integer makes one
+    ``fra_decode_device_compare`` call on that GPU: the decoded pixels never leave the device, the raster's window goes
+    there, and only the reports come back (``one_sided_nan`` is then ``None`` where a band has both unordered and
+    differing pixels, see ``compare.report_from_bands``)."""
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    if window is None and bbox is None:
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            mv = memoryview(src)
+            index, _ = read_index_bytes(bytes(mv[:4 + struct.unpack(">I", mv[:4])[0]]))
+        else:
+            index = open_streaming(Path(src)).index
+        window = (0, 0, int(index["height"]), int(index["width"]))
+    index, win, blob, items = _window_items(src, window, bbox)
+    dt = np.dtype(index["dtype"])
+    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
+    raster = np.asarray(raster)
+    if raster.shape != (B, H, W) or raster.dtype != dt:
+        raise ValueError(f"the raster must be {(B, H, W)} of {dt} as the container's index says, got {raster.shape} of "
+                         f"{raster.dtype}")
+    r, c, h, w = win
+    ref = raster[:, r:r + h, c:c + w]
+    if any(st < 0 or st % dt.itemsize for st in ref.strides) or not ref.dtype.isnative:
+        ref = np.ascontiguousarray(ref, dtype=dt.newbyteorder("="))
+    return _compare_window(win, blob, items, ref, device, semantics), win, index
+
+
+def check_against_tiff(container: Path, tiff: Path, window: Optional[Sequence[int]] = None,
+                       bbox: Optional[Sequence[float]] = None, device: Optional[int] = None,
+                       semantics: str = "pcm16", count_one_sided_nans: bool = False):
+    """:func:`compare_with_raster` of a streaming container against the GeoTIFF it was made from -> ``(report, window,
+    index)``; the report also carries what ``compare.display_comparison_table`` prints (names, shapes, dtypes, CRS).
+    With a window only that window of the TIFF is read (in-package reader).  A TIFF whose shape or dtype is not the
+    index's raises ``ValueError``.
+
+    ``count_one_sided_nans``: a GPU report leaves ``one_sided_nan`` open (``None``) when a band has both unordered and
+    differing pixels; the window is then read once more (``fra_decode_device_window``) and the pixels with a NaN on
+    one side only are counted on the host.  The host path always counts them."""
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    container, tiff = Path(container), Path(tiff)
+    index = open_streaming(container).index
+    dt = np.dtype(index["dtype"])
+    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
+    g = GeoTIFF(tiff)
+    try:
+        info = g.info
+        shape, tdt = (info.count, info.height, info.width), np.dtype(info.dtype)
+        if shape != (B, H, W) or tdt != dt:
+            raise ValueError(f"{tiff.name} is {shape} of {tdt}, the container holds {(B, H, W)} of {dt}")
+        if window is None and bbox is None:
+            window = (0, 0, H, W)
+        index, win, blob, items = _window_items(container, window, bbox)
+        ref = np.zeros((B, win[2], win[3]), dtype=dt)
+        g.read_window_into(ref, *win)
+        crs = str(info.crs)
+    finally:
+        g.close()
+    report = _compare_window(win, blob, items, ref, device, semantics, count_one_sided_nans)
+    report.update({
+        "file1": container.name, "file2": tiff.name, "shape_match": True, "dtype_match": True,
+        "crs_match": str(index.get("crs")) == crs, "file1_shape": (B, H, W), "file2_shape": shape,
+        "file1_dtype": str(dt), "file2_dtype": str(tdt), "file1_crs": str(index.get("crs")), "file2_crs": crs,
+        "window": list(win), "semantics": semantics,
+    })
+    return report, win, index
 
 
 def read_overview(src, factor: int, resampling: str = "average", device: Optional[int] = None,

@@ -349,6 +349,65 @@ FRA_API int fra_decode_device_decimated(fra_ctx *ctx, const fra_decode_job *job,
 /* HIP-event time (ms) of the calling thread's last k_decimate (fra_decimate or fra_decode_device_decimated) */
 FRA_API int fra_decimate_timing(float *ms);
 
+/* Comparison of two rasters a and b of one dtype (any fra_dtype) and shape (channels, h, w): one report per band.
+ *   Integer dtypes: d = (int64)a - (int64)b, exact, never wrapping (|d| <= 2^32 - 1).  differing = pixels with d != 0;
+ *     first_row / first_col = the first of them in row-major order, relative to the rasters' origin (-1, -1: none);
+ *     max_abs = max |d| (a double, exact); sum_abs = sum |d| (exact uint64); sum_sq_lo / _hi = sum d^2 as an exact 128-bit
+ *     integer; a_min, a_max, b_min, b_max exact doubles; unordered = 0, fsum_abs = fsum_sq = 0.  More than 2^32 pixels per
+ *     band are refused (FRA_E_INVALID), which keeps sum_abs inside 64 bits.
+ *   f32 / f64: every element is converted to f64.  Both non-NaN: the pixel is equal iff a == b (-0.0 equals +0.0);
+ *     d = 0.0 when equal, else a - b (+-inf propagates by plain IEEE arithmetic); |d| goes to max_abs and fsum_abs, d * d to
+ *     fsum_sq.  Both NaN: counted in unordered, not in differing, contributes nothing.  Exactly one NaN: counted in
+ *     unordered and in differing, eligible for first_*, contributes nothing to max_abs or the sums.  The minima and maxima
+ *     skip NaN and are NaN when the band holds no number.  sum_abs = sum_sq_* = 0.  differing == 0 is exactly
+ *     numpy.array_equal(a, b, equal_nan=True).
+ *     fsum_abs and fsum_sq are f64 sums and no summation order is implied; but no float atomics are used -- each workgroup
+ *     reduces by a fixed lane tree to one partial record and a second kernel adds a band's partials in index order -- so two
+ *     calls on the same inputs and layout return byte-identical reports.
+ *   count = h * w in every report. */
+typedef struct {
+  uint64_t count, differing, unordered;
+  int64_t  first_row, first_col;
+  uint64_t sum_abs, sum_sq_lo, sum_sq_hi;
+  double   max_abs, fsum_abs, fsum_sq, a_min, a_max, b_min, b_max;
+  uint64_t reserved;  /* 0 */
+} fra_compare_band;   /* 128 bytes */
+typedef struct {
+  const void *a; int32_t a_on_device;       /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int64_t a_band_stride, a_row_stride, a_col_stride;  /* elements, >= 0 */
+  const void *b; int32_t b_on_device;
+  int64_t b_band_stride, b_row_stride, b_col_stride;
+  int32_t dtype;                            /* fra_dtype, of a and b */
+  int32_t channels, height, width;          /* >= 1 */
+} fra_compare_job;
+/* k_compare + k_compare_fold alone, over host or device rasters.  Synchronous; bands (host memory) receives `channels`
+ * reports.  Host rasters are staged as fra_decimate stages them: each must be one allocation spanning every addressed
+ * element from element 0.  Neither raster is written.  Both are read with 16-byte loads when, for both, the column stride
+ * is 1 and the base, the row stride and the band stride are multiples of 16 bytes; element by element otherwise (any
+ * layout, e.g. pixel-interleaved).  FRA_E_INVALID, before any GPU work, for a null argument, a bad dtype, a bad layout
+ * (channels, height or width < 1, a negative stride) and more than 2^32 pixels per band. */
+FRA_API int fra_compare(fra_ctx *ctx, const fra_compare_job *job, fra_compare_band *bands /* channels */);
+/* The windowed read compared with a reference raster, a = what fra_decode_device_window would have written for `roi` (in
+ * dst_dtype, after its denormalisation and saturation), b = ref: does this container give that raster back, and if not, by
+ * how much.  roi, the items and infos mean what they mean there.  ref (host or device) is addressed relative to the region,
+ * in job->dst_dtype: pixel (R, C) of channel ch at ch*ref_band_stride + (R - roi.row_off)*ref_row_stride +
+ * (C - roi.col_off)*ref_col_stride; first_row / first_col are relative to the region too.  job->dst, dst_on_device and the
+ * job's strides are ignored (they may be null / 0).  The call runs fra_decode_device_window into a per-call device buffer
+ * of the region (band-planar, rows padded to 16 bytes), so every refusal and message of the windowed read is this call's as
+ * well; then k_compare of that buffer against ref on the context's stream.  The decoded region never leaves the device and
+ * its buffer is released on every path.  Device memory: the windowed read's scratch beside the region buffer, then the
+ * region buffer beside a staged host ref.
+ *   FRA_E_INVALID before any GPU work: a null argument (ref and bands included), a negative ref stride, more than 2^32
+ * pixels, and items whose intersections with roi do not add up to roi's area ("the items do not cover the region"): every
+ * pixel of the region must be decoded, since every one is compared.  Overlapping items remain the caller's contract.
+ *   Afterwards fra_decode_device_timing reports the inner windowed read and fra_compare_timing the comparison. */
+FRA_API int fra_decode_device_compare(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi, const void *ref,
+                                      int32_t ref_on_device, int64_t ref_band_stride, int64_t ref_row_stride,
+                                      int64_t ref_col_stride, fra_compare_band *bands /* channels */,
+                                      fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last k_compare + k_compare_fold (fra_compare or fra_decode_device_compare) */
+FRA_API int fra_compare_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

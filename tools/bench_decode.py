@@ -43,6 +43,18 @@ raster, ``read_overview(device=0)`` against ``streaming_to_raster(device=0)`` al
 checked.  The other legs are skipped.
 
     python tools/bench_decode.py --decimate 8 --steps 5 --warmup 2
+
+``--compare`` times the comparison of the scene's container with its own synthetic raster, resident on the device
+(``fra_decode_device_compare``: the whole raster decoded with ``pcm16`` semantics to uint16 and compared there, only the
+reports come back), against the plain windowed read of the same region to a device destination in the same run
+(``plain_wall_ms`` / ``plain_ms`` against ``compare_wall_ms`` / the inner read + ``k_compare_ms``).  ``k_compare_ms`` is
+the HIP-event time of ``k_compare`` + ``k_compare_fold`` and ``k_compare_TBps`` = (bytes of both rasters read) / that
+time.  The synthetic raster's rows (10980 uint16) are not 16-byte aligned, so that call reads element by element;
+``aligned`` repeats it against a copy of the raster with rows padded to 16 bytes (16-byte loads).  Both must give the
+same reports, and band 0 must equal ``compare.compare_arrays`` of the plain read and the raster.  The other legs are
+skipped.
+
+    python tools/bench_decode.py --compare --steps 5 --warmup 2
 """
 from __future__ import annotations
 
@@ -61,6 +73,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "flac-raster_amd"))
 
 from flac_raster import _native as N  # noqa: E402
+from flac_raster.compare import compare_arrays, report_from_bands  # noqa: E402
 from flac_raster.geo import Affine  # noqa: E402
 from flac_raster.resample import FACTORS, decimate, decimated_shape  # noqa: E402
 from flac_raster.streaming import assemble_streaming, read_overview, streaming_to_raster  # noqa: E402
@@ -97,6 +110,8 @@ def main():
     ap.add_argument("--decimate", type=int, default=0, metavar="K", choices=(0,) + FACTORS,
                     help="time the decimated read of the whole raster at 1/K against the full decode")
     ap.add_argument("--resampling", default="average", choices=("nearest", "average"), help="with --decimate")
+    ap.add_argument("--compare", action="store_true",
+                    help="time the comparison of the container with its source raster against the plain read")
     args = ap.parse_args()
 
     ctx = N.Context(0)
@@ -182,6 +197,75 @@ def main():
                        "k_dec_scatter": [round(k[2], 3) for k in kern],
                        "k_dec_verify": [round(k[2], 3) for k in ver_kern]},
         }
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
+
+    if args.compare:
+        if len(wins) != len(calculate_tiles(H, W, TILE)):
+            raise SystemExit("--compare needs every tile: the region compared is the whole raster")
+        roi = (0, 0, H, W)
+        citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
+        plain_wall, plain_ms = [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ctx.decode_device_window((frames_ptr, total), citems, dev_out, dt, B, (H * W, W, 1), roi, N.DENORM_PCM16)
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                plain_wall.append((t1 - t0) * 1e3)
+                plain_ms.append(ctx.decode_timing()[3])
+        raster = np.empty((B, H, W), dt)
+        ctx.d2h(raster, dev_raster)
+        decoded = np.empty((B, H, W), dt)
+        ctx.d2h(decoded, dev_out)
+        want = compare_arrays(decoded[:1], raster[:1])["bands"][0]
+        del decoded
+        rs = -(-W // 8) * 8  # rows on 16-byte boundaries
+        padded = np.zeros((B, H, rs), dt)
+        padded[:, :, :W] = raster
+        del raster
+        dev_padded = ctx.alloc(padded.nbytes)
+        ctx.h2d(dev_padded, padded)
+        del padded
+        legs = {}
+        for name, ref, strides in (("as_is", dev_raster, (H * W, W, 1)), ("aligned", dev_padded, (H * rs, rs, 1))):
+            wall, inner, kc = [], [], []
+            for s in range(args.warmup + args.steps):
+                t0 = time.perf_counter()
+                bands, _ = ctx.decode_device_compare((frames_ptr, total), citems, ref, dt, B, roi, N.DENORM_PCM16,
+                                                     ref_strides=strides)
+                t1 = time.perf_counter()
+                if s >= args.warmup:
+                    wall.append((t1 - t0) * 1e3)
+                    inner.append(ctx.decode_timing()[3])
+                    kc.append(ctx.compare_timing())
+            legs[name] = (wall, inner, kc, b"".join(bytes(r) for r in bands), report_from_bands(bands, dt))
+        ctx.free(dev_padded)
+        if legs["as_is"][3] != legs["aligned"][3]:
+            raise SystemExit("compare: element loads and 16-byte loads give different reports")
+        rep = legs["as_is"][4]
+        if rep["bands"][0] != want:
+            raise SystemExit(f"compare: band 0 differs from compare_arrays: {rep['bands'][0]} != {want}")
+        med = statistics.median
+        moved = 2 * B * H * W * dt.itemsize
+        res = {
+            "workload": f"compare C4-like {W}x{H}x{B} uint16 (pcm16), tile {TILE}, level {LEVEL}, {len(wins)} tiles, "
+                        "whole raster against its source on the device",
+            "tiles": len(wins), "frames": nfr, "steps": args.steps, "warmup": args.warmup,
+            "band0_equals_compare_arrays": True, "reports_equal_on_both_paths": True,
+            "differing": rep["differing"], "max_difference": rep["max_difference"],
+            "mean_difference": rep["mean_difference"], "rmse": rep["rmse"],
+            "plain_ms": round(med(plain_ms), 3), "plain_wall_ms": round(med(plain_wall), 3),
+            "k_compare_bytes": moved, "region_buffer_bytes": B * H * rs * dt.itemsize,
+        }
+        for name, (wall, inner, kc, _, _) in legs.items():
+            res[name] = {"compare_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3),
+                         "k_compare_ms": round(med(kc), 4), "k_compare_TBps": round(moved / (med(kc) * 1e-3) / 1e12, 3),
+                         "wall_over_plain": round(med(wall) / med(plain_wall), 3),
+                         "all_ms": {"k_compare": [round(v, 4) for v in kc], "compare_wall": [round(v, 3) for v in wall]}}
+        res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall]}
         print(json.dumps(res), flush=True)
         plan.close()
         ctx.free(dev_out)

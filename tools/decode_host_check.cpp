@@ -8,9 +8,9 @@
 //     ranges of every file (first frame only, a middle range, through the last frame) the selected frames and their
 //     first samples must equal what the full chain assigns to the same frames, and a bit-flipped variant must fail
 //     exactly when the flipped byte lies in a selected frame;
-//   * the argument validation of fra_decode_device, fra_decode_device_window and the verify entry behind
-//     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), which returns
-//     before any GPU work.
+//   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
+//     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated reads
+//     and the comparison (fra_compare, fra_decode_device_compare), which returns before any GPU work.
 // usage: decode_host_check [--concat] file.flac ...
 #include <cstdarg>
 #include <cstdio>
@@ -359,6 +359,55 @@ int main(int argc, char** argv) {
     { auto j = mj; j.height = 0; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: zero height accepted"); }
     { auto j = mj; j.dst_row_stride = -1; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: negative stride accepted"); }
     EXPECT(fra_decimate_timing(nullptr) == FRA_E_INVALID, "decimate timing: null accepted");
+  }
+  // ... and of the comparison (fra_compare.hip): refused before any GPU work
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;
+    dj.items = &di;
+    dj.dst = nullptr;  // ignored by the compared read, as are the job's strides
+    dj.band_stride = dj.row_stride = dj.col_stride = -1;
+    const fra_window r48{0, 0, 4, 8};
+    static int32_t ref[64];
+    fra_compare_band bands[1];
+    auto cmp = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, const void* rf, int64_t bs, int64_t rs,
+                   int64_t cs, fra_compare_band* b, fra_decoded* o) {
+      return fra_decode_device_compare(c, j, r, rf, 0, bs, rs, cs, b, o);
+    };
+    EXPECT(cmp(nullptr, &dj, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: null ctx accepted");
+    EXPECT(cmp(ctx, nullptr, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: null job accepted");
+    EXPECT(cmp(ctx, &dj, nullptr, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: null roi accepted");
+    EXPECT(cmp(ctx, &dj, &r48, nullptr, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: null ref accepted");
+    EXPECT(cmp(ctx, &dj, &r48, ref, 32, 8, 1, nullptr, inf) == FRA_E_INVALID, "compared read: null bands accepted");
+    EXPECT(cmp(ctx, &dj, &r48, ref, 32, 8, 1, bands, nullptr) == FRA_E_INVALID, "compared read: null infos accepted");
+    EXPECT(cmp(ctx, &dj, &r48, ref, -1, 8, 1, bands, inf) == FRA_E_INVALID && g_msg.find("layout") != std::string::npos, "compared read: negative band stride accepted");
+    EXPECT(cmp(ctx, &dj, &r48, ref, 32, -8, 1, bands, inf) == FRA_E_INVALID, "compared read: negative row stride accepted");
+    EXPECT(cmp(ctx, &dj, &r48, ref, 32, 8, -1, bands, inf) == FRA_E_INVALID, "compared read: negative column stride accepted");
+    { fra_window r = r48; r.height = 5; EXPECT(cmp(ctx, &dj, &r, ref, 40, 8, 1, bands, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "compared read: uncovered row accepted"); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "compared read: uncovered column accepted"); }
+    { auto j = dj; j.nitems = 0; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(cmp(ctx, &dj, &r, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID && g_msg.find("region of interest") != std::string::npos, "compared read: zero-width roi accepted"); }
+    { fra_window r{0, 0, 65537, 65536}; EXPECT(cmp(ctx, &dj, &r, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID && g_msg.find("2^32 pixels") != std::string::npos, "compared read: more than 2^32 pixels accepted"); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID && g_msg.find("dtype") != std::string::npos, "compared read: dtype 9 accepted"); }
+    { auto j = dj; j.denorm = 7; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: denorm 7 accepted"); }
+    { auto j = dj; j.channels = 0; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: no channels accepted"); }
+    { auto x = di; x.window = {0, 0, -8, 1}; auto j = dj; j.items = &x; EXPECT(cmp(ctx, &j, &r48, ref, 32, 8, 1, bands, inf) == FRA_E_INVALID, "compared read: capacity window accepted"); }
+    fra_compare_job cj{};
+    cj.a = dst; cj.b = ref; cj.dtype = FRA_I32; cj.channels = 1; cj.height = 8; cj.width = 8;
+    cj.a_band_stride = cj.b_band_stride = 64; cj.a_row_stride = cj.b_row_stride = 8; cj.a_col_stride = cj.b_col_stride = 1;
+    EXPECT(fra_compare(nullptr, &cj, bands) == FRA_E_INVALID, "compare: null ctx accepted");
+    EXPECT(fra_compare(ctx, nullptr, bands) == FRA_E_INVALID, "compare: null job accepted");
+    EXPECT(fra_compare(ctx, &cj, nullptr) == FRA_E_INVALID, "compare: null bands accepted");
+    { auto j = cj; j.a = nullptr; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID, "compare: null a accepted"); }
+    { auto j = cj; j.b = nullptr; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID, "compare: null b accepted"); }
+    { auto j = cj; j.dtype = 8; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID && g_msg.find("dtype") != std::string::npos, "compare: dtype 8 accepted"); }
+    { auto j = cj; j.width = 0; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID && g_msg.find("layout") != std::string::npos, "compare: zero width accepted"); }
+    { auto j = cj; j.channels = 0; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID, "compare: no channels accepted"); }
+    { auto j = cj; j.b_row_stride = -8; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID, "compare: negative stride accepted"); }
+    { auto j = cj; j.height = 65537; j.width = 65536; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID && g_msg.find("2^32 pixels") != std::string::npos, "compare: more than 2^32 pixels accepted"); }
+    EXPECT(fra_compare_timing(nullptr) == FRA_E_INVALID, "compare timing: null accepted");
   }
   printf("argument validation checked\n");
 #endif
