@@ -60,7 +60,7 @@ static int stage_norm(fra_plan* p, const Group& gr, hipStream_t s) {
     ma.streams += gr.w0 + c0;
     ma.norm += gr.w0 + c0;
     if (ma.lut) ma.lut += (int64_t)(gr.w0 + c0) * a.lut_stride;
-    const int vec = (p->mm_vec && (uintptr_t)p->d_raster % p->mm_vec == 0) ? p->mm_vec : 0;  // pointer alignment
+    const int vec = minmax_vec(p);  // pointer alignment
     // the full grid (max_blocks 0), one workgroup per row block, in pipelined executes as in serial ones --
     // measured against one workgroup per CU striding over the blocks: C4 step 1.666 -> 1.626 ms, 8-way share
     // 0.292 -> 0.274 ms, 4-way 0.505 -> 0.488 ms, C5 neutral, C3 1.089 -> 1.101

@@ -21,14 +21,31 @@ struct HostRows {
   int64_t plane;  // elements between the channels of a band-planar raster
   volatile int64_t* rows_done;
 };
+// the copies below move rows as runs: one run per channel for band-planar rasters (band_stride >= row_stride), one
+// run holding every channel for pixel- and line-interleaved ones
+static bool planar_runs(const fra_job& j) { return j.channels > 1 && j.band_stride >= j.row_stride; }
+// rows the plan's windows reach ([0, rows)) and the elements one such row spans from its first element: up to the
+// last window column, in a run of every channel up to the last channel's
+static void row_extent(const fra_plan* p, int64_t* rows, int64_t* span) {
+  const fra_job& j = p->job;
+  int64_t nr = 0, cols = 0;
+  for (const fra_window& w : p->windows)
+    if (w.height > 0 && w.width > 0) {
+      nr = std::max<int64_t>(nr, (int64_t)w.row_off + w.height);
+      cols = std::max<int64_t>(cols, (int64_t)w.col_off + w.width);
+    }
+  *rows = nr;
+  *span = cols ? (cols - 1) * j.col_stride + (planar_runs(j) ? 0 : (int64_t)(j.channels - 1) * j.band_stride) + 1 : 0;
+}
 // H2D of raster rows [r0, r1) of every band (channel) of the job: one contiguous run per channel for band-planar
-// rasters (band_stride >= row_stride), one run for pixel-interleaved ones -- split where a ring wraps --, clamped
-// to the plan's extent (the last row of the last channel may end before row_stride does)
-static int copy_rows_h2d(fra_plan* p, const HostRows& h, int64_t r0, int64_t r1, hipStream_t st) {
+// rasters, one run for interleaved ones -- split where a ring wraps --, clamped to the plan's extent (the last row
+// of the last channel may end before row_stride does).  A run ends with its last row (`span`, <= row_stride
+// unless the raster has one row only: encode_host refuses rows that overlap)
+static int copy_rows_h2d(fra_plan* p, const HostRows& h, int64_t span, int64_t r0, int64_t r1, hipStream_t st) {
   const fra_job& j = p->job;
   const int es = elem_size(j.dtype);
   const int64_t extent = (int64_t)(p->raster_bytes / es);
-  const bool planar = j.channels > 1 && j.band_stride >= j.row_stride;
+  const bool planar = planar_runs(j);
   const int nrun = planar ? j.channels : 1;
   for (int c = 0; c < nrun; c++) {
     const int64_t dbase = (int64_t)c * (planar ? j.band_stride : 0);
@@ -36,7 +53,7 @@ static int copy_rows_h2d(fra_plan* p, const HostRows& h, int64_t r0, int64_t r1,
     for (int64_t r = r0; r < r1;) {
       const int64_t rr = r % h.rows, n = std::min(r1 - r, h.rows - rr);
       const int64_t a = dbase + r * j.row_stride;
-      const int64_t b = std::min(extent, dbase + (r + n) * j.row_stride);
+      const int64_t b = std::min(extent, dbase + (r + n - 1) * j.row_stride + std::max(j.row_stride, span));
       if (b > a)
         HIPCHK(hipMemcpyAsync((uint8_t*)p->d_raster_owned + a * es, h.base + (hbase + rr * j.row_stride) * es,
                               (size_t)(b - a) * es, hipMemcpyHostToDevice, st));
@@ -183,6 +200,15 @@ static int encode_host(fra_plan* p, const void* host_raster, uint8_t* host_out, 
                        uint64_t* total_bytes, const volatile int64_t* rows_ready, int64_t ring_rows,
                        volatile int64_t* rows_done) {
   if (!p || (!host_raster && p->raster_bytes) || (!host_out && capacity)) return set_err(FRA_E_INVALID, "null argument");
+  // rows go H2D as whole runs of row_stride elements, band after band: a raster whose rows overlap (a zero row
+  // stride, a sliding view) would be encoded from rows that have not arrived.  Refused here, before any GPU work
+  int64_t nrows = 0, span = 0;
+  row_extent(p, &nrows, &span);
+  if (nrows > 1 && p->job.row_stride < span)
+    return set_err(FRA_E_INVALID,
+                   "host raster layout: rows overlap (row_stride %lld < the %lld elements a row spans); the host "
+                   "paths copy whole rows -- encode such a raster device-resident (fra_plan_execute)",
+                   (long long)p->job.row_stride, (long long)span);
   const bool ring = ring_rows > 0;
   const HostRows host{(const uint8_t*)host_raster, ring ? ring_rows : INT64_MAX,
                       ring ? ring_rows * p->job.row_stride : p->job.band_stride, rows_done};
@@ -223,7 +249,7 @@ static int encode_host(fra_plan* p, const void* host_raster, uint8_t* host_out, 
     if (!wait_rows(rows_ready, hb.r1, publish))
       return set_err(FRA_E_STATE, "the raster producer failed (rows_ready < 0)");
     if (hb.r1 > hb.r0)
-      if (int rc = copy_rows_h2d(p, host, hb.r0, hb.r1, p->h2d)) return rc;
+      if (int rc = copy_rows_h2d(p, host, span, hb.r0, hb.r1, p->h2d)) return rc;
     HIPCHK(hipEventRecord(p->hev[2 * b], p->h2d));
     copies = b + 1;
     publish();

@@ -185,6 +185,9 @@ void collect_times(fra_plan* p);  // timing mode: add the last execute's phase t
 int plan_own_raster(fra_plan* p);  // the plan's own device raster (host-resident jobs), made on first use
 // 8-byte sample vectors as an execute decides them: the device raster's alignment (hipMalloc's for host rasters)
 inline void set_vec8(fra_plan* p) { p->args.vec8 = (p->ld_vec8 && (uintptr_t)p->d_raster % 8 == 0) ? 1 : 0; }
+// bytes per load of the min/max pass as an execute decides them: the layout's vector width when the device raster
+// is aligned to it, else 0 (scalar k_minmax; a 16-byte layout does not fall back to 8-byte vectors)
+inline int minmax_vec(const fra_plan* p) { return (p->mm_vec && (uintptr_t)p->d_raster % p->mm_vec == 0) ? p->mm_vec : 0; }
 // fra_exec.hip
 bool wave_path(const fra_plan* p, const ExecEnv& env);
 int run_host_band(fra_plan* p, int b, const ExecEnv& env);

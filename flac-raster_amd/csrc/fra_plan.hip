@@ -512,7 +512,10 @@ int fra_plan_flags(fra_plan* p, int32_t* flags) {
   set_vec8(p);
   const ExecEnv env = env_exec();
   const int k17 = env.keep17 >= 0 ? env.keep17 : p->k17;
-  *flags = (p->pipe ? FRA_PLAN_PIPELINED : 0) | (wave_path(p, env) ? FRA_PLAN_WAVE : 0) | (k17 ? FRA_PLAN_KEEP17 : 0);
+  const int mv = p->job.norm != 0 ? minmax_vec(p) : 0;
+  *flags = (p->pipe ? FRA_PLAN_PIPELINED : 0) | (wave_path(p, env) ? FRA_PLAN_WAVE : 0) | (k17 ? FRA_PLAN_KEEP17 : 0) |
+           (p->args.vec8 ? FRA_PLAN_LOAD_VEC8 : 0) | (mv == 16 ? FRA_PLAN_MINMAX_VEC16 : 0) |
+           (mv == 8 ? FRA_PLAN_MINMAX_VEC8 : 0) | (p->args.off32 ? FRA_PLAN_OFF32 : 0);
   return FRA_OK;
 }
 

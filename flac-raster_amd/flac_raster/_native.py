@@ -124,6 +124,9 @@ class CompareJob(C.Structure):
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
 E_SPACE = -6
+# fra_plan_flags (Plan.flags)
+PLAN_DIRECT_WRITE, PLAN_PIPELINED, PLAN_WAVE, PLAN_KEEP17 = 1, 2, 4, 8
+PLAN_LOAD_VEC8, PLAN_MINMAX_VEC16, PLAN_MINMAX_VEC8, PLAN_OFF32 = 16, 32, 64, 128
 DENORM_NONE, DENORM_INT, DENORM_PCM16 = 0, 1, 2
 
 
@@ -711,7 +714,10 @@ class Plan:
     def flags(self) -> int:
         """``FRA_PLAN_*`` bits: 2 cross-execute pipelined, 4 full frames on the per-wave analysis kernel, 8 (with 4)
         its next execute keeps residuals up to 17 bits (else 16; picked per execute from an earlier one's count of
-        waves that needed bit 16); 1, direct write, is never set since r03."""
+        waves that needed bit 16); 1, direct write, is never set since r03.  The load paths of the next execute for
+        the current raster pointer: 16 (``PLAN_LOAD_VEC8``) the analysis loads 8-byte sample vectors, 32 / 64
+        (``PLAN_MINMAX_VEC16`` / ``PLAN_MINMAX_VEC8``) the min/max pass loads 16- / 8-byte vectors, 128
+        (``PLAN_OFF32``) 32-bit lane offsets."""
         f = C.c_int32()
         _check(load().fra_plan_flags(self.h, C.byref(f)))
         return f.value

@@ -141,7 +141,14 @@ FRA_API void fra_plan_destroy(fra_plan *plan);
  * for full link rate.  Frames land at the offsets fra_plan_result reports; *total_bytes = their sum.
  * If capacity < total, FRA_E_SPACE is returned (frames beyond capacity are not copied; the complete
  * output stays on the device for fra_plan_download).  Synchronous: returns when the frames are in
- * host_out.  A plan's capacity bound: fra_plan_capacity. */
+ * host_out.  A plan's capacity bound: fra_plan_capacity.
+ * Layout contract of the three host entries (fra_plan_encode_host, _progress, fra_plan_encode_ring): rows are
+ * copied as whole runs of row_stride elements, so the rows of a raster taller than one row must not overlap --
+ * row_stride >= the elements one row spans, (C - 1) * col_stride + 1 with C the largest column end (col_off +
+ * width) of the plan's windows, plus (channels - 1) * band_stride for an interleaved raster (band_stride <
+ * row_stride).  A job with row_stride == 0 or any smaller stride than that (numpy broadcast or sliding views) is
+ * refused with FRA_E_INVALID before any GPU work; fra_plan_create accepts it, and a device-resident raster
+ * (fra_plan_execute) encodes it.  Padded rows, column offsets, pixel- and line-interleaved rasters are fine. */
 FRA_API int fra_plan_encode_host(fra_plan *plan, const void *host_raster, uint8_t *host_out, uint64_t capacity,
                                  uint64_t *total_bytes);
 /* The same pipelined pass over a raster that is still being produced (file-to-container path: a decoder
@@ -176,11 +183,21 @@ FRA_API int fra_plan_capacity(fra_plan *plan, uint64_t *capacity, int32_t *host_
  * set (the direct-write path was measured slower than slots + k_assemble and removed in r03).  KEEP17 (with
  * WAVE) = the next execute's k_analyze_w keeps residuals up to 17 bits (else 16): a pipelined plan picks the
  * instance from how many waves of an earlier execute needed bit 16 (FRA_KEEP17=0/1 in the environment forces it);
- * both produce the same bytes. */
+ * both produce the same bytes.
+ * The load paths of the next execute, for the plan's strides, windows and current raster pointer (a host raster is
+ * copied to a hipMalloc'ed, 256-byte aligned buffer): LOAD_VEC8 = the analysis kernels load samples as 8-byte
+ * vectors (else element by element); MINMAX_VEC16 / MINMAX_VEC8 = the min/max pass loads 16- / 8-byte vectors
+ * (neither: element by element, also when norm == 0 and nothing is reduced); OFF32 = every frame's rows of one
+ * channel span less than 2^31 bytes, so the vector loads may use 32-bit lane offsets (else 64-bit addresses; WAVE
+ * needs LOAD_VEC8 and OFF32).  Every combination produces the same bytes. */
 #define FRA_PLAN_DIRECT_WRITE 1
 #define FRA_PLAN_PIPELINED 2
 #define FRA_PLAN_WAVE 4
 #define FRA_PLAN_KEEP17 8
+#define FRA_PLAN_LOAD_VEC8 16
+#define FRA_PLAN_MINMAX_VEC16 32
+#define FRA_PLAN_MINMAX_VEC8 64
+#define FRA_PLAN_OFF32 128
 FRA_API int fra_plan_flags(fra_plan *plan, int32_t *flags);
 
 /* page-locked host memory (hipHostMalloc / hipHostRegister, portable across devices) */

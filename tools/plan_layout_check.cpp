@@ -2,7 +2,10 @@
 // arithmetic behind fra_plan_create, built with g++ and host sanitizers (make -C flac-raster_amd/csrc plancheck)
 // and run without a GPU.  It lays out a handful of jobs -- an empty window, edge tiles, a small block size, ranged
 // plans, windows out of row order, a plan large enough for several host bands and frame groups -- and checks the
-// invariants the kernels and the host pipeline rely on.
+// invariants the kernels and the host pipeline rely on.  It also pins layout_loads: for raster layouts of every kind
+// (padded rows and bands, interleaved, zero and overlapping strides, rows 2^29 elements apart) the vector width and
+// row block of the min/max pass, the 8-byte sample vectors, the 32-bit offsets and the wave kernel's eligibility,
+// against values worked out by hand.
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -171,7 +174,137 @@ static void check_layout(const char* what, const fra_job& j, const int32_t* fran
          L.hbands.size(), L.part.size(), L.out_cap);
 }
 
+// ---- layout_loads: which load paths a layout allows.  Every expectation below is worked out by hand from the rule
+// in fra_layout.h (V = vector bytes / itemsize; every window start, width, row stride and -- with more than one
+// channel -- band stride a multiple of V; col_stride 1; the two 2^32 bounds of the min/max pass; the 2^31-byte span
+// of a frame's rows for 32-bit lane offsets) and written out as numbers.
+struct Loads {
+  int mm_vec, mm_rows;
+  bool vec8, off32, wave_ok;
+};
+struct LoadJob {
+  int dtype, channels, level, norm;
+  int64_t band, row, col;
+  int blocksize = 4096;
+};
+static void check_loads(const char* what, const LoadJob& q, const std::vector<fra_window>& w, const Loads& want) {
+  g_what = what;
+  fra_job j{};
+  j.dtype = q.dtype;
+  j.channels = q.channels;
+  j.band_stride = q.band;
+  j.row_stride = q.row;
+  j.col_stride = q.col;
+  j.windows = w.data();
+  j.nwindows = (int)w.size();
+  j.level = q.level;
+  j.blocksize = q.blocksize;
+  j.norm = q.norm;
+  PlanLayout L;
+  const int rc = build_layout(j, j.windows, nullptr, 1, L);
+  EXPECT(rc == FRA_OK, "build_layout: %d (%s)", rc, g_msg.c_str());
+  if (rc) return;
+  EXPECT(L.mm_vec == want.mm_vec, "mm_vec %d, expected %d", L.mm_vec, want.mm_vec);
+  EXPECT(L.mm_rows == want.mm_rows, "mm_rows %d, expected %d", L.mm_rows, want.mm_rows);
+  EXPECT(L.ld_vec8 == want.vec8, "ld_vec8 %d, expected %d", (int)L.ld_vec8, (int)want.vec8);
+  EXPECT(L.ld_off32 == want.off32, "ld_off32 %d, expected %d", (int)L.ld_off32, (int)want.off32);
+  EXPECT(L.wave_ok == want.wave_ok, "wave_ok %d, expected %d", (int)L.wave_ok, (int)want.wave_ok);
+  int tallest = 0;
+  for (const fra_window& x : w) tallest = std::max(tallest, x.height);
+  if (L.mm_vec) EXPECT(L.mm_max_rows == tallest, "mm_max_rows %d, tallest window %d", L.mm_max_rows, tallest);
+  printf("%-58s mm_vec %2d rows %2d vec8 %d off32 %d wave_ok %d\n", what, L.mm_vec, L.mm_rows, (int)L.ld_vec8,
+         (int)L.ld_off32, (int)L.wave_ok);
+}
+
+static void check_load_paths() {
+  // a 72 x 264 raster; the aligned windows start at elements 0 and 8 * row + 16 and are 264 and 128 wide, the
+  // unaligned ones start at 3 * row + 5 (131 wide) and 0 (1 wide)
+  const int H = 72, W = 264;
+  const std::vector<fra_window> al = {{0, 0, 72, 264}, {8, 16, 40, 128}}, un = {{3, 5, 33, 131}, {0, 0, 1, 1}};
+  const int64_t P = (int64_t)H * W;  // 19008 = 16 * 1188
+  // min/max rows per workgroup = min(64, 2048 / (264 / V)): V 8 -> 33 vectors -> 62; V 4 -> 66 -> 31; V 2 -> 132 -> 15
+
+  // uint16 (V = 8 for 16 bytes, 4 for 8 bytes), 3 bands, level 5, norm 16: the wave kernel's plans
+  const auto u16 = [](int64_t b, int64_t r, int64_t c) { return LoadJob{FRA_U16, 3, 5, 16, b, r, c}; };
+  check_loads("u16 planar", u16(P, W, 1), al, {16, 62, true, true, true});            // 264, 19008, 2128 % 8 == 0
+  check_loads("u16 planar, unaligned windows", u16(P, W, 1), un, {0, 1, false, true, true});  // 797 and width 131 odd
+  check_loads("u16 rows + 16 bytes", u16(72 * 272, 272, 1), al, {16, 62, true, true, true});  // 272 % 8 == 0
+  check_loads("u16 rows + 8 bytes", u16(72 * 268, 268, 1), al, {8, 31, true, true, true});    // 268 % 8 == 4, % 4 == 0
+  check_loads("u16 rows + 13 elements", u16(72 * 277, 277, 1), al, {0, 1, false, true, true});  // 277 odd
+  check_loads("u16 bands + 8 bytes", u16(P + 4, W, 1), al, {8, 31, true, true, true});        // 19012 % 8 == 4
+  check_loads("u16 bands + 1 element", u16(P + 1, W, 1), al, {0, 1, false, true, true});      // 19009 odd
+  check_loads("u16 pixel-interleaved", u16(1, 3 * W, 3), al, {0, 1, false, true, true});      // col_stride 3
+  check_loads("u16 line-interleaved", u16(W, 3 * W, 1), al, {16, 62, true, true, true});      // 792 % 8 == 0, band 264
+  check_loads("u16 band_stride 0", u16(0, W, 1), al, {16, 62, true, true, true});
+  check_loads("u16 row_stride 0", u16(W, 0, 1), al, {16, 62, true, true, true});              // starts 0 and 16
+  check_loads("u16 row_stride 8", u16(832, 8, 1), al, {16, 62, true, true, true});            // starts 0 and 80
+  check_loads("u16 row_stride 8, unaligned windows", u16(832, 8, 1), un, {0, 1, false, true, true});  // start 29
+  // ... one band: the band stride does not matter
+  check_loads("u16 one band, odd band stride", LoadJob{FRA_U16, 1, 5, 16, P + 1, W, 1}, al, {16, 62, true, true, true});
+  // level 8 leaves the wave kernel's levels (3..6); a block size that is not 4096 too, and 4090 % 4 != 0 stops
+  // the 8-byte sample vectors (the min/max pass does not look at the block size)
+  check_loads("u16 planar, level 8", LoadJob{FRA_U16, 3, 8, 16, P, W, 1}, al, {16, 62, true, true, false});
+  check_loads("u16 planar, block 4090", LoadJob{FRA_U16, 3, 5, 16, P, W, 1, 4090}, al, {16, 62, false, true, false});
+
+  // uint8 (V = 16 / 8), 2 bands, level 5: 264 % 16 == 8, so never 16-byte vectors at this width
+  const auto u8 = [](int64_t b, int64_t r, int64_t c) { return LoadJob{FRA_U8, 2, 5, 16, b, r, c}; };
+  check_loads("u8 planar", u8(P, W, 1), al, {8, 62, true, true, true});
+  check_loads("u8 rows + 16 bytes", u8(72 * 280, 280, 1), al, {8, 62, true, true, true});     // 280 % 16 == 8
+  check_loads("u8 rows + 8 bytes", u8(72 * 272, 272, 1), al, {8, 62, true, true, true});      // 272 % 16 == 0, widths not
+  check_loads("u8 rows + 13 elements", u8(72 * 277, 277, 1), al, {0, 1, false, true, true});
+  check_loads("u8 bands + 8 bytes", u8(P + 8, W, 1), al, {8, 62, true, true, true});
+  check_loads("u8 line-interleaved", u8(W, 2 * W, 1), al, {8, 62, true, true, true});         // band 264 % 16 == 8
+  check_loads("u8 pixel-interleaved", u8(1, 2 * W, 2), al, {0, 1, false, true, true});
+  {  // 16-byte vectors once everything is a multiple of 16; a window of more than 65535 vectors has none
+    const std::vector<fra_window> w16 = {{0, 0, 40, 256}, {8, 16, 20, 64}};
+    check_loads("u8 256 wide", u8(72 * 256, 256, 1), w16, {16, 64, true, true, true});        // 16 vectors: min(64, 128)
+    const std::vector<fra_window> wide = {{0, 0, 1, 1 << 20}};
+    check_loads("u8 2^20 wide", LoadJob{FRA_U8, 1, 5, 16, 1 << 20, 1 << 20, 1}, wide, {0, 1, true, true, true});
+  }
+
+  // float32 (V = 4 / 2), 2 bands, level 8, norm 24: a 32-bps plan of the levels the layout marks for a wave kernel
+  // (levels >= 7), which no execute takes
+  const auto f32 = [](int64_t b, int64_t r, int64_t c) { return LoadJob{FRA_F32, 2, 8, 24, b, r, c}; };
+  check_loads("f32 planar", f32(P, W, 1), al, {16, 31, true, true, true});
+  check_loads("f32 rows + 8 bytes", f32(72 * 266, 266, 1), al, {8, 15, true, true, true});    // 266 % 4 == 2
+  check_loads("f32 bands + 8 bytes", f32(P + 2, W, 1), al, {8, 15, true, true, true});
+  check_loads("f32 bands + 1 element", f32(P + 1, W, 1), al, {0, 1, false, true, true});
+  check_loads("f32 pixel-interleaved", f32(1, 2 * W, 2), al, {0, 1, false, true, true});
+  check_loads("f32 planar, level 5", LoadJob{FRA_F32, 2, 5, 24, P, W, 1}, al, {16, 31, true, true, false});
+
+  // int16 raw samples (norm 0): no min/max pass at all, sample vectors as for uint16, no wave kernel
+  check_loads("i16 norm 0 planar", LoadJob{FRA_I16, 2, 5, 0, P, W, 1}, al, {0, 1, true, true, false});
+  check_loads("i16 norm 0 rows + 13", LoadJob{FRA_I16, 2, 5, 0, 72 * 277, 277, 1}, al, {0, 1, false, true, false});
+  // float64: no vector path
+  check_loads("f64 planar", LoadJob{FRA_F64, 1, 5, 24, P, W, 1}, al, {0, 1, false, true, false});
+  check_loads("f64 rows + 16 bytes", LoadJob{FRA_F64, 1, 5, 24, 72 * 266, 266, 1}, al, {0, 1, false, true, false});
+  check_loads("f64 pixel-interleaved", LoadJob{FRA_F64, 1, 5, 24, 1, W, 1}, al, {0, 1, false, true, false});
+
+  // pixel-interleaved uint16 with col_stride 2, windows 1..257 wide (the scalar loader's width classes)
+  {
+    const std::vector<fra_window> w = {{0, 0, 40, 256}, {40, 0, 36, 255}, {76, 0, 36, 257}, {112, 0, 9000, 1}};
+    check_loads("u16 col_stride 2", LoadJob{FRA_U16, 2, 5, 16, 1, 2 * 4104, 2}, w, {0, 1, false, true, true});
+  }
+
+  // the two 2^32 bounds and the 2^31-byte span, uint16, one band, the window 3 x 8192: 1024 16-byte vectors a
+  // row -> 2 rows per workgroup; a frame spans ceil(4096 / 8192) + 1 = 2 rows
+  const std::vector<fra_window> big = {{0, 0, 3, 8192}};
+  const auto huge = [](int64_t r) { return LoadJob{FRA_U16, 1, 5, 16, 0, r, 1}; };
+  const int64_t R29 = int64_t(1) << 29;
+  // (2 * 2^29 + 8192) * 2 bytes = 2^31 + 16384: 64-bit offsets; 2 rows * 2^29 * 2 bytes = 2^31 < 2^32: vectors stay
+  check_loads("u16 row_stride 2^29", huge(R29), big, {16, 2, true, false, true});
+  // (2 * (2^29 - 8192) + 8192) * 2 = 2^31 - 16384
+  check_loads("u16 row_stride 2^29 - 8192", huge(R29 - 8192), big, {16, 2, true, true, true});
+  // (2 * (2^29 - 4096) + 8192) * 2 = 2^31 exactly: not below it
+  check_loads("u16 row_stride 2^29 - 4096", huge(R29 - 4096), big, {16, 2, true, false, true});
+  // 2 rows * 2^30 * 2 bytes = 2^32: no 16-byte vectors; 8-byte ones take 1 row of 2048 vectors: 2^31 bytes
+  check_loads("u16 row_stride 2^30", huge(2 * R29), big, {8, 1, true, false, true});
+  // 1 row * 2^31 * 2 bytes = 2^32: scalar min/max
+  check_loads("u16 row_stride 2^31", huge(4 * R29), big, {0, 1, true, false, true});
+}
+
 int main() {
+  check_load_paths();
   {
     const std::vector<fra_window> w = {{0, 0, 0, 0}};
     check_layout("an empty window", job_u16(64, 64, 1, 4096, w), nullptr, 1, true);
