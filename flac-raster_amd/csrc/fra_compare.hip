@@ -30,6 +30,7 @@
 
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
+#include "fra_region.h"
 
 extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
 
@@ -420,59 +421,38 @@ FRA_API int fra_decode_device_compare(fra_ctx* ctx, const fra_decode_job* job, c
   if (ref_band_stride < 0 || ref_row_stride < 0 || ref_col_stride < 0)
     return fra_internal_set_error(FRA_E_INVALID, "bad reference layout (strides %lld, %lld, %lld)",
                                   (long long)ref_band_stride, (long long)ref_row_stride, (long long)ref_col_stride);
-  fra_decode_job inner = *job;  // the job's own dst and strides are ignored: the region goes to a buffer of this call
-  inner.dst_on_device = 1;
-  inner.band_stride = 0, inner.row_stride = 0, inner.col_stride = 1;
   // what the windowed read refuses at once is left to it (it does so before any GPU work, with its own message)
-  bool refer = roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
-               (job->nitems && !job->items) || (!job->data && job->len) || job->dst_dtype < FRA_U8 ||
-               job->dst_dtype > FRA_F64 || job->denorm < FRA_DENORM_NONE || job->denorm > FRA_DENORM_PCM16 ||
-               (job->denorm == FRA_DENORM_NONE && job->dst_dtype != FRA_I16 && job->dst_dtype != FRA_I32) ||
-               job->channels < 1 || job->channels > 8 || (job->flags & FRA_DECODE_CONCAT);
-  for (int i = 0; !refer && i < job->nitems; i++) {
-    const fra_window& w = job->items[i].window;
-    refer = w.height < 0 || w.width < 0 || w.row_off < 0 || w.col_off < 0;
-  }
+  const bool refer = roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
+                     (job->nitems && !job->items) || (!job->data && job->len) || job->dst_dtype < FRA_U8 ||
+                     job->dst_dtype > FRA_F64 || job->denorm < FRA_DENORM_NONE || job->denorm > FRA_DENORM_PCM16 ||
+                     (job->denorm == FRA_DENORM_NONE && job->dst_dtype != FRA_I16 && job->dst_dtype != FRA_I32) ||
+                     job->channels < 1 || job->channels > 8 || (job->flags & FRA_DECODE_CONCAT) ||
+                     !fra_region::item_windows_ok(job);
   if (refer) {
+    fra_decode_job inner = *job;  // the job's own dst and strides are ignored: the region goes to a buffer of this call
+    inner.dst_on_device = 1;
+    inner.band_stride = 0, inner.row_stride = 0, inner.col_stride = 1;
     inner.dst = (void*)bands;  // any non-null pointer: the call returns before it is looked at
     const int rc = fra_decode_device_window(ctx, &inner, roi, infos);
     return rc ? rc : fra_internal_set_error(FRA_E_INVALID, "bad arguments");
   }
   const int64_t h = roi->height, w = roi->width;
   if (const int rc = too_many_pixels(h, w)) return rc;
-  int64_t covered = 0;
-  for (int i = 0; i < job->nitems; i++) {
-    const fra_window& t = job->items[i].window;
-    const int64_t ra = std::max<int64_t>(t.row_off, roi->row_off);
-    const int64_t rb = std::min<int64_t>((int64_t)t.row_off + t.height, (int64_t)roi->row_off + h);
-    const int64_t ca = std::max<int64_t>(t.col_off, roi->col_off);
-    const int64_t cb = std::min<int64_t>((int64_t)t.col_off + t.width, (int64_t)roi->col_off + w);
-    if (rb > ra && cb > ca) covered += (rb - ra) * (cb - ca);
-  }
-  if (covered != h * w)
-    return fra_internal_set_error(FRA_E_INVALID, "the items do not cover the region (%lld of its %lld pixels)",
-                                  (long long)covered, (long long)(h * w));
-
-  const size_t es = (size_t)elem_size(job->dst_dtype);
-  const int64_t vlen = 16 / (int64_t)es;
-  const int64_t rs = (w + vlen - 1) / vlen * vlen;  // rows start on 16-byte boundaries, for k_compare's vector loads
-  CmpArgs g{};
-  g.abs_ = h * rs, g.ars = rs, g.acs = 1;
-  g.bbs = ref_band_stride, g.brs = ref_row_stride, g.bcs = ref_col_stride;
-  g.h = (int32_t)h, g.w = (int32_t)w;
+  if (const int rc = fra_region::check_cover(job, roi)) return rc;
 
   int device = 0;
   hipStream_t s = nullptr;
   fra_internal_ctx_stream(ctx, &device, &s);
   (void)hipSetDevice(device);
   HipArena sc;  // the region buffer, the staged reference, partials, reports and events: released on every path
-  void* d_region = nullptr;
-  HIPCHK(sc.alloc(&d_region, (size_t)job->channels * (size_t)(h * rs) * es));
-  inner.dst = d_region;  // the region at full resolution: band-planar, in dst_dtype, on the device
-  inner.band_stride = h * rs;
-  inner.row_stride = rs;
-  inner.col_stride = 1;
-  if (const int rc = fra_decode_device_window(ctx, &inner, roi, infos)) return rc;  // synchronous; its scratch is gone
+  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
+  int64_t rs = 0;
+  if (const int rc = fra_region::decode(ctx, job, roi, infos, sc, &d_region, &rs)) return rc;
+  const size_t es = (size_t)elem_size(job->dst_dtype);
+  CmpArgs g{};
+  g.abs_ = h * rs, g.ars = rs, g.acs = 1;
+  g.bbs = ref_band_stride, g.brs = ref_row_stride, g.bcs = ref_col_stride;
+  g.h = (int32_t)h, g.w = (int32_t)w;
 
   const void* d_ref = nullptr;
   if (const int rc = stage(sc, s, ref, ref_on_device,

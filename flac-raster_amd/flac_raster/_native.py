@@ -121,6 +121,32 @@ class CompareJob(C.Structure):
     ]
 
 
+class StatsOpts(C.Structure):
+    _fields_ = [("bins", C.c_int32), ("flags", C.c_int32), ("hist_lo", C.c_double), ("hist_hi", C.c_double),
+                ("nodata", C.c_double)]
+
+
+class StatsJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("band_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64), ("opts", StatsOpts),
+    ]
+
+
+class StatsBand(C.Structure):
+    """One band's report of ``fra_stats`` / ``fra_decode_device_stats`` (160 bytes; the rule: ``stats.py``)."""
+
+    _fields_ = [
+        ("count", C.c_uint64), ("valid", C.c_uint64), ("nan", C.c_uint64), ("nodata", C.c_uint64),
+        ("below", C.c_uint64), ("above", C.c_uint64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64),
+        ("sq_lo", C.c_uint64), ("sq_hi", C.c_uint64), ("min", C.c_double), ("max", C.c_double),
+        ("fin_min", C.c_double), ("fin_max", C.c_double), ("fsum", C.c_double), ("mean", C.c_double),
+        ("fm2", C.c_double), ("hist_lo", C.c_double), ("hist_hi", C.c_double), ("hist_scale", C.c_double),
+    ]
+
+
+STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
 E_SPACE = -6
@@ -171,7 +197,7 @@ EXPORTS = [
     "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
     "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify", "fra_decimate",
     "fra_decode_device_decimated", "fra_decimate_timing", "fra_compare", "fra_decode_device_compare",
-    "fra_compare_timing",
+    "fra_compare_timing", "fra_stats", "fra_decode_device_stats", "fra_stats_timing",
 ]
 
 
@@ -248,6 +274,11 @@ def load():
             L.fra_decode_device_compare.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), vp, i32, C.c_int64,
                                                     C.c_int64, C.c_int64, C.POINTER(CompareBand), C.POINTER(Decoded)]
             L.fra_compare_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_stats"):
+            L.fra_stats.argtypes = [vp, C.POINTER(StatsJob), C.POINTER(StatsBand), C.POINTER(u64)]
+            L.fra_decode_device_stats.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(StatsOpts),
+                                                  C.POINTER(StatsBand), C.POINTER(u64), C.POINTER(Decoded)]
+            L.fra_stats_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -414,7 +445,7 @@ class Context:
 
     def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
                       denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None,
-                      compare=None) -> List[Decoded]:
+                      compare=None, stats=None) -> List[Decoded]:
         """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
 
         ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
@@ -428,7 +459,8 @@ class Context:
         :class:`NativeError`; there is no fallback to the host decoder.  (``roi``: see
         :meth:`decode_device_window`; ``decimate`` = (factor, resampling code): see
         :meth:`decode_device_decimated`; ``compare`` = (ref pointer, on device, element strides, reports array): see
-        :meth:`decode_device_compare`, ``dst`` is then ``None``.)"""
+        :meth:`decode_device_compare`, ``dst`` is then ``None``; ``stats`` = (options, reports array, histogram
+        pointer): see :meth:`decode_device_stats`, ``dst`` is then ``None`` too.)"""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -464,7 +496,11 @@ class Context:
         job.channels = channels
         job.band_stride, job.row_stride, job.col_stride = (int(v) for v in strides)
         infos = (Decoded * max(1, len(items)))()
-        if compare is not None:
+        if stats is not None:
+            opts, bands, hist = stats
+            rc = load().fra_decode_device_stats(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
+                                                C.byref(opts), bands, hist, infos)
+        elif compare is not None:
             ref, ref_on_device, rst, bands = compare
             rc = load().fra_decode_device_compare(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                   C.c_void_p(int(ref)), 1 if ref_on_device else 0, int(rst[0]),
@@ -632,6 +668,74 @@ class Context:
         """HIP-event ms of this thread's last ``k_compare`` + fold (:meth:`compare` / :meth:`decode_device_compare`)."""
         ms = C.c_float()
         _check(load().fra_compare_timing(C.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _stats_opts(bins, hist_range, nodata):
+        """The ``StatsOpts`` of a request (checked by ``stats.check_options``)."""
+        from .stats import check_options, flags_of
+
+        bins, mode, nodata = check_options(bins, hist_range, nodata)
+        o = StatsOpts()
+        o.bins, o.flags = bins, flags_of(mode, nodata)
+        if isinstance(mode, tuple):
+            o.hist_lo, o.hist_hi = mode
+        o.nodata = 0.0 if nodata is None else nodata
+        return o
+
+    def decode_device_stats(self, data, items, dst_dtype, channels: int, roi, denorm: int = DENORM_NONE, bins: int = 0,
+                            hist_range=None, nodata=None):
+        """The statistics of ``roi`` of the tile streams (``fra_decode_device_stats``): the records of
+        ``stats.stats_arrays(what decode_device_window would have written, bins, hist_range, nodata)``, one per band,
+        without the decoded region leaving the GPU.
+
+        ``data``, ``items``, ``roi``, ``denorm`` as :meth:`decode_device_window`; ``bins``, ``hist_range``, ``nodata``
+        as ``stats.stats_arrays``.  The items must cover the region.  Returns ``(reports, histogram (channels, bins)
+        uint64 or None, infos)``."""
+        if roi is None:
+            raise ValueError("roi is required")
+        o = self._stats_opts(bins, hist_range, nodata)
+        bands = (StatsBand * max(1, channels))()
+        hist = np.zeros((channels, o.bins), np.uint64) if o.bins else None
+        hp = hist.ctypes.data_as(C.POINTER(C.c_uint64)) if hist is not None else None
+        infos = self.decode_device(data, items, None, np.dtype(dst_dtype), channels, (0, 0, 0), denorm, False, roi,
+                                   stats=(o, bands, hp))
+        return list(bands)[:channels], hist, infos
+
+    def stats(self, src, bins: int = 0, hist_range=None, nodata=None, *, dtype=None, shape=None, strides=None):
+        """Band statistics and histograms of a raster on this context's GPU (``fra_stats``, the rule of
+        ``flac_raster.stats``): ``(one StatsBand per band, histogram (B, bins) uint64 or None)``.
+
+        ``src``: a numpy array ``(B, h, w)`` / ``(h, w)`` of one of the eight raster dtypes with any non-negative
+        strides (a view is fine: it is copied to the device from its first element to its last), or a device pointer
+        (int) with ``dtype``, ``shape`` = (B, h, w) and element ``strides`` (default band-planar).  It is not written.
+        ``bins``, ``hist_range`` (``(lo, hi)``, ``"auto"`` / ``None``), ``nodata`` as ``stats.stats_arrays``."""
+        job = StatsJob()
+        if isinstance(src, np.ndarray):
+            a = src if src.ndim == 3 else src[None]
+            if a.ndim != 3:
+                raise ValueError("src must be (B, h, w) or (h, w)")
+            dt, (B, h, w), st = a.dtype, a.shape, _element_strides(a)
+            job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
+        else:
+            dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
+            st = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
+            job.src, job.src_on_device = C.c_void_p(int(src)), 1
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"unsupported dtype {dt}")
+        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
+        job.band_stride, job.row_stride, job.col_stride = st
+        job.opts = self._stats_opts(bins, hist_range, nodata)
+        bands = (StatsBand * max(1, B))()
+        hist = np.zeros((B, job.opts.bins), np.uint64) if job.opts.bins else None
+        hp = hist.ctypes.data_as(C.POINTER(C.c_uint64)) if hist is not None else None
+        _check(load().fra_stats(self.h, C.byref(job), bands, hp))
+        return list(bands)[:B], hist
+
+    def stats_timing(self) -> float:
+        """HIP-event ms of this thread's last statistics kernels (:meth:`stats` / :meth:`decode_device_stats`)."""
+        ms = C.c_float()
+        _check(load().fra_stats_timing(C.byref(ms)))
         return ms.value
 
     def decode_timing(self) -> List[float]:

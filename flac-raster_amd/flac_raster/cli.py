@@ -363,6 +363,84 @@ def check(
         raise typer.Exit(1)
 
 
+@app.command()
+def stats(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width'"),
+    bins: Optional[int] = typer.Option(None, "--bins", help="Histogram bins, 0 ... 65536 (default: the exact value "
+                                       "histogram for dtypes of at most 16 bits, else 256)"),
+    hist_range: Optional[str] = typer.Option(None, "--range", help="Histogram range 'lo,hi' (default: each band's finite "
+                                             "minimum and maximum)"),
+    nodata: Optional[float] = typer.Option(None, "--nodata", help="Nodata value (default: the TIFF's own tag)"),
+    percentiles: str = typer.Option("2,50,98", "--percentiles", help="Percentiles to print, from the histogram"),
+    semantics: str = typer.Option("pcm16", "--semantics", help="Container pixels: pcm16 (what convert back gives) or int"),
+    export_json: Optional[Path] = typer.Option(None, "--export", "-e", help="Export the full report to JSON"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Band statistics, histogram and percentiles of a streaming FLAC file or a GeoTIFF."""
+    import numpy as np
+
+    from .stats import display_stats_table, exact_range, percentile
+    from .streaming import container_stats, is_streaming_container, open_streaming, tiff_stats
+    from .tiff import GeoTIFF
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        path = _local(file_path)
+        if not path.exists():
+            console.print(f"[red]File not found: {path}[/red]")
+            raise typer.Exit(1)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        qs = [float(x.strip()) for x in percentiles.split(",") if x.strip()]
+        with open(path, "rb") as f:
+            is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+        is_container = not is_tiff and is_streaming_container(path)
+        if not is_tiff and not is_container:
+            console.print("[red]Error: a streaming FLAC file (convert --streaming) or a GeoTIFF is needed[/red]")
+            raise typer.Exit(1)
+        if is_container:
+            dt = np.dtype(open_streaming(path).index["dtype"])
+        else:
+            g = GeoTIFF(path)
+            try:
+                dt = np.dtype(g.info.dtype)
+            finally:
+                g.close()
+        rng = tuple(float(x.strip()) for x in hist_range.split(",")) if hist_range else None
+        if rng is not None and len(rng) != 2:
+            console.print("[red]Error: --range takes 'lo,hi'[/red]")
+            raise typer.Exit(1)
+        if bins is None and rng is None and dt.kind in "iu" and dt.itemsize <= 2:
+            lo, hi, bins = exact_range(dt)  # bin i holds exactly the value lo + i: exact percentiles
+            rng = (lo, hi)
+        elif bins is None:
+            bins = 256
+        dev = device if device is not None else (0 if _gpu_present() else None)
+        if is_container:
+            bands, got, _ = container_stats(path, window=win, bbox=box, bins=bins, hist_range=rng, nodata=nodata,
+                                            device=dev, semantics=semantics)
+        else:
+            bands, got, _ = tiff_stats(path, window=win, bbox=box, bins=bins, hist_range=rng, nodata=nodata, device=dev)
+        display_stats_table(bands, qs, title=f"{path.name}: rows {got[0]}..{got[0] + got[2]}, columns "
+                                             f"{got[1]}..{got[1] + got[3]} ({dt})")
+        if export_json:
+            for b in bands:
+                b["percentiles"] = {f"{q:g}": percentile(b, q) for q in qs}
+            export_json.write_text(json.dumps({"file": path.name, "dtype": str(dt), "window": list(got),
+                                               "semantics": semantics if is_container else None,
+                                               "device": dev, "bands": bands}, indent=2))
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Statistics failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
 def _show_tiff_info(path: Path):
     from .tiff import GeoTIFF
 

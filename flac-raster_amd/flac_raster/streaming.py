@@ -577,6 +577,73 @@ def check_against_tiff(container: Path, tiff: Path, window: Optional[Sequence[in
     return report, win, index
 
 
+# ------------------------------------------------------------------------------------------ statistics
+def container_stats(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                    bins: int = 0, hist_range=None, nodata: Optional[float] = None, device: Optional[int] = None,
+                    semantics: str = "pcm16"):
+    """Band statistics and histograms of a streaming container (path or bytes), or of a window of it -> ``(report,
+    window, index)``: ``stats.stats_arrays(read_window(src, ...)[0], bins, hist_range, nodata)``, one dict per band.
+
+    ``window`` / ``bbox`` as in :func:`read_window` (default: the whole raster); ``bins``, ``hist_range`` (``(lo, hi)``,
+    ``"auto"`` / ``None``) and ``nodata`` as ``stats.stats_arrays``.  ``device=None`` reads the window on the host and
+    applies the numpy rule; an integer makes one ``fra_decode_device_stats`` call on that GPU: the decoded pixels never
+    leave the device and only the reports and the histogram come back."""
+    from . import _native
+    from .stats import check_options, report_from_bands, stats_arrays
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    check_options(bins, hist_range, nodata)
+    if window is None and bbox is None:
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            mv = memoryview(src)
+            index, _ = read_index_bytes(bytes(mv[:4 + struct.unpack(">I", mv[:4])[0]]))
+        else:
+            index = open_streaming(Path(src)).index
+        window = (0, 0, int(index["height"]), int(index["width"]))
+    index, win, blob, items = _window_items(src, window, bbox)
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    if device is None:
+        out = np.zeros((B, win[2], win[3]), dtype=dt)
+        _decode_window_on_host(blob, items, win, out, semantics)
+        return stats_arrays(out, bins, hist_range, nodata), win, index
+    ctx = _native.default_context(int(device))
+    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+    bands, hist, _ = ctx.decode_device_stats(np.frombuffer(blob, dtype=np.uint8), items, dt, B, win, denorm, bins,
+                                             hist_range, nodata)
+    return report_from_bands(bands, hist, dt), win, index
+
+
+def tiff_stats(path: Path, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+               bins: int = 0, hist_range=None, nodata: Optional[float] = None, device: Optional[int] = None):
+    """Band statistics and histograms of a GeoTIFF, or of a window of it -> ``(report, window, info)``.  The window is
+    read with the in-package reader; an integer ``device`` hands it to ``fra_stats`` on that GPU, ``None`` to the numpy
+    rule.  ``nodata=None`` takes the TIFF's own nodata tag, when it has one."""
+    from . import _native
+    from .stats import report_from_bands, stats_arrays
+
+    g = GeoTIFF(Path(path))
+    try:
+        info = g.info
+        dt = np.dtype(info.dtype)
+        if window is None and bbox is None:
+            win = (0, 0, info.height, info.width)
+        else:
+            win = resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)},
+                                 window, bbox)
+        if nodata is None and info.nodata is not None:
+            nodata = float(info.nodata)
+        a = np.zeros((info.count, win[2], win[3]), dtype=dt)
+        g.read_window_into(a, *win)
+    finally:
+        g.close()
+    if device is None:
+        return stats_arrays(a, bins, hist_range, nodata), win, info
+    bands, hist = _native.default_context(int(device)).stats(a, bins, hist_range, nodata)
+    return report_from_bands(bands, hist, dt), win, info
+
+
 def read_overview(src, factor: int, resampling: str = "average", device: Optional[int] = None,
                   semantics: str = "pcm16"):
     """The whole raster of a streaming container (path or bytes) at ``1 / factor`` resolution -> ``(raster (B,

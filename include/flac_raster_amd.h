@@ -425,6 +425,70 @@ FRA_API int fra_decode_device_compare(fra_ctx *ctx, const fra_decode_job *job, c
 /* HIP-event time (ms) of the calling thread's last k_compare + k_compare_fold (fra_compare or fra_decode_device_compare) */
 FRA_API int fra_compare_timing(float *ms);
 
+/* Band statistics and histograms of a raster (channels, h, w) of any fra_dtype: one report per band.
+ *   Which pixels count.  Every element is taken as f64 (exact for all eight dtypes).  nan = the NaN pixels (floats only);
+ *     nodata = the pixels with (double)x == opts.nodata, counted only with FRA_STATS_NODATA (a NaN nodata matches
+ *     nothing); valid = the rest, and only valid pixels enter anything below.  count = h * w = valid + nan + nodata.
+ *     +-inf are valid numbers.
+ *   Extremes.  min, max over the valid pixels, exact doubles, +-inf included; NaN when valid == 0.  fin_min, fin_max the
+ *     same over the finite valid pixels, NaN when there is none; for integers they equal min / max.
+ *   Integer dtypes.  sum = the exact 128-bit two's-complement sum of x (sum_lo uint64, sum_hi int64); sq = the exact
+ *     unsigned 128-bit sum of x^2 (sq_lo, sq_hi).  No order is implied, nothing wraps.  More than 2^32 pixels per band are
+ *     refused, which keeps sum inside 65 bits and sq inside 96.  fsum = mean = fm2 = 0.0.
+ *   f32 / f64.  fsum = the f64 sum of x; mean = fsum / (double)valid, one IEEE division; fm2 = the f64 sum of
+ *     (x - mean) * (x - mean), the corrected two-pass form with mean read back from the first pass on the device.  No
+ *     summation order is implied, but no float atomics are used -- lane tree, then the waves in order, then the partials in
+ *     index order -- so two calls on the same inputs and layout return byte-identical reports.  Plain IEEE arithmetic:
+ *     +-inf propagate into fsum, mean and fm2, which may become inf or NaN.  valid == 0: fsum = fm2 = 0.0, mean = NaN.
+ *     The integer sums are 0.
+ *   Histogram.  opts.bins in 0 ... 65536, 0 = none; hist is channels x bins uint64, zero where nothing falls.  The range of
+ *     a band is [opts.hist_lo, opts.hist_hi] (both finite, lo <= hi), or with FRA_STATS_AUTO_RANGE [fin_min, fin_max] of
+ *     that band, read on the device from the first pass.  scale = hi > lo ? (double)bins / (hi - lo) : 0.0, and a scale
+ *     that is not finite is taken as 0.0.  A valid pixel with x < lo goes to below, one with x > hi to above, any other
+ *     to bin min(bins - 1, (int64)floor((x - lo) * scale)) (bin 0 when scale == 0.0): the subtraction, the product and
+ *     the floor are separate f64 operations.  A band without an automatic range (no finite valid pixel) bins nothing and
+ *     has below = above = 0.  hist_lo, hist_hi, hist_scale are the values used: 0 when bins == 0, NaN / NaN / 0 for a band
+ *     without a range.  When hi - lo == bins the scale is exactly 1.0 and bin i holds exactly the pixels of value lo + i:
+ *     uint16 over [0, 65536] with 65536 bins is the exact value histogram, and so for every dtype of <= 16 bits. */
+#define FRA_STATS_AUTO_RANGE 1
+#define FRA_STATS_NODATA 2
+typedef struct {
+  int32_t bins, flags;
+  double hist_lo, hist_hi, nodata;
+} fra_stats_opts;
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype */
+  int32_t channels, height, width;          /* >= 1 */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+  fra_stats_opts opts;
+} fra_stats_job;
+typedef struct {
+  uint64_t count, valid, nan, nodata, below, above;
+  uint64_t sum_lo; int64_t sum_hi; uint64_t sq_lo, sq_hi;
+  double   min, max, fin_min, fin_max, fsum, mean, fm2, hist_lo, hist_hi, hist_scale;
+} fra_stats_band;     /* 160 bytes */
+/* k_stats + its fold (and, for floats and for an automatic range, the second pass + its fold) alone, over a host or
+ * device raster of any layout.  Synchronous; bands (host memory) receives `channels` reports and hist (host memory)
+ * channels x bins counts; hist may be null only when bins == 0.  A host raster is staged as fra_compare stages it (one
+ * allocation spanning every addressed element from element 0) and never written; 16-byte loads when the column stride
+ * is 1 and the base, the row stride and the band stride are multiples of 16 bytes, element loads otherwise.
+ * FRA_E_INVALID, before any GPU work: a null argument, a bad dtype or layout, more than 2^32 pixels per band, bins
+ * outside 0 ... 65536, unknown flag bits, a non-finite or inverted explicit range, a null hist with bins > 0. */
+FRA_API int fra_stats(fra_ctx *ctx, const fra_stats_job *job, fra_stats_band *bands /* channels */,
+                      uint64_t *hist /* channels x bins */);
+/* The statistics of what fra_decode_device_window would have written for `roi`, in dst_dtype, after its
+ * denormalisation and saturation.  roi, the items and infos mean what they mean there; job->dst and the job's strides
+ * are ignored.  The region goes to a per-call device buffer (band-planar, rows padded to 16 bytes) and never leaves the
+ * device; every refusal and message of the windowed read is this call's as well, items that do not cover the region are
+ * refused as by fra_decode_device_compare, and the options as by fra_stats.  Afterwards fra_decode_device_timing
+ * reports the inner windowed read and fra_stats_timing the statistics. */
+FRA_API int fra_decode_device_stats(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                    const fra_stats_opts *opts, fra_stats_band *bands /* channels */,
+                                    uint64_t *hist /* channels x bins */, fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last statistics kernels, both passes and folds */
+FRA_API int fra_stats_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

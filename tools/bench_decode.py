@@ -55,6 +55,17 @@ same reports, and band 0 must equal ``compare.compare_arrays`` of the plain read
 skipped.
 
     python tools/bench_decode.py --compare --steps 5 --warmup 2
+
+``--stats`` times the band statistics of the same container (``fra_decode_device_stats``: the whole raster decoded
+with ``pcm16`` semantics to uint16 and described there, only the reports and the histogram come back) in five legs: the
+plain read to a device destination, ``bins = 0`` (one pass), 256 bins over the automatic range (two passes), the exact
+65536-bin histogram (one pass, and one more per further window of 8192 bins that a band's values reach), and the kernels alone (``fra_stats``) on a
+constant raster on the device, with 256 bins and with 65536 -- the worst case for same-address atomics.  Per leg ``stats_wall_ms``, the
+inner read, ``k_stats_ms`` (HIP events over both passes and folds) and ``k_stats_TBps`` = bytes read by the passes /
+that time; ``band_reads`` counts them: a band is read once per pass and once more per further window of 8192 bins that
+its values reach (the launches of the other windows leave without reading).  It exits non-zero unless band 0 of every leg equals ``stats.stats_arrays`` of the plain read.
+
+    python tools/bench_decode.py --stats --steps 5 --warmup 2
 """
 from __future__ import annotations
 
@@ -112,6 +123,8 @@ def main():
     ap.add_argument("--resampling", default="average", choices=("nearest", "average"), help="with --decimate")
     ap.add_argument("--compare", action="store_true",
                     help="time the comparison of the container with its source raster against the plain read")
+    ap.add_argument("--stats", action="store_true",
+                    help="time the band statistics and histograms of the container against the plain read")
     args = ap.parse_args()
 
     ctx = N.Context(0)
@@ -265,6 +278,96 @@ def main():
                          "k_compare_ms": round(med(kc), 4), "k_compare_TBps": round(moved / (med(kc) * 1e-3) / 1e12, 3),
                          "wall_over_plain": round(med(wall) / med(plain_wall), 3),
                          "all_ms": {"k_compare": [round(v, 4) for v in kc], "compare_wall": [round(v, 3) for v in wall]}}
+        res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall]}
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
+
+    if args.stats:
+        from flac_raster.stats import exact_range, report_from_bands as stats_report, stats_arrays
+
+        if len(wins) != len(calculate_tiles(H, W, TILE)):
+            raise SystemExit("--stats needs every tile: the region described is the whole raster")
+        roi = (0, 0, H, W)
+        citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
+        plain_wall, plain_ms = [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ctx.decode_device_window((frames_ptr, total), citems, dev_out, dt, B, (H * W, W, 1), roi, N.DENORM_PCM16)
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                plain_wall.append((t1 - t0) * 1e3)
+                plain_ms.append(ctx.decode_timing()[3])
+        decoded = np.empty((B, H, W), dt)
+        ctx.d2h(decoded, dev_out)
+        elo, ehi, ebins = exact_range(dt)
+        med = statistics.median
+        once = B * H * W * dt.itemsize
+        res = {
+            "workload": f"stats C4-like {W}x{H}x{B} uint16 (pcm16), tile {TILE}, level {LEVEL}, {len(wins)} tiles, "
+                        "whole raster",
+            "tiles": len(wins), "frames": nfr, "steps": args.steps, "warmup": args.warmup,
+            "band0_equals_stats_arrays": True,
+            "plain_ms": round(med(plain_ms), 3), "plain_wall_ms": round(med(plain_wall), 3), "raster_bytes": once,
+        }
+        def band_reads(rep, passes):
+            """Reads of a band's pixels, summed over the bands: one per pass, one per further window its values reach."""
+            n = 0
+            for b in rep:
+                n += passes
+                if b["bins"] > 8192 and b["hist_range"] is not None and b["fin_min"] is not None:
+                    lo, hi = b["hist_range"]
+                    at = lambda x: 0 if b["hist_scale"] == 0.0 else int(min(b["bins"] - 1, (x - lo) * b["hist_scale"] // 1))  # noqa: E731
+                    xa, xb = max(b["fin_min"], lo), min(b["fin_max"], hi)
+                    if xa <= xb:
+                        n += sum(1 for k in range(1, -(-b["bins"] // 8192)) if at(xb) >= k * 8192 and at(xa) < (k + 1) * 8192)
+            return n
+
+        for name, bins, rng, passes in (("bins0", 0, None, 1), ("bins256_auto", 256, "auto", 2),
+                                        ("exact65536", ebins, (elo, ehi), 1)):
+            want = stats_arrays(decoded[:1], bins, rng)[0]
+            wall, inner, ks = [], [], []
+            for s in range(args.warmup + args.steps):
+                t0 = time.perf_counter()
+                bands, hist, _ = ctx.decode_device_stats((frames_ptr, total), citems, dt, B, roi, N.DENORM_PCM16, bins,
+                                                         rng)
+                t1 = time.perf_counter()
+                if s >= args.warmup:
+                    wall.append((t1 - t0) * 1e3)
+                    inner.append(ctx.decode_timing()[3])
+                    ks.append(ctx.stats_timing())
+            rep_all = stats_report(bands, hist, dt)
+            got = rep_all[0]
+            reads = band_reads(rep_all, passes)
+            if got != want:
+                diff = {k: (got[k], want[k]) for k in want if k != "histogram" and got[k] != want[k]}
+                raise SystemExit(f"stats {name}: band 0 differs from stats_arrays: {diff or 'in the histogram'}")
+            res[name] = {"stats_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3),
+                         "k_stats_ms": round(med(ks), 4), "passes": passes, "band_reads": reads,
+                         "k_stats_TBps": round(reads * (once // B) / (med(ks) * 1e-3) / 1e12, 3),
+                         "wall_over_plain": round(med(wall) / med(plain_wall), 3),
+                         "all_ms": {"k_stats": [round(v, 4) for v in ks], "stats_wall": [round(v, 3) for v in wall]}}
+        res["band0"] = {k: got[k] for k in ("valid", "min", "max", "mean", "std")}
+        del decoded
+        # the kernels alone on a constant raster: every pixel of a band in one bin
+        const = np.full((B, H, W), 12345, dt)
+        ctx.h2d(dev_out, const)
+        for name, bins, rng in (("constant_256", 256, (0.0, 65536.0)), ("constant_65536", ebins, (elo, ehi))):
+            ks = []
+            for s in range(args.warmup + args.steps):
+                bands, hist = ctx.stats(dev_out, bins, rng, dtype=dt, shape=(B, H, W), strides=(H * W, W, 1))
+                if s >= args.warmup:
+                    ks.append(ctx.stats_timing())
+            j = 12345 * bins // 65536
+            if any(int(hist[b, j]) != H * W or int(hist[b].sum()) != H * W or r.sum_lo != 12345 * H * W
+                   for b, r in enumerate(bands)):
+                raise SystemExit(f"stats {name}: the constant raster is not counted exactly")
+            reads = band_reads(stats_report(bands, hist, dt), 1)  # 12345 lies in the second window of 65536 bins
+            res[name] = {"k_stats_ms": round(med(ks), 4), "passes": 1, "band_reads": reads,
+                         "k_stats_TBps": round(reads * (once // B) / (med(ks) * 1e-3) / 1e12, 3),
+                         "all_ms": {"k_stats": [round(v, 4) for v in ks]}}
         res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall]}
         print(json.dumps(res), flush=True)
         plan.close()

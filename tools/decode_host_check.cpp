@@ -10,7 +10,8 @@
 //     exactly when the flipped byte lies in a selected frame;
 //   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated reads
-//     and the comparison (fra_compare, fra_decode_device_compare), which returns before any GPU work.
+//     the comparison (fra_compare, fra_decode_device_compare) and the statistics (fra_stats, fra_decode_device_stats),
+//     which returns before any GPU work.
 // usage: decode_host_check [--concat] file.flac ...
 #include <cstdarg>
 #include <cstdio>
@@ -408,6 +409,62 @@ int main(int argc, char** argv) {
     { auto j = cj; j.b_row_stride = -8; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID, "compare: negative stride accepted"); }
     { auto j = cj; j.height = 65537; j.width = 65536; EXPECT(fra_compare(ctx, &j, bands) == FRA_E_INVALID && g_msg.find("2^32 pixels") != std::string::npos, "compare: more than 2^32 pixels accepted"); }
     EXPECT(fra_compare_timing(nullptr) == FRA_E_INVALID, "compare timing: null accepted");
+  }
+  // ... and of the statistics (fra_stats.hip): refused before any GPU work
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;
+    dj.items = &di;
+    dj.dst = nullptr;  // ignored, as are the job's strides
+    dj.band_stride = dj.row_stride = dj.col_stride = -1;
+    const fra_window r48{0, 0, 4, 8};
+    fra_stats_band bands[1];
+    uint64_t hist[8];
+    fra_stats_opts none{};
+    fra_stats_opts eight{};
+    eight.bins = 8; eight.hist_lo = 0.0; eight.hist_hi = 1.0;
+    auto st = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, const fra_stats_opts* o, fra_stats_band* b,
+                  uint64_t* h, fra_decoded* d) { return fra_decode_device_stats(c, j, r, o, b, h, d); };
+    EXPECT(st(nullptr, &dj, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: null ctx accepted");
+    EXPECT(st(ctx, nullptr, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: null job accepted");
+    EXPECT(st(ctx, &dj, nullptr, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: null roi accepted");
+    EXPECT(st(ctx, &dj, &r48, nullptr, bands, hist, inf) == FRA_E_INVALID, "statistics read: null options accepted");
+    EXPECT(st(ctx, &dj, &r48, &none, nullptr, hist, inf) == FRA_E_INVALID, "statistics read: null bands accepted");
+    EXPECT(st(ctx, &dj, &r48, &none, bands, hist, nullptr) == FRA_E_INVALID, "statistics read: null infos accepted");
+    EXPECT(st(ctx, &dj, &r48, &eight, bands, nullptr, inf) == FRA_E_INVALID && g_msg.find("null histogram") != std::string::npos, "statistics read: null histogram with bins accepted");
+    for (int b : {-1, 65537}) { auto o = eight; o.bins = b; EXPECT(st(ctx, &dj, &r48, &o, bands, hist, inf) == FRA_E_INVALID && g_msg.find("bins") != std::string::npos, "statistics read: %d bins accepted", b); }
+    { auto o = eight; o.flags = 4; EXPECT(st(ctx, &dj, &r48, &o, bands, hist, inf) == FRA_E_INVALID && g_msg.find("flags") != std::string::npos, "statistics read: flag 4 accepted"); }
+    { auto o = eight; o.hist_lo = 2.0; EXPECT(st(ctx, &dj, &r48, &o, bands, hist, inf) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics read: inverted range accepted"); }
+    { auto o = eight; o.hist_hi = HUGE_VAL; EXPECT(st(ctx, &dj, &r48, &o, bands, hist, inf) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics read: infinite range accepted"); }
+    { fra_window r = r48; r.height = 5; EXPECT(st(ctx, &dj, &r, &none, bands, hist, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "statistics read: uncovered row accepted"); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "statistics read: uncovered column accepted"); }
+    { auto j = dj; j.nitems = 0; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(st(ctx, &dj, &r, &none, bands, hist, inf) == FRA_E_INVALID && g_msg.find("region of interest") != std::string::npos, "statistics read: zero-width roi accepted"); }
+    { fra_window r{0, 0, 65537, 65536}; EXPECT(st(ctx, &dj, &r, &none, bands, hist, inf) == FRA_E_INVALID && g_msg.find("2^32 pixels") != std::string::npos, "statistics read: more than 2^32 pixels accepted"); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID && g_msg.find("dtype") != std::string::npos, "statistics read: dtype 9 accepted"); }
+    { auto j = dj; j.denorm = 7; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: denorm 7 accepted"); }
+    { auto j = dj; j.channels = 0; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: no channels accepted"); }
+    { auto x = di; x.window = {0, 0, -8, 1}; auto j = dj; j.items = &x; EXPECT(st(ctx, &j, &r48, &none, bands, hist, inf) == FRA_E_INVALID, "statistics read: capacity window accepted"); }
+    fra_stats_job sj{};
+    sj.src = dst; sj.dtype = FRA_I32; sj.channels = 1; sj.height = 8; sj.width = 8;
+    sj.band_stride = 64; sj.row_stride = 8; sj.col_stride = 1;
+    EXPECT(fra_stats(nullptr, &sj, bands, hist) == FRA_E_INVALID, "statistics: null ctx accepted");
+    EXPECT(fra_stats(ctx, nullptr, bands, hist) == FRA_E_INVALID, "statistics: null job accepted");
+    EXPECT(fra_stats(ctx, &sj, nullptr, hist) == FRA_E_INVALID, "statistics: null bands accepted");
+    { auto j = sj; j.src = nullptr; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID, "statistics: null src accepted"); }
+    { auto j = sj; j.dtype = 8; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("dtype") != std::string::npos, "statistics: dtype 8 accepted"); }
+    { auto j = sj; j.width = 0; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("layout") != std::string::npos, "statistics: zero width accepted"); }
+    { auto j = sj; j.channels = 0; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID, "statistics: no channels accepted"); }
+    { auto j = sj; j.row_stride = -8; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID, "statistics: negative stride accepted"); }
+    { auto j = sj; j.height = 65537; j.width = 65536; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("2^32 pixels") != std::string::npos, "statistics: more than 2^32 pixels accepted"); }
+    { auto j = sj; j.opts = eight; EXPECT(fra_stats(ctx, &j, bands, nullptr) == FRA_E_INVALID && g_msg.find("null histogram") != std::string::npos, "statistics: null histogram with bins accepted"); }
+    for (int b : {-1, 65537}) { auto j = sj; j.opts = eight; j.opts.bins = b; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("bins") != std::string::npos, "statistics: %d bins accepted", b); }
+    { auto j = sj; j.opts.flags = 8; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("flags") != std::string::npos, "statistics: flag 8 accepted"); }
+    { auto j = sj; j.opts = eight; j.opts.hist_hi = -1.0; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics: inverted range accepted"); }
+    { auto j = sj; j.opts = eight; j.opts.hist_lo = -HUGE_VAL; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics: infinite range accepted"); }
+    EXPECT(fra_stats_timing(nullptr) == FRA_E_INVALID, "statistics timing: null accepted");
   }
   printf("argument validation checked\n");
 #endif
