@@ -112,6 +112,14 @@ __device__ __forceinline__ double rdlane_f64(double v, int l) {
 }
 
 
+// The low 16 bits of rint(x w) for |x w| < 2^15 (a 16-bit sample times a window coefficient in [0, 1]): the f32
+// product as before, then + 1.5 * 2^23 instead of v_rndne_f32 and v_cvt_i32_f32 -- in [2^23, 2^24) the f32 grid is
+// the integers, so the one round-to-nearest-even add IS the rint, and the sum's bit pattern is 0x4B400000 + rint:
+// its low 16 bits are the integer's (two's complement).  The byte split of the MFMA operands reads no others
+__device__ __forceinline__ int32_t wround16(float x, float w) {
+  return __float_as_int(__fadd_rn(__fmul_rn(x, w), 12582912.0f));
+}
+
 // Levinson-Durbin (op sequence of levinson_wave / oracle ora_levinson) where each lane keeps only what its
 // order lo needs: the prediction error after step lo - 1 (e, step 0's for lo = 0) and that step's row,
 // negated (lp = -lpc, the quantiser's input), so neither the rows nor the errors go through LDS
@@ -225,8 +233,8 @@ __device__ __forceinline__ int32_t wnorm(uint32_t r, const WNorm& q) {
 }
 template <typename T>
 __device__ __forceinline__ void wload_lut(const void* base, const WaveDev& wd, int c,
-                                          const int32_t* lut, uint32_t* sw, int lane, uint32_t& orv, int32_t& vmin,
-                                          int32_t& vmax, bool stamp, const WNorm& wn) {
+                                          const int32_t* lut, uint32_t* sw, int lane, uint32_t& orv, uint32_t& anv,
+                                          bool stamp, const WNorm& wn) {
   constexpr int V = 8 / (int)sizeof(T);
   constexpr int NV = kMaxBlock / 64 / V;
   constexpr uint32_t step = 64 * V;
@@ -251,8 +259,10 @@ __device__ __forceinline__ void wload_lut(const void* base, const WaveDev& wd, i
     if (col >= w) { col -= w; roff += rsb; }
   }
   if (stamp) FRA_WSTAMP_WAIT(11)
-  uint32_t orp = 0;
-  i16x2 pmin = {32767, 32767}, pmax = {-32768, -32768};
+  // OR and AND of the packed pairs: the OR gives the wasted bits, and the frame is CONSTANT exactly when the AND of
+  // all its 16-bit patterns equals their OR (every bit the same in every sample) -- two bit operations per four
+  // samples where a packed min and max took four
+  uint32_t orp = 0, anp = 0xFFFFFFFFu;
 #pragma unroll
   for (int kv = 0; kv < NV; kv++) {
     int32_t g[V];
@@ -266,7 +276,11 @@ __device__ __forceinline__ void wload_lut(const void* base, const WaveDev& wd, i
       constexpr int EB = 8 * (int)sizeof(T);
       const uint32_t wsrc = e < V / 2 ? xw.x : xw.y;
       const uint32_t raw = (wsrc >> (EB * (e % (V / 2)))) & ((1u << EB) - 1u);
-      g[e] = arith ? wnorm<T>(raw, wn) : *(const int32_t*)((const char*)lut + (raw << 2));
+      // (the byte offset is opaque to the compiler: seen through, it formed the gather addresses of each vector's
+      // second dword with 64-bit adds, v_lshl_add_u64, instead of the uniform base + 32-bit offset form)
+      uint32_t off = raw << 2;
+      asm("" : "+v"(off));
+      g[e] = arith ? wnorm<T>(raw, wn) : *(const int32_t*)((const char*)lut + off);
     }
     const int i = (lane + 64 * kv) * V;
 #pragma unroll
@@ -276,16 +290,68 @@ __device__ __forceinline__ void wload_lut(const void* base, const WaveDev& wd, i
       const uint32_t p1 = __builtin_amdgcn_perm((uint32_t)g[4 * h + 3], (uint32_t)g[4 * h + 2], 0x05040100u);
       *reinterpret_cast<uint2*>(&sw[sdw(s >> 4, (s & 15) >> 1)]) = make_uint2(p0, p1);
       orp |= p0 | p1;
-      const i16x2 a0 = __builtin_bit_cast(i16x2, p0), a1 = __builtin_bit_cast(i16x2, p1);
-      pmin = __builtin_elementwise_min(pmin, __builtin_elementwise_min(a0, a1));
-      pmax = __builtin_elementwise_max(pmax, __builtin_elementwise_max(a0, a1));
+      anp &= p0 & p1;
     }
   }
   orv |= (orp | (orp >> 16)) & 0xFFFFu;
-  vmin = min(vmin, min((int32_t)pmin.x, (int32_t)pmin.y));
-  vmax = max(vmax, max((int32_t)pmax.x, (int32_t)pmax.y));
+  anv &= anp & (anp >> 16);
   if (stamp) FRA_WSTAMP_WAIT(12)
 }
+
+// The shifted predictions (pred_raw >> sh) of the four samples b .. b + 3, their dot chains abreast: the first pair
+// of each chain in the three-operand form (accumulator 0: no v_mov per sample), and between two dots of one chain
+// -- and between a chain's last dot and its shift -- the three other samples' instructions, which is the distance
+// the dot pipeline wants before another opcode reads its result (the compiler spent an s_nop per sample on it).
+// X[k] = the pair (x[b - 2 NP + k], x[b - 2 NP + k + 1]); sample i, pair p reads X[i + 2 NP - 2 - 2 p].  Int32
+// wrap-around sums: the order of the pairs does not matter, the bits are pred_raw's.  `sh` is wave-uniform.
+#define FRA_DOT4(a, b, c, d, q, c0, c1, c2, c3)                   \
+  "v_dot2_i32_i16 %[p0], %[x" #a "], %[q" #q "], " c0 "\n\t"      \
+  "v_dot2_i32_i16 %[p1], %[x" #b "], %[q" #q "], " c1 "\n\t"      \
+  "v_dot2_i32_i16 %[p2], %[x" #c "], %[q" #q "], " c2 "\n\t"      \
+  "v_dot2_i32_i16 %[p3], %[x" #d "], %[q" #q "], " c3 "\n\t"
+#define FRA_DOT4_FIRST(a, b, c, d, q) FRA_DOT4(a, b, c, d, q, "0", "0", "0", "0")
+#define FRA_DOT4_NEXT(a, b, c, d, q) FRA_DOT4(a, b, c, d, q, "%[p0]", "%[p1]", "%[p2]", "%[p3]")
+#define FRA_SHR4                              \
+  "v_ashrrev_i32 %[p0], %[sh], %[p0]\n\t"     \
+  "v_ashrrev_i32 %[p1], %[sh], %[p1]\n\t"     \
+  "v_ashrrev_i32 %[p2], %[sh], %[p2]\n\t"     \
+  "v_ashrrev_i32 %[p3], %[sh], %[p3]"
+#define FRA_P4_OUT [p0] "=&v"(p[0]), [p1] "=&v"(p[1]), [p2] "=&v"(p[2]), [p3] "=&v"(p[3])
+template <int NP>
+__device__ __forceinline__ void pred4_w(const uint32_t (&D)[14], int b, const fra_short2 (&Q)[NP], int sh,
+                                        int32_t (&p)[4]) {
+  static_assert(NP >= 1 && NP <= 4, "orders 1-8");
+  uint32_t X[2 * NP + 2];
+#pragma unroll
+  for (int k = 0; k < 2 * NP + 2; k++) X[k] = pair_at(D, b - 2 * NP + k);
+  if constexpr (NP == 1) {
+    asm(FRA_DOT4_FIRST(0, 1, 2, 3, 0) FRA_SHR4
+        : FRA_P4_OUT
+        : [sh] "s"(sh), [q0] "s"(Q[0]), [x0] "v"(X[0]), [x1] "v"(X[1]), [x2] "v"(X[2]), [x3] "v"(X[3]));
+  } else if constexpr (NP == 2) {
+    asm(FRA_DOT4_FIRST(2, 3, 4, 5, 0) FRA_DOT4_NEXT(0, 1, 2, 3, 1) FRA_SHR4
+        : FRA_P4_OUT
+        : [sh] "s"(sh), [q0] "s"(Q[0]), [q1] "s"(Q[1]), [x0] "v"(X[0]), [x1] "v"(X[1]), [x2] "v"(X[2]), [x3] "v"(X[3]),
+          [x4] "v"(X[4]), [x5] "v"(X[5]));
+  } else if constexpr (NP == 3) {
+    asm(FRA_DOT4_FIRST(4, 5, 6, 7, 0) FRA_DOT4_NEXT(2, 3, 4, 5, 1) FRA_DOT4_NEXT(0, 1, 2, 3, 2) FRA_SHR4
+        : FRA_P4_OUT
+        : [sh] "s"(sh), [q0] "s"(Q[0]), [q1] "s"(Q[1]), [q2] "s"(Q[2]), [x0] "v"(X[0]), [x1] "v"(X[1]), [x2] "v"(X[2]),
+          [x3] "v"(X[3]), [x4] "v"(X[4]), [x5] "v"(X[5]), [x6] "v"(X[6]), [x7] "v"(X[7]));
+  } else {
+    asm(FRA_DOT4_FIRST(6, 7, 8, 9, 0) FRA_DOT4_NEXT(4, 5, 6, 7, 1) FRA_DOT4_NEXT(2, 3, 4, 5, 2)
+        FRA_DOT4_NEXT(0, 1, 2, 3, 3) FRA_SHR4
+        : FRA_P4_OUT
+        : [sh] "s"(sh), [q0] "s"(Q[0]), [q1] "s"(Q[1]), [q2] "s"(Q[2]), [q3] "s"(Q[3]), [x0] "v"(X[0]), [x1] "v"(X[1]),
+          [x2] "v"(X[2]), [x3] "v"(X[3]), [x4] "v"(X[4]), [x5] "v"(X[5]), [x6] "v"(X[6]), [x7] "v"(X[7]), [x8] "v"(X[8]),
+          [x9] "v"(X[9]));
+  }
+}
+#undef FRA_P4_OUT
+#undef FRA_SHR4
+#undef FRA_DOT4_NEXT
+#undef FRA_DOT4_FIRST
+#undef FRA_DOT4
 
 // 16-bit path: sum of |LPC residual| of order O over one chunk (lpc_abs16_raw without the kept residuals),
 // warm-up positions (< O, chunk 0) masked
@@ -296,36 +362,54 @@ __device__ __forceinline__ uint32_t lpc_abs16_w(const uint32_t (&D)[14], const i
   q_pairs_rev<NP>(q, Q);
   uint32_t acc = 0;
 #pragma unroll
-  for (int jj = 0; jj < kChunk; jj++) {
-    const int32_t r = sample_at(D, 12 + jj) - (pred_raw<NP>(D, 12 + jj, Q) >> sh);
-    const uint32_t rb = (uint32_t)r ^ kBias;
-    acc = sad_acc(rb, (jj < O && head) ? rb : kBias, acc);
+  for (int jb = 0; jb < kChunk; jb += 4) {
+    int32_t p[4];
+    pred4_w<NP>(D, 12 + jb, Q, sh, p);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int jj = jb + i;
+      const int32_t r = sample_at(D, 12 + jj) - p[i];
+      const uint32_t rb = (uint32_t)r ^ kBias;
+      acc = sad_acc(rb, (jj < O && head) ? rb : kBias, acc);
+    }
   }
   return acc;
 }
 
-// the same sum, plus the chunk's zig-zag residuals packed two per dword (u[2p] low, u[2p+1] high: their low 16
-// bits) and bit 16 of each in `hb` (bit jj; r05): exact whenever every u < 2^17, which `um`, the OR of all u, tells
+// TWICE the same sum, plus the chunk's zig-zag residuals packed two per dword (u[2p] low, u[2p+1] high: their low 16
+// bits) and bit 16 of each in `hb` (bit jj; r05): exact whenever every u < 2^17, which `um`, the OR of all u, tells.
+// The sum comes from the zig-zag values the pass forms anyway: u = 2 |r| - (r < 0), so 2 sum |r| = sum u - sum (r >> 31),
+// two three-operand adds per pair of samples instead of a re-bias and a SAD per sample (|r| < 2^27 as in the exact
+// pass -- a 16-bit sample minus a shifted 32-bit prediction of a quantised model -- so 16 of them fit 32 bits)
 template <int O, bool K17>
 __device__ __forceinline__ uint32_t lpc_abs16_pk(const uint32_t (&D)[14], const int32_t* q, int sh, bool head,
                                                  uint32_t (&pk)[kChunk / 2], uint32_t& um, uint32_t& hb) {
   constexpr int NP = (O + 1) / 2;
   fra_short2 Q[NP];
   q_pairs_rev<NP>(q, Q);
-  uint32_t acc = 0;
+  uint32_t su = 0, ss = 0;
   uint32_t u[kChunk];
   hb = 0;
 #pragma unroll
-  for (int jj = 0; jj < kChunk; jj++) {
-    const int32_t r = sample_at(D, 12 + jj) - (pred_raw<NP>(D, 12 + jj, Q) >> sh);
-    const uint32_t rb = (uint32_t)r ^ kBias;
-    const bool warm = jj < O && head;
-    acc = sad_acc(rb, warm ? rb : kBias, acc);
-    u[jj] = warm ? 0u : zz32(r);
-    um |= u[jj];
-  }
+  for (int jb = 0; jb < kChunk; jb += 4) {
+    int32_t p[4];
+    pred4_w<NP>(D, 12 + jb, Q, sh, p);
 #pragma unroll
-  for (int p = 0; p < kChunk / 2; p++) pk[p] = (u[2 * p + 1] << 16) | (u[2 * p] & 0xFFFFu);
+    for (int i = 0; i < 4; i++) {
+      const int jj = jb + i;
+      const int32_t r = sample_at(D, 12 + jj) - p[i];
+      uint32_t sg = (uint32_t)(r >> 31);
+      asm("" : "+v"(sg));  // (one sign word for both uses: seen through, the sum is rebuilt from r >> 31 logical)
+      const bool warm = jj < O && head;
+      u[jj] = warm ? 0u : (((uint32_t)r << 1) ^ sg);
+      su += u[jj];
+      ss += warm ? 0u : sg;
+      um |= u[jj];
+    }
+  }
+  const uint32_t acc = su - ss;
+#pragma unroll
+  for (int p = 0; p < kChunk / 2; p++) pk[p] = __builtin_amdgcn_perm(u[2 * p + 1], u[2 * p], 0x05040100u);  // low halves
   // bit 16 of each residual only when some lane has one (a wave-uniform branch: rare on most rasters); u >> 16 is
   // 0 or 1 whenever the kept residuals are used at all (every u < 2^17)
   if (K17 && __any(um > 0xFFFFu)) {
@@ -413,8 +497,7 @@ k_analyze_w(JobArgs a, int src) {
 #endif
 
   // ---- 1. load + normalise (table gather), OR / min / max
-  uint32_t orv = 0;
-  int32_t vmin = INT32_MAX, vmax = INT32_MIN;
+  uint32_t orv = 0, anv = 0xFFFFu;
   // (the lambdas capture these locals, not the kernel arguments: taking the arguments' address costs registers)
   const void* const raster = a.raster;
   const int32_t* const lut = a.lut + (int64_t)wd.stream * a.lut_stride;
@@ -426,20 +509,20 @@ k_analyze_w(JobArgs a, int src) {
     wn.rcp = np.rcp;
     wn.flip = src == ST_I16 ? 0x8000u : (src == ST_I8 ? 0x80u : 0u);
   }
-  auto load_samples = [&](uint32_t& ov, int32_t& mn, int32_t& mx, bool first) {
-    if (src == ST_U8 || src == ST_I8) wload_lut<uint8_t>(raster, wd, c, lut, sw, lane, ov, mn, mx, first, wn);  // uniform
-    else wload_lut<uint16_t>(raster, wd, c, lut, sw, lane, ov, mn, mx, first, wn);
+  auto load_samples = [&](uint32_t& ov, uint32_t& an, bool first) {
+    if (src == ST_U8 || src == ST_I8) wload_lut<uint8_t>(raster, wd, c, lut, sw, lane, ov, an, first, wn);  // uniform
+    else wload_lut<uint16_t>(raster, wd, c, lut, sw, lane, ov, an, first, wn);
   };
-  load_samples(orv, vmin, vmax, true);
+  load_samples(orv, anv, true);
   orv = wave_or32(orv);
   wsync();  // every lane's sample stores before any lane's reads
   FRA_WSTAMP(1)
-  vmin = (int32_t)(wave_min32((uint32_t)vmin ^ 0x80000000u) ^ 0x80000000u);
-  vmax = (int32_t)(~wave_min32(~((uint32_t)vmax ^ 0x80000000u)) ^ 0x80000000u);
-  FRA_WSTOP_AT(1, orv ^ (uint32_t)vmin ^ (uint32_t)vmax ^ sw[lane] ^ sw[2047 - lane])
+  anv = ~wave_or32(~anv) & 0xFFFFu;  // the AND of every sample's 16 bits (orv: their OR)
+  FRA_WSTOP_AT(1, orv ^ (anv << 16) ^ sw[lane] ^ sw[2047 - lane])
 
   // ---- 2. CONSTANT / wasted bits (3.2, 3.3)
-  if (vmin == vmax) {
+  if (anv == orv) {  // all samples equal
+    const int32_t vmin = lo16(orv);  // the value
     if (lane == 0) {
       d->type = 0; d->order = 0; d->wasted = 0; d->sbps = (uint8_t)bps; d->cval = vmin;
       d->bits = 8u + (uint32_t)bps; d->porder = 0; d->method = 0; d->precision = 0; d->shift = 0;
@@ -570,7 +653,7 @@ k_analyze_w(JobArgs a, int src) {
     gt2 = (uint64_t)wave_sum32(pf2);
   }
 #if defined(FRA_WPAD) && FRA_WPAD > 0
-  {  // diagnostic build only (tools/gpu_r04_pad.sh): FRA_WPAD extra independent VALU instructions per wave
+  {  // diagnostic build only (make wpad256 / wpad512): FRA_WPAD extra independent VALU instructions per wave
     uint32_t p0 = lane, p1 = lane + 1, p2 = lane + 2, p3 = lane + 3;
 #pragma unroll
     for (int k = 0; k < FRA_WPAD / 4; k++) {
@@ -643,9 +726,9 @@ k_analyze_w(JobArgs a, int src) {
 #pragma unroll
               for (int e = 0; e < 8; e++) wc[e] = wp[16 * (8 * hf + e)];
 #pragma unroll
-              for (int e = 0; e < 8; e++) y[e] = (int32_t)__builtin_rintf((float)sp[16 * (8 * hf + e)] * wc[e]);
+              for (int e = 0; e < 8; e++) y[e] = wround16((float)sp[16 * (8 * hf + e)], wc[e]);
             }
-            if (blk == 0 && hf == 0) yfirst = y[0];
+            if (blk == 0 && hf == 0) yfirst = lo16((uint32_t)y[0]);
 #pragma unroll
             for (int dd = 0; dd < 2; dd++) {
               const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)y[4 * dd + 1], (uint32_t)y[4 * dd], 0x05010400u);
@@ -662,7 +745,7 @@ k_analyze_w(JobArgs a, int src) {
           {
             const bool in = blk < kWIters - 1 || g4 < 3;  // the next row lies inside the block of n samples
             const float x16 = in ? (float)sp[256] : 0.0f;
-            y16 = (int32_t)__builtin_rintf(x16 * (in ? wp[256] : 0.0f));
+            y16 = wround16(x16, in ? wp[256] : 0.0f);  // (only its bytes 0 and 1 are used below)
           }
           H[4] = (uint32_t)y16 >> 8;
           L[4] = (uint32_t)y16 ^ 0x80u;
@@ -839,7 +922,7 @@ k_analyze_w(JobArgs a, int src) {
 #pragma unroll
           for (int p = 0; p < kChunk / 4; p++) *reinterpret_cast<uint2*>(po + 2 * p) = make_uint2(pk[2 * p], pk[2 * p + 1]);
           hk |= (uint64_t)hb << (16 * j);
-          const uint64_t gs = bperm64(group_sum_auto(2ull * acc, gsl), psrc);
+          const uint64_t gs = bperm64(group_sum_auto((uint64_t)acc, gsl), psrc);  // (acc: already 2 sum |r|)
           psum = pj == j ? gs : psum;
         };
         keep_iter(0, std::true_type{});
@@ -906,9 +989,8 @@ k_analyze_w(JobArgs a, int src) {
   FRA_WSTAMP_VAL(9, kept_w ? 0 : (type != 3 ? 3 : (wm != 5 + keep_wi ? 4 : 5)))  // why the sample path
   auto reload = [&]() {  // the keep pass replaced the samples: load them once more
     wsync();
-    uint32_t ov = 0;
-    int32_t mn = 0, mx = 0;
-    load_samples(ov, mn, mx, false);
+    uint32_t ov = 0, an = 0;
+    load_samples(ov, an, false);
     wsync();
     if (w) shift_wasted();
     wsync();
@@ -960,7 +1042,12 @@ k_analyze_w(JobArgs a, int src) {
       for (int k = 0; k < 6; k++) cy[k] = (uint32_t)__builtin_amdgcn_readlane((int)D[8 + k], 63);
       if (type == 3) {
 #pragma unroll
-        for (int jj = 0; jj < kChunk; jj++) un[jj] = zz32(sample_at(D, 12 + jj) - (pred_raw<4>(D, 12 + jj, Q) >> sh));
+        for (int jb = 0; jb < kChunk; jb += 4) {
+          int32_t p[4];
+          pred4_w<4>(D, 12 + jb, Q, sh, p);
+#pragma unroll
+          for (int i = 0; i < 4; i++) un[jb + i] = zz32(sample_at(D, 12 + jb + i) - p[i]);
+        }
       } else {  // FIXED: the o-th finite difference in place
         int32_t x[28];
         unpack28(D, x);
@@ -1140,7 +1227,9 @@ k_analyze_w(JobArgs a, int src) {
     const uint32_t nw = (fbits + 31) >> 5;
     const int pb = big ? 5 : 4;
     const uint32_t pos = hdr + (uint32_t)o * sbps + (type == 3 ? 9u + (uint32_t)o * prec : 0u);
-    uint32_t totl[kWIters];
+    // (one inclusive scan per iteration serves both: its last lane is the iteration's total, and scan - own bits
+    // the lane's first bit inside the iteration -- put_codes ran the scan a second time)
+    uint32_t excl[kWIters];
     uint32_t B[kWIters + 1];
     B[0] = pos + 6;
 #pragma unroll
@@ -1149,8 +1238,10 @@ k_analyze_w(JobArgs a, int src) {
       const uint32_t kcur = kc[j], k0 = k0r[j];
       const uint32_t f = kcur + 1 == k0 ? fk[j][0] : kcur == k0 ? fk[j][1] : fk[j][2];
       const bool pstart = ((t << 4) & (pz - 1)) == 0;
-      totl[j] = f + (uint32_t)(kChunk - (t == 0 ? o : 0)) * (kcur + 1u) + (pstart ? (uint32_t)pb : 0u);
-      B[j + 1] = B[j] + wave_sum32(totl[j]);
+      const uint32_t tot = f + (uint32_t)(kChunk - (t == 0 ? o : 0)) * (kcur + 1u) + (pstart ? (uint32_t)pb : 0u);
+      const uint32_t sc = wave_incl_scan32(tot);
+      excl[j] = sc - tot;
+      B[j + 1] = B[j] + (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
     }
     // the LDS bit buffer aliases the residuals (kept) or samples and is filled iteration by iteration, each
     // iteration's residuals computed before its words are zeroed and written: iteration j's last word + the
@@ -1199,9 +1290,9 @@ k_analyze_w(JobArgs a, int src) {
     auto put_codes = [&](uint32_t* buf, int j, const uint32_t (&un)[kChunk]) {
       const int t = 64 * j + lane;
       const bool head = t == 0;
-      const uint32_t kcur = kc[j], tot = totl[j];
+      const uint32_t kcur = kc[j];
       const bool pstart = ((t << 4) & (pz - 1)) == 0;
-      uint32_t p = B[j] + wave_incl_scan32(tot) - tot;
+      uint32_t p = B[j] + excl[j];
       if (pstart) { lds_put(buf, p, kcur, pb); p += (uint32_t)pb; }
       // Rice code (stop bit + kcur low bits) left-aligned: bit 31 = the stop bit
       const uint32_t sal = 31u - kcur;
