@@ -1,5 +1,5 @@
-// fra_region.h -- what the reads that reduce a decoded region on the device share (fra_decimate.hip, fra_compare.hip,
-// fra_stats.hip): the check that the items cover the region, and the windowed read (fra_decode_device_window, called as
+// fra_region.h -- what the reads that reduce a decoded region on the device share (fra_decimate.hip, fra_resample.hip,
+// fra_compare.hip, fra_stats.hip): the check that the items cover the region, and the windowed read (fra_decode_device_window, called as
 // any caller would: same kernels, refusals and messages) into a per-call device buffer of the region.
 #pragma once
 #include <algorithm>

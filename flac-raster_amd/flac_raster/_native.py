@@ -101,6 +101,16 @@ class DecimateJob(C.Structure):
     ]
 
 
+class ResampleJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("src_band_stride", C.c_int64), ("src_row_stride", C.c_int64),
+        ("src_col_stride", C.c_int64), ("out_height", C.c_int32), ("out_width", C.c_int32), ("resampling", C.c_int32),
+        ("dst", C.c_void_p), ("dst_on_device", C.c_int32), ("dst_band_stride", C.c_int64),
+        ("dst_row_stride", C.c_int64), ("dst_col_stride", C.c_int64),
+    ]
+
+
 class CompareBand(C.Structure):
     """One band's report of ``fra_compare`` / ``fra_decode_device_compare`` (128 bytes; the rule: ``compare.py``)."""
 
@@ -149,6 +159,7 @@ class StatsBand(C.Structure):
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
+RESAMPLE_BILINEAR, RESAMPLE_CUBIC = 2, 3
 E_SPACE = -6
 # fra_plan_flags (Plan.flags)
 PLAN_DIRECT_WRITE, PLAN_PIPELINED, PLAN_WAVE, PLAN_KEEP17 = 1, 2, 4, 8
@@ -197,7 +208,8 @@ EXPORTS = [
     "fra_plan_encode_ring", "fra_plan_host_band_rows", "fra_plan_create_ranged", "fra_decode_device",
     "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify", "fra_decimate",
     "fra_decode_device_decimated", "fra_decimate_timing", "fra_compare", "fra_decode_device_compare",
-    "fra_compare_timing", "fra_stats", "fra_decode_device_stats", "fra_stats_timing",
+    "fra_compare_timing", "fra_stats", "fra_decode_device_stats", "fra_stats_timing", "fra_resample",
+    "fra_decode_device_resampled", "fra_resample_timing",
 ]
 
 
@@ -279,6 +291,11 @@ def load():
             L.fra_decode_device_stats.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(StatsOpts),
                                                   C.POINTER(StatsBand), C.POINTER(u64), C.POINTER(Decoded)]
             L.fra_stats_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_resample"):
+            L.fra_resample.argtypes = [vp, C.POINTER(ResampleJob)]
+            L.fra_decode_device_resampled.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32, i32,
+                                                      C.POINTER(Decoded)]
+            L.fra_resample_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -445,7 +462,7 @@ class Context:
 
     def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
                       denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None,
-                      compare=None, stats=None) -> List[Decoded]:
+                      compare=None, stats=None, resample=None) -> List[Decoded]:
         """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
 
         ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
@@ -460,7 +477,8 @@ class Context:
         :meth:`decode_device_window`; ``decimate`` = (factor, resampling code): see
         :meth:`decode_device_decimated`; ``compare`` = (ref pointer, on device, element strides, reports array): see
         :meth:`decode_device_compare`, ``dst`` is then ``None``; ``stats`` = (options, reports array, histogram
-        pointer): see :meth:`decode_device_stats`, ``dst`` is then ``None`` too.)"""
+        pointer): see :meth:`decode_device_stats`, ``dst`` is then ``None`` too; ``resample`` = (out_height, out_width,
+        resampling code): see :meth:`decode_device_resampled`.)"""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -505,6 +523,9 @@ class Context:
             rc = load().fra_decode_device_compare(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                   C.c_void_p(int(ref)), 1 if ref_on_device else 0, int(rst[0]),
                                                   int(rst[1]), int(rst[2]), bands, infos)
+        elif resample is not None:
+            rc = load().fra_decode_device_resampled(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
+                                                    int(resample[0]), int(resample[1]), int(resample[2]), infos)
         elif decimate is not None:
             rc = load().fra_decode_device_decimated(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                     int(decimate[0]), int(decimate[1]), infos)
@@ -598,6 +619,75 @@ class Context:
         """HIP-event ms of this thread's last ``k_decimate`` (:meth:`decimate` / :meth:`decode_device_decimated`)."""
         ms = C.c_float()
         _check(load().fra_decimate_timing(C.byref(ms)))
+        return ms.value
+
+    def decode_device_resampled(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
+                                out_shape, resampling: str = "nearest", denorm: int = DENORM_NONE) -> List[Decoded]:
+        """``roi`` at ``out_shape`` = (oh, ow) (``fra_decode_device_resampled``): exactly ``resample.resample`` of what
+        :meth:`decode_device_window` would have written, without the full-resolution region leaving the GPU.
+
+        Arguments as :meth:`decode_device_window`, except that ``dst`` and ``strides`` address the ``(oh, ow)``
+        output.  ``resampling``: ``"nearest"``, ``"average"``, ``"bilinear"`` or ``"cubic"``.  The items must cover
+        the region."""
+        from .resample import check_average_size, check_out_shape, resampling_any_code
+
+        if roi is None:
+            raise ValueError("roi is required")
+        oh, ow = check_out_shape(out_shape)
+        mode = resampling_any_code(resampling)
+        if mode == RESAMPLE_AVERAGE and int(roi[2]) > 0 and int(roi[3]) > 0:
+            check_average_size(int(roi[2]), int(roi[3]), oh, ow, dst_dtype)
+        return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi,
+                                  resample=(oh, ow, mode))
+
+    def resample(self, src, out_shape, resampling: str = "nearest", dst=None, *, dtype=None, shape=None,
+                 strides=None, dst_strides=None):
+        """A raster at ``out_shape`` = (oh, ow) on this context's GPU (``fra_resample``, the rule of
+        ``flac_raster.resample.resample``).
+
+        ``src``, ``dst`` and the keyword arguments as :meth:`decimate`; ``dst`` is ``(B, oh, ow)``.  ``resampling``:
+        ``"nearest"``, ``"average"``, ``"bilinear"`` or ``"cubic"``.  Returns ``dst``."""
+        from .resample import check_out_shape, resampling_any_code
+
+        (oh, ow), mode = check_out_shape(out_shape), resampling_any_code(resampling)
+        job = ResampleJob()
+        if isinstance(src, np.ndarray):
+            a = src if src.ndim == 3 else src[None]
+            if a.ndim != 3:
+                raise ValueError("src must be (B, h, w) or (h, w)")
+            dt, (B, h, w), sst = a.dtype, a.shape, _element_strides(a)
+            job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
+        else:
+            dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
+            sst = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
+            job.src, job.src_on_device = C.c_void_p(int(src)), 1
+        if dt not in DTYPE_CODES:
+            raise TypeError(f"unsupported dtype {dt}")
+        ret = dst
+        if dst is None:
+            ret = dst = np.zeros((B, oh, ow), dtype=dt)
+            if isinstance(src, np.ndarray) and src.ndim == 2:
+                ret = dst[0]
+        if isinstance(dst, np.ndarray):
+            d = dst if dst.ndim == 3 else dst[None]
+            if d.shape != (B, oh, ow) or d.dtype != dt:
+                raise ValueError(f"dst must be {(B, oh, ow)} of {dt}, got {d.shape} of {d.dtype}")
+            dstr = _element_strides(d)
+            job.dst, job.dst_on_device = C.c_void_p(d.ctypes.data), 0
+        else:
+            dstr = tuple(int(v) for v in dst_strides) if dst_strides is not None else (oh * ow, ow, 1)
+            job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
+        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
+        job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
+        job.out_height, job.out_width, job.resampling = oh, ow, mode
+        job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
+        _check(load().fra_resample(self.h, C.byref(job)))
+        return ret
+
+    def resample_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_resample`` (:meth:`resample` / :meth:`decode_device_resampled`)."""
+        ms = C.c_float()
+        _check(load().fra_resample_timing(C.byref(ms)))
         return ms.value
 
     def decode_device_compare(self, data, items, ref, dst_dtype, channels: int, roi, denorm: int = DENORM_NONE,

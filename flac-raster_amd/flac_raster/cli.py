@@ -201,7 +201,9 @@ def window(
     pixels: Optional[str] = typer.Option(None, "--window", "-w", help="Pixel window: 'row,col,height,width'"),
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
     decimate: int = typer.Option(1, "--decimate", help="Write the window at 1/K resolution: K = 2, 4, 8, 16, 32 or 64"),
-    resampling: str = typer.Option("nearest", "--resampling", help="With --decimate: nearest or average"),
+    resampling: str = typer.Option("nearest", "--resampling", help="With --decimate: nearest or average; with "
+                                   "--out-shape: nearest, average, bilinear or cubic"),
+    out_shape: Optional[str] = typer.Option(None, "--out-shape", help="Write the window resampled to 'H,W' pixels"),
 ):
     """Read a pixel window of a streaming FLAC file to GeoTIFF (only the tiles and frames it needs)."""
     from .streaming import window_to_tiff
@@ -215,9 +217,12 @@ def window(
         win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
         # the given device, else device 0 when a GPU is present, else the host decoder (as convert)
         dev = device if device is not None else (0 if _gpu_present() else None)
+        shape = tuple(int(x.strip()) for x in out_shape.split(",")) if out_shape else None
         got, idx = window_to_tiff(path, output, window=win, bbox=box, device=dev, decimate=decimate,
-                                  resampling=resampling)
+                                  resampling=resampling, out_shape=shape)
         scale = f" at 1/{decimate} resolution ({resampling})" if decimate != 1 else ""
+        if shape:
+            scale = f" as {shape[0]} x {shape[1]} ({resampling})"
         console.print(f"[green]Saved rows {got[0]}..{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]} of "
                       f"{idx['height']} x {idx['width']}{scale} to: {output}[/green]")
     except typer.Exit:
@@ -232,8 +237,11 @@ def window(
 def overview(
     flac_file: str = typer.Argument(..., help="Streaming FLAC file"),
     output: Path = typer.Option(..., "--output", "-o", help="Output TIFF file path"),
-    factor: int = typer.Option(..., "--factor", help="Write the raster at 1/K resolution: K = 2, 4, 8, 16, 32 or 64"),
-    resampling: str = typer.Option("average", "--resampling", help="nearest or average"),
+    factor: Optional[int] = typer.Option(None, "--factor", help="Write the raster at 1/K resolution: K = 2, 4, 8, 16, "
+                                         "32 or 64"),
+    resampling: str = typer.Option("average", "--resampling", help="nearest or average; with --size also bilinear "
+                                   "or cubic"),
+    size: Optional[int] = typer.Option(None, "--size", help="Write the raster with its longest side N pixels"),
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
 ):
     """Write a reduced-resolution preview of a whole streaming FLAC file to GeoTIFF."""
@@ -242,8 +250,12 @@ def overview(
     try:
         path = _local(flac_file)
         dev = device if device is not None else (0 if _gpu_present() else None)
-        shape, idx = overview_to_tiff(path, output, factor, resampling, device=dev)
-        console.print(f"[green]Saved {idx['height']} x {idx['width']} at 1/{factor} resolution ({resampling}) as "
+        if (factor is None) == (size is None):
+            console.print("[red]Error: give exactly one of --factor and --size[/red]")
+            raise typer.Exit(1)
+        shape, idx = overview_to_tiff(path, output, factor, resampling, device=dev, max_size=size)
+        how = f"at 1/{factor} resolution" if size is None else f"with longest side {size}"
+        console.print(f"[green]Saved {idx['height']} x {idx['width']} {how} ({resampling}) as "
                       f"{shape[1]} x {shape[2]} to: {output}[/green]")
     except typer.Exit:
         raise

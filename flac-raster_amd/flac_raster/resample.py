@@ -14,16 +14,42 @@ are smaller).  The output is ``ceil(h / k) x ceil(w / k)`` in the input's dtype.
               ``log2 k`` levels); the row sums are accumulated top to bottom (``acc = row_0; acc += row_1; ...``; rows
               the block does not have are not added); ``out = dtype(acc / float64(n))``.  Plain IEEE arithmetic: NaN
               and infinities propagate, nothing is skipped.
+
+Resampling to any output size (``resample``, ``k_resample``): ``(B, h, w) -> (B, oh, ow)``, ``1 <= oh, ow <= 65536``,
+larger or smaller than the input, same dtype.  Each axis is handled alone and the same way (columns below); with
+``g = gcd(w, ow)``, ``w' = w / g`` and ``ow' = ow / g`` (rows: ``h'``, ``oh'``).  Every coordinate is an integer, every
+value operation an IEEE float64 operation rounded on its own; NaN and infinities propagate, there is no nodata.
+
+The centre of output column ``C`` lies at source coordinate ``(C + 1/2) w / ow - 1/2``: ``num = (2 C + 1) w' - ow'``,
+``den = 2 ow'``, ``i0 = floor(num / den)``, ``t = float64(num - i0 den) / float64(den)``.
+
+``nearest``   ``out[R, C] = in[min(((2 R + 1) h') // (2 oh'), h - 1), min(((2 C + 1) w') // (2 ow'), w - 1)]``
+``bilinear``  taps ``i0, i0 + 1`` with weights ``[1.0 - t, t]``
+``cubic``     taps ``i0 - 1 .. i0 + 2`` (Catmull-Rom, a = -1/2) with weights ``((-0.5 t + 1.0) t - 0.5) t``,
+              ``((1.5 t - 2.5) t) t + 1.0``, ``((-1.5 t + 2.0) t + 0.5) t``, ``((0.5 t - 0.5) t) t``.
+              Both: every tap index is clamped to the raster; vertically first, ``c_i = sum_j float64(x[j][i]) wy_j``
+              for every tap column, top to bottom (``acc = p0; acc += p1; ...``), then ``v = sum_i c_i wx_i`` left to
+              right.  Float dtypes: ``dtype(v)``; integer dtypes: ``rint(v)`` (half to even) clamped to the dtype.
+``average``   area weights in units of ``1 / ow'`` of a source pixel: output column ``C`` covers ``[C w', (C + 1) w')``,
+              source column ``i`` covers ``[i ow', (i + 1) ow')``, ``vx_i`` = the length of their intersection where
+              positive (they sum to ``w'``); ``vy_j`` likewise; ``n = h' w'``.  Integer dtypes: ``S = sum_j sum_i vy_j
+              vx_i x[j][i]`` exact in int64, ``out = rint(float64(S) / float64(n))``; refused when ``n 2^(8 itemsize)
+              > 2^63``.  Float dtypes: ``c_i = sum_j float64(vy_j) float64(x[j][i])`` top to bottom, ``acc = sum_i
+              float64(vx_i) c_i`` left to right, ``out = dtype(acc / float64(n))``; refused when ``n > 2^53``.
+When the output has the input's size every mode returns the input.
 """
 
 from __future__ import annotations
 
+from math import gcd
 from typing import Sequence, Tuple
 
 import numpy as np
 
 FACTORS = (2, 4, 8, 16, 32, 64)
 RESAMPLING = {"nearest": 0, "average": 1}
+RESAMPLING_ANY = {"nearest": 0, "average": 1, "bilinear": 2, "cubic": 3}  # of resample(); decimate() knows the first two
+MAX_OUT = 65536
 _DTYPES = tuple(np.dtype(t) for t in (np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.float32,
                                       np.float64))
 
@@ -92,3 +118,141 @@ def decimate(raster: np.ndarray, factor: int, resampling: str = "nearest") -> np
         if is_float:
             return (acc / n).astype(a.dtype)
         return np.rint(acc.astype(np.float64) / n).astype(a.dtype)
+
+
+# ------------------------------------------------------------------------------- any output size
+def resampling_any_code(resampling) -> int:
+    if resampling not in RESAMPLING_ANY:
+        raise ValueError(f"resampling must be one of {tuple(RESAMPLING_ANY)}, got {resampling!r}")
+    return RESAMPLING_ANY[resampling]
+
+
+def check_out_shape(out_shape) -> Tuple[int, int]:
+    try:
+        oh, ow = out_shape
+        ok = int(oh) == oh and int(ow) == ow and 1 <= oh <= MAX_OUT and 1 <= ow <= MAX_OUT
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"out_shape must be (height, width) with 1 <= height, width <= {MAX_OUT}, got {out_shape!r}")
+    return int(oh), int(ow)
+
+
+def max_size_shape(h: int, w: int, max_size: int) -> Tuple[int, int]:
+    """The output shape whose longest side is ``max_size``; the other is ``max(1, round(side max_size / longest))``."""
+    n, longest = int(max_size), max(int(h), int(w))
+    if n != max_size or not 1 <= n <= MAX_OUT:
+        raise ValueError(f"max_size must be an integer in 1 .. {MAX_OUT}, got {max_size!r}")
+    other = max(1, round(min(int(h), int(w)) * n / longest))
+    return (n, other) if h >= w else (other, n)
+
+
+def check_average_size(h: int, w: int, oh: int, ow: int, dtype) -> int:
+    """``n = h' w'`` of the area average, refused where the rule's arithmetic would no longer be exact."""
+    n = (h // gcd(h, oh)) * (w // gcd(w, ow))
+    dt = np.dtype(dtype)
+    if dt.kind == "f":
+        if n > 2**53:
+            raise ValueError(f"average: {h} x {w} -> {oh} x {ow} has n = {n} > 2^53 weights per output pixel")
+    elif n * 2**(8 * dt.itemsize) > 2**63:
+        raise ValueError(f"average: {h} x {w} -> {oh} x {ow} with n = {n} overflows the 64-bit sum of {dt.name}")
+    return n
+
+
+def resampled_transform(transform: Sequence[float], window: Sequence[int],
+                        out_shape: Sequence[int]) -> Tuple[float, ...]:
+    """The geotransform ``(a, b, c, d, e, f)`` of a region ``window`` = (row_off, col_off, height, width) of the raster
+    ``transform`` belongs to, resampled to ``out_shape``.  At ``height / oh = width / ow = k`` this is
+    ``decimated_transform``."""
+    a, b, c, d, e, f = (float(v) for v in tuple(transform)[:6])
+    row, col, h, w = (int(v) for v in tuple(window)[:4])
+    oh, ow = check_out_shape(out_shape)
+    sx, sy = w / ow, h / oh
+    return a * sx, b * sy, c + col * a + row * b, d * sx, e * sy, f + col * d + row * e
+
+
+def _centres(n_in: int, n_out: int):
+    """``(i0, t)`` of every output index along one axis."""
+    g = gcd(n_in, n_out)
+    ni, no = n_in // g, n_out // g
+    num = (2 * np.arange(n_out, dtype=np.int64) + 1) * ni - no
+    den = 2 * no
+    i0 = num // den
+    return i0, (num - i0 * den).astype(np.float64) / np.float64(den)
+
+
+def _tap_weights(t: np.ndarray, mode: int):
+    if mode == 2:
+        return [1.0 - t, t]
+    return [((-0.5 * t + 1.0) * t - 0.5) * t, ((1.5 * t - 2.5) * t) * t + 1.0, ((-1.5 * t + 2.0) * t + 0.5) * t,
+            ((0.5 * t - 0.5) * t) * t]
+
+
+def _area_taps(n_in: int, n_out: int):
+    """``(first, weights)`` along one axis: ``weights[k, C]`` is the integer weight of source index ``first[C] + k``
+    for output ``C`` (0 past its last tap)."""
+    g = gcd(n_in, n_out)
+    ni, no = n_in // g, n_out // g
+    C = np.arange(n_out, dtype=np.int64)
+    first = (C * ni) // no
+    taps = int((-(-(C + 1) * ni // no) - first).max())
+    i = first[None, :] + np.arange(taps, dtype=np.int64)[:, None]
+    wts = np.minimum((i + 1) * no, ((C + 1) * ni)[None, :]) - np.maximum(i * no, (C * ni)[None, :])
+    return first, np.maximum(wts, 0)
+
+
+def resample(raster: np.ndarray, out_shape: Sequence[int], resampling: str = "nearest") -> np.ndarray:
+    """``raster`` ``(B, h, w)`` or ``(h, w)`` resampled to ``out_shape`` = (oh, ow) (the module's rule), same dtype."""
+    mode = resampling_any_code(resampling)
+    oh, ow = check_out_shape(out_shape)
+    a = np.asarray(raster)
+    if a.ndim == 2:
+        return resample(a[None], (oh, ow), resampling)[0]
+    if a.ndim != 3 or a.shape[1] < 1 or a.shape[2] < 1:
+        raise ValueError(f"expected a (B, h, w) or (h, w) raster with h, w >= 1, got shape {a.shape}")
+    if a.dtype.newbyteorder("=") not in _DTYPES:
+        raise TypeError(f"unsupported dtype {a.dtype}")
+    B, h, w = a.shape
+    dt = a.dtype
+    is_float = dt.kind == "f"
+    if (oh, ow) == (h, w):
+        return np.array(a, order="C")
+    if mode == 0:
+        gh, gw = gcd(h, oh), gcd(w, ow)
+        rows = np.minimum(((2 * np.arange(oh, dtype=np.int64) + 1) * (h // gh)) // (2 * (oh // gh)), h - 1)
+        cols = np.minimum(((2 * np.arange(ow, dtype=np.int64) + 1) * (w // gw)) // (2 * (ow // gw)), w - 1)
+        return np.ascontiguousarray(a[:, rows[:, None], cols[None, :]])
+    with np.errstate(invalid="ignore", over="ignore"):
+        if mode == 1:
+            n = check_average_size(h, w, oh, ow, dt)
+            acc_t = np.float64 if is_float else np.int64
+            x = a.astype(acc_t)
+            firsty, vy = _area_taps(h, oh)
+            firstx, vx = _area_taps(w, ow)
+            cols = None  # (B, oh, w): every source column summed down the rows of output row R
+            for k in range(vy.shape[0]):
+                term = vy[k].astype(acc_t)[None, :, None] * x[:, np.minimum(firsty + k, h - 1), :]
+                cols = term if k == 0 else np.where((vy[k] > 0)[None, :, None], cols + term, cols)
+            acc = None
+            for k in range(vx.shape[0]):
+                term = vx[k].astype(acc_t)[None, None, :] * cols[:, :, np.minimum(firstx + k, w - 1)]
+                acc = term if k == 0 else np.where((vx[k] > 0)[None, None, :], acc + term, acc)
+            if is_float:
+                return (acc / np.float64(n)).astype(dt, order="C")
+            return np.rint(acc.astype(np.float64) / np.float64(n)).astype(dt, order="C")
+        x = a.astype(np.float64)
+        i0y, ty = _centres(h, oh)
+        i0x, tx = _centres(w, ow)
+        off = 0 if mode == 2 else -1
+        cols = None  # (B, oh, w): every source column combined vertically for output row R
+        for k, wy in enumerate(_tap_weights(ty, mode)):
+            term = x[:, np.clip(i0y + off + k, 0, h - 1), :] * wy[None, :, None]
+            cols = term if k == 0 else cols + term
+        v = None
+        for k, wx in enumerate(_tap_weights(tx, mode)):
+            term = cols[:, :, np.clip(i0x + off + k, 0, w - 1)] * wx[None, None, :]
+            v = term if k == 0 else v + term
+        if is_float:
+            return v.astype(dt, order="C")
+        info = np.iinfo(dt)
+        return np.clip(np.rint(v), np.float64(info.min), np.float64(info.max)).astype(dt, order="C")

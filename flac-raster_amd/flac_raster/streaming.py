@@ -9,8 +9,9 @@ the window transform (rasterio ``windows.transform`` arithmetic), no nodata, the
 
 Reader = the index parse + byte-range slicing of ``cli.extract`` (``cli.py:238-313``); ``streaming_to_raster`` decodes
 the whole container, ``read_window`` a pixel window of it (only the byte ranges of the tiles it intersects are read,
-and on the GPU only the frames that hold its rows are decoded), at full resolution or decimated by 2 .. 64
-(``decimate=``), and ``read_overview`` the whole raster decimated (``resample`` states the rule).
+and on the GPU only the frames that hold its rows are decoded), at full resolution, decimated by 2 .. 64
+(``decimate=``) or resampled to any size (``out_shape=``), and ``read_overview`` the whole raster decimated or resampled
+(``resample`` states the rules).
 """
 
 from __future__ import annotations
@@ -362,7 +363,7 @@ def resolve_window(index: Dict, window: Optional[Sequence[int]] = None,
 
 def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
                 device: Optional[int] = None, semantics: str = "pcm16", decimate: int = 1,
-                resampling: str = "nearest"):
+                resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None):
     """A pixel window of a streaming container (path or bytes) -> ``(raster (B, h, w) in the index's dtype, window,
     index)``, bit-identical to cropping :func:`streaming_to_raster`.
 
@@ -371,6 +372,11 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     window is still the clipped full-resolution one (``resample.decimated_transform`` gives the result's transform).
     On the host the window is read as below and decimated with numpy; on a GPU one ``fra_decode_device_decimated``
     call decodes and decimates it there and only the small result comes back.
+
+    ``out_shape`` = (oh, ow), not together with ``decimate``: the window resampled to that size, larger or smaller,
+    ``resample.resample(window's raster, out_shape, resampling)`` with ``resampling`` one of ``nearest``, ``average``,
+    ``bilinear``, ``cubic`` (``resample.resampled_transform`` gives the result's transform).  On the host the window
+    is read and resampled with numpy; on a GPU one ``fra_decode_device_resampled`` call does both there.
 
     ``window`` = (row_off, col_off, height, width) or ``bbox`` = (xmin, ymin, xmax, ymax), see :func:`resolve_window`;
     the returned window is the clipped one.  Of a file only the index and the byte ranges of the intersecting tiles
@@ -381,13 +387,30 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     if semantics not in ("pcm16", "int"):
         raise ValueError("semantics must be 'pcm16' or 'int'")
     k = 1
-    if decimate != 1:
+    if out_shape is not None:
+        if decimate != 1:
+            raise ValueError("give decimate or out_shape, not both")
+        out_shape = resample.check_out_shape(out_shape)
+        resample.resampling_any_code(resampling)
+    elif decimate != 1:
         k = resample.check_factor(decimate)
         resample.resampling_code(resampling)
     index, win, blob, items = _window_items(src, window, bbox)
     R, C_, h, w = win
     dt = np.dtype(index["dtype"])
     B = int(index["bands"])
+    if out_shape is not None:
+        if device is None:
+            out = np.zeros((B, h, w), dtype=dt)
+            _decode_window_on_host(blob, items, win, out, semantics)
+            return resample.resample(out, out_shape, resampling), win, index
+        oh, ow = out_shape
+        out = np.zeros((B, oh, ow), dtype=dt)
+        ctx = _native.default_context(int(device))
+        ctx.decode_device_resampled(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win,
+                                    out_shape, resampling,
+                                    _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, win, index
     if device is not None and k > 1:
         oh, ow = resample.decimated_shape(h, w, k)
         out = np.zeros((B, oh, ow), dtype=dt)
@@ -644,25 +667,58 @@ def tiff_stats(path: Path, window: Optional[Sequence[int]] = None, bbox: Optiona
     return report_from_bands(bands, hist, dt), win, info
 
 
-def read_overview(src, factor: int, resampling: str = "average", device: Optional[int] = None,
-                  semantics: str = "pcm16"):
+def _index_of(src):
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))[0]
+    return open_streaming(Path(src)).index
+
+
+def read_overview(src, factor: Optional[int] = None, resampling: str = "average", device: Optional[int] = None,
+                  semantics: str = "pcm16", out_shape: Optional[Sequence[int]] = None,
+                  max_size: Optional[int] = None):
     """The whole raster of a streaming container (path or bytes) at ``1 / factor`` resolution -> ``(raster (B,
     ceil(H / k), ceil(W / k)) in the index's dtype, index)``: ``resample.decimate(streaming_to_raster(src)[0], factor,
     resampling)``.  ``device=None`` reads the raster on the host and decimates it with numpy; an integer makes one
     ``fra_decode_device_decimated`` call on that GPU: the full-resolution raster exists only in device memory and the
     overview alone is copied back (the container's bytes go to the device as they are, as in
-    :func:`streaming_to_raster`)."""
+    :func:`streaming_to_raster`).
+
+    Instead of ``factor``: ``out_shape`` = (oh, ow), the whole raster resampled to that size
+    (``resample.resample``, ``resampling`` any of its four; on a GPU one ``fra_decode_device_resampled`` call), or
+    ``max_size`` = N, the output shape whose longest side is N (``resample.max_size_shape``)."""
     from . import _native
 
+    if out_shape is not None or max_size is not None:
+        if factor is not None or (out_shape is not None and max_size is not None):
+            raise ValueError("give exactly one of factor, out_shape and max_size")
+        index = _index_of(src)
+        H, W = int(index["height"]), int(index["width"])
+        if max_size is not None:
+            out_shape = resample.max_size_shape(H, W, max_size)
+        if device is None:
+            out, _, index = read_window(src, window=(0, 0, H, W), device=None, semantics=semantics,
+                                        resampling=resampling, out_shape=out_shape)
+            return out, index
+        if semantics not in ("pcm16", "int"):
+            raise ValueError("semantics must be 'pcm16' or 'int'")
+        oh, ow = resample.check_out_shape(out_shape)
+        resample.resampling_any_code(resampling)
+        data = _container_bytes(src)  # as they are, as below
+        index, items = _tile_items(data)
+        dt, B = np.dtype(index["dtype"]), int(index["bands"])
+        out = np.zeros((B, oh, ow), dtype=dt)
+        _native.default_context(int(device)).decode_device_resampled(
+            np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), (0, 0, H, W), (oh, ow), resampling,
+            _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+        return out, index
+    if factor is None:
+        raise ValueError("give exactly one of factor, out_shape and max_size")
     k = resample.check_factor(factor)
     resample.resampling_code(resampling)
     if semantics not in ("pcm16", "int"):
         raise ValueError("semantics must be 'pcm16' or 'int'")
     if device is None:
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            index, _ = read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))
-        else:
-            index = open_streaming(Path(src)).index
+        index = _index_of(src)
         out, _, index = read_window(src, window=(0, 0, int(index["height"]), int(index["width"])), device=None,
                                     semantics=semantics, decimate=k, resampling=resampling)
         return out, index
@@ -680,17 +736,19 @@ def read_overview(src, factor: int, resampling: str = "average", device: Optiona
 
 def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] = None,
                    bbox: Optional[Sequence[float]] = None, device: Optional[int] = None, decimate: int = 1,
-                   resampling: str = "nearest"):
+                   resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None):
     """A pixel window of a streaming container -> GeoTIFF with the index's CRS and the transform shifted to the
-    window's origin (``decimate`` > 1: the window at that fraction of the resolution, pixel size scaled to match);
-    returns ``(window, index)``."""
+    window's origin (``decimate`` > 1: the window at that fraction of the resolution, ``out_shape``: the window
+    resampled to that size; pixel size scaled to match); returns ``(window, index)``."""
     from .tiff import write_geotiff
 
     raster, win, index = read_window(Path(path), window=window, bbox=bbox, device=device, decimate=decimate,
-                                     resampling=resampling)
+                                     resampling=resampling, out_shape=out_shape)
     t = index.get("transform")
     crs = index.get("crs")
-    if t and decimate != 1:
+    if t and out_shape is not None:
+        transform = resample.resampled_transform(t, win, out_shape)
+    elif t and decimate != 1:
         transform = resample.decimated_transform(t, win, decimate)
     else:
         transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
@@ -698,15 +756,19 @@ def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] 
     return win, index
 
 
-def overview_to_tiff(path: Path, tiff_path: Path, factor: int, resampling: str = "average",
-                     device: Optional[int] = None):
-    """The whole raster of a streaming container at ``1 / factor`` resolution -> GeoTIFF with the index's CRS and the
-    pixel size scaled by ``factor``; returns ``(raster shape, index)``."""
+def overview_to_tiff(path: Path, tiff_path: Path, factor: Optional[int] = None, resampling: str = "average",
+                     device: Optional[int] = None, max_size: Optional[int] = None):
+    """The whole raster of a streaming container at ``1 / factor`` resolution, or with its longest side ``max_size``
+    pixels -> GeoTIFF with the index's CRS and the pixel size scaled to match; returns ``(raster shape, index)``."""
     from .tiff import write_geotiff
 
-    raster, index = read_overview(Path(path), factor, resampling, device=device)
+    raster, index = read_overview(Path(path), factor, resampling, device=device, max_size=max_size)
     t = index.get("transform")
     crs = index.get("crs")
-    write_geotiff(Path(tiff_path), raster, transform=resample.decimated_transform(t, (0, 0), factor) if t else None,
+    if t and max_size is not None:
+        transform = resample.resampled_transform(t, (0, 0, int(index["height"]), int(index["width"])), raster.shape[1:])
+    else:
+        transform = resample.decimated_transform(t, (0, 0), factor) if t else None
+    write_geotiff(Path(tiff_path), raster, transform=transform,
                   crs=crs if crs and crs != "None" else None)
     return raster.shape, index

@@ -317,7 +317,7 @@ def verify_on_device(plan: "_native.Plan", raster_ptr: int,
 
 def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int], raster_ptr: int,
                           strides: Optional[Tuple[int, int, int]] = None, decimate: int = 1,
-                          resampling: str = "nearest"):
+                          resampling: str = "nearest", out_shape: Optional[Tuple[int, int]] = None):
     """The windowed counterpart of :func:`verify_on_device`: decode the pixels ``window`` (row_off, col_off, height,
     width, in the plan's raster coordinates) of an executed plan's device output into ``raster_ptr``, a device buffer
     of int16 (16-bps plans) / int32 whose element 0 is the window's first pixel (default ``strides``: band-planar
@@ -327,12 +327,24 @@ def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int
 
     ``decimate`` = 2 .. 64: the window at that fraction of the resolution (``resample.decimate`` of the above with
     ``resampling``, ``fra_decode_device_decimated``); ``raster_ptr`` and the default ``strides`` then address the
-    ``resample.decimated_shape(height, width, decimate)`` output, and the plan's tiles must cover the window."""
+    ``resample.decimated_shape(height, width, decimate)`` output, and the plan's tiles must cover the window.
+
+    ``out_shape`` = (oh, ow), not together with ``decimate``: the window resampled to that size
+    (``resample.resample`` with ``resampling``, any of its four; ``fra_decode_device_resampled``); ``raster_ptr`` and
+    the default ``strides`` then address the ``(oh, ow)`` output."""
+    if out_shape is not None and decimate != 1:
+        raise ValueError("give decimate or out_shape, not both")
     infos, data, items = _plan_items(plan)
     if not items:
         return []
     _, _, h, w = (int(v) for v in window)
     dt = np.int16 if all(i.bps <= 16 for i in infos) else np.int32
+    if out_shape is not None:
+        from .resample import check_out_shape
+
+        oh, ow = check_out_shape(out_shape)
+        return plan.ctx.decode_device_resampled(data, items, int(raster_ptr), dt, infos[0].channels,
+                                                strides or (oh * ow, ow, 1), window, (oh, ow), resampling)
     if decimate != 1:
         from .resample import decimated_shape
 

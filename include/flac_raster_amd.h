@@ -366,6 +366,71 @@ FRA_API int fra_decode_device_decimated(fra_ctx *ctx, const fra_decode_job *job,
 /* HIP-event time (ms) of the calling thread's last k_decimate (fra_decimate or fra_decode_device_decimated) */
 FRA_API int fra_decimate_timing(float *ms);
 
+/* Resampled reads: a raster, or a region of a set of tile streams, at any output size: (channels, h, w) ->
+ * (channels, oh, ow), 1 <= oh, ow <= 65536, larger or smaller than the input, in the input's dtype (any fra_dtype).
+ * Each axis is handled alone and the same way (columns below): g = gcd(w, ow), w' = w / g, ow' = ow / g; rows: h', oh'.
+ * Every coordinate is an integer (no floating-point coordinate is formed); every value operation is an IEEE f64
+ * operation rounded on its own (no contraction).  NaN and +-inf propagate, nothing is skipped, there is no nodata.
+ *   The centre of output column C lies at source coordinate (C + 1/2) w / ow - 1/2:
+ *     num = (2 C + 1) w' - ow', den = 2 ow', i0 = floor(num / den) (negative for the first columns when upsampling),
+ *     t = (double)(num - i0 den) / (double)den, one correctly rounded division of two exact integers.
+ *   FRA_RESAMPLE_NEAREST   out[R, C] = in[min(((2 R + 1) h') / (2 oh'), h - 1), min(((2 C + 1) w') / (2 ow'), w - 1)]
+ *                          (for k dividing h and w and (oh, ow) = (h / k, w / k): the decimation's nearest)
+ *   FRA_RESAMPLE_BILINEAR  taps i0, i0 + 1, weights [1.0 - t, t]
+ *   FRA_RESAMPLE_CUBIC     taps i0 - 1 .. i0 + 2 (Catmull-Rom, a = -1/2), weights by exactly these operations:
+ *                            ((-0.5 t + 1.0) t - 0.5) t,  ((1.5 t - 2.5) t) t + 1.0,
+ *                            ((-1.5 t + 2.0) t + 0.5) t,  ((0.5 t - 0.5) t) t
+ *                          Both: every tap index is clamped to [0, w - 1]; vertically first, for every tap column
+ *                          c_i = sum_j (double)x[j][i] wy_j top to bottom (acc = p0; acc += p1; ...), then
+ *                          v = sum_i c_i wx_i left to right the same way.  f32 / f64: out = (T)v; integer dtypes:
+ *                          out = rint(v), half to even, clamped to the dtype's range (cubic overshoots).
+ *   FRA_RESAMPLE_AVERAGE   area weights in units of 1 / ow' of a source pixel: output column C covers [C w', (C + 1) w'),
+ *                          source column i covers [i ow', (i + 1) ow'); vx_i = min((i + 1) ow', (C + 1) w') -
+ *                          max(i ow', C w') for the columns where it is positive (they sum to w'); vy_j likewise;
+ *                          n = h' w'.  Integer dtypes: S = sum_j sum_i vy_j vx_i x[j][i], exact in int64 (no summation
+ *                          order is implied), out = rint((double)S / (double)n), half to even; FRA_E_INVALID when
+ *                          n 2^(8 itemsize) > 2^63.  f32 / f64: c_i = sum_j (double)vy_j (double)x[j][i] top to bottom,
+ *                          acc = sum_i (double)vx_i c_i left to right, out = (T)(acc / (double)n); FRA_E_INVALID when
+ *                          n > 2^53.  (For k dividing h and w and (oh, ow) = (h / k, w / k) every weight is 1 and the
+ *                          integer result is the decimation's average.)
+ *   When (oh, ow) = (h, w) every mode returns the input.
+ * With a geotransform (a, b, c, d, e, f), the input's origin at (row, col), sx = w / ow and sy = h / oh the output's
+ * transform is (a sx, b sy, c + col a + row b, d sx, e sy, f + col d + row e). */
+#define FRA_RESAMPLE_BILINEAR 2
+#define FRA_RESAMPLE_CUBIC 3
+#define FRA_RESAMPLE_MAX_OUT 65536
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype, of src and dst */
+  int32_t channels, height, width;          /* >= 1 */
+  int64_t src_band_stride, src_row_stride, src_col_stride;  /* elements, >= 0 */
+  int32_t out_height, out_width;            /* 1 .. FRA_RESAMPLE_MAX_OUT */
+  int32_t resampling;                       /* FRA_RESAMPLE_* (all four) */
+  void *dst; int32_t dst_on_device;         /* (channels, out_height, out_width) through the strides below */
+  int64_t dst_band_stride, dst_row_stride, dst_col_stride;
+} fra_resample_job;
+/* k_resample alone, over a host or device raster of any dtype.  Synchronous.  Host buffers are staged as fra_decimate
+ * stages them (one allocation spanning every addressed element from element 0; the elements of dst that are not
+ * outputs keep the caller's values).  The average reads rows with 16-byte loads when src_col_stride == 1 and src, the
+ * row stride and the band stride are multiples of 16 bytes, element by element otherwise.
+ * FRA_E_INVALID, before any GPU work, for a null argument, a bad dtype or layout, an output size outside
+ * 1 .. 65536, an unknown resampling code and the two overflow bounds of the average. */
+FRA_API int fra_resample(fra_ctx *ctx, const fra_resample_job *job);
+/* The windowed read at any output size: exactly the resampling (rule above) of what fra_decode_device_window would
+ * have written for `roi`, in dst_dtype, after its denormalisation and saturation.  Built as
+ * fra_decode_device_decimated is: the windowed read into a per-call device buffer of the region (its refusals and
+ * messages are this call's), then k_resample on the context's stream, then, for a host dst, the copy back; the job's
+ * dst and strides address the out_height x out_width output and no other element is written.  The region buffer is
+ * released on every path.
+ *   FRA_E_INVALID before any GPU work: a null argument, an output size outside 1 .. 65536, an unknown resampling code,
+ * the overflow bounds of the average, and items that do not cover the region ("the items do not cover the region").
+ *   Afterwards fra_decode_device_timing reports the inner windowed read and fra_resample_timing the resampling. */
+FRA_API int fra_decode_device_resampled(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                        int32_t out_height, int32_t out_width, int32_t resampling,
+                                        fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last k_resample (fra_resample or fra_decode_device_resampled) */
+FRA_API int fra_resample_timing(float *ms);
+
 /* Comparison of two rasters a and b of one dtype (any fra_dtype) and shape (channels, h, w): one report per band.
  *   Integer dtypes: d = (int64)a - (int64)b, exact, never wrapping (|d| <= 2^32 - 1).  differing = pixels with d != 0;
  *     first_row / first_col = the first of them in row-major order, relative to the rasters' origin (-1, -1: none);

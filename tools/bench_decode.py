@@ -44,6 +44,18 @@ checked.  The other legs are skipped.
 
     python tools/bench_decode.py --decimate 8 --steps 5 --warmup 2
 
+``--resample H,W`` (``--resampling`` nearest | average | bilinear | cubic, default average; ``--region r,c,h,w``, default
+the whole raster) times the read of the region resampled to H x W (``fra_decode_device_resampled``) in the same three
+legs as ``--decimate``: the full decode (``device_ms``); the resampled decode of the same resident frames
+(``kernels_resampled`` with ``k_resample_ms``, ``resampled_wall_ms``; ``k_resample_TBps`` = ``k_resample_bytes`` / its
+event time, the bytes being the region once plus the output for ``average`` and at most the taps of every output
+otherwise); and container bytes -> host raster, ``read_overview(out_shape=)`` against ``streaming_to_raster`` (with
+``--region``: ``read_window(out_shape=)`` against the plain ``read_window``), alternating (``e2e_resampled_ms`` /
+``e2e_full_ms``).  Band 0 of the result must equal ``resample.resample`` of band 0 of the full
+decode (an output row of an arbitrary size depends on the whole raster's height, so the band is checked whole).
+
+    python tools/bench_decode.py --resample 1373,1373 --steps 5 --warmup 2
+
 ``--compare`` times the comparison of the scene's container with its own synthetic raster, resident on the device
 (``fra_decode_device_compare``: the whole raster decoded with ``pcm16`` semantics to uint16 and compared there, only the
 reports come back), against the plain windowed read of the same region to a device destination in the same run
@@ -86,8 +98,8 @@ sys.path.insert(0, str(ROOT / "flac-raster_amd"))
 from flac_raster import _native as N  # noqa: E402
 from flac_raster.compare import compare_arrays, report_from_bands  # noqa: E402
 from flac_raster.geo import Affine  # noqa: E402
-from flac_raster.resample import FACTORS, decimate, decimated_shape  # noqa: E402
-from flac_raster.streaming import assemble_streaming, read_overview, streaming_to_raster  # noqa: E402
+from flac_raster.resample import FACTORS, RESAMPLING, RESAMPLING_ANY, decimate, decimated_shape, resample  # noqa: E402
+from flac_raster.streaming import assemble_streaming, read_overview, read_window, streaming_to_raster  # noqa: E402
 from flac_raster.tiles import calculate_tiles, streams_from  # noqa: E402
 
 SEED = 20240607
@@ -120,12 +132,18 @@ def main():
     ap.add_argument("--verify", action="store_true", help="time fra_plan_verify against the plain decode")
     ap.add_argument("--decimate", type=int, default=0, metavar="K", choices=(0,) + FACTORS,
                     help="time the decimated read of the whole raster at 1/K against the full decode")
-    ap.add_argument("--resampling", default="average", choices=("nearest", "average"), help="with --decimate")
+    ap.add_argument("--resampling", default="average", choices=tuple(RESAMPLING_ANY),
+                    help="with --decimate (nearest or average) or --resample (any)")
+    ap.add_argument("--resample", default=None, metavar="H,W",
+                    help="time the read of the region resampled to H x W against the full decode")
+    ap.add_argument("--region", default=None, metavar="r,c,h,w", help="with --resample: the region (default: all)")
     ap.add_argument("--compare", action="store_true",
                     help="time the comparison of the container with its source raster against the plain read")
     ap.add_argument("--stats", action="store_true",
                     help="time the band statistics and histograms of the container against the plain read")
     args = ap.parse_args()
+    if args.decimate and args.resampling not in RESAMPLING:
+        ap.error("--decimate takes --resampling nearest or average")
 
     ctx = N.Context(0)
     dt = np.dtype(np.uint16)
@@ -377,6 +395,78 @@ def main():
 
     _, frames = plan.download()
     streams = streams_from(infos, frames)
+
+    if args.resample:
+        oh, ow = (int(v) for v in args.resample.split(","))
+        mode = args.resampling
+        roi = tuple(int(v) for v in args.region.split(",")) if args.region else (0, 0, H, W)
+        r0, c0, h, w = roi
+        dev_small = ctx.alloc(B * oh * ow * 2)
+        rs_wall, rs_kern, rs_k = [], [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ctx.decode_device_resampled((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi,
+                                        (oh, ow), mode)
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                rs_wall.append((t1 - t0) * 1e3)
+                rs_kern.append(ctx.decode_timing())
+                rs_k.append(ctx.resample_timing())
+        got = np.empty((B, oh, ow), np.int16)
+        ctx.d2h(got, dev_small)
+        ctx.free(dev_small)
+        full = np.empty((B, H, W), np.int16)
+        ctx.d2h(full, dev_out)
+        if not np.array_equal(got[0], resample(full[0, r0:r0 + h, c0:c0 + w], (oh, ow), mode)):
+            raise SystemExit("the resampled decode differs from resample.resample of the full decode")
+        del full
+        data = assemble_streaming(wins, streams, (B, H, W), dt, Affine(10.0, 0.0, 0.0, 0.0, -10.0, 0.0), "EPSG:32633",
+                                  TILE)
+        small_ms, full_ms = [], []
+        n_e2e = min(1, args.warmup) + min(3, args.steps)
+        for s in range(n_e2e):
+            t0 = time.perf_counter()
+            if args.region:
+                small = read_window(data, window=roi, device=0, out_shape=(oh, ow), resampling=mode)[0]
+            else:
+                small = read_overview(data, out_shape=(oh, ow), resampling=mode, device=0)[0]
+            t1 = time.perf_counter()
+            big = streaming_to_raster(data, device=0)[0] if not args.region else read_window(data, window=roi, device=0)[0]
+            t2 = time.perf_counter()
+            if s == 0 and not np.array_equal(small[0], resample(big[0], (oh, ow), mode)):
+                raise SystemExit("the resampled read differs from resample.resample of the plain read")
+            del big
+            if s >= min(1, args.warmup):
+                small_ms.append((t1 - t0) * 1e3)
+                full_ms.append((t2 - t1) * 1e3)
+        med = statistics.median
+        kr = med(rs_k)
+        taps = {"nearest": 1, "average": 0, "bilinear": 4, "cubic": 16}[mode]
+        moved = (B * h * w * 2 if mode == "average" else min(B * h * w, taps * B * oh * ow) * 2) + B * oh * ow * 2
+        names = ("k_dec_parse_ms", "k_dec_restore_ms", "k_dec_scatter_ms")
+        res = {
+            "workload": f"resample {h}x{w} at ({r0}, {c0}) -> {oh}x{ow} ({mode}) of C4-like {W}x{H}x{B} uint16, tile "
+                        f"{TILE}, level {LEVEL}, {len(wins)} tiles",
+            "region": list(roi), "output": [B, oh, ow], "resampling": mode, "tiles": len(wins), "frames": nfr,
+            "steps": args.steps, "warmup": args.warmup, "band0_equals_numpy_rule": True,
+            "device_ms": round(med(dev_ms), 3), "device_wall_ms": round(med(dev_wall), 3),
+            "kernels_full": {n: round(med([q[i] for q in kern]), 3) for i, n in enumerate(names)},
+            "resampled_wall_ms": round(med(rs_wall), 3),
+            "resampled_events_ms": round(med([q[3] for q in rs_kern]) + kr, 3),
+            "kernels_resampled": dict({n: round(med([q[i] for q in rs_kern]), 3) for i, n in enumerate(names)},
+                                      k_resample_ms=round(kr, 4)),
+            "k_resample_bytes": moved, "k_resample_TBps": round(moved / (kr * 1e-3) / 1e12, 3),
+            "e2e_resampled_ms": round(med(small_ms), 2), "e2e_full_ms": round(med(full_ms), 2),
+            "e2e_full_over_resampled": round(med(full_ms) / med(small_ms), 2),
+            "all_ms": {"k_resample": [round(v, 4) for v in rs_k], "resampled_wall": [round(v, 2) for v in rs_wall],
+                       "device": [round(v, 3) for v in dev_ms], "e2e_resampled": [round(v, 2) for v in small_ms],
+                       "e2e_full": [round(v, 2) for v in full_ms]},
+        }
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
 
     if args.decimate:
         k, mode = args.decimate, args.resampling

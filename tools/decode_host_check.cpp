@@ -9,7 +9,7 @@
 //     first samples must equal what the full chain assigns to the same frames, and a bit-flipped variant must fail
 //     exactly when the flipped byte lies in a selected frame;
 //   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
-//     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated reads
+//     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
 //     the comparison (fra_compare, fra_decode_device_compare) and the statistics (fra_stats, fra_decode_device_stats),
 //     which returns before any GPU work.
 // usage: decode_host_check [--concat] file.flac ...
@@ -360,6 +360,56 @@ int main(int argc, char** argv) {
     { auto j = mj; j.height = 0; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: zero height accepted"); }
     { auto j = mj; j.dst_row_stride = -1; EXPECT(fra_decimate(ctx, &j) == FRA_E_INVALID, "decimate: negative stride accepted"); }
     EXPECT(fra_decimate_timing(nullptr) == FRA_E_INVALID, "decimate timing: null accepted");
+  }
+  // ... and of the resampled reads (fra_resample.hip): refused before any GPU work
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;
+    dj.items = &di;
+    const fra_window r48{0, 0, 4, 8};
+    auto rs = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, int oh, int ow, int mode, fra_decoded* o) {
+      return fra_decode_device_resampled(c, j, r, oh, ow, mode, o);
+    };
+    EXPECT(rs(nullptr, &dj, &r48, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: null ctx accepted");
+    EXPECT(rs(ctx, nullptr, &r48, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: null job accepted");
+    EXPECT(rs(ctx, &dj, nullptr, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: null roi accepted");
+    EXPECT(rs(ctx, &dj, &r48, 3, 5, 1, nullptr) == FRA_E_INVALID, "resampled read: null infos accepted");
+    for (int n : {0, -1, 65537}) {
+      EXPECT(rs(ctx, &dj, &r48, n, 5, 1, inf) == FRA_E_INVALID && g_msg.find("output size") != std::string::npos, "resampled read: out height %d accepted", n);
+      EXPECT(rs(ctx, &dj, &r48, 3, n, 1, inf) == FRA_E_INVALID && g_msg.find("output size") != std::string::npos, "resampled read: out width %d accepted", n);
+    }
+    for (int m : {4, -1}) EXPECT(rs(ctx, &dj, &r48, 3, 5, m, inf) == FRA_E_INVALID && g_msg.find("resampling") != std::string::npos, "resampled read: resampling %d accepted", m);
+    for (int m : {0, 1, 2, 3}) { fra_window r = r48; r.height = 5; EXPECT(rs(ctx, &dj, &r, 3, 5, m, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "resampled read: uncovered row accepted (mode %d)", m); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "resampled read: uncovered column accepted"); }
+    { auto j = dj; j.nitems = 0; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(rs(ctx, &dj, &r, 3, 5, 1, inf) == FRA_E_INVALID && g_msg.find("region of interest") != std::string::npos, "resampled read: zero-width roi accepted"); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst = nullptr; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: null dst accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf) == FRA_E_INVALID, "resampled read: dtype 9 accepted"); }
+    int32_t out[16];
+    fra_resample_job mj{};
+    mj.src = dst; mj.dtype = FRA_I32; mj.channels = 1; mj.height = 8; mj.width = 8;
+    mj.src_band_stride = 64; mj.src_row_stride = 8; mj.src_col_stride = 1;
+    mj.out_height = 3; mj.out_width = 5; mj.resampling = FRA_RESAMPLE_AVERAGE;
+    mj.dst = out; mj.dst_band_stride = 15; mj.dst_row_stride = 5; mj.dst_col_stride = 1;
+    EXPECT(fra_resample(nullptr, &mj) == FRA_E_INVALID, "resample: null ctx accepted");
+    EXPECT(fra_resample(ctx, nullptr) == FRA_E_INVALID, "resample: null job accepted");
+    { auto j = mj; j.src = nullptr; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: null src accepted"); }
+    { auto j = mj; j.dst = nullptr; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: null dst accepted"); }
+    for (int n : {0, -1, 65537}) {
+      { auto j = mj; j.out_height = n; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: out height %d accepted", n); }
+      { auto j = mj; j.out_width = n; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: out width %d accepted", n); }
+    }
+    for (int m : {4, -1}) { auto j = mj; j.resampling = m; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: resampling %d accepted", m); }
+    { auto j = mj; j.dtype = 8; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: dtype 8 accepted"); }
+    { auto j = mj; j.height = 0; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: zero height accepted"); }
+    { auto j = mj; j.dst_row_stride = -1; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID, "resample: negative stride accepted"); }
+    // the overflow bounds of the average: n = h' w'; n 2^(8 itemsize) > 2^63 (integers), n > 2^53 (floats)
+    { auto j = mj; j.height = 65537; j.width = 65537; j.out_height = 1; j.out_width = 1; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "resample: int32 average of 2^32 weights accepted"); }
+    { auto j = mj; j.dtype = FRA_U8; j.height = (1 << 28) + 1; j.width = (1 << 27) + 1; j.out_height = 2; j.out_width = 2; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "resample: uint8 average of 2^55 weights accepted"); }
+    { auto j = mj; j.dtype = FRA_F64; j.height = (1 << 27) + 1; j.width = (1 << 26) + 1; j.out_height = 2; j.out_width = 2; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "resample: f64 average of 2^53 weights accepted"); }
+    EXPECT(fra_resample_timing(nullptr) == FRA_E_INVALID, "resample timing: null accepted");
   }
   // ... and of the comparison (fra_compare.hip): refused before any GPU work
   {
