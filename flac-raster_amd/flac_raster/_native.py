@@ -209,7 +209,8 @@ EXPORTS = [
     "fra_decode_device_timing", "fra_decode_device_window", "fra_plan_verify", "fra_decimate",
     "fra_decode_device_decimated", "fra_decimate_timing", "fra_compare", "fra_decode_device_compare",
     "fra_compare_timing", "fra_stats", "fra_decode_device_stats", "fra_stats_timing", "fra_resample",
-    "fra_decode_device_resampled", "fra_resample_timing",
+    "fra_decode_device_resampled", "fra_resample_timing", "fra_resample_masked", "fra_decimate_masked",
+    "fra_decode_device_resampled_masked", "fra_decode_device_decimated_masked", "fra_resample_masked_timing",
 ]
 
 
@@ -296,6 +297,14 @@ def load():
             L.fra_decode_device_resampled.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32, i32,
                                                       C.POINTER(Decoded)]
             L.fra_resample_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_resample_masked"):
+            L.fra_resample_masked.argtypes = [vp, C.POINTER(ResampleJob), C.c_double, C.POINTER(u64)]
+            L.fra_decimate_masked.argtypes = [vp, C.POINTER(DecimateJob), C.c_double, C.POINTER(u64)]
+            L.fra_decode_device_resampled_masked.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32, i32,
+                                                             C.POINTER(Decoded), C.c_double, C.POINTER(u64)]
+            L.fra_decode_device_decimated_masked.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32,
+                                                             C.POINTER(Decoded), C.c_double, C.POINTER(u64)]
+            L.fra_resample_masked_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -307,6 +316,23 @@ def _check(rc: int):
     if rc != 0:
         msg = load().fra_last_error()
         raise NativeError(f"flac_raster_amd error {rc}: {msg.decode() if msg else ''}")
+
+
+def _masked_args(nodata, filled, dtype, channels: int):
+    """``(nodata, fill counts pointer)`` of a nodata-aware entry, ``None`` without a nodata value."""
+    if nodata is None:
+        if filled is not None:
+            raise ValueError("filled needs a nodata value")
+        return None
+    from .resample import check_nodata
+
+    nd = check_nodata(nodata, dtype)
+    if filled is None:
+        return nd, None
+    if not (isinstance(filled, np.ndarray) and filled.dtype == np.uint64 and filled.shape == (int(channels),)
+            and filled.flags.c_contiguous and filled.flags.writeable):
+        raise ValueError(f"filled must be a writable contiguous uint64 array of {int(channels)}")
+    return nd, filled.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
 def device_count() -> int:
@@ -462,7 +488,7 @@ class Context:
 
     def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
                       denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None,
-                      compare=None, stats=None, resample=None) -> List[Decoded]:
+                      compare=None, stats=None, resample=None, masked=None) -> List[Decoded]:
         """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
 
         ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
@@ -478,7 +504,8 @@ class Context:
         :meth:`decode_device_decimated`; ``compare`` = (ref pointer, on device, element strides, reports array): see
         :meth:`decode_device_compare`, ``dst`` is then ``None``; ``stats`` = (options, reports array, histogram
         pointer): see :meth:`decode_device_stats`, ``dst`` is then ``None`` too; ``resample`` = (out_height, out_width,
-        resampling code): see :meth:`decode_device_resampled`.)"""
+        resampling code): see :meth:`decode_device_resampled`; ``masked`` = (nodata, fill counts pointer or ``None``) beside
+        ``resample`` or ``decimate``: their nodata-aware entries.)"""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -523,9 +550,17 @@ class Context:
             rc = load().fra_decode_device_compare(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                   C.c_void_p(int(ref)), 1 if ref_on_device else 0, int(rst[0]),
                                                   int(rst[1]), int(rst[2]), bands, infos)
+        elif resample is not None and masked is not None:
+            rc = load().fra_decode_device_resampled_masked(
+                self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), int(resample[0]), int(resample[1]),
+                int(resample[2]), infos, float(masked[0]), masked[1])
         elif resample is not None:
             rc = load().fra_decode_device_resampled(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                     int(resample[0]), int(resample[1]), int(resample[2]), infos)
+        elif decimate is not None and masked is not None:
+            rc = load().fra_decode_device_decimated_masked(
+                self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), int(decimate[0]), int(decimate[1]), infos,
+                float(masked[0]), masked[1])
         elif decimate is not None:
             rc = load().fra_decode_device_decimated(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
                                                     int(decimate[0]), int(decimate[1]), infos)
@@ -552,23 +587,26 @@ class Context:
         return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi)
 
     def decode_device_decimated(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
-                                factor: int, resampling: str = "nearest", denorm: int = DENORM_NONE) -> List[Decoded]:
+                                factor: int, resampling: str = "nearest", denorm: int = DENORM_NONE, nodata=None,
+                                filled=None) -> List[Decoded]:
         """``roi`` at ``1 / factor`` resolution (``fra_decode_device_decimated``): exactly
         ``resample.decimate`` of what :meth:`decode_device_window` would have written, without the full-resolution
         region leaving the GPU.
 
         Arguments as :meth:`decode_device_window`, except that ``dst`` and ``strides`` address the
         ``resample.decimated_shape(roi[2], roi[3], factor)`` output.  ``factor``: 2, 4, 8, 16, 32 or 64; ``resampling``:
-        ``"nearest"`` or ``"average"``.  The items must cover the region."""
+        ``"nearest"`` or ``"average"``.  The items must cover the region.  ``nodata`` / ``filled``: as :meth:`decimate`
+        (``fra_decode_device_decimated_masked``)."""
         from .resample import check_factor, resampling_code
 
         if roi is None:
             raise ValueError("roi is required")
         return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi,
-                                  (check_factor(factor), resampling_code(resampling)))
+                                  (check_factor(factor), resampling_code(resampling)),
+                                  masked=_masked_args(nodata, filled, dst_dtype, channels))
 
     def decimate(self, src, factor: int, resampling: str = "nearest", dst=None, *, dtype=None, shape=None,
-                 strides=None, dst_strides=None):
+                 strides=None, dst_strides=None, nodata=None, filled=None):
         """A raster at ``1 / factor`` resolution on this context's GPU (``fra_decimate``, the rule of
         ``flac_raster.resample``).
 
@@ -576,7 +614,11 @@ class Context:
         strides (a view is fine: it is copied to the device from its first element to its last), or a device pointer
         (int) with ``dtype``, ``shape`` = (B, h, w) and element ``strides`` (default band-planar).  ``dst``: ``None``
         (a new array is returned), a numpy array view ``(B, oh, ow)`` (the elements between its outputs keep their
-        values), or a device pointer with element ``dst_strides`` (default band-planar).  Returns ``dst``."""
+        values), or a device pointer with element ``dst_strides`` (default band-planar).  Returns ``dst``.
+
+        ``nodata``: the nodata-aware rule (``fra_decimate_masked``; ``ValueError`` for a value the dtype does not
+        admit); ``filled``, then, an optional ``uint64`` array of ``B`` that receives per band the number of output
+        pixels no valid pixel reached.  ``None`` is the unmasked kernel."""
         from .resample import check_factor, decimated_shape, resampling_code
 
         k, mode = check_factor(factor), resampling_code(resampling)
@@ -612,7 +654,11 @@ class Context:
         job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
         job.factor, job.resampling = k, mode
         job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
-        _check(load().fra_decimate(self.h, C.byref(job)))
+        masked = _masked_args(nodata, filled, dt, B)
+        if masked is not None:
+            _check(load().fra_decimate_masked(self.h, C.byref(job), *masked))
+        else:
+            _check(load().fra_decimate(self.h, C.byref(job)))
         return ret
 
     def decimate_timing(self) -> float:
@@ -622,13 +668,14 @@ class Context:
         return ms.value
 
     def decode_device_resampled(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
-                                out_shape, resampling: str = "nearest", denorm: int = DENORM_NONE) -> List[Decoded]:
+                                out_shape, resampling: str = "nearest", denorm: int = DENORM_NONE, nodata=None,
+                                filled=None) -> List[Decoded]:
         """``roi`` at ``out_shape`` = (oh, ow) (``fra_decode_device_resampled``): exactly ``resample.resample`` of what
         :meth:`decode_device_window` would have written, without the full-resolution region leaving the GPU.
 
         Arguments as :meth:`decode_device_window`, except that ``dst`` and ``strides`` address the ``(oh, ow)``
         output.  ``resampling``: ``"nearest"``, ``"average"``, ``"bilinear"`` or ``"cubic"``.  The items must cover
-        the region."""
+        the region.  ``nodata`` / ``filled``: as :meth:`decimate` (``fra_decode_device_resampled_masked``)."""
         from .resample import check_average_size, check_out_shape, resampling_any_code
 
         if roi is None:
@@ -638,15 +685,16 @@ class Context:
         if mode == RESAMPLE_AVERAGE and int(roi[2]) > 0 and int(roi[3]) > 0:
             check_average_size(int(roi[2]), int(roi[3]), oh, ow, dst_dtype)
         return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi,
-                                  resample=(oh, ow, mode))
+                                  resample=(oh, ow, mode), masked=_masked_args(nodata, filled, dst_dtype, channels))
 
     def resample(self, src, out_shape, resampling: str = "nearest", dst=None, *, dtype=None, shape=None,
-                 strides=None, dst_strides=None):
+                 strides=None, dst_strides=None, nodata=None, filled=None):
         """A raster at ``out_shape`` = (oh, ow) on this context's GPU (``fra_resample``, the rule of
         ``flac_raster.resample.resample``).
 
         ``src``, ``dst`` and the keyword arguments as :meth:`decimate`; ``dst`` is ``(B, oh, ow)``.  ``resampling``:
-        ``"nearest"``, ``"average"``, ``"bilinear"`` or ``"cubic"``.  Returns ``dst``."""
+        ``"nearest"``, ``"average"``, ``"bilinear"`` or ``"cubic"``.  Returns ``dst``.  ``nodata`` / ``filled``: as
+        :meth:`decimate` (``fra_resample_masked``)."""
         from .resample import check_out_shape, resampling_any_code
 
         (oh, ow), mode = check_out_shape(out_shape), resampling_any_code(resampling)
@@ -681,13 +729,23 @@ class Context:
         job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
         job.out_height, job.out_width, job.resampling = oh, ow, mode
         job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
-        _check(load().fra_resample(self.h, C.byref(job)))
+        masked = _masked_args(nodata, filled, dt, B)
+        if masked is not None:
+            _check(load().fra_resample_masked(self.h, C.byref(job), *masked))
+        else:
+            _check(load().fra_resample(self.h, C.byref(job)))
         return ret
 
     def resample_timing(self) -> float:
         """HIP-event ms of this thread's last ``k_resample`` (:meth:`resample` / :meth:`decode_device_resampled`)."""
         ms = C.c_float()
         _check(load().fra_resample_timing(C.byref(ms)))
+        return ms.value
+
+    def resample_masked_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_resample_masked`` (any read with ``nodata``)."""
+        ms = C.c_float()
+        _check(load().fra_resample_masked_timing(C.byref(ms)))
         return ms.value
 
     def decode_device_compare(self, data, items, ref, dst_dtype, channels: int, roi, denorm: int = DENORM_NONE,

@@ -193,6 +193,12 @@ def extract(
         raise typer.Exit(1)
 
 
+def _print_nodata_shares(nodata, shares):
+    """The share of output pixels that are nodata, per band (after a read with ``--nodata``)."""
+    if nodata is not None:
+        console.print(f"nodata {nodata:g}: " + ", ".join(f"band {b + 1} {100.0 * s:.2f} %" for b, s in enumerate(shares)))
+
+
 @app.command()
 def window(
     flac_file: str = typer.Argument(..., help="Streaming FLAC file"),
@@ -204,6 +210,8 @@ def window(
     resampling: str = typer.Option("nearest", "--resampling", help="With --decimate: nearest or average; with "
                                    "--out-shape: nearest, average, bilinear or cubic"),
     out_shape: Optional[str] = typer.Option(None, "--out-shape", help="Write the window resampled to 'H,W' pixels"),
+    nodata: Optional[float] = typer.Option(None, "--nodata", help="With --decimate or --out-shape: leave pixels of this "
+                                           "value (and NaN) out of every result and tag the TIFF with it"),
 ):
     """Read a pixel window of a streaming FLAC file to GeoTIFF (only the tiles and frames it needs)."""
     from .streaming import window_to_tiff
@@ -218,13 +226,15 @@ def window(
         # the given device, else device 0 when a GPU is present, else the host decoder (as convert)
         dev = device if device is not None else (0 if _gpu_present() else None)
         shape = tuple(int(x.strip()) for x in out_shape.split(",")) if out_shape else None
+        shares: list = []
         got, idx = window_to_tiff(path, output, window=win, bbox=box, device=dev, decimate=decimate,
-                                  resampling=resampling, out_shape=shape)
+                                  resampling=resampling, out_shape=shape, nodata=nodata, shares=shares)
         scale = f" at 1/{decimate} resolution ({resampling})" if decimate != 1 else ""
         if shape:
             scale = f" as {shape[0]} x {shape[1]} ({resampling})"
         console.print(f"[green]Saved rows {got[0]}..{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]} of "
                       f"{idx['height']} x {idx['width']}{scale} to: {output}[/green]")
+        _print_nodata_shares(nodata, shares)
     except typer.Exit:
         raise
     except Exception as e:
@@ -243,6 +253,8 @@ def overview(
                                    "or cubic"),
     size: Optional[int] = typer.Option(None, "--size", help="Write the raster with its longest side N pixels"),
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+    nodata: Optional[float] = typer.Option(None, "--nodata", help="Leave pixels of this value (and NaN) out of every "
+                                           "result and tag the TIFF with it"),
 ):
     """Write a reduced-resolution preview of a whole streaming FLAC file to GeoTIFF."""
     from .streaming import overview_to_tiff
@@ -253,10 +265,13 @@ def overview(
         if (factor is None) == (size is None):
             console.print("[red]Error: give exactly one of --factor and --size[/red]")
             raise typer.Exit(1)
-        shape, idx = overview_to_tiff(path, output, factor, resampling, device=dev, max_size=size)
+        shares: list = []
+        shape, idx = overview_to_tiff(path, output, factor, resampling, device=dev, max_size=size, nodata=nodata,
+                                      shares=shares)
         how = f"at 1/{factor} resolution" if size is None else f"with longest side {size}"
         console.print(f"[green]Saved {idx['height']} x {idx['width']} {how} ({resampling}) as "
                       f"{shape[1]} x {shape[2]} to: {output}[/green]")
+        _print_nodata_shares(nodata, shares)
     except typer.Exit:
         raise
     except Exception as e:

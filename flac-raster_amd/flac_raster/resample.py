@@ -37,6 +37,48 @@ The centre of output column ``C`` lies at source coordinate ``(C + 1/2) w / ow -
               > 2^63``.  Float dtypes: ``c_i = sum_j float64(vy_j) float64(x[j][i])`` top to bottom, ``acc = sum_i
               float64(vx_i) c_i`` left to right, ``out = dtype(acc / float64(n))``; refused when ``n > 2^53``.
 When the output has the input's size every mode returns the input.
+
+Nodata-aware reads (``resample(..., nodata=nd)``, ``decimate(..., nodata=nd)``, ``k_resample_masked``; the same words as
+``include/flac_raster_amd.h``):
+
+ A nodata value nd is a double.
+   For integer dtypes nd must be an integer inside the dtype's range.
+   For float32 / float64 nd must be NaN, or finite and exactly representable in the dtype.
+   Anything else is refused before any GPU work: ValueError in Python, FRA_E_INVALID in the C ABI.  An infinite nd
+   is refused too.
+   A pixel x is invalid when (double)x == nd, the same test as the statistics.  In float dtypes a NaN pixel is also
+   invalid, whatever nd is.  +-inf are valid and propagate by IEEE arithmetic.  The fill is (T)nd.
+ Coordinates, taps, weights, g, h', w', i0 and t are exactly those of the unmasked rule.  Only the value arithmetic
+ below is new.  Every f64 operation is rounded on its own.
+   nearest   unchanged: it picks one pixel, invalid or not.
+   average   (resample)  Down the output row's source rows j, top to bottom, for every source column i:
+             integer dtypes: c_i = the sum of vy_j x[j][i] over the valid pixels, exact in int64; float dtypes: the
+             first valid term initialises c_i and later valid terms are added (c_i = term; c_i += term; ...).
+             u_i = the integer sum of vy_j over the valid pixels.
+             Then over the output's source columns i, left to right, skipping the columns with u_i == 0:
+             S = sum_i vx_i c_i (floats: acc = (double)vx_i * c_i, the first non-skipped column initialising) and
+             W = sum_i vx_i u_i, exact in int64, 1 <= W <= n.  W == 0 gives the fill.  Otherwise integers give
+             rint((double)S / (double)W), half to even (between the valid extremes: no clamp), and floats give
+             (T)(acc / (double)W).  The two overflow bounds of the unmasked average apply unchanged.
+             With no invalid pixel the result equals the unmasked resampling bit for bit in every dtype, -0.0
+             included.  An average of valid pixels that happens to land on nd is written as it is (possible only
+             when nd lies strictly inside the data's range); nothing is nudged.
+   average   (decimate, factor k)  The same arithmetic with h' = w' = k and oh' = ow' = 1: every weight is 1, the tap
+             ranges are clipped at the raster's edge, the output is ceil(h / k) x ceil(w / k), and edge blocks need
+             no special case because the divisor is W, the count of valid pixels.  The float summation order is the
+             one above, not the adjacent-pair tree of the unmasked decimation.  So for k dividing h and w the
+             decimation equals the resampling to (h / k, w / k) bit for bit in every dtype, and with no invalid
+             pixel it equals the unmasked decimation for integer dtypes only.
+   bilinear, cubic   If all taps of the output (4 or 16, after clamping) are valid, the result is the unmasked
+             formula exactly, with no division.  Otherwise the result is the masked bilinear of the same centre,
+             whichever of the two modes was asked for (a cubic kernel's negative weights cannot be renormalised
+             safely): taps i0, i0 + 1 per axis, clamped, weights wy = [1.0 - ty, ty] and wx likewise.  Vertically
+             c_i = the sum of (double)x[j][i] * wy_j over the valid j in ascending order, the first valid term
+             initialising, and u_i = the sum of wy_j over the valid j.  Horizontally, over the columns with at
+             least one valid tap, v = sum_i c_i * wx_i and Wt = sum_i u_i * wx_i in ascending order, the first such
+             column initialising both.  No valid tap, or Wt <= 0.0 (a lone valid tap with weight exactly 0), gives
+             the fill.  Otherwise q = v / Wt; floats give (T)q, integers rint(q) clamped to the dtype.
+   When (oh, ow) = (h, w) every mode of the resampling returns the input.
 """
 
 from __future__ import annotations
@@ -81,19 +123,24 @@ def decimated_transform(transform: Sequence[float], window: Sequence[int], k: in
     return a * k, b * k, c + col * a + row * b, d * k, e * k, f + col * d + row * e
 
 
-def decimate(raster: np.ndarray, factor: int, resampling: str = "nearest") -> np.ndarray:
-    """``raster`` ``(B, h, w)`` or ``(h, w)`` at ``1 / factor`` resolution (the module's rule), same dtype."""
+def decimate(raster: np.ndarray, factor: int, resampling: str = "nearest", nodata=None) -> np.ndarray:
+    """``raster`` ``(B, h, w)`` or ``(h, w)`` at ``1 / factor`` resolution (the module's rule), same dtype.  With
+    ``nodata`` the average leaves that value (and NaN) out: the nodata-aware rule."""
     k = check_factor(factor)
     mode = resampling_code(resampling)
     a = np.asarray(raster)
     if a.ndim == 2:
-        return decimate(a[None], k, resampling)[0]
+        return decimate(a[None], k, resampling, nodata)[0]
     if a.ndim != 3 or a.shape[1] < 1 or a.shape[2] < 1:
         raise ValueError(f"expected a (B, h, w) or (h, w) raster with h, w >= 1, got shape {a.shape}")
     if a.dtype.newbyteorder("=") not in _DTYPES:
         raise TypeError(f"unsupported dtype {a.dtype}")
     B, h, w = a.shape
     oh, ow = decimated_shape(h, w, k)
+    if nodata is not None:
+        nd = check_nodata(nodata, a.dtype)
+        if mode == 1:
+            return _masked_area(a, *_block_taps(h, k), *_block_taps(w, k), nd)
     if mode == 0:
         rows = np.minimum(np.arange(oh) * k + k // 2, h - 1)
         cols = np.minimum(np.arange(ow) * k + k // 2, w - 1)
@@ -201,13 +248,156 @@ def _area_taps(n_in: int, n_out: int):
     return first, np.maximum(wts, 0)
 
 
-def resample(raster: np.ndarray, out_shape: Sequence[int], resampling: str = "nearest") -> np.ndarray:
-    """``raster`` ``(B, h, w)`` or ``(h, w)`` resampled to ``out_shape`` = (oh, ow) (the module's rule), same dtype."""
+def _tap_filter(x: np.ndarray, oh: int, ow: int, mode: int) -> np.ndarray:
+    """The bilinear (2) or cubic (3) combination of ``x`` (B, h, w) float64, before the conversion to the dtype."""
+    h, w = x.shape[1:]
+    i0y, ty = _centres(h, oh)
+    i0x, tx = _centres(w, ow)
+    off = 0 if mode == 2 else -1
+    cols = None  # (B, oh, w): every source column combined vertically for output row R
+    for k, wy in enumerate(_tap_weights(ty, mode)):
+        term = x[:, np.clip(i0y + off + k, 0, h - 1), :] * wy[None, :, None]
+        cols = term if k == 0 else cols + term
+    v = None
+    for k, wx in enumerate(_tap_weights(tx, mode)):
+        term = cols[:, :, np.clip(i0x + off + k, 0, w - 1)] * wx[None, None, :]
+        v = term if k == 0 else v + term
+    return v
+
+
+# ------------------------------------------------------------------------------- nodata-aware
+def check_nodata(nodata, dtype) -> float:
+    """``nodata`` as the float the rule admits for ``dtype``: an integer inside an integer dtype's range; for floats
+    NaN, or finite and exactly representable.  ``ValueError`` otherwise."""
+    dt = np.dtype(dtype).newbyteorder("=")
+    if dt not in _DTYPES:
+        raise TypeError(f"unsupported dtype {dt}")
+    try:
+        nd = float(nodata)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"nodata must be a number, got {nodata!r}") from None
+    if dt.kind == "f":
+        with np.errstate(over="ignore"):
+            ok = nd != nd or (abs(nd) != float("inf") and float(dt.type(nd)) == nd)
+    else:
+        info = np.iinfo(dt)
+        ok = nd == nd and abs(nd) != float("inf") and nd == int(nd) and info.min <= nd <= info.max
+    if not ok:
+        raise ValueError(f"nodata {nodata!r} is not a value of {dt.name}: an integer in range; for floats NaN, or "
+                         "finite and exact")
+    return nd
+
+
+def fill_value(nodata: float, dtype):
+    """The fill ``(T)nd`` of a checked nodata value."""
+    dt = np.dtype(dtype)
+    return dt.type(nodata) if dt.kind == "f" else dt.type(int(nodata))
+
+
+def valid_mask(a: np.ndarray, nodata: float) -> np.ndarray:
+    """The pixels that are neither ``nodata`` nor, in a float dtype, NaN."""
+    if a.dtype.kind == "f":
+        return ~(a == fill_value(nodata, a.dtype)) & ~np.isnan(a)
+    return a != fill_value(nodata, a.dtype)
+
+
+def _block_taps(n: int, k: int):
+    """``(first, weights)`` of the decimation by ``k`` along one axis, as ``_area_taps`` gives them: block ``C`` starts
+    at ``C k`` and every index it has inside the raster weighs 1."""
+    first = np.arange(-(-n // k), dtype=np.int64) * k
+    return first, ((first[None, :] + np.arange(k, dtype=np.int64)[:, None]) < n).astype(np.int64)
+
+
+def _masked_area(a: np.ndarray, firsty, vy, firstx, vx, nd: float) -> np.ndarray:
+    """The nodata-aware average of ``a`` (B, h, w) over the integer taps of the two axes."""
+    B, h, w = a.shape
+    dt = a.dtype
+    is_float = dt.kind == "f"
+    acc_t = np.float64 if is_float else np.int64
+    valid = valid_mask(a, nd)
+    x = a.astype(acc_t)
+    oh, ow = len(firsty), len(firstx)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        c = np.zeros((B, oh, w), acc_t)  # every source column summed down the valid rows of output row R
+        u = np.zeros((B, oh, w), np.int64)  # ... and the weights of those rows
+        for k in range(vy.shape[0]):
+            rows = np.minimum(firsty + k, h - 1)
+            ok = valid[:, rows, :] & (vy[k] > 0)[None, :, None]
+            term = vy[k].astype(acc_t)[None, :, None] * x[:, rows, :]
+            c = np.where(ok, np.where(u > 0, c + term, term), c) if is_float else c + np.where(ok, term, 0)
+            u = u + np.where(ok, vy[k][None, :, None], 0)
+        S = np.zeros((B, oh, ow), acc_t)
+        W = np.zeros((B, oh, ow), np.int64)
+        for k in range(vx.shape[0]):
+            cols = np.minimum(firstx + k, w - 1)
+            uu = u[:, :, cols]
+            ok = (uu > 0) & (vx[k] > 0)[None, None, :]  # a column without a valid pixel is skipped
+            term = vx[k].astype(acc_t)[None, None, :] * c[:, :, cols]
+            S = np.where(ok, np.where(W > 0, S + term, term), S) if is_float else S + np.where(ok, term, 0)
+            W = W + np.where(ok, vx[k][None, None, :] * uu, 0)
+        div = np.where(W > 0, W, 1).astype(np.float64)
+        q = S / div if is_float else np.rint(S.astype(np.float64) / div)
+        return np.where(W > 0, q.astype(dt), fill_value(nd, dt)).astype(dt, order="C")
+
+
+def _masked_taps(a: np.ndarray, oh: int, ow: int, mode: int, nd: float) -> np.ndarray:
+    """The nodata-aware bilinear (2) or cubic (3) of ``a`` (B, h, w)."""
+    B, h, w = a.shape
+    dt = a.dtype
+    valid = valid_mask(a, nd)
+    x = a.astype(np.float64)
+    i0y, ty = _centres(h, oh)
+    i0x, tx = _centres(w, ow)
+    off, nt = (0, 2) if mode == 2 else (-1, 4)
+    whole = _tap_filter(x, oh, ow, mode)  # what the outputs whose taps are all valid get
+    rows_ok = np.ones((B, oh, w), bool)
+    for k in range(nt):
+        rows_ok &= valid[:, np.clip(i0y + off + k, 0, h - 1), :]
+    all_ok = np.ones((B, oh, ow), bool)
+    for k in range(nt):
+        all_ok &= rows_ok[:, :, np.clip(i0x + off + k, 0, w - 1)]
+    # the masked bilinear of every centre
+    c = np.zeros((B, oh, w))
+    u = np.zeros((B, oh, w))
+    have = np.zeros((B, oh, w), bool)
+    for k, wy in enumerate((1.0 - ty, ty)):
+        rows = np.clip(i0y + k, 0, h - 1)
+        ok = valid[:, rows, :]
+        term = x[:, rows, :] * wy[None, :, None]
+        wk = np.broadcast_to(wy[None, :, None], term.shape)
+        c = np.where(ok, np.where(have, c + term, term), c)
+        u = np.where(ok, np.where(have, u + wk, wk), u)
+        have = have | ok
+    v = np.zeros((B, oh, ow))
+    wt = np.zeros((B, oh, ow))
+    seen = np.zeros((B, oh, ow), bool)
+    for k, wx in enumerate((1.0 - tx, tx)):
+        cols = np.clip(i0x + k, 0, w - 1)
+        ok = have[:, :, cols]
+        tc = c[:, :, cols] * wx[None, None, :]
+        tu = u[:, :, cols] * wx[None, None, :]
+        v = np.where(ok, np.where(seen, v + tc, tc), v)
+        wt = np.where(ok, np.where(seen, wt + tu, tu), wt)
+        seen = seen | ok
+    fill = ~all_ok & (~seen | (wt <= 0.0))
+    q = np.where(all_ok, whole, v / np.where(wt > 0.0, wt, 1.0))
+    if dt.kind == "f":
+        out = q.astype(dt, order="C")
+    else:
+        info = np.iinfo(dt)
+        out = np.clip(np.rint(np.where(fill, 0.0, q)), np.float64(info.min), np.float64(info.max)).astype(dt, order="C")
+    out[fill] = fill_value(nd, dt)
+    return out
+
+
+def resample(raster: np.ndarray, out_shape: Sequence[int], resampling: str = "nearest", nodata=None) -> np.ndarray:
+    """``raster`` ``(B, h, w)`` or ``(h, w)`` resampled to ``out_shape`` = (oh, ow) (the module's rule), same dtype.
+    With ``nodata`` the average, the bilinear and the cubic leave that value (and NaN) out: the nodata-aware rule."""
     mode = resampling_any_code(resampling)
     oh, ow = check_out_shape(out_shape)
     a = np.asarray(raster)
     if a.ndim == 2:
-        return resample(a[None], (oh, ow), resampling)[0]
+        return resample(a[None], (oh, ow), resampling, nodata)[0]
     if a.ndim != 3 or a.shape[1] < 1 or a.shape[2] < 1:
         raise ValueError(f"expected a (B, h, w) or (h, w) raster with h, w >= 1, got shape {a.shape}")
     if a.dtype.newbyteorder("=") not in _DTYPES:
@@ -215,8 +405,15 @@ def resample(raster: np.ndarray, out_shape: Sequence[int], resampling: str = "ne
     B, h, w = a.shape
     dt = a.dtype
     is_float = dt.kind == "f"
+    nd = None if nodata is None else check_nodata(nodata, dt)
     if (oh, ow) == (h, w):
         return np.array(a, order="C")
+    if nd is not None and mode != 0:
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            if mode == 1:
+                check_average_size(h, w, oh, ow, dt)
+                return _masked_area(a, *_area_taps(h, oh), *_area_taps(w, ow), nd)
+            return _masked_taps(a, oh, ow, mode, nd)
     if mode == 0:
         gh, gw = gcd(h, oh), gcd(w, ow)
         rows = np.minimum(((2 * np.arange(oh, dtype=np.int64) + 1) * (h // gh)) // (2 * (oh // gh)), h - 1)
@@ -240,18 +437,7 @@ def resample(raster: np.ndarray, out_shape: Sequence[int], resampling: str = "ne
             if is_float:
                 return (acc / np.float64(n)).astype(dt, order="C")
             return np.rint(acc.astype(np.float64) / np.float64(n)).astype(dt, order="C")
-        x = a.astype(np.float64)
-        i0y, ty = _centres(h, oh)
-        i0x, tx = _centres(w, ow)
-        off = 0 if mode == 2 else -1
-        cols = None  # (B, oh, w): every source column combined vertically for output row R
-        for k, wy in enumerate(_tap_weights(ty, mode)):
-            term = x[:, np.clip(i0y + off + k, 0, h - 1), :] * wy[None, :, None]
-            cols = term if k == 0 else cols + term
-        v = None
-        for k, wx in enumerate(_tap_weights(tx, mode)):
-            term = cols[:, :, np.clip(i0x + off + k, 0, w - 1)] * wx[None, None, :]
-            v = term if k == 0 else v + term
+        v = _tap_filter(a.astype(np.float64), oh, ow, mode)
         if is_float:
             return v.astype(dt, order="C")
         info = np.iinfo(dt)

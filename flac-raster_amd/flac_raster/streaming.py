@@ -363,7 +363,7 @@ def resolve_window(index: Dict, window: Optional[Sequence[int]] = None,
 
 def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
                 device: Optional[int] = None, semantics: str = "pcm16", decimate: int = 1,
-                resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None):
+                resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None, nodata=None):
     """A pixel window of a streaming container (path or bytes) -> ``(raster (B, h, w) in the index's dtype, window,
     index)``, bit-identical to cropping :func:`streaming_to_raster`.
 
@@ -377,6 +377,10 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     ``resample.resample(window's raster, out_shape, resampling)`` with ``resampling`` one of ``nearest``, ``average``,
     ``bilinear``, ``cubic`` (``resample.resampled_transform`` gives the result's transform).  On the host the window
     is read and resampled with numpy; on a GPU one ``fra_decode_device_resampled`` call does both there.
+
+    ``nodata`` (with ``decimate`` or ``out_shape``): the nodata-aware rule of ``resample``: pixels of that value, and
+    NaN, are left out of every result, and an output no valid pixel reaches holds the value.  The container stores no
+    nodata value, so it is always the caller's; ``None`` is the unmasked read.  On a GPU the ``_masked`` entries.
 
     ``window`` = (row_off, col_off, height, width) or ``bbox`` = (xmin, ymin, xmax, ymax), see :func:`resolve_window`;
     the returned window is the clipped one.  Of a file only the index and the byte ranges of the intersecting tiles
@@ -399,24 +403,29 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     R, C_, h, w = win
     dt = np.dtype(index["dtype"])
     B = int(index["bands"])
+    if nodata is not None:
+        if out_shape is None and k == 1:
+            raise ValueError("nodata needs decimate or out_shape")
+        nodata = resample.check_nodata(nodata, dt)
     if out_shape is not None:
         if device is None:
             out = np.zeros((B, h, w), dtype=dt)
             _decode_window_on_host(blob, items, win, out, semantics)
-            return resample.resample(out, out_shape, resampling), win, index
+            return resample.resample(out, out_shape, resampling, nodata), win, index
         oh, ow = out_shape
         out = np.zeros((B, oh, ow), dtype=dt)
         ctx = _native.default_context(int(device))
         ctx.decode_device_resampled(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win,
                                     out_shape, resampling,
-                                    _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+                                    _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT, nodata=nodata)
         return out, win, index
     if device is not None and k > 1:
         oh, ow = resample.decimated_shape(h, w, k)
         out = np.zeros((B, oh, ow), dtype=dt)
         ctx = _native.default_context(int(device))
         ctx.decode_device_decimated(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win, k,
-                                    resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+                                    resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT,
+                                    nodata=nodata)
         return out, win, index
     out = np.zeros((B, h, w), dtype=dt)
     if device is not None:
@@ -426,7 +435,7 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
         return out, win, index
     _decode_window_on_host(blob, items, win, out, semantics)
     if k > 1:
-        out = resample.decimate(out, k, resampling)
+        out = resample.decimate(out, k, resampling, nodata)
     return out, win, index
 
 
@@ -675,7 +684,7 @@ def _index_of(src):
 
 def read_overview(src, factor: Optional[int] = None, resampling: str = "average", device: Optional[int] = None,
                   semantics: str = "pcm16", out_shape: Optional[Sequence[int]] = None,
-                  max_size: Optional[int] = None):
+                  max_size: Optional[int] = None, nodata=None):
     """The whole raster of a streaming container (path or bytes) at ``1 / factor`` resolution -> ``(raster (B,
     ceil(H / k), ceil(W / k)) in the index's dtype, index)``: ``resample.decimate(streaming_to_raster(src)[0], factor,
     resampling)``.  ``device=None`` reads the raster on the host and decimates it with numpy; an integer makes one
@@ -685,7 +694,8 @@ def read_overview(src, factor: Optional[int] = None, resampling: str = "average"
 
     Instead of ``factor``: ``out_shape`` = (oh, ow), the whole raster resampled to that size
     (``resample.resample``, ``resampling`` any of its four; on a GPU one ``fra_decode_device_resampled`` call), or
-    ``max_size`` = N, the output shape whose longest side is N (``resample.max_size_shape``)."""
+    ``max_size`` = N, the output shape whose longest side is N (``resample.max_size_shape``).  ``nodata``: as
+    :func:`read_window`."""
     from . import _native
 
     if out_shape is not None or max_size is not None:
@@ -697,7 +707,7 @@ def read_overview(src, factor: Optional[int] = None, resampling: str = "average"
             out_shape = resample.max_size_shape(H, W, max_size)
         if device is None:
             out, _, index = read_window(src, window=(0, 0, H, W), device=None, semantics=semantics,
-                                        resampling=resampling, out_shape=out_shape)
+                                        resampling=resampling, out_shape=out_shape, nodata=nodata)
             return out, index
         if semantics not in ("pcm16", "int"):
             raise ValueError("semantics must be 'pcm16' or 'int'")
@@ -709,7 +719,7 @@ def read_overview(src, factor: Optional[int] = None, resampling: str = "average"
         out = np.zeros((B, oh, ow), dtype=dt)
         _native.default_context(int(device)).decode_device_resampled(
             np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), (0, 0, H, W), (oh, ow), resampling,
-            _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+            _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT, nodata=nodata)
         return out, index
     if factor is None:
         raise ValueError("give exactly one of factor, out_shape and max_size")
@@ -720,7 +730,7 @@ def read_overview(src, factor: Optional[int] = None, resampling: str = "average"
     if device is None:
         index = _index_of(src)
         out, _, index = read_window(src, window=(0, 0, int(index["height"]), int(index["width"])), device=None,
-                                    semantics=semantics, decimate=k, resampling=resampling)
+                                    semantics=semantics, decimate=k, resampling=resampling, nodata=nodata)
         return out, index
     data = _container_bytes(src)
     index, items = _tile_items(data)
@@ -730,20 +740,38 @@ def read_overview(src, factor: Optional[int] = None, resampling: str = "average"
     out = np.zeros((B, oh, ow), dtype=dt)
     ctx = _native.default_context(int(device))
     ctx.decode_device_decimated(np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), (0, 0, H, W),
-                                k, resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
+                                k, resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT,
+                                nodata=nodata)
     return out, index
+
+
+def _tiff_nodata(nodata, dtype):
+    """A nodata value as the TIFF tag writes it: an integer for an integer dtype."""
+    if nodata is None:
+        return None
+    nd = resample.check_nodata(nodata, dtype)
+    return nd if np.dtype(dtype).kind == "f" else int(nd)
+
+
+def nodata_share(raster: np.ndarray, nodata) -> list:
+    """Per band of ``raster`` (B, h, w), the share of pixels that are ``nodata`` or, in a float dtype, NaN."""
+    nd = resample.check_nodata(nodata, raster.dtype)
+    return [float(1.0 - resample.valid_mask(band, nd).mean()) for band in raster]
 
 
 def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] = None,
                    bbox: Optional[Sequence[float]] = None, device: Optional[int] = None, decimate: int = 1,
-                   resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None):
+                   resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None, nodata=None,
+                   shares: Optional[list] = None):
     """A pixel window of a streaming container -> GeoTIFF with the index's CRS and the transform shifted to the
     window's origin (``decimate`` > 1: the window at that fraction of the resolution, ``out_shape``: the window
-    resampled to that size; pixel size scaled to match); returns ``(window, index)``."""
+    resampled to that size; pixel size scaled to match; ``nodata``: as :func:`read_window`, and the TIFF carries the
+    value in its nodata tag; ``shares``, a list, then receives :func:`nodata_share` of what was written); returns
+    ``(window, index)``."""
     from .tiff import write_geotiff
 
     raster, win, index = read_window(Path(path), window=window, bbox=bbox, device=device, decimate=decimate,
-                                     resampling=resampling, out_shape=out_shape)
+                                     resampling=resampling, out_shape=out_shape, nodata=nodata)
     t = index.get("transform")
     crs = index.get("crs")
     if t and out_shape is not None:
@@ -752,17 +780,23 @@ def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] 
         transform = resample.decimated_transform(t, win, decimate)
     else:
         transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
-    write_geotiff(Path(tiff_path), raster, transform=transform, crs=crs if crs and crs != "None" else None)
+    write_geotiff(Path(tiff_path), raster, transform=transform, crs=crs if crs and crs != "None" else None,
+                  nodata=_tiff_nodata(nodata, raster.dtype))
+    if nodata is not None and shares is not None:
+        shares.extend(nodata_share(raster, nodata))
     return win, index
 
 
 def overview_to_tiff(path: Path, tiff_path: Path, factor: Optional[int] = None, resampling: str = "average",
-                     device: Optional[int] = None, max_size: Optional[int] = None):
+                     device: Optional[int] = None, max_size: Optional[int] = None, nodata=None,
+                     shares: Optional[list] = None):
     """The whole raster of a streaming container at ``1 / factor`` resolution, or with its longest side ``max_size``
-    pixels -> GeoTIFF with the index's CRS and the pixel size scaled to match; returns ``(raster shape, index)``."""
+    pixels -> GeoTIFF with the index's CRS and the pixel size scaled to match (``nodata``: as :func:`read_window`, and
+    the TIFF carries the value in its nodata tag; ``shares`` as :func:`window_to_tiff`); returns ``(raster shape,
+    index)``."""
     from .tiff import write_geotiff
 
-    raster, index = read_overview(Path(path), factor, resampling, device=device, max_size=max_size)
+    raster, index = read_overview(Path(path), factor, resampling, device=device, max_size=max_size, nodata=nodata)
     t = index.get("transform")
     crs = index.get("crs")
     if t and max_size is not None:
@@ -770,5 +804,7 @@ def overview_to_tiff(path: Path, tiff_path: Path, factor: Optional[int] = None, 
     else:
         transform = resample.decimated_transform(t, (0, 0), factor) if t else None
     write_geotiff(Path(tiff_path), raster, transform=transform,
-                  crs=crs if crs and crs != "None" else None)
+                  crs=crs if crs and crs != "None" else None, nodata=_tiff_nodata(nodata, raster.dtype))
+    if nodata is not None and shares is not None:
+        shares.extend(nodata_share(raster, nodata))
     return raster.shape, index

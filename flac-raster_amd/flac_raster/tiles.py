@@ -317,7 +317,8 @@ def verify_on_device(plan: "_native.Plan", raster_ptr: int,
 
 def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int], raster_ptr: int,
                           strides: Optional[Tuple[int, int, int]] = None, decimate: int = 1,
-                          resampling: str = "nearest", out_shape: Optional[Tuple[int, int]] = None):
+                          resampling: str = "nearest", out_shape: Optional[Tuple[int, int]] = None, nodata=None,
+                          filled=None):
     """The windowed counterpart of :func:`verify_on_device`: decode the pixels ``window`` (row_off, col_off, height,
     width, in the plan's raster coordinates) of an executed plan's device output into ``raster_ptr``, a device buffer
     of int16 (16-bps plans) / int32 whose element 0 is the window's first pixel (default ``strides``: band-planar
@@ -331,9 +332,15 @@ def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int
 
     ``out_shape`` = (oh, ow), not together with ``decimate``: the window resampled to that size
     (``resample.resample`` with ``resampling``, any of its four; ``fra_decode_device_resampled``); ``raster_ptr`` and
-    the default ``strides`` then address the ``(oh, ow)`` output."""
+    the default ``strides`` then address the ``(oh, ow)`` output.
+
+    ``nodata`` (with ``decimate`` or ``out_shape``): the nodata-aware rule of ``resample`` in the decoded samples'
+    dtype (the ``_masked`` entries); ``filled``: an optional ``uint64`` array of one word per channel that receives the
+    number of output pixels no valid pixel reached."""
     if out_shape is not None and decimate != 1:
         raise ValueError("give decimate or out_shape, not both")
+    if out_shape is None and decimate == 1 and (nodata is not None or filled is not None):
+        raise ValueError("nodata needs decimate or out_shape")
     infos, data, items = _plan_items(plan)
     if not items:
         return []
@@ -344,12 +351,14 @@ def read_window_on_device(plan: "_native.Plan", window: Tuple[int, int, int, int
 
         oh, ow = check_out_shape(out_shape)
         return plan.ctx.decode_device_resampled(data, items, int(raster_ptr), dt, infos[0].channels,
-                                                strides or (oh * ow, ow, 1), window, (oh, ow), resampling)
+                                                strides or (oh * ow, ow, 1), window, (oh, ow), resampling,
+                                                nodata=nodata, filled=filled)
     if decimate != 1:
         from .resample import decimated_shape
 
         oh, ow = decimated_shape(h, w, decimate)
         return plan.ctx.decode_device_decimated(data, items, int(raster_ptr), dt, infos[0].channels,
-                                                strides or (oh * ow, ow, 1), window, decimate, resampling)
+                                                strides or (oh * ow, ow, 1), window, decimate, resampling,
+                                                nodata=nodata, filled=filled)
     return plan.ctx.decode_device_window(data, items, int(raster_ptr), dt, infos[0].channels,
                                          strides or (h * w, w, 1), window)

@@ -431,6 +431,75 @@ FRA_API int fra_decode_device_resampled(fra_ctx *ctx, const fra_decode_job *job,
 /* HIP-event time (ms) of the calling thread's last k_resample (fra_resample or fra_decode_device_resampled) */
 FRA_API int fra_resample_timing(float *ms);
 
+/* Nodata-aware reads: the resampling and the decimation above with one value, and NaN, left out of every result.
+ *
+ * A nodata value nd is a double.
+ *   For integer dtypes nd must be an integer inside the dtype's range.
+ *   For float32 / float64 nd must be NaN, or finite and exactly representable in the dtype.
+ *   Anything else is refused before any GPU work: ValueError in Python, FRA_E_INVALID in the C ABI.  An infinite nd
+ *   is refused too.
+ *   A pixel x is invalid when (double)x == nd, the same test as the statistics.  In float dtypes a NaN pixel is also
+ *   invalid, whatever nd is.  +-inf are valid and propagate by IEEE arithmetic.  The fill is (T)nd.
+ * Coordinates, taps, weights, g, h', w', i0 and t are exactly those of the unmasked rule.  Only the value arithmetic
+ * below is new.  Every f64 operation is rounded on its own.
+ *   nearest   unchanged: it picks one pixel, invalid or not.
+ *   average   (resample)  Down the output row's source rows j, top to bottom, for every source column i:
+ *             integer dtypes: c_i = the sum of vy_j x[j][i] over the valid pixels, exact in int64; float dtypes: the
+ *             first valid term initialises c_i and later valid terms are added (c_i = term; c_i += term; ...).
+ *             u_i = the integer sum of vy_j over the valid pixels.
+ *             Then over the output's source columns i, left to right, skipping the columns with u_i == 0:
+ *             S = sum_i vx_i c_i (floats: acc = (double)vx_i * c_i, the first non-skipped column initialising) and
+ *             W = sum_i vx_i u_i, exact in int64, 1 <= W <= n.  W == 0 gives the fill.  Otherwise integers give
+ *             rint((double)S / (double)W), half to even (between the valid extremes: no clamp), and floats give
+ *             (T)(acc / (double)W).  The two overflow bounds of the unmasked average apply unchanged.
+ *             With no invalid pixel the result equals the unmasked resampling bit for bit in every dtype, -0.0
+ *             included.  An average of valid pixels that happens to land on nd is written as it is (possible only
+ *             when nd lies strictly inside the data's range); nothing is nudged.
+ *   average   (decimate, factor k)  The same arithmetic with h' = w' = k and oh' = ow' = 1: every weight is 1, the tap
+ *             ranges are clipped at the raster's edge, the output is ceil(h / k) x ceil(w / k), and edge blocks need
+ *             no special case because the divisor is W, the count of valid pixels.  The float summation order is the
+ *             one above, not the adjacent-pair tree of the unmasked decimation.  So for k dividing h and w the
+ *             decimation equals the resampling to (h / k, w / k) bit for bit in every dtype, and with no invalid
+ *             pixel it equals the unmasked decimation for integer dtypes only.
+ *   bilinear, cubic   If all taps of the output (4 or 16, after clamping) are valid, the result is the unmasked
+ *             formula exactly, with no division.  Otherwise the result is the masked bilinear of the same centre,
+ *             whichever of the two modes was asked for (a cubic kernel's negative weights cannot be renormalised
+ *             safely): taps i0, i0 + 1 per axis, clamped, weights wy = [1.0 - ty, ty] and wx likewise.  Vertically
+ *             c_i = the sum of (double)x[j][i] * wy_j over the valid j in ascending order, the first valid term
+ *             initialising, and u_i = the sum of wy_j over the valid j.  Horizontally, over the columns with at
+ *             least one valid tap, v = sum_i c_i * wx_i and Wt = sum_i u_i * wx_i in ascending order, the first such
+ *             column initialising both.  No valid tap, or Wt <= 0.0 (a lone valid tap with weight exactly 0), gives
+ *             the fill.  Otherwise q = v / Wt; floats give (T)q, integers rint(q) clamped to the dtype.
+ *   When (oh, ow) = (h, w) every mode of the resampling returns the input.
+ *
+ * filled (host memory, `channels` words, may be NULL) receives per band the number of output pixels that no valid pixel
+ * reached: those written as the fill by the average, the bilinear and the cubic; for the nearest and for an output of
+ * the input's size, the picked pixels that are invalid.  The kernel adds them up within each wave and issues one
+ * atomicAdd per workgroup into a zeroed device array. */
+/* fra_resample with a nodata value (rule above).  Buffers, layouts and refusals as fra_resample; also FRA_E_INVALID,
+ * before any GPU work, for a nodata value the dtype does not admit. */
+FRA_API int fra_resample_masked(fra_ctx *ctx, const fra_resample_job *job, double nodata,
+                                uint64_t *filled /* channels, may be NULL */);
+/* fra_decimate with a nodata value (rule above).  Buffers, layouts and refusals as fra_decimate; also FRA_E_INVALID,
+ * before any GPU work, for a nodata value the dtype does not admit. */
+FRA_API int fra_decimate_masked(fra_ctx *ctx, const fra_decimate_job *job, double nodata,
+                                uint64_t *filled /* channels, may be NULL */);
+/* fra_decode_device_resampled with a nodata value: the windowed read into a per-call device buffer of the region (its
+ * refusals and messages are this call's), then k_resample_masked, then, for a host dst, the copy back.  The region buffer
+ * is released on every path.  FRA_E_INVALID before any GPU work for everything fra_decode_device_resampled refuses so,
+ * and for a nodata value that dst_dtype does not admit. */
+FRA_API int fra_decode_device_resampled_masked(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                               int32_t out_height, int32_t out_width, int32_t resampling,
+                                               fra_decoded *infos /* nitems */, double nodata,
+                                               uint64_t *filled /* channels, may be NULL */);
+/* fra_decode_device_decimated with a nodata value, built the same way.  FRA_E_INVALID before any GPU work for everything
+ * fra_decode_device_decimated refuses so, and for a nodata value that dst_dtype does not admit. */
+FRA_API int fra_decode_device_decimated_masked(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                               int32_t factor, int32_t resampling, fra_decoded *infos /* nitems */,
+                                               double nodata, uint64_t *filled /* channels, may be NULL */);
+/* HIP-event time (ms) of the calling thread's last k_resample_masked (any of the four entries above) */
+FRA_API int fra_resample_masked_timing(float *ms);
+
 /* Comparison of two rasters a and b of one dtype (any fra_dtype) and shape (channels, h, w): one report per band.
  *   Integer dtypes: d = (int64)a - (int64)b, exact, never wrapping (|d| <= 2^32 - 1).  differing = pixels with d != 0;
  *     first_row / first_col = the first of them in row-major order, relative to the rasters' origin (-1, -1: none);

@@ -56,6 +56,14 @@ decode (an output row of an arbitrary size depends on the whole raster's height,
 
     python tools/bench_decode.py --resample 1373,1373 --steps 5 --warmup 2
 
+``--nodata X`` with ``--decimate`` or ``--resample`` times the nodata-aware read instead (``k_resample_masked`` through the
+``_masked`` entries; the same JSON keys, the kernel's time from ``fra_resample_masked_timing``) and checks it against
+the rule with that value.  X is a value of the decoded int16 samples, or ``corner``: what pixel (0, 0) decodes to, the
+value of the scene's corner of zeros; 32767 is a value the scene does not hold.  ``nodata_share_band0`` reports how much
+of band 0 is X.
+
+    python tools/bench_decode.py --resample 1373,1373 --nodata corner --steps 5 --warmup 2
+
 ``--compare`` times the comparison of the scene's container with its own synthetic raster, resident on the device
 (``fra_decode_device_compare``: the whole raster decoded with ``pcm16`` semantics to uint16 and compared there, only the
 reports come back), against the plain windowed read of the same region to a device destination in the same run
@@ -137,6 +145,9 @@ def main():
     ap.add_argument("--resample", default=None, metavar="H,W",
                     help="time the read of the region resampled to H x W against the full decode")
     ap.add_argument("--region", default=None, metavar="r,c,h,w", help="with --resample: the region (default: all)")
+    ap.add_argument("--nodata", default=None, metavar="X",
+                    help="with --decimate or --resample: the nodata-aware read with this value of the decoded int16 "
+                         "('corner': what pixel (0, 0) decodes to)")
     ap.add_argument("--compare", action="store_true",
                     help="time the comparison of the container with its source raster against the plain read")
     ap.add_argument("--stats", action="store_true",
@@ -144,6 +155,10 @@ def main():
     args = ap.parse_args()
     if args.decimate and args.resampling not in RESAMPLING:
         ap.error("--decimate takes --resampling nearest or average")
+    if args.nodata is not None and not (args.decimate or args.resample):
+        ap.error("--nodata goes with --decimate or --resample")
+    if args.nodata not in (None, "corner"):
+        args.nodata = float(args.nodata)
 
     ctx = N.Context(0)
     dt = np.dtype(np.uint16)
@@ -179,6 +194,12 @@ def main():
             dev_ms.append(ms[3])
             kern.append(ms[:3])
             dev_wall.append((t1 - t0) * 1e3)
+    corner = args.nodata == "corner"
+    if corner:
+        first = np.empty(1, np.int16)
+        ctx.d2h(first, dev_out)
+        args.nodata = float(first[0])
+    nd = {} if args.nodata is None else {"nodata": args.nodata}  # the keyword of the nodata-aware reads and rules
 
     if args.verify:
         ver_wall, ver_ms, ver_kern = [], [], []
@@ -406,34 +427,40 @@ def main():
         for s in range(args.warmup + args.steps):
             t0 = time.perf_counter()
             ctx.decode_device_resampled((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi,
-                                        (oh, ow), mode)
+                                        (oh, ow), mode, **nd)
             t1 = time.perf_counter()
             if s >= args.warmup:
                 rs_wall.append((t1 - t0) * 1e3)
                 rs_kern.append(ctx.decode_timing())
-                rs_k.append(ctx.resample_timing())
+                rs_k.append(ctx.resample_masked_timing() if nd else ctx.resample_timing())
         got = np.empty((B, oh, ow), np.int16)
         ctx.d2h(got, dev_small)
         ctx.free(dev_small)
         full = np.empty((B, H, W), np.int16)
         ctx.d2h(full, dev_out)
-        if not np.array_equal(got[0], resample(full[0, r0:r0 + h, c0:c0 + w], (oh, ow), mode)):
+        if not np.array_equal(got[0], resample(full[0, r0:r0 + h, c0:c0 + w], (oh, ow), mode, **nd)):
             raise SystemExit("the resampled decode differs from resample.resample of the full decode")
+        nd_share = float((full[0, r0:r0 + h, c0:c0 + w] == args.nodata).mean()) if nd else None
         del full
         data = assemble_streaming(wins, streams, (B, H, W), dt, Affine(10.0, 0.0, 0.0, 0.0, -10.0, 0.0), "EPSG:32633",
                                   TILE)
         small_ms, full_ms = [], []
         n_e2e = min(1, args.warmup) + min(3, args.steps)
+        # (the container reads give the scene's uint16, the decode above its int16 samples)
+        e2e_nd = {}
+        if nd:
+            at00 = read_window(data, window=(0, 0, 1, 1), device=0)[0]
+            e2e_nd = {"nodata": float(at00[0, 0, 0]) if corner else min(max(args.nodata + 32768.0, 0.0), 65535.0)}
         for s in range(n_e2e):
             t0 = time.perf_counter()
             if args.region:
-                small = read_window(data, window=roi, device=0, out_shape=(oh, ow), resampling=mode)[0]
+                small = read_window(data, window=roi, device=0, out_shape=(oh, ow), resampling=mode, **e2e_nd)[0]
             else:
-                small = read_overview(data, out_shape=(oh, ow), resampling=mode, device=0)[0]
+                small = read_overview(data, out_shape=(oh, ow), resampling=mode, device=0, **e2e_nd)[0]
             t1 = time.perf_counter()
             big = streaming_to_raster(data, device=0)[0] if not args.region else read_window(data, window=roi, device=0)[0]
             t2 = time.perf_counter()
-            if s == 0 and not np.array_equal(small[0], resample(big[0], (oh, ow), mode)):
+            if s == 0 and not np.array_equal(small[0], resample(big[0], (oh, ow), mode, **e2e_nd)):
                 raise SystemExit("the resampled read differs from resample.resample of the plain read")
             del big
             if s >= min(1, args.warmup):
@@ -449,6 +476,7 @@ def main():
                         f"{TILE}, level {LEVEL}, {len(wins)} tiles",
             "region": list(roi), "output": [B, oh, ow], "resampling": mode, "tiles": len(wins), "frames": nfr,
             "steps": args.steps, "warmup": args.warmup, "band0_equals_numpy_rule": True,
+            "nodata": args.nodata, "nodata_share_band0": nd_share,
             "device_ms": round(med(dev_ms), 3), "device_wall_ms": round(med(dev_wall), 3),
             "kernels_full": {n: round(med([q[i] for q in kern]), 3) for i, n in enumerate(names)},
             "resampled_wall_ms": round(med(rs_wall), 3),
@@ -477,12 +505,12 @@ def main():
         for s in range(args.warmup + args.steps):
             t0 = time.perf_counter()
             ctx.decode_device_decimated((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi, k,
-                                        mode)
+                                        mode, **nd)
             t1 = time.perf_counter()
             if s >= args.warmup:
                 dec_wall.append((t1 - t0) * 1e3)
                 dec_kern.append(ctx.decode_timing())
-                dec_k.append(ctx.decimate_timing())
+                dec_k.append(ctx.resample_masked_timing() if nd else ctx.decimate_timing())
         # one more call with the free device memory sampled beside it: the peak of the call
         hip = C.CDLL("libamdhip64.so")
         free, tot = C.c_size_t(), C.c_size_t()
@@ -498,7 +526,8 @@ def main():
 
         th = threading.Thread(target=sample, daemon=True)
         th.start()
-        ctx.decode_device_decimated((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi, k, mode)
+        ctx.decode_device_decimated((frames_ptr, total), items, dev_small, np.int16, B, (oh * ow, ow, 1), roi, k, mode,
+                                    **nd)
         stop.set()
         th.join()
         # the result against the numpy rule over the full decode: the top 2048 rows and the ragged bottom blocks
@@ -508,9 +537,10 @@ def main():
         ctx.d2h(full, dev_out)
         top = 2048 // k
         tail = oh - 4
-        if not (np.array_equal(got[:, :top], decimate(full[:, :2048], k, mode))
-                and np.array_equal(got[:, tail:], decimate(full[:, tail * k:], k, mode))):
+        if not (np.array_equal(got[:, :top], decimate(full[:, :2048], k, mode, **nd))
+                and np.array_equal(got[:, tail:], decimate(full[:, tail * k:], k, mode, **nd))):
             raise SystemExit("the decimated decode differs from resample.decimate of the full decode")
+        nd_share = float((full[0] == args.nodata).mean()) if nd else None
         del full
         ctx.free(dev_small)
         # container bytes -> host raster, both ways, alternating
@@ -518,13 +548,18 @@ def main():
                                   TILE)
         ov_ms, full_ms = [], []
         n_e2e = min(1, args.warmup) + min(3, args.steps)
+        # (the container reads give the scene's uint16, the decode above its int16 samples)
+        e2e_nd = {}
+        if nd:
+            at00 = read_window(data, window=(0, 0, 1, 1), device=0)[0]
+            e2e_nd = {"nodata": float(at00[0, 0, 0]) if corner else min(max(args.nodata + 32768.0, 0.0), 65535.0)}
         for s in range(n_e2e):
             t0 = time.perf_counter()
-            small, _ = read_overview(data, k, mode, device=0)
+            small, _ = read_overview(data, k, mode, device=0, **e2e_nd)
             t1 = time.perf_counter()
             big, _ = streaming_to_raster(data, device=0)
             t2 = time.perf_counter()
-            if s == 0 and not np.array_equal(small[:, :top], decimate(big[:, :2048], k, mode)):
+            if s == 0 and not np.array_equal(small[:, :top], decimate(big[:, :2048], k, mode, **e2e_nd)):
                 raise SystemExit("read_overview differs from resample.decimate of streaming_to_raster")
             del big
             if s >= min(1, args.warmup):
@@ -540,6 +575,7 @@ def main():
                         f"{len(wins)} tiles, whole raster",
             "factor": k, "resampling": mode, "output": [B, oh, ow], "tiles": len(wins), "frames": nfr,
             "steps": args.steps, "warmup": args.warmup, "equals_numpy_rule_on_checked_rows": True,
+            "nodata": args.nodata, "nodata_share_band0": nd_share,
             "device_ms": round(med(dev_ms), 3), "device_wall_ms": round(med(dev_wall), 3),
             "kernels_full": {n: round(med([q[i] for q in kern]), 3) for i, n in enumerate(names)},
             "decimated_wall_ms": round(med(dec_wall), 3),

@@ -10,9 +10,11 @@
 //     exactly when the flipped byte lies in a selected frame;
 //   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
+//     their nodata-aware entries (fra_resample_masked.hip: a nodata value the dtype does not admit included),
 //     the comparison (fra_compare, fra_decode_device_compare) and the statistics (fra_stats, fra_decode_device_stats),
 //     which returns before any GPU work.
 // usage: decode_host_check [--concat] file.flac ...
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -410,6 +412,98 @@ int main(int argc, char** argv) {
     { auto j = mj; j.dtype = FRA_U8; j.height = (1 << 28) + 1; j.width = (1 << 27) + 1; j.out_height = 2; j.out_width = 2; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "resample: uint8 average of 2^55 weights accepted"); }
     { auto j = mj; j.dtype = FRA_F64; j.height = (1 << 27) + 1; j.width = (1 << 26) + 1; j.out_height = 2; j.out_width = 2; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "resample: f64 average of 2^53 weights accepted"); }
     EXPECT(fra_resample_timing(nullptr) == FRA_E_INVALID, "resample timing: null accepted");
+  }
+  // ... and of the nodata-aware reads (fra_resample_masked.hip): the unmasked refusals, and a nodata value the dtype
+  // does not admit, before any GPU work
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;  // dst_dtype int32
+    dj.items = &di;
+    const fra_window r48{0, 0, 4, 8};
+    const double qnan = std::nan(""), inf_v = HUGE_VAL;
+    uint64_t filled[8];
+    auto bad_nodata = [&](int rc) { return rc == FRA_E_INVALID && g_msg.find("nodata") != std::string::npos; };
+    auto rs = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, int oh, int ow, int mode, fra_decoded* o, double nd) {
+      return fra_decode_device_resampled_masked(c, j, r, oh, ow, mode, o, nd, filled);
+    };
+    EXPECT(rs(nullptr, &dj, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: null ctx accepted");
+    EXPECT(rs(ctx, nullptr, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: null job accepted");
+    EXPECT(rs(ctx, &dj, nullptr, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: null roi accepted");
+    EXPECT(rs(ctx, &dj, &r48, 3, 5, 1, nullptr, 0.0) == FRA_E_INVALID, "masked resampled read: null infos accepted");
+    for (int n : {0, -1, 65537}) {
+      EXPECT(rs(ctx, &dj, &r48, n, 5, 1, inf, 0.0) == FRA_E_INVALID && g_msg.find("output size") != std::string::npos, "masked resampled read: out height %d accepted", n);
+      EXPECT(rs(ctx, &dj, &r48, 3, n, 1, inf, 0.0) == FRA_E_INVALID && g_msg.find("output size") != std::string::npos, "masked resampled read: out width %d accepted", n);
+    }
+    for (int m : {4, -1}) EXPECT(rs(ctx, &dj, &r48, 3, 5, m, inf, 0.0) == FRA_E_INVALID && g_msg.find("resampling") != std::string::npos, "masked resampled read: resampling %d accepted", m);
+    for (double nd : {0.5, 2147483648.0, -2147483649.0, qnan, inf_v, -inf_v})
+      for (int m : {0, 1, 2, 3}) EXPECT(bad_nodata(rs(ctx, &dj, &r48, 3, 5, m, inf, nd)), "masked resampled read: nodata %g of int32 accepted (mode %d)", nd, m);
+    for (int m : {0, 1, 2, 3}) { fra_window r = r48; r.height = 5; EXPECT(rs(ctx, &dj, &r, 3, 5, m, inf, 0.0) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "masked resampled read: uncovered row accepted (mode %d)", m); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "masked resampled read: uncovered column accepted"); }
+    { auto j = dj; j.nitems = 0; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(rs(ctx, &dj, &r, 3, 5, 1, inf, 0.0) == FRA_E_INVALID && g_msg.find("region of interest") != std::string::npos, "masked resampled read: zero-width roi accepted"); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst = nullptr; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: null dst accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(rs(ctx, &j, &r48, 3, 5, 1, inf, 0.0) == FRA_E_INVALID, "masked resampled read: dtype 9 accepted"); }
+    auto dec = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, int k, int mode, fra_decoded* o, double nd) {
+      return fra_decode_device_decimated_masked(c, j, r, k, mode, o, nd, filled);
+    };
+    EXPECT(dec(nullptr, &dj, &r48, 2, 1, inf, 0.0) == FRA_E_INVALID, "masked decimated read: null ctx accepted");
+    EXPECT(dec(ctx, nullptr, &r48, 2, 1, inf, 0.0) == FRA_E_INVALID, "masked decimated read: null job accepted");
+    EXPECT(dec(ctx, &dj, nullptr, 2, 1, inf, 0.0) == FRA_E_INVALID, "masked decimated read: null roi accepted");
+    EXPECT(dec(ctx, &dj, &r48, 2, 1, nullptr, 0.0) == FRA_E_INVALID, "masked decimated read: null infos accepted");
+    for (int k : {0, 1, 3, 128, -2}) EXPECT(dec(ctx, &dj, &r48, k, 1, inf, 0.0) == FRA_E_INVALID, "masked decimated read: factor %d accepted", k);
+    for (int m : {2, -1}) EXPECT(dec(ctx, &dj, &r48, 2, m, inf, 0.0) == FRA_E_INVALID, "masked decimated read: resampling %d accepted", m);
+    for (double nd : {0.5, 2147483648.0, qnan, inf_v}) EXPECT(bad_nodata(dec(ctx, &dj, &r48, 2, 1, inf, nd)), "masked decimated read: nodata %g of int32 accepted", nd);
+    { fra_window r = r48; r.height = 5; EXPECT(dec(ctx, &dj, &r, 2, 1, inf, 0.0) == FRA_E_INVALID && g_msg.find("do not cover") != std::string::npos, "masked decimated read: uncovered row accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(dec(ctx, &dj, &r, 2, 1, inf, 0.0) == FRA_E_INVALID && g_msg.find("region of interest") != std::string::npos, "masked decimated read: zero-width roi accepted"); }
+    { auto j = dj; j.dst = nullptr; EXPECT(dec(ctx, &j, &r48, 2, 1, inf, 0.0) == FRA_E_INVALID, "masked decimated read: null dst accepted"); }
+    { auto x = di; x.window = {0, 0, -8, 1}; auto j = dj; j.items = &x; EXPECT(dec(ctx, &j, &r48, 2, 1, inf, 0.0) == FRA_E_INVALID, "masked decimated read: capacity window accepted"); }
+    int32_t out[16];
+    fra_resample_job mj{};
+    mj.src = dst; mj.dtype = FRA_I32; mj.channels = 1; mj.height = 8; mj.width = 8;
+    mj.src_band_stride = 64; mj.src_row_stride = 8; mj.src_col_stride = 1;
+    mj.out_height = 3; mj.out_width = 5; mj.resampling = FRA_RESAMPLE_AVERAGE;
+    mj.dst = out; mj.dst_band_stride = 15; mj.dst_row_stride = 5; mj.dst_col_stride = 1;
+    EXPECT(fra_resample_masked(nullptr, &mj, 0.0, filled) == FRA_E_INVALID, "masked resample: null ctx accepted");
+    EXPECT(fra_resample_masked(ctx, nullptr, 0.0, filled) == FRA_E_INVALID, "masked resample: null job accepted");
+    { auto j = mj; j.src = nullptr; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked resample: null src accepted"); }
+    { auto j = mj; j.dst = nullptr; EXPECT(fra_resample_masked(ctx, &j, 0.0, nullptr) == FRA_E_INVALID, "masked resample: null dst accepted"); }
+    for (int n : {0, -1, 65537}) { auto j = mj; j.out_height = n; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked resample: out height %d accepted", n); }
+    for (int m : {4, -1}) { auto j = mj; j.resampling = m; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked resample: resampling %d accepted", m); }
+    { auto j = mj; j.dtype = 8; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked resample: dtype 8 accepted"); }
+    { auto j = mj; j.height = 0; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked resample: zero height accepted"); }
+    { auto j = mj; j.dst_row_stride = -1; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked resample: negative stride accepted"); }
+    { auto j = mj; j.height = 65537; j.width = 65537; j.out_height = 1; j.out_width = 1; EXPECT(fra_resample_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "masked resample: int32 average of 2^32 weights accepted"); }
+    // a nodata value per dtype: outside the range, fractional, inexact in f32, infinite; NaN for an integer dtype
+    struct { int dtype; double nd; } bad[] = {
+        {FRA_U8, 256.0}, {FRA_U8, -1.0}, {FRA_I8, 128.0}, {FRA_I8, -129.0}, {FRA_U16, 65536.0}, {FRA_I16, -32769.0},
+        {FRA_U32, 4294967296.0}, {FRA_I32, 2147483648.0}, {FRA_U16, 0.5}, {FRA_I32, qnan}, {FRA_U8, inf_v},
+        {FRA_F32, 0.1}, {FRA_F32, 16777217.0}, {FRA_F32, 1e300}, {FRA_F32, inf_v}, {FRA_F64, -inf_v}};
+    for (const auto& c : bad) {
+      auto j = mj; j.dtype = c.dtype;
+      EXPECT(bad_nodata(fra_resample_masked(ctx, &j, c.nd, filled)), "masked resample: nodata %g of dtype %d accepted", c.nd, c.dtype);
+      fra_decimate_job k{};
+      k.src = dst; k.dtype = c.dtype; k.channels = 1; k.height = 8; k.width = 8;
+      k.src_band_stride = 64; k.src_row_stride = 8; k.src_col_stride = 1;
+      k.factor = 2; k.resampling = FRA_RESAMPLE_AVERAGE;
+      k.dst = out; k.dst_band_stride = 16; k.dst_row_stride = 4; k.dst_col_stride = 1;
+      EXPECT(bad_nodata(fra_decimate_masked(ctx, &k, c.nd, nullptr)), "masked decimate: nodata %g of dtype %d accepted", c.nd, c.dtype);
+    }
+    fra_decimate_job kj{};
+    kj.src = dst; kj.dtype = FRA_I32; kj.channels = 1; kj.height = 8; kj.width = 8;
+    kj.src_band_stride = 64; kj.src_row_stride = 8; kj.src_col_stride = 1;
+    kj.factor = 2; kj.resampling = FRA_RESAMPLE_AVERAGE;
+    kj.dst = out; kj.dst_band_stride = 16; kj.dst_row_stride = 4; kj.dst_col_stride = 1;
+    EXPECT(fra_decimate_masked(nullptr, &kj, 0.0, filled) == FRA_E_INVALID, "masked decimate: null ctx accepted");
+    EXPECT(fra_decimate_masked(ctx, nullptr, 0.0, filled) == FRA_E_INVALID, "masked decimate: null job accepted");
+    { auto j = kj; j.src = nullptr; EXPECT(fra_decimate_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked decimate: null src accepted"); }
+    for (int k : {0, 1, 3, 128}) { auto j = kj; j.factor = k; EXPECT(fra_decimate_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked decimate: factor %d accepted", k); }
+    { auto j = kj; j.resampling = 2; EXPECT(fra_decimate_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked decimate: resampling 2 accepted"); }
+    { auto j = kj; j.dtype = 8; EXPECT(fra_decimate_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked decimate: dtype 8 accepted"); }
+    { auto j = kj; j.height = 0; EXPECT(fra_decimate_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked decimate: zero height accepted"); }
+    { auto j = kj; j.dst_row_stride = -1; EXPECT(fra_decimate_masked(ctx, &j, 0.0, filled) == FRA_E_INVALID, "masked decimate: negative stride accepted"); }
+    EXPECT(fra_resample_masked_timing(nullptr) == FRA_E_INVALID, "masked resample timing: null accepted");
   }
   // ... and of the comparison (fra_compare.hip): refused before any GPU work
   {
