@@ -17,8 +17,10 @@
 // k_compare_fold: one workgroup per band.  Counts, extremes and the integer sums are folded by the same tree (they do not
 // depend on the order); the two f64 sums are added strictly in partial order.  Equal inputs and layout give equal bytes.
 //
-// fra_decode_device_compare calls the windowed read (fra_decode_device_window) as any caller would, with a device buffer
-// of the region as its destination, exactly as fra_decode_device_decimated does: same kernels, refusals and messages.
+// This unit holds the kernels, their launch and the 2^32-pixel refusal.  Shared with the other region-reducing units
+// (fra_region.h): the dtype and layout refusal, what is left to the windowed read (the variant that ignores the job's
+// destination), the staging of host rasters, the region decoded by fra_decode_device_window as any caller would, and
+// the timed launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,11 +34,11 @@
 #include "fra_host.h"
 #include "fra_region.h"
 
-extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
-
 static_assert(sizeof(fra_compare_band) == 128, "fra_compare_band is 128 bytes");
 
 namespace {
+
+using namespace fra_region;
 
 constexpr uint64_t kNone = ~0ull;  // no differing pixel
 
@@ -301,23 +303,24 @@ constexpr int64_t kMaxPixels = (int64_t)1 << 32;  // per band: sum_abs stays ins
 constexpr int64_t kBlocks = 4096;                 // workgroups aimed at: 16 per CU
 constexpr int64_t kMinSlots = 1024;               // slots of a workgroup, at least (4 per thread), rows permitting
 
-// elements addressed from element 0 by a (channels, rows, cols) raster of the given strides
-int64_t extent_of(int64_t channels, int64_t rows, int64_t cols, int64_t bs, int64_t rs, int64_t cs) {
-  return (channels - 1) * bs + (rows - 1) * rs + (cols - 1) * cs + 1;
+int too_many_pixels(int64_t h, int64_t w) {
+  if (h * w <= kMaxPixels) return FRA_OK;
+  return fra_internal_set_error(FRA_E_INVALID, "more than 2^32 pixels per band (%lld x %lld) are not compared in one call",
+                                (long long)h, (long long)w);
 }
 
-bool aligned16(const void* p, int64_t bs, int64_t rs, int64_t cs, size_t es) {
-  return cs == 1 && ((uintptr_t)p % 16) == 0 && (((uint64_t)rs * es) % 16) == 0 && (((uint64_t)bs * es) % 16) == 0;
-}
-
-// k_compare + k_compare_fold over device rasters between two events, the reports to `bands` on the host; enqueues only
-// (the partials and the device reports belong to `sc`)
-int launch_compare(int dtype, int channels, CmpArgs g, const void* d_a, const void* d_b, HipArena& sc, hipEvent_t e0,
-                   hipEvent_t e1, hipStream_t s, fra_compare_band* bands) {
+// k_compare + k_compare_fold over two (channels, h, w) device rasters, timed, and the reports to `bands` on the host
+// (the partials and the device reports belong to the call)
+int run_compare(Call& c, int dtype, int channels, int32_t h, int32_t w, const void* d_a, const Strides& sa,
+                const void* d_b, const Strides& sb, fra_compare_band* bands) {
   const size_t es = (size_t)elem_size(dtype);
   const int64_t V = 16 / (int64_t)es;
+  CmpArgs g{};
   g.a = d_a, g.b = d_b;
-  g.vec = aligned16(d_a, g.abs_, g.ars, g.acs, es) && aligned16(d_b, g.bbs, g.brs, g.bcs, es);
+  g.abs_ = sa.band, g.ars = sa.row, g.acs = sa.col;
+  g.bbs = sb.band, g.brs = sb.row, g.bcs = sb.col;
+  g.h = h, g.w = w;
+  g.vec = aligned16(d_a, sa, es) && aligned16(d_b, sb, es);
   const int64_t nvec = ((int64_t)g.w + V - 1) / V;
   int64_t rpb = std::max<int64_t>(((int64_t)g.h * channels + kBlocks - 1) / kBlocks, (kMinSlots + nvec - 1) / nvec);
   rpb = std::min<int64_t>(rpb, std::max<int64_t>(1, ((int64_t)1 << 31) / nvec));  // a chunk's slots are counted in 32 bits
@@ -327,44 +330,25 @@ int launch_compare(int dtype, int channels, CmpArgs g, const void* d_a, const vo
   if (grid > INT32_MAX) return fra_internal_set_error(FRA_E_INVALID, "the raster is too large for one comparison");
   g.nvec = (uint32_t)nvec, g.rpb = (uint32_t)rpb, g.nchunks = (uint32_t)nchunks;
   g.step_rows = (uint32_t)(256 / nvec), g.step_vecs = (uint32_t)(256 % nvec);
-  HIPCHK(sc.alloc(&g.partials, (size_t)grid * sizeof(Partial)));
+  HIPCHK(c.sc.alloc(&g.partials, (size_t)grid * sizeof(Partial)));
   fra_compare_band* d_bands = nullptr;
-  HIPCHK(sc.alloc(&d_bands, (size_t)channels * sizeof(fra_compare_band)));
-  HIPCHK(hipEventRecord(e0, s));
-  switch (dtype) {
-    case FRA_U8: hipLaunchKernelGGL(k_compare<uint8_t>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_I8: hipLaunchKernelGGL(k_compare<int8_t>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_U16: hipLaunchKernelGGL(k_compare<uint16_t>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_I16: hipLaunchKernelGGL(k_compare<int16_t>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_U32: hipLaunchKernelGGL(k_compare<uint32_t>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_I32: hipLaunchKernelGGL(k_compare<int32_t>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_F32: hipLaunchKernelGGL(k_compare<float>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-    case FRA_F64: hipLaunchKernelGGL(k_compare<double>, dim3((unsigned)grid), dim3(256), 0, s, g); break;
-  }
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_compare_fold, dim3((unsigned)channels), dim3(256), 0, s, (const Partial*)g.partials, g.nchunks,
-                     g.h, g.w, (int32_t)(dtype == FRA_F32 || dtype == FRA_F64), d_bands);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, s));
-  HIPCHK(hipMemcpyAsync(bands, d_bands, (size_t)channels * sizeof(fra_compare_band), hipMemcpyDeviceToHost, s));
-  return FRA_OK;
-}
-
-int too_many_pixels(int64_t h, int64_t w) {
-  if (h * w <= kMaxPixels) return FRA_OK;
-  return fra_internal_set_error(FRA_E_INVALID, "more than 2^32 pixels per band (%lld x %lld) are not compared in one call",
-                                (long long)h, (long long)w);
-}
-
-// a host raster copied to the device from its element 0 to the last one addressed; a device raster as it is
-int stage(HipArena& sc, hipStream_t s, const void* p, int on_device, size_t bytes, const void** d) {
-  *d = p;
-  if (on_device) return FRA_OK;
-  void* q = nullptr;
-  HIPCHK(sc.alloc(&q, bytes));
-  HIPCHK(hipMemcpyAsync(q, p, bytes, hipMemcpyHostToDevice, s));
-  *d = q;
-  return FRA_OK;
+  HIPCHK(c.sc.alloc(&d_bands, (size_t)channels * sizeof(fra_compare_band)));
+  return timed(
+      c, &g_compare_ms,
+      [&]() -> int {
+        with_dtype(dtype, [&](auto t) {
+          hipLaunchKernelGGL(k_compare<decltype(t)>, dim3((unsigned)grid), dim3(256), 0, c.s, g);
+        });
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_compare_fold, dim3((unsigned)channels), dim3(256), 0, c.s, (const Partial*)g.partials,
+                           g.nchunks, g.h, g.w, (int32_t)(dtype == FRA_F32 || dtype == FRA_F64), d_bands);
+        HIPCHK(hipGetLastError());
+        return FRA_OK;
+      },
+      [&]() -> int {
+        HIPCHK(hipMemcpyAsync(bands, d_bands, (size_t)channels * sizeof(fra_compare_band), hipMemcpyDeviceToHost, c.s));
+        return FRA_OK;
+      });
 }
 
 }  // namespace
@@ -379,39 +363,17 @@ FRA_API int fra_compare_timing(float* ms) {
 
 FRA_API int fra_compare(fra_ctx* ctx, const fra_compare_job* job, fra_compare_band* bands) {
   if (!ctx || !job || !bands || !job->a || !job->b) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  if (job->dtype < FRA_U8 || job->dtype > FRA_F64) return fra_internal_set_error(FRA_E_INVALID, "bad dtype %d", job->dtype);
-  if (job->channels < 1 || job->height < 1 || job->width < 1 || job->a_band_stride < 0 || job->a_row_stride < 0 ||
-      job->a_col_stride < 0 || job->b_band_stride < 0 || job->b_row_stride < 0 || job->b_col_stride < 0)
-    return fra_internal_set_error(FRA_E_INVALID, "bad raster layout (%d x %d x %d)", job->channels, job->height,
-                                  job->width);
-  if (const int rc = too_many_pixels(job->height, job->width)) return rc;
-  CmpArgs g{};
-  g.abs_ = job->a_band_stride, g.ars = job->a_row_stride, g.acs = job->a_col_stride;
-  g.bbs = job->b_band_stride, g.brs = job->b_row_stride, g.bcs = job->b_col_stride;
-  g.h = job->height, g.w = job->width;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // staged rasters, partials, reports and events of this call, released on every path
+  const Strides sa{job->a_band_stride, job->a_row_stride, job->a_col_stride};
+  const Strides sb{job->b_band_stride, job->b_row_stride, job->b_col_stride};
+  const int32_t ch = job->channels, h = job->height, w = job->width;
+  if (const int rc = check_raster(job->dtype, ch, h, w, sa, sb)) return rc;
+  if (const int rc = too_many_pixels(h, w)) return rc;
+  Call c(ctx);
   const size_t es = (size_t)elem_size(job->dtype);
   const void *d_a = nullptr, *d_b = nullptr;
-  if (const int rc = stage(sc, s, job->a, job->a_on_device,
-                           (size_t)extent_of(job->channels, g.h, g.w, g.abs_, g.ars, g.acs) * es, &d_a))
-    return rc;
-  if (const int rc = stage(sc, s, job->b, job->b_on_device,
-                           (size_t)extent_of(job->channels, g.h, g.w, g.bbs, g.brs, g.bcs) * es, &d_b))
-    return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_compare(job->dtype, job->channels, g, d_a, d_b, sc, e0, e1, s, bands)) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_compare_ms = ms;
-  return FRA_OK;
+  if (const int rc = stage_in(c, job->a, job->a_on_device, (size_t)extent_of(ch, h, w, sa) * es, &d_a)) return rc;
+  if (const int rc = stage_in(c, job->b, job->b_on_device, (size_t)extent_of(ch, h, w, sb) * es, &d_b)) return rc;
+  return run_compare(c, job->dtype, ch, h, w, d_a, sa, d_b, sb, bands);
 }
 
 FRA_API int fra_decode_device_compare(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, const void* ref,
@@ -421,52 +383,20 @@ FRA_API int fra_decode_device_compare(fra_ctx* ctx, const fra_decode_job* job, c
   if (ref_band_stride < 0 || ref_row_stride < 0 || ref_col_stride < 0)
     return fra_internal_set_error(FRA_E_INVALID, "bad reference layout (strides %lld, %lld, %lld)",
                                   (long long)ref_band_stride, (long long)ref_row_stride, (long long)ref_col_stride);
-  // what the windowed read refuses at once is left to it (it does so before any GPU work, with its own message)
-  const bool refer = roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
-                     (job->nitems && !job->items) || (!job->data && job->len) || job->dst_dtype < FRA_U8 ||
-                     job->dst_dtype > FRA_F64 || job->denorm < FRA_DENORM_NONE || job->denorm > FRA_DENORM_PCM16 ||
-                     (job->denorm == FRA_DENORM_NONE && job->dst_dtype != FRA_I16 && job->dst_dtype != FRA_I32) ||
-                     job->channels < 1 || job->channels > 8 || (job->flags & FRA_DECODE_CONCAT) ||
-                     !fra_region::item_windows_ok(job);
-  if (refer) {
-    fra_decode_job inner = *job;  // the job's own dst and strides are ignored: the region goes to a buffer of this call
-    inner.dst_on_device = 1;
-    inner.band_stride = 0, inner.row_stride = 0, inner.col_stride = 1;
-    inner.dst = (void*)bands;  // any non-null pointer: the call returns before it is looked at
-    const int rc = fra_decode_device_window(ctx, &inner, roi, infos);
-    return rc ? rc : fra_internal_set_error(FRA_E_INVALID, "bad arguments");
-  }
-  const int64_t h = roi->height, w = roi->width;
+  if (left_to_window_read_no_dst(job, roi)) return refer_to_window_read(ctx, job, roi, infos, true);
+  const int32_t h = roi->height, w = roi->width;
   if (const int rc = too_many_pixels(h, w)) return rc;
-  if (const int rc = fra_region::check_cover(job, roi)) return rc;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // the region buffer, the staged reference, partials, reports and events: released on every path
+  if (const int rc = check_cover(job, roi)) return rc;
+  Call c(ctx);
   void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
   int64_t rs = 0;
-  if (const int rc = fra_region::decode(ctx, job, roi, infos, sc, &d_region, &rs)) return rc;
-  const size_t es = (size_t)elem_size(job->dst_dtype);
-  CmpArgs g{};
-  g.abs_ = h * rs, g.ars = rs, g.acs = 1;
-  g.bbs = ref_band_stride, g.brs = ref_row_stride, g.bcs = ref_col_stride;
-  g.h = (int32_t)h, g.w = (int32_t)w;
-
+  if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
+  const Strides sa{(int64_t)h * rs, rs, 1}, sb{ref_band_stride, ref_row_stride, ref_col_stride};
   const void* d_ref = nullptr;
-  if (const int rc = stage(sc, s, ref, ref_on_device,
-                           (size_t)extent_of(job->channels, h, w, g.bbs, g.brs, g.bcs) * es, &d_ref))
+  if (const int rc = stage_in(c, ref, ref_on_device,
+                              (size_t)extent_of(job->channels, h, w, sb) * (size_t)elem_size(job->dst_dtype), &d_ref))
     return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_compare(job->dst_dtype, job->channels, g, d_region, d_ref, sc, e0, e1, s, bands)) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_compare_ms = ms;
-  return FRA_OK;
+  return run_compare(c, job->dst_dtype, job->channels, h, w, d_region, sa, d_ref, sb, bands);
 }
 
 }  // extern "C"

@@ -17,12 +17,12 @@
 // (band, block row, column segment); all indices are 64-bit.
 // k_decimate<T, 0>: one thread per output element, one load each.
 //
-// fra_decode_device_decimated calls the windowed read (fra_decode_device_window) as any caller would, with a device
-// buffer of the region as its destination: same kernels, same refusals, same messages.  fra_decode_dev.hip knows
-// nothing of this unit.
+// This unit holds the kernel, its launch and the order of its entries' refusals.  Shared: the host scaffold of the
+// five region-reducing units (fra_region.h: the dtype and layout refusal, what is left to the windowed read, staging,
+// the region decoded by fra_decode_device_window as any caller would, the timed launch), and with the resampling
+// units AccOf, log2_factor and check_factor (fra_resample.h).  fra_decode_dev.hip knows nothing of this unit.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -31,10 +31,12 @@
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
 #include "fra_region.h"
-
-extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
+#include "fra_resample.h"
 
 namespace {
+
+using namespace fra_region;
+using fra_rs::AccOf;
 
 struct DecimArgs {
   const void* src;
@@ -46,9 +48,6 @@ struct DecimArgs {
   int32_t nseg;  // workgroups per block row (average) / per output row (nearest)
   int32_t vec;   // 16-byte row loads are aligned (scs == 1; base, row and band strides multiples of 16 bytes)
 };
-
-template <typename T>
-struct AccOf { using type = std::conditional_t<std::is_floating_point<T>::value, double, long long>; };
 
 template <typename A>
 __device__ inline A lane_xor(A v, int m) {
@@ -146,51 +145,28 @@ void launch_t(int mode, unsigned grid, hipStream_t s, const DecimArgs& a) {
   else hipLaunchKernelGGL((k_decimate<T, 1>), dim3(grid), dim3(256), 0, s, a);
 }
 
-int log2_factor(int k) {
-  for (int l = 1; l <= 6; l++)
-    if (k == (1 << l)) return l;
-  return 0;
-}
-
-// k_decimate over device buffers between two events; enqueues only
-int launch_decimate(int dtype, int mode, int channels, DecimArgs a, const void* d_src, void* d_dst, hipEvent_t e0,
-                    hipEvent_t e1, hipStream_t s) {
-  const size_t es = (size_t)elem_size(dtype);
-  a.src = d_src;
-  a.dst = d_dst;
-  a.vec = a.scs == 1 && ((uintptr_t)d_src % 16) == 0 && (((uint64_t)a.srs * es) % 16) == 0 &&
-          (((uint64_t)a.sbs * es) % 16) == 0;
-  const int64_t per_row = mode == FRA_RESAMPLE_NEAREST ? a.ow : ((int64_t)a.w + (16 / (int64_t)es) - 1) / (16 / (int64_t)es);
+// k_decimate by `factor` over `io`, timed, and the destination copied back (`r` holds the sizes)
+int launch_decimate(Call& c, const Io& io, int dtype, int mode, int channels, const fra_rs::ResampleArgs& r, int factor) {
+  const int64_t V = 16 / (int64_t)elem_size(dtype);
+  DecimArgs a{};
+  a.src = io.src, a.dst = io.out.dev;
+  a.sbs = io.ss.band, a.srs = io.ss.row, a.scs = io.ss.col;
+  a.dbs = io.ds.band, a.drs = io.ds.row, a.dcs = io.ds.col;
+  a.h = r.h, a.w = r.w, a.oh = r.oh, a.ow = r.ow;
+  a.k = factor, a.logk = fra_rs::log2_factor(factor);
+  a.vec = aligned16(io.src, io.ss, (size_t)elem_size(dtype));
+  const int64_t per_row = mode == FRA_RESAMPLE_NEAREST ? a.ow : ((int64_t)a.w + V - 1) / V;
   a.nseg = (int32_t)((per_row + 255) / 256);
   const int64_t grid = (int64_t)channels * a.oh * a.nseg;
   if (grid > INT32_MAX) return fra_internal_set_error(FRA_E_INVALID, "the raster is too large for one decimation");
-  HIPCHK(hipEventRecord(e0, s));
-  switch (dtype) {
-    case FRA_U8: launch_t<uint8_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_I8: launch_t<int8_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_U16: launch_t<uint16_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_I16: launch_t<int16_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_U32: launch_t<uint32_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_I32: launch_t<int32_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_F32: launch_t<float>(mode, (unsigned)grid, s, a); break;
-    case FRA_F64: launch_t<double>(mode, (unsigned)grid, s, a); break;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, s));
-  return FRA_OK;
-}
-
-int check_factor(int32_t factor, int32_t resampling) {
-  if (!log2_factor(factor))
-    return fra_internal_set_error(FRA_E_INVALID, "the decimation factor must be 2, 4, 8, 16, 32 or 64 (got %d)", factor);
-  if (resampling != FRA_RESAMPLE_NEAREST && resampling != FRA_RESAMPLE_AVERAGE)
-    return fra_internal_set_error(FRA_E_INVALID, "unknown resampling %d (0 nearest, 1 average)", resampling);
-  return FRA_OK;
-}
-
-// elements addressed from element 0 by a (channels, rows, cols) raster of the given strides
-int64_t extent_of(int64_t channels, int64_t rows, int64_t cols, int64_t bs, int64_t rs, int64_t cs) {
-  return (channels - 1) * bs + (rows - 1) * rs + (cols - 1) * cs + 1;
+  return timed(
+      c, &g_decimate_ms,
+      [&]() -> int {
+        with_dtype(dtype, [&](auto t) { launch_t<decltype(t)>(mode, (unsigned)grid, c.s, a); });
+        HIPCHK(hipGetLastError());
+        return FRA_OK;
+      },
+      [&] { return copy_back(c, io.out); });
 }
 
 }  // namespace
@@ -205,102 +181,26 @@ FRA_API int fra_decimate_timing(float* ms) {
 
 FRA_API int fra_decimate(fra_ctx* ctx, const fra_decimate_job* job) {
   if (!ctx || !job || !job->src || !job->dst) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  if (const int rc = check_factor(job->factor, job->resampling)) return rc;
-  if (job->dtype < FRA_U8 || job->dtype > FRA_F64) return fra_internal_set_error(FRA_E_INVALID, "bad dtype %d", job->dtype);
-  if (job->channels < 1 || job->height < 1 || job->width < 1 || job->src_band_stride < 0 || job->src_row_stride < 0 ||
-      job->src_col_stride < 0 || job->dst_band_stride < 0 || job->dst_row_stride < 0 || job->dst_col_stride < 0)
-    return fra_internal_set_error(FRA_E_INVALID, "bad raster layout (%d x %d x %d)", job->channels, job->height,
-                                  job->width);
-  const int k = job->factor;
-  DecimArgs a{};
-  a.sbs = job->src_band_stride, a.srs = job->src_row_stride, a.scs = job->src_col_stride;
-  a.dbs = job->dst_band_stride, a.drs = job->dst_row_stride, a.dcs = job->dst_col_stride;
-  a.h = job->height, a.w = job->width;
-  a.oh = (int32_t)(((int64_t)a.h + k - 1) / k), a.ow = (int32_t)(((int64_t)a.w + k - 1) / k);
-  a.k = k, a.logk = log2_factor(k);
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // staging buffers and events of this call, released on every path
-  const size_t es = (size_t)elem_size(job->dtype);
-  const size_t src_bytes = (size_t)extent_of(job->channels, a.h, a.w, a.sbs, a.srs, a.scs) * es;
-  const size_t dst_bytes = (size_t)extent_of(job->channels, a.oh, a.ow, a.dbs, a.drs, a.dcs) * es;
-  const void* d_src = job->src;
-  void* d_dst = job->dst;
-  if (!job->src_on_device) {
-    void* p = nullptr;
-    HIPCHK(sc.alloc(&p, src_bytes));
-    HIPCHK(hipMemcpyAsync(p, job->src, src_bytes, hipMemcpyHostToDevice, s));
-    d_src = p;
-  }
-  if (!job->dst_on_device) {  // staged whole, so that the elements between the outputs keep the caller's values
-    HIPCHK(sc.alloc(&d_dst, dst_bytes));
-    HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_decimate(job->dtype, job->resampling, job->channels, a, d_src, d_dst, e0, e1, s)) return rc;
-  if (!job->dst_on_device) HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_decimate_ms = ms;
-  return FRA_OK;
+  RasterJob r = raster_job(*job);
+  fra_rs::ResampleArgs sizes{};
+  if (const int rc = fra_rs::check_factor(r.h, r.w, job->factor, job->resampling, &sizes)) return rc;
+  if (const int rc = check_raster(r)) return rc;
+  r.oh = sizes.oh, r.ow = sizes.ow;
+  return run_raster(ctx, r, [&](Call& c, const Io& io) {
+    return launch_decimate(c, io, r.dtype, job->resampling, r.channels, sizes, job->factor);
+  });
 }
 
 FRA_API int fra_decode_device_decimated(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, int32_t factor,
                                         int32_t resampling, fra_decoded* infos) {
   if (!ctx || !job || !roi || !infos) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  if (const int rc = check_factor(factor, resampling)) return rc;
-  // what the windowed read refuses at once is left to it (it does so before any GPU work, with its own message)
-  const bool refer = roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
-                     (job->nitems && !job->items) || !job->dst || job->dst_dtype < FRA_U8 || job->dst_dtype > FRA_F64 ||
-                     job->channels < 1 || job->channels > 8 || job->band_stride < 0 || job->row_stride < 0 ||
-                     job->col_stride < 0 || (job->flags & FRA_DECODE_CONCAT) || !fra_region::item_windows_ok(job);
-  if (refer) {
-    const int rc = fra_decode_device_window(ctx, job, roi, infos);
-    return rc ? rc : fra_internal_set_error(FRA_E_INVALID, "bad arguments");
-  }
-  const int64_t h = roi->height, w = roi->width;
-  if (const int rc = fra_region::check_cover(job, roi)) return rc;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // the region buffer, the staged output and the events: released on every path
-  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
-  int64_t rs = 0;
-  if (const int rc = fra_region::decode(ctx, job, roi, infos, sc, &d_region, &rs)) return rc;
-
-  const int k = factor;
-  DecimArgs a{};
-  const size_t es = (size_t)elem_size(job->dst_dtype);
-  a.sbs = h * rs, a.srs = rs, a.scs = 1;
-  a.dbs = job->band_stride, a.drs = job->row_stride, a.dcs = job->col_stride;
-  a.h = (int32_t)h, a.w = (int32_t)w;
-  a.oh = (int32_t)((h + k - 1) / k), a.ow = (int32_t)((w + k - 1) / k);
-  a.k = k, a.logk = log2_factor(k);
-
-  const size_t dst_bytes = (size_t)extent_of(job->channels, a.oh, a.ow, a.dbs, a.drs, a.dcs) * es;
-  void* d_dst = job->dst;
-  if (!job->dst_on_device) {
-    HIPCHK(sc.alloc(&d_dst, dst_bytes));
-    HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_decimate(job->dst_dtype, resampling, job->channels, a, d_region, d_dst, e0, e1, s)) return rc;
-  if (!job->dst_on_device) HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_decimate_ms = ms;
-  return FRA_OK;
+  fra_rs::ResampleArgs sizes{};
+  if (const int rc = fra_rs::check_factor(roi->height, roi->width, factor, resampling, &sizes)) return rc;
+  if (left_to_window_read(job, roi)) return refer_to_window_read(ctx, job, roi, infos, false);
+  if (const int rc = check_cover(job, roi)) return rc;
+  return run_region(ctx, job, roi, infos, sizes.oh, sizes.ow, [&](Call& c, const Io& io) {
+    return launch_decimate(c, io, job->dst_dtype, resampling, job->channels, sizes, factor);
+  });
 }
 
 }  // extern "C"

@@ -1,6 +1,15 @@
-// fra_region.h -- what the reads that reduce a decoded region on the device share (fra_decimate.hip, fra_resample.hip,
-// fra_compare.hip, fra_stats.hip): the check that the items cover the region, and the windowed read (fra_decode_device_window, called as
-// any caller would: same kernels, refusals and messages) into a per-call device buffer of the region.
+// fra_region.h -- the host scaffold of the five units that reduce a raster or a decoded region on the device
+// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip).  Once each:
+//   * the refusals they share: a bad dtype or raster layout (check_raster), items that do not cover the region
+//     (check_cover), and what is left to the windowed read, which refuses it with its own message
+//     (left_to_window_read, left_to_window_read_no_dst, refer_to_window_read);
+//   * the dtype dispatch (with_dtype), the extent of a strided raster (extent_of) and the test for aligned 16-byte
+//     row loads (aligned16);
+//   * a call's stream and arena (Call), the staging of host buffers (stage_in, stage_out, copy_back), the kernels'
+//     time between two events (timed), and the two frames around a unit's kernels: a raster job (run_raster) and a
+//     region decoded by the windowed read (fra_decode_device_window, called as any caller would: same kernels,
+//     refusals and messages) into a per-call device buffer (decode, run_region).
+// Every function is inline: the units are separate translation units of one library and of one check program.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -8,7 +17,49 @@
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
 
+#ifdef __HIPCC__
+// the context's device and stream (fra_api.hip)
+extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
+#endif
+
 namespace fra_region {
+
+struct Strides { int64_t band, row, col; };  // in elements
+
+// elements addressed from element 0 by a (channels, rows, cols) raster of the given strides
+inline int64_t extent_of(int64_t channels, int64_t rows, int64_t cols, const Strides& s) {
+  return (channels - 1) * s.band + (rows - 1) * s.row + (cols - 1) * s.col + 1;
+}
+
+// 16-byte row loads are aligned: column stride 1; base, row and band strides multiples of 16 bytes
+inline bool aligned16(const void* p, const Strides& s, size_t es) {
+  return s.col == 1 && ((uintptr_t)p % 16) == 0 && (((uint64_t)s.row * es) % 16) == 0 &&
+         (((uint64_t)s.band * es) % 16) == 0;
+}
+
+// FRA_E_INVALID for a dtype outside fra_dtype, then for a (channels, h, w) raster without a pixel or a negative
+// stride in either of two layouts (a unit with one layout passes it twice)
+inline int check_raster(int dtype, int32_t channels, int32_t h, int32_t w, const Strides& a, const Strides& b) {
+  if (dtype < FRA_U8 || dtype > FRA_F64) return fra_internal_set_error(FRA_E_INVALID, "bad dtype %d", dtype);
+  if (channels < 1 || h < 1 || w < 1 || a.band < 0 || a.row < 0 || a.col < 0 || b.band < 0 || b.row < 0 || b.col < 0)
+    return fra_internal_set_error(FRA_E_INVALID, "bad raster layout (%d x %d x %d)", channels, h, w);
+  return FRA_OK;
+}
+
+// f(T{}) for the element type T of a checked dtype
+template <typename F>
+inline void with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case FRA_U8: f(uint8_t{}); break;
+    case FRA_I8: f(int8_t{}); break;
+    case FRA_U16: f(uint16_t{}); break;
+    case FRA_I16: f(int16_t{}); break;
+    case FRA_U32: f(uint32_t{}); break;
+    case FRA_I32: f(int32_t{}); break;
+    case FRA_F32: f(float{}); break;
+    case FRA_F64: f(double{}); break;
+  }
+}
 
 // FRA_E_INVALID unless the intersections of the items with roi add up to roi's area (the item windows and roi are
 // non-negative: the caller has left everything else to the windowed read)
@@ -38,7 +89,101 @@ inline bool item_windows_ok(const fra_decode_job* job) {
   return true;
 }
 
+// What the windowed read refuses at once (before any GPU work, with its own message) is left to it: a unit that finds
+// one of these refers the call to it (refer_to_window_read).  The part that does not depend on a destination ...
+inline bool region_left_to_window_read(const fra_decode_job* job, const fra_window* roi) {
+  return roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
+         (job->nitems && !job->items) || job->dst_dtype < FRA_U8 || job->dst_dtype > FRA_F64 || job->channels < 1 ||
+         job->channels > 8 || (job->flags & FRA_DECODE_CONCAT) || !item_windows_ok(job);
+}
+// ... for a read into the job's destination (the decimated and resampled reads)
+inline bool left_to_window_read(const fra_decode_job* job, const fra_window* roi) {
+  return region_left_to_window_read(job, roi) || !job->dst || job->band_stride < 0 || job->row_stride < 0 ||
+         job->col_stride < 0;
+}
+// ... and for a read that ignores the job's destination and strides (the comparison and the statistics)
+inline bool left_to_window_read_no_dst(const fra_decode_job* job, const fra_window* roi) {
+  return region_left_to_window_read(job, roi) || (!job->data && job->len) || job->denorm < FRA_DENORM_NONE ||
+         job->denorm > FRA_DENORM_PCM16 ||
+         (job->denorm == FRA_DENORM_NONE && job->dst_dtype != FRA_I16 && job->dst_dtype != FRA_I32);
+}
+
+// the windowed read's code for a call that was left to it, or "bad arguments"; `needs_dummy_dst`: the job's own dst
+// and strides are ignored
+inline int refer_to_window_read(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos,
+                                bool needs_dummy_dst) {
+  fra_decode_job inner = *job;
+  if (needs_dummy_dst) {
+    inner.dst = (void*)infos;  // any non-null pointer: the call returns before it is looked at
+    inner.dst_on_device = 1;
+    inner.band_stride = 0, inner.row_stride = 0, inner.col_stride = 1;
+  }
+  const int rc = fra_decode_device_window(ctx, &inner, roi, infos);
+  return rc ? rc : fra_internal_set_error(FRA_E_INVALID, "bad arguments");
+}
+
 #ifdef __HIPCC__
+// A call's stream, on its context's device, and the owner of what the call makes: staging buffers, partials, reports
+// and events are released on every path.
+struct Call {
+  hipStream_t s = nullptr;
+  HipArena sc;
+  explicit Call(fra_ctx* ctx) {
+    int device = 0;
+    fra_internal_ctx_stream(ctx, &device, &s);
+    (void)hipSetDevice(device);
+  }
+};
+
+// a host raster copied to the device from its element 0 to the last one addressed; a device raster as it is
+inline int stage_in(Call& c, const void* p, int on_device, size_t bytes, const void** d) {
+  *d = p;
+  if (on_device) return FRA_OK;
+  void* q = nullptr;
+  HIPCHK(c.sc.alloc(&q, bytes));
+  HIPCHK(hipMemcpyAsync(q, p, bytes, hipMemcpyHostToDevice, c.s));
+  *d = q;
+  return FRA_OK;
+}
+
+// A destination the kernels write through `dev`.  A host destination is staged whole, so that the elements between
+// the outputs keep the caller's values, and copied back whole after the kernels.
+struct StagedOut {
+  void* dev = nullptr;
+  void* host = nullptr;  // null: a device destination, nothing to copy back
+  size_t bytes = 0;
+};
+inline int stage_out(Call& c, void* p, int on_device, size_t bytes, StagedOut* o) {
+  *o = StagedOut{p, nullptr, bytes};
+  if (on_device) return FRA_OK;
+  o->host = p;
+  HIPCHK(c.sc.alloc(&o->dev, bytes));
+  HIPCHK(hipMemcpyAsync(o->dev, p, bytes, hipMemcpyHostToDevice, c.s));
+  return FRA_OK;
+}
+inline int copy_back(Call& c, const StagedOut& o) {
+  if (o.host) HIPCHK(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c.s));
+  return FRA_OK;
+}
+
+// `enqueue` (the kernels) between two events of the call's arena, then `after` (the copies to the host), then the
+// stream is waited for; *ms: the kernels' time.  Both return a code and enqueue only.
+template <typename Enqueue, typename After>
+inline int timed(Call& c, float* ms, Enqueue&& enqueue, After&& after) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPCHK(c.sc.event(&e0, hipEventDefault));
+  HIPCHK(c.sc.event(&e1, hipEventDefault));
+  HIPCHK(hipEventRecord(e0, c.s));
+  if (const int rc = enqueue()) return rc;
+  HIPCHK(hipEventRecord(e1, c.s));
+  if (const int rc = after()) return rc;
+  HIPCHK(hipStreamSynchronize(c.s));
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, e0, e1);
+  *ms = t;
+  return FRA_OK;
+}
+
 // roi at full resolution in job->dst_dtype into device memory of `sc`: band-planar, rows of *row_stride elements that
 // start on 16-byte boundaries (for the vector loads of the kernel that follows), bands of roi->height rows.  The job's
 // own dst and strides are not looked at.  Synchronous; the windowed read's scratch is gone on return.
@@ -57,6 +202,62 @@ inline int decode(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi
   inner.col_stride = 1;
   *row_stride = rs;
   return fra_decode_device_window(ctx, &inner, roi, infos);
+}
+
+// a checked raster job: a (channels, h, w) source and a (channels, oh, ow) destination of one dtype
+struct RasterJob {
+  const void* src;
+  int32_t src_on_device, dtype, channels, h, w;
+  Strides ss;
+  void* dst;
+  int32_t dst_on_device, oh, ow;
+  Strides ds;
+};
+// the fields fra_decimate_job and fra_resample_job share; the unit works out the output size
+template <typename Job>
+inline RasterJob raster_job(const Job& j) {
+  return RasterJob{j.src, j.src_on_device, j.dtype, j.channels, j.height, j.width,
+                   Strides{j.src_band_stride, j.src_row_stride, j.src_col_stride},
+                   j.dst, j.dst_on_device, 0, 0, Strides{j.dst_band_stride, j.dst_row_stride, j.dst_col_stride}};
+}
+inline int check_raster(const RasterJob& j) { return check_raster(j.dtype, j.channels, j.h, j.w, j.ss, j.ds); }
+
+// what a unit's kernels work on: a device source and a destination, with their strides
+struct Io {
+  const void* src;
+  Strides ss;
+  StagedOut out;
+  Strides ds;
+};
+
+// A raster job from the staging of its host buffers on: body(call, io) plans and runs the unit's kernels (timed) and
+// copies the destination back (copy_back).
+template <typename Body>
+inline int run_raster(fra_ctx* ctx, const RasterJob& j, Body&& body) {
+  Call c(ctx);
+  const size_t es = (size_t)elem_size(j.dtype);
+  Io io{nullptr, j.ss, {}, j.ds};
+  if (const int rc = stage_in(c, j.src, j.src_on_device, (size_t)extent_of(j.channels, j.h, j.w, j.ss) * es, &io.src))
+    return rc;
+  if (const int rc = stage_out(c, j.dst, j.dst_on_device, (size_t)extent_of(j.channels, j.oh, j.ow, j.ds) * es, &io.out))
+    return rc;
+  return body(c, io);
+}
+
+// The same for a region: decoded into a per-call buffer, which is the body's source; the job's dst and strides are
+// the (channels, oh, ow) destination.
+template <typename Body>
+inline int run_region(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, int32_t oh,
+                      int32_t ow, Body&& body) {
+  Call c(ctx);
+  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
+  int64_t rs = 0;
+  if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
+  Io io{d_region, {(int64_t)roi->height * rs, rs, 1}, {}, {job->band_stride, job->row_stride, job->col_stride}};
+  const size_t es = (size_t)elem_size(job->dst_dtype);
+  if (const int rc = stage_out(c, job->dst, job->dst_on_device, (size_t)extent_of(job->channels, oh, ow, io.ds) * es, &io.out))
+    return rc;
+  return body(c, io);
 }
 #endif
 

@@ -22,75 +22,27 @@
 // For 8- and 16-bit integers whose column sums fit 32 bits (h' 2^(8 itemsize) <= 2^31) the columns are accumulated with
 // 24-bit multiplies in 32 bits (NARROW); the output's sum is 64-bit always.
 // No atomics, nothing shared between workgroups; all indices are 64-bit.
+//
+// This unit holds the kernel and its launch.  Shared with fra_resample_masked.hip (fra_resample.h): the kernel's
+// arguments, udiv, centre, tap_weights, from_f64, the refusals of the sizes and the grid of a launch; with all five
+// region-reducing units (fra_region.h): the dtype and layout refusal, what is left to the windowed read, staging, the
+// decoded region and the timed launch.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <numeric>
 #include <type_traits>
 
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
 #include "fra_region.h"
-
-extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
+#include "fra_resample.h"
 
 namespace {
 
-struct ResampleArgs {
-  const void* src;
-  void* dst;
-  int64_t sbs, srs, scs;  // source element strides: band, row, column
-  int64_t dbs, drs, dcs;  // destination element strides
-  int32_t h, w, oh, ow;
-  int64_t hr, ohr, wr, owr;  // h', oh', w', ow'
-  int32_t nseg;              // workgroups per output row
-  int32_t per;               // average: output columns of a workgroup
-  int32_t vec;  // average: 16-byte row loads are aligned (scs == 1; base, row and band strides multiples of 16 bytes)
-  int32_t narrow;  // average of 8- and 16-bit integers: a column's sum fits 32 bits (h' 2^(8 itemsize) <= 2^31)
-};
-
-template <typename T>
-struct AccOf { using type = std::conditional_t<std::is_floating_point<T>::value, double, long long>; };
-
-// a / b for a >= 0, b > 0; the 32-bit division when both fit (the 64-bit one is several times as long)
-__device__ inline int64_t udiv(int64_t a, int64_t b) {
-  if ((((uint64_t)a | (uint64_t)b) >> 32) == 0) return (int64_t)((uint32_t)a / (uint32_t)b);
-  return (int64_t)((uint64_t)a / (uint64_t)b);
-}
-
-// i0 and t of output index C along an axis of reduced sizes (nr source, onr output)
-__device__ inline void centre(int64_t C, int64_t nr, int64_t onr, int64_t* i0, double* t) {
-  const int64_t num = (2 * C + 1) * nr - onr, den = 2 * onr;  // num > -den: the floor of a negative num is -1
-  *i0 = num < 0 ? -1 : udiv(num, den);
-  *t = (double)(num - *i0 * den) / (double)den;
-}
-
-template <int MODE>
-__device__ inline void tap_weights(double t, double* wt) {
-  if constexpr (MODE == FRA_RESAMPLE_BILINEAR) {
-    wt[0] = 1.0 - t;
-    wt[1] = t;
-  } else {
-    wt[0] = ((-0.5 * t + 1.0) * t - 0.5) * t;
-    wt[1] = ((1.5 * t - 2.5) * t) * t + 1.0;
-    wt[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
-    wt[3] = ((0.5 * t - 0.5) * t) * t;
-  }
-}
-
-template <typename T>
-__device__ inline T from_f64(double v) {
-  if constexpr (std::is_floating_point<T>::value) {
-    return (T)v;
-  } else {
-    constexpr double lo = std::is_signed<T>::value ? -(double)(1ull << (8 * sizeof(T) - 1)) : 0.0;
-    constexpr double hi = (double)((1ull << (8 * sizeof(T) - (std::is_signed<T>::value ? 1 : 0))) - 1);
-    return (T)(long long)fmin(fmax(rint(v), lo), hi);
-  }
-}
+using namespace fra_region;
+using namespace fra_rs;
 
 template <typename T, int MODE, bool NARROW = false>
 __global__ void __launch_bounds__(256) k_resample(ResampleArgs a) {
@@ -255,71 +207,18 @@ void launch_t(int mode, unsigned grid, hipStream_t s, const ResampleArgs& a) {
   }
 }
 
-// the sizes of a job into `a`; FRA_E_INVALID for an output size, a code or an average the rule refuses
-int check_sizes(int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t resampling, int dtype, ResampleArgs* a) {
-  if (oh < 1 || oh > FRA_RESAMPLE_MAX_OUT || ow < 1 || ow > FRA_RESAMPLE_MAX_OUT)
-    return fra_internal_set_error(FRA_E_INVALID, "the output size must be 1 .. %d in each dimension (got %d x %d)",
-                                  FRA_RESAMPLE_MAX_OUT, oh, ow);
-  if (resampling < FRA_RESAMPLE_NEAREST || resampling > FRA_RESAMPLE_CUBIC)
-    return fra_internal_set_error(FRA_E_INVALID, "unknown resampling %d (0 nearest, 1 average, 2 bilinear, 3 cubic)",
-                                  resampling);
-  const int64_t gh = std::gcd((int64_t)h, (int64_t)oh), gw = std::gcd((int64_t)w, (int64_t)ow);
-  a->h = h, a->w = w, a->oh = oh, a->ow = ow;
-  a->hr = h / gh, a->ohr = oh / gh, a->wr = w / gw, a->owr = ow / gw;
-  if (resampling == FRA_RESAMPLE_AVERAGE) {
-    const int64_t n = a->hr * a->wr;  // < 2^62
-    const bool is_float = dtype == FRA_F32 || dtype == FRA_F64;
-    if (is_float ? n > ((int64_t)1 << 53) : n > ((int64_t)1 << (63 - 8 * elem_size(dtype))))
-      return fra_internal_set_error(FRA_E_INVALID,
-                                    "average: %d x %d -> %d x %d has n = %lld weights per output pixel, more than the "
-                                    "rule's exact arithmetic holds",
-                                    h, w, oh, ow, (long long)n);
-  }
-  return FRA_OK;
-}
-
-// k_resample over device buffers between two events; enqueues only
-int launch_resample(int dtype, int mode, int channels, ResampleArgs a, const void* d_src, void* d_dst, hipEvent_t e0,
-                    hipEvent_t e1, hipStream_t s) {
-  const size_t es = (size_t)elem_size(dtype);
-  a.src = d_src;
-  a.dst = d_dst;
-  if (a.oh == a.h && a.ow == a.w) mode = FRA_RESAMPLE_NEAREST;  // the input itself, in every mode
-  a.vec = a.scs == 1 && ((uintptr_t)d_src % 16) == 0 && (((uint64_t)a.srs * es) % 16) == 0 &&
-          (((uint64_t)a.sbs * es) % 16) == 0;
-  a.per = 1;
-  if (mode == FRA_RESAMPLE_AVERAGE) {
-    // `per` consecutive outputs cover at most ceil(per w / ow) + 1 source columns, V - 1 more from the aligned start
-    const int64_t V = 16 / (int64_t)es, room = 256 * V - V - 1;
-    a.per = (int32_t)std::min<int64_t>(std::max<int64_t>(room * a.owr / a.wr, 1), a.ow);
-    a.nseg = (int32_t)(((int64_t)a.ow + a.per - 1) / a.per);
-    a.per = (int32_t)(((int64_t)a.ow + a.nseg - 1) / a.nseg);  // the same workgroups, evenly filled
-    // the weights of a column's rows sum to h' and each is at most min(h', oh') <= 65536
-    a.narrow = dtype <= FRA_I16 && a.hr <= ((int64_t)1 << (31 - 8 * (int)es));
-  } else {
-    a.nseg = (int32_t)(((int64_t)a.ow + 255) / 256);
-  }
-  const int64_t grid = (int64_t)channels * a.oh * a.nseg;
-  if (grid > INT32_MAX) return fra_internal_set_error(FRA_E_INVALID, "the raster is too large for one resampling");
-  HIPCHK(hipEventRecord(e0, s));
-  switch (dtype) {
-    case FRA_U8: launch_t<uint8_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_I8: launch_t<int8_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_U16: launch_t<uint16_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_I16: launch_t<int16_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_U32: launch_t<uint32_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_I32: launch_t<int32_t>(mode, (unsigned)grid, s, a); break;
-    case FRA_F32: launch_t<float>(mode, (unsigned)grid, s, a); break;
-    case FRA_F64: launch_t<double>(mode, (unsigned)grid, s, a); break;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, s));
-  return FRA_OK;
-}
-
-// elements addressed from element 0 by a (channels, rows, cols) raster of the given strides
-int64_t extent_of(int64_t channels, int64_t rows, int64_t cols, int64_t bs, int64_t rs, int64_t cs) {
-  return (channels - 1) * bs + (rows - 1) * rs + (cols - 1) * cs + 1;
+// k_resample over `io`, timed, and the destination copied back (`a` holds the sizes)
+int launch_resample(Call& c, const Io& io, int dtype, int mode, int channels, ResampleArgs a) {
+  unsigned grid = 0;
+  if (const int rc = plan_grid(&a, io, dtype, channels, &mode, true, false, &grid)) return rc;
+  return timed(
+      c, &g_resample_ms,
+      [&]() -> int {
+        with_dtype(dtype, [&](auto t) { launch_t<decltype(t)>(mode, grid, c.s, a); });
+        HIPCHK(hipGetLastError());
+        return FRA_OK;
+      },
+      [&] { return copy_back(c, io.out); });
 }
 
 }  // namespace
@@ -334,96 +233,29 @@ FRA_API int fra_resample_timing(float* ms) {
 
 FRA_API int fra_resample(fra_ctx* ctx, const fra_resample_job* job) {
   if (!ctx || !job || !job->src || !job->dst) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  if (job->dtype < FRA_U8 || job->dtype > FRA_F64) return fra_internal_set_error(FRA_E_INVALID, "bad dtype %d", job->dtype);
-  if (job->channels < 1 || job->height < 1 || job->width < 1 || job->src_band_stride < 0 || job->src_row_stride < 0 ||
-      job->src_col_stride < 0 || job->dst_band_stride < 0 || job->dst_row_stride < 0 || job->dst_col_stride < 0)
-    return fra_internal_set_error(FRA_E_INVALID, "bad raster layout (%d x %d x %d)", job->channels, job->height,
-                                  job->width);
+  RasterJob r = raster_job(*job);
+  if (const int rc = check_raster(r)) return rc;
   ResampleArgs a{};
-  if (const int rc = check_sizes(job->height, job->width, job->out_height, job->out_width, job->resampling, job->dtype, &a))
-    return rc;
-  a.sbs = job->src_band_stride, a.srs = job->src_row_stride, a.scs = job->src_col_stride;
-  a.dbs = job->dst_band_stride, a.drs = job->dst_row_stride, a.dcs = job->dst_col_stride;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // staging buffers and events of this call, released on every path
-  const size_t es = (size_t)elem_size(job->dtype);
-  const size_t src_bytes = (size_t)extent_of(job->channels, a.h, a.w, a.sbs, a.srs, a.scs) * es;
-  const size_t dst_bytes = (size_t)extent_of(job->channels, a.oh, a.ow, a.dbs, a.drs, a.dcs) * es;
-  const void* d_src = job->src;
-  void* d_dst = job->dst;
-  if (!job->src_on_device) {
-    void* p = nullptr;
-    HIPCHK(sc.alloc(&p, src_bytes));
-    HIPCHK(hipMemcpyAsync(p, job->src, src_bytes, hipMemcpyHostToDevice, s));
-    d_src = p;
-  }
-  if (!job->dst_on_device) {  // staged whole, so that the elements between the outputs keep the caller's values
-    HIPCHK(sc.alloc(&d_dst, dst_bytes));
-    HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_resample(job->dtype, job->resampling, job->channels, a, d_src, d_dst, e0, e1, s)) return rc;
-  if (!job->dst_on_device) HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_resample_ms = ms;
-  return FRA_OK;
+  if (const int rc = check_sizes(r.h, r.w, job->out_height, job->out_width, job->resampling, r.dtype, &a)) return rc;
+  r.oh = a.oh, r.ow = a.ow;
+  return run_raster(ctx, r, [&](Call& c, const Io& io) {
+    return launch_resample(c, io, r.dtype, job->resampling, r.channels, a);
+  });
 }
 
 FRA_API int fra_decode_device_resampled(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi,
                                         int32_t out_height, int32_t out_width, int32_t resampling, fra_decoded* infos) {
   if (!ctx || !job || !roi || !infos) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  // what the windowed read refuses at once is left to it (it does so before any GPU work, with its own message)
-  const bool refer = roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
-                     (job->nitems && !job->items) || !job->dst || job->dst_dtype < FRA_U8 || job->dst_dtype > FRA_F64 ||
-                     job->channels < 1 || job->channels > 8 || job->band_stride < 0 || job->row_stride < 0 ||
-                     job->col_stride < 0 || (job->flags & FRA_DECODE_CONCAT) || !fra_region::item_windows_ok(job);
-  if (refer) {
-    ResampleArgs unused{};
-    if (const int rc = check_sizes(1, 1, out_height, out_width, resampling, FRA_U8, &unused)) return rc;
-    const int rc = fra_decode_device_window(ctx, job, roi, infos);
-    return rc ? rc : fra_internal_set_error(FRA_E_INVALID, "bad arguments");
-  }
   ResampleArgs a{};
-  if (const int rc = check_sizes(roi->height, roi->width, out_height, out_width, resampling, job->dst_dtype, &a)) return rc;
-  const int64_t h = roi->height;
-  if (const int rc = fra_region::check_cover(job, roi)) return rc;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // the region buffer, the staged output and the events: released on every path
-  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
-  int64_t rs = 0;
-  if (const int rc = fra_region::decode(ctx, job, roi, infos, sc, &d_region, &rs)) return rc;
-
-  const size_t es = (size_t)elem_size(job->dst_dtype);
-  a.sbs = h * rs, a.srs = rs, a.scs = 1;
-  a.dbs = job->band_stride, a.drs = job->row_stride, a.dcs = job->col_stride;
-  const size_t dst_bytes = (size_t)extent_of(job->channels, a.oh, a.ow, a.dbs, a.drs, a.dcs) * es;
-  void* d_dst = job->dst;
-  if (!job->dst_on_device) {
-    HIPCHK(sc.alloc(&d_dst, dst_bytes));
-    HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
+  if (left_to_window_read(job, roi)) {
+    if (const int rc = check_sizes(1, 1, out_height, out_width, resampling, FRA_U8, &a)) return rc;
+    return refer_to_window_read(ctx, job, roi, infos, false);
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_resample(job->dst_dtype, resampling, job->channels, a, d_region, d_dst, e0, e1, s)) return rc;
-  if (!job->dst_on_device) HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_resample_ms = ms;
-  return FRA_OK;
+  if (const int rc = check_sizes(roi->height, roi->width, out_height, out_width, resampling, job->dst_dtype, &a)) return rc;
+  if (const int rc = check_cover(job, roi)) return rc;
+  return run_region(ctx, job, roi, infos, a.oh, a.ow, [&](Call& c, const Io& io) {
+    return launch_resample(c, io, job->dst_dtype, resampling, job->channels, a);
+  });
 }
 
 }  // extern "C"

@@ -29,6 +29,10 @@
 // kLdsBins = 8192: 32 KiB of LDS per workgroup, so the 160 KiB of a CU still hold four workgroups of 256 threads (16
 // waves), which a bandwidth-bound loop needs; a uint32 bin per 4-byte bank, so lanes that hit different bins conflict
 // only on equal banks and lanes that hit one bin serialise -- which the merge above bounds per slot.
+//
+// This unit holds the kernels, their launch and the refusals of the options and of 2^32 pixels.  Shared with the other
+// region-reducing units (fra_region.h): the dtype and layout refusal, what is left to the windowed read (the variant
+// that ignores the job's destination), the staging of a host raster, the decoded region and the timed launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,11 +46,11 @@
 #include "fra_host.h"
 #include "fra_region.h"
 
-extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
-
 static_assert(sizeof(fra_stats_band) == 160, "fra_stats_band is 160 bytes");
 
 namespace {
+
+using namespace fra_region;
 
 constexpr int kLdsBins = 8192;   // bins a workgroup counts in LDS (32 KiB)
 constexpr int kMaxBins = 65536;
@@ -440,15 +444,6 @@ constexpr int64_t kMaxPixels = (int64_t)1 << 32;  // per band: the integer sums 
 constexpr int64_t kBlocks = 4096;                 // workgroups aimed at: 16 per CU
 constexpr int64_t kMinSlots = 1024;               // slots of a workgroup, at least (4 per thread), rows permitting
 
-// elements addressed from element 0 by a (channels, rows, cols) raster of the given strides
-int64_t extent_of(int64_t channels, int64_t rows, int64_t cols, int64_t bs, int64_t rs, int64_t cs) {
-  return (channels - 1) * bs + (rows - 1) * rs + (cols - 1) * cs + 1;
-}
-
-bool aligned16(const void* p, int64_t bs, int64_t rs, int64_t cs, size_t es) {
-  return cs == 1 && ((uintptr_t)p % 16) == 0 && (((uint64_t)rs * es) % 16) == 0 && (((uint64_t)bs * es) % 16) == 0;
-}
-
 template <typename T, int PASS, int HMODE>
 void launch_one(unsigned grid, size_t lds, hipStream_t s, const StatsArgs& g) {
   hipLaunchKernelGGL((k_stats<T, PASS, HMODE>), dim3(grid), dim3(256), lds, s, g);
@@ -471,28 +466,24 @@ void launch_pass(int pass, int hmode, unsigned grid, size_t lds, hipStream_t s, 
 }
 
 void launch_dtype(int dtype, int pass, int hmode, unsigned grid, size_t lds, hipStream_t s, const StatsArgs& g) {
-  switch (dtype) {
-    case FRA_U8: launch_pass<uint8_t>(pass, hmode, grid, lds, s, g); break;
-    case FRA_I8: launch_pass<int8_t>(pass, hmode, grid, lds, s, g); break;
-    case FRA_U16: launch_pass<uint16_t>(pass, hmode, grid, lds, s, g); break;
-    case FRA_I16: launch_pass<int16_t>(pass, hmode, grid, lds, s, g); break;
-    case FRA_U32: launch_pass<uint32_t>(pass, hmode, grid, lds, s, g); break;
-    case FRA_I32: launch_pass<int32_t>(pass, hmode, grid, lds, s, g); break;
-    case FRA_F32: launch_pass<float>(pass, hmode, grid, lds, s, g); break;
-    case FRA_F64: launch_pass<double>(pass, hmode, grid, lds, s, g); break;
-  }
+  with_dtype(dtype, [&](auto t) { launch_pass<decltype(t)>(pass, hmode, grid, lds, s, g); });
 }
 
-// the statistics kernels over a device raster between two events, the reports to `bands` and the counts to `hist` on
-// the host; enqueues only (the partials, the device reports and the device histogram belong to `sc`)
-int launch_stats(int dtype, int channels, StatsArgs g, const fra_stats_opts& o, const void* d_src, HipArena& sc,
-                 hipEvent_t e0, hipEvent_t e1, hipStream_t s, fra_stats_band* bands, uint64_t* hist) {
+// the statistics kernels over a (channels, h, w) device raster, timed, the reports to `bands` and the counts to `hist`
+// on the host (the partials, the device reports and the device histogram belong to the call)
+int run_stats(Call& c, int dtype, int channels, int32_t h, int32_t w, const void* d_src, const Strides& ss,
+              const fra_stats_opts& o, fra_stats_band* bands, uint64_t* hist) {
+  hipStream_t s = c.s;
+  HipArena& sc = c.sc;
+  StatsArgs g{};
+  g.bs = ss.band, g.rs = ss.row, g.cs = ss.col;
+  g.h = h, g.w = w;
   const size_t es = (size_t)elem_size(dtype);
   const int64_t V = 16 / (int64_t)es;
   const bool is_float = dtype == FRA_F32 || dtype == FRA_F64;
   const bool automatic = (o.flags & FRA_STATS_AUTO_RANGE) != 0;
   g.src = d_src;
-  g.vec = aligned16(d_src, g.bs, g.rs, g.cs, es);
+  g.vec = aligned16(d_src, ss, es);
   g.bins = o.bins, g.flags = o.flags, g.nodata = o.nodata;
   g.lo = g.hi = g.scale = 0.0;
   if (o.bins > 0 && !automatic) {
@@ -527,30 +518,35 @@ int launch_stats(int dtype, int channels, StatsArgs g, const fra_stats_opts& o, 
     g.bin0 = bin0, g.nbins = std::min(kLdsBins, o.bins - bin0);
     return (size_t)g.nbins * sizeof(uint32_t);
   };
-  HIPCHK(hipEventRecord(e0, s));
-  {
-    const size_t lds = fused ? window(0) : 0;
-    launch_dtype(dtype, 1, fused ? hmode : 0, (unsigned)grid, lds, s, g);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_stats_fold, dim3((unsigned)channels), dim3(256), 0, s, g, (int32_t)is_float, (int32_t)fused);
-  HIPCHK(hipGetLastError());
-  // pass 2 reads the records k_stats_fold wrote: once for fm2, below / above and the first window (then folded), and
-  // once more per further window of bins, for its counts alone
-  for (int bin0 = fused ? kLdsBins : 0; bin0 == 0 ? second : bin0 < o.bins; bin0 += kLdsBins) {
-    const size_t lds = hmode ? window(bin0) : 0;
-    launch_dtype(dtype, 2, hmode, (unsigned)grid, lds, s, g);
-    HIPCHK(hipGetLastError());
-    if (bin0 == 0) {
-      hipLaunchKernelGGL(k_stats_fold2, dim3((unsigned)channels), dim3(256), 0, s, g, (int32_t)is_float);
-      HIPCHK(hipGetLastError());
-    }
-    if (!hmode) break;
-  }
-  HIPCHK(hipEventRecord(e1, s));
-  HIPCHK(hipMemcpyAsync(bands, g.bands, (size_t)channels * sizeof(fra_stats_band), hipMemcpyDeviceToHost, s));
-  if (o.bins > 0) HIPCHK(hipMemcpyAsync(hist, g.hist, hist_bytes, hipMemcpyDeviceToHost, s));
-  return FRA_OK;
+  return timed(
+      c, &g_stats_ms,
+      [&]() -> int {
+        {
+          const size_t lds = fused ? window(0) : 0;
+          launch_dtype(dtype, 1, fused ? hmode : 0, (unsigned)grid, lds, s, g);
+          HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_stats_fold, dim3((unsigned)channels), dim3(256), 0, s, g, (int32_t)is_float, (int32_t)fused);
+        HIPCHK(hipGetLastError());
+        // pass 2 reads the records k_stats_fold wrote: once for fm2, below / above and the first window (then folded),
+        // and once more per further window of bins, for its counts alone
+        for (int bin0 = fused ? kLdsBins : 0; bin0 == 0 ? second : bin0 < o.bins; bin0 += kLdsBins) {
+          const size_t lds = hmode ? window(bin0) : 0;
+          launch_dtype(dtype, 2, hmode, (unsigned)grid, lds, s, g);
+          HIPCHK(hipGetLastError());
+          if (bin0 == 0) {
+            hipLaunchKernelGGL(k_stats_fold2, dim3((unsigned)channels), dim3(256), 0, s, g, (int32_t)is_float);
+            HIPCHK(hipGetLastError());
+          }
+          if (!hmode) break;
+        }
+        return FRA_OK;
+      },
+      [&]() -> int {
+        HIPCHK(hipMemcpyAsync(bands, g.bands, (size_t)channels * sizeof(fra_stats_band), hipMemcpyDeviceToHost, s));
+        if (o.bins > 0) HIPCHK(hipMemcpyAsync(hist, g.hist, hist_bytes, hipMemcpyDeviceToHost, s));
+        return FRA_OK;
+      });
 }
 
 int too_many_pixels(int64_t h, int64_t w) {
@@ -573,20 +569,6 @@ int check_opts(const fra_stats_opts* o, const uint64_t* hist) {
   return FRA_OK;
 }
 
-// launch_stats between two events of `sc`, waited for; the time to g_stats_ms
-int run_stats(int dtype, int channels, const StatsArgs& g, const fra_stats_opts& o, const void* d_src, HipArena& sc,
-              hipStream_t s, fra_stats_band* bands, uint64_t* hist) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPCHK(sc.event(&e0, hipEventDefault));
-  HIPCHK(sc.event(&e1, hipEventDefault));
-  if (const int rc = launch_stats(dtype, channels, g, o, d_src, sc, e0, e1, s, bands, hist)) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  g_stats_ms = ms;
-  return FRA_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -599,32 +581,17 @@ FRA_API int fra_stats_timing(float* ms) {
 
 FRA_API int fra_stats(fra_ctx* ctx, const fra_stats_job* job, fra_stats_band* bands, uint64_t* hist) {
   if (!ctx || !job || !bands || !job->src) return fra_internal_set_error(FRA_E_INVALID, "null argument");
-  if (job->dtype < FRA_U8 || job->dtype > FRA_F64) return fra_internal_set_error(FRA_E_INVALID, "bad dtype %d", job->dtype);
-  if (job->channels < 1 || job->height < 1 || job->width < 1 || job->band_stride < 0 || job->row_stride < 0 ||
-      job->col_stride < 0)
-    return fra_internal_set_error(FRA_E_INVALID, "bad raster layout (%d x %d x %d)", job->channels, job->height,
-                                  job->width);
-  if (const int rc = too_many_pixels(job->height, job->width)) return rc;
+  const Strides ss{job->band_stride, job->row_stride, job->col_stride};
+  const int32_t ch = job->channels, h = job->height, w = job->width;
+  if (const int rc = check_raster(job->dtype, ch, h, w, ss, ss)) return rc;
+  if (const int rc = too_many_pixels(h, w)) return rc;
   if (const int rc = check_opts(&job->opts, hist)) return rc;
-  StatsArgs g{};
-  g.bs = job->band_stride, g.rs = job->row_stride, g.cs = job->col_stride;
-  g.h = job->height, g.w = job->width;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // the staged raster, partials, reports, histogram and events of this call, released on every path
-  const size_t es = (size_t)elem_size(job->dtype);
-  const void* d_src = job->src;
-  if (!job->src_on_device) {  // copied from its element 0 to the last one addressed
-    const size_t bytes = (size_t)extent_of(job->channels, g.h, g.w, g.bs, g.rs, g.cs) * es;
-    void* q = nullptr;
-    HIPCHK(sc.alloc(&q, bytes));
-    HIPCHK(hipMemcpyAsync(q, job->src, bytes, hipMemcpyHostToDevice, s));
-    d_src = q;
-  }
-  return run_stats(job->dtype, job->channels, g, job->opts, d_src, sc, s, bands, hist);
+  Call c(ctx);
+  const void* d_src = nullptr;
+  if (const int rc = stage_in(c, job->src, job->src_on_device,
+                              (size_t)extent_of(ch, h, w, ss) * (size_t)elem_size(job->dtype), &d_src))
+    return rc;
+  return run_stats(c, job->dtype, ch, h, w, d_src, ss, job->opts, bands, hist);
 }
 
 FRA_API int fra_decode_device_stats(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi,
@@ -632,37 +599,15 @@ FRA_API int fra_decode_device_stats(fra_ctx* ctx, const fra_decode_job* job, con
                                     fra_decoded* infos) {
   if (!ctx || !job || !roi || !opts || !bands || !infos) return fra_internal_set_error(FRA_E_INVALID, "null argument");
   if (const int rc = check_opts(opts, hist)) return rc;
-  // what the windowed read refuses at once is left to it (it does so before any GPU work, with its own message)
-  const bool refer = roi->height <= 0 || roi->width <= 0 || roi->row_off < 0 || roi->col_off < 0 || job->nitems < 0 ||
-                     (job->nitems && !job->items) || (!job->data && job->len) || job->dst_dtype < FRA_U8 ||
-                     job->dst_dtype > FRA_F64 || job->denorm < FRA_DENORM_NONE || job->denorm > FRA_DENORM_PCM16 ||
-                     (job->denorm == FRA_DENORM_NONE && job->dst_dtype != FRA_I16 && job->dst_dtype != FRA_I32) ||
-                     job->channels < 1 || job->channels > 8 || (job->flags & FRA_DECODE_CONCAT) ||
-                     !fra_region::item_windows_ok(job);
-  if (refer) {
-    fra_decode_job inner = *job;  // the job's own dst and strides are ignored
-    inner.dst = (void*)bands;     // any non-null pointer: the call returns before it is looked at
-    inner.dst_on_device = 1;
-    inner.band_stride = 0, inner.row_stride = 0, inner.col_stride = 1;
-    const int rc = fra_decode_device_window(ctx, &inner, roi, infos);
-    return rc ? rc : fra_internal_set_error(FRA_E_INVALID, "bad arguments");
-  }
-  const int64_t h = roi->height, w = roi->width;
+  if (left_to_window_read_no_dst(job, roi)) return refer_to_window_read(ctx, job, roi, infos, true);
+  const int32_t h = roi->height, w = roi->width;
   if (const int rc = too_many_pixels(h, w)) return rc;
-  if (const int rc = fra_region::check_cover(job, roi)) return rc;
-
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // the region buffer, partials, reports, histogram and events: released on every path
-  void* d_region = nullptr;
+  if (const int rc = check_cover(job, roi)) return rc;
+  Call c(ctx);
+  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
   int64_t rs = 0;
-  if (const int rc = fra_region::decode(ctx, job, roi, infos, sc, &d_region, &rs)) return rc;
-  StatsArgs g{};
-  g.bs = h * rs, g.rs = rs, g.cs = 1;
-  g.h = (int32_t)h, g.w = (int32_t)w;
-  return run_stats(job->dst_dtype, job->channels, g, *opts, d_region, sc, s, bands, hist);
+  if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
+  return run_stats(c, job->dst_dtype, job->channels, h, w, d_region, Strides{(int64_t)h * rs, rs, 1}, *opts, bands, hist);
 }
 
 }  // extern "C"

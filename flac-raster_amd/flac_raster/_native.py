@@ -435,6 +435,51 @@ class HostRegistration:
             self.ok = False
 
 
+def _raster_source(job, src, dtype, shape, strides):
+    """Fills ``job.src`` / ``job.src_on_device`` / ``job.dtype`` / ``job.channels`` / ``job.height`` / ``job.width``
+    from a raster given as a numpy array ``(B, h, w)`` / ``(h, w)`` or as a device pointer (int) with ``dtype``,
+    ``shape`` and element ``strides`` (default band-planar); returns ``(dtype, (B, h, w), element strides)``."""
+    if isinstance(src, np.ndarray):
+        a = src if src.ndim == 3 else src[None]
+        if a.ndim != 3:
+            raise ValueError("src must be (B, h, w) or (h, w)")
+        dt, (B, h, w), st = a.dtype, a.shape, _element_strides(a)
+        job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
+    else:
+        dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
+        st = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
+        job.src, job.src_on_device = C.c_void_p(int(src)), 1
+    if dt not in DTYPE_CODES:
+        raise TypeError(f"unsupported dtype {dt}")
+    job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
+    return dt, (B, h, w), st
+
+
+def _raster_job(job, src, dst, dtype, shape, strides, dst_strides, out_shape):
+    """Fills what ``DecimateJob`` and ``ResampleJob`` share: the source (:func:`_raster_source`) and the destination
+    ``(B, oh, ow)`` with ``(oh, ow) = out_shape(h, w)`` -- ``None`` (a new array), a numpy array view or a device
+    pointer with element ``dst_strides`` (default band-planar).  Returns ``(what the caller returns, dtype, B)``."""
+    dt, (B, h, w), sst = _raster_source(job, src, dtype, shape, strides)
+    oh, ow = out_shape(h, w)
+    ret = dst
+    if dst is None:
+        ret = dst = np.zeros((B, oh, ow), dtype=dt)
+        if isinstance(src, np.ndarray) and src.ndim == 2:
+            ret = dst[0]
+    if isinstance(dst, np.ndarray):
+        d = dst if dst.ndim == 3 else dst[None]
+        if d.shape != (B, oh, ow) or d.dtype != dt:
+            raise ValueError(f"dst must be {(B, oh, ow)} of {dt}, got {d.shape} of {d.dtype}")
+        dstr = _element_strides(d)
+        job.dst, job.dst_on_device = C.c_void_p(d.ctypes.data), 0
+    else:
+        dstr = tuple(int(v) for v in dst_strides) if dst_strides is not None else (oh * ow, ow, 1)
+        job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
+    job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
+    job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
+    return ret, dt, B
+
+
 class Context:
     """One HIP device + stream (``fra_ctx``)."""
 
@@ -623,37 +668,9 @@ class Context:
 
         k, mode = check_factor(factor), resampling_code(resampling)
         job = DecimateJob()
-        if isinstance(src, np.ndarray):
-            a = src if src.ndim == 3 else src[None]
-            if a.ndim != 3:
-                raise ValueError("src must be (B, h, w) or (h, w)")
-            dt, (B, h, w), sst = a.dtype, a.shape, _element_strides(a)
-            job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
-        else:
-            dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
-            sst = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
-            job.src, job.src_on_device = C.c_void_p(int(src)), 1
-        if dt not in DTYPE_CODES:
-            raise TypeError(f"unsupported dtype {dt}")
-        oh, ow = decimated_shape(h, w, k)
-        ret = dst
-        if dst is None:
-            ret = dst = np.zeros((B, oh, ow), dtype=dt)
-            if isinstance(src, np.ndarray) and src.ndim == 2:
-                ret = dst[0]
-        if isinstance(dst, np.ndarray):
-            d = dst if dst.ndim == 3 else dst[None]
-            if d.shape != (B, oh, ow) or d.dtype != dt:
-                raise ValueError(f"dst must be {(B, oh, ow)} of {dt}, got {d.shape} of {d.dtype}")
-            dstr = _element_strides(d)
-            job.dst, job.dst_on_device = C.c_void_p(d.ctypes.data), 0
-        else:
-            dstr = tuple(int(v) for v in dst_strides) if dst_strides is not None else (oh * ow, ow, 1)
-            job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
-        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
-        job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
+        ret, dt, B = _raster_job(job, src, dst, dtype, shape, strides, dst_strides,
+                                 lambda h, w: decimated_shape(h, w, k))
         job.factor, job.resampling = k, mode
-        job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
         masked = _masked_args(nodata, filled, dt, B)
         if masked is not None:
             _check(load().fra_decimate_masked(self.h, C.byref(job), *masked))
@@ -699,36 +716,8 @@ class Context:
 
         (oh, ow), mode = check_out_shape(out_shape), resampling_any_code(resampling)
         job = ResampleJob()
-        if isinstance(src, np.ndarray):
-            a = src if src.ndim == 3 else src[None]
-            if a.ndim != 3:
-                raise ValueError("src must be (B, h, w) or (h, w)")
-            dt, (B, h, w), sst = a.dtype, a.shape, _element_strides(a)
-            job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
-        else:
-            dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
-            sst = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
-            job.src, job.src_on_device = C.c_void_p(int(src)), 1
-        if dt not in DTYPE_CODES:
-            raise TypeError(f"unsupported dtype {dt}")
-        ret = dst
-        if dst is None:
-            ret = dst = np.zeros((B, oh, ow), dtype=dt)
-            if isinstance(src, np.ndarray) and src.ndim == 2:
-                ret = dst[0]
-        if isinstance(dst, np.ndarray):
-            d = dst if dst.ndim == 3 else dst[None]
-            if d.shape != (B, oh, ow) or d.dtype != dt:
-                raise ValueError(f"dst must be {(B, oh, ow)} of {dt}, got {d.shape} of {d.dtype}")
-            dstr = _element_strides(d)
-            job.dst, job.dst_on_device = C.c_void_p(d.ctypes.data), 0
-        else:
-            dstr = tuple(int(v) for v in dst_strides) if dst_strides is not None else (oh * ow, ow, 1)
-            job.dst, job.dst_on_device = C.c_void_p(int(dst)), 1
-        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
-        job.src_band_stride, job.src_row_stride, job.src_col_stride = sst
+        ret, dt, B = _raster_job(job, src, dst, dtype, shape, strides, dst_strides, lambda h, w: (oh, ow))
         job.out_height, job.out_width, job.resampling = oh, ow, mode
-        job.dst_band_stride, job.dst_row_stride, job.dst_col_stride = dstr
         masked = _masked_args(nodata, filled, dt, B)
         if masked is not None:
             _check(load().fra_resample_masked(self.h, C.byref(job), *masked))
@@ -859,19 +848,7 @@ class Context:
         (int) with ``dtype``, ``shape`` = (B, h, w) and element ``strides`` (default band-planar).  It is not written.
         ``bins``, ``hist_range`` (``(lo, hi)``, ``"auto"`` / ``None``), ``nodata`` as ``stats.stats_arrays``."""
         job = StatsJob()
-        if isinstance(src, np.ndarray):
-            a = src if src.ndim == 3 else src[None]
-            if a.ndim != 3:
-                raise ValueError("src must be (B, h, w) or (h, w)")
-            dt, (B, h, w), st = a.dtype, a.shape, _element_strides(a)
-            job.src, job.src_on_device = C.c_void_p(a.ctypes.data), 0
-        else:
-            dt, (B, h, w) = np.dtype(dtype), (int(v) for v in shape)
-            st = tuple(int(v) for v in strides) if strides is not None else (h * w, w, 1)
-            job.src, job.src_on_device = C.c_void_p(int(src)), 1
-        if dt not in DTYPE_CODES:
-            raise TypeError(f"unsupported dtype {dt}")
-        job.dtype, job.channels, job.height, job.width = DTYPE_CODES[dt], B, h, w
+        _, (B, _, _), st = _raster_source(job, src, dtype, shape, strides)
         job.band_stride, job.row_stride, job.col_stride = st
         job.opts = self._stats_opts(bins, hist_range, nodata)
         bands = (StatsBand * max(1, B))()

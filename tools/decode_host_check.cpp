@@ -12,7 +12,7 @@
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
 //     their nodata-aware entries (fra_resample_masked.hip: a nodata value the dtype does not admit included),
 //     the comparison (fra_compare, fra_decode_device_compare) and the statistics (fra_stats, fra_decode_device_stats),
-//     which returns before any GPU work.
+//     which returns before any GPU work, and the order of these refusals (inputs that break two rules at once).
 // usage: decode_host_check [--concat] file.flac ...
 #include <cmath>
 #include <cstdarg>
@@ -609,6 +609,68 @@ int main(int argc, char** argv) {
     { auto j = sj; j.opts = eight; j.opts.hist_hi = -1.0; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics: inverted range accepted"); }
     { auto j = sj; j.opts = eight; j.opts.hist_lo = -HUGE_VAL; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics: infinite range accepted"); }
     EXPECT(fra_stats_timing(nullptr) == FRA_E_INVALID, "statistics timing: null accepted");
+  }
+  // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;  // dst_dtype int32
+    dj.items = &di;
+    const fra_window r48{0, 0, 4, 8};
+    fra_window r40 = r48;
+    r40.width = 0;
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    int32_t out[16];
+    static int32_t ref[64];
+    uint64_t filled[8], hist[8];
+    fra_decimate_job kj{};
+    kj.src = dst; kj.dtype = FRA_I32; kj.channels = 1; kj.height = 8; kj.width = 8;
+    kj.src_band_stride = 64; kj.src_row_stride = 8; kj.src_col_stride = 1;
+    kj.factor = 2; kj.resampling = FRA_RESAMPLE_AVERAGE;
+    kj.dst = out; kj.dst_band_stride = 16; kj.dst_row_stride = 4; kj.dst_col_stride = 1;
+    fra_resample_job mj{};
+    mj.src = dst; mj.dtype = FRA_I32; mj.channels = 1; mj.height = 8; mj.width = 8;
+    mj.src_band_stride = 64; mj.src_row_stride = 8; mj.src_col_stride = 1;
+    mj.out_height = 3; mj.out_width = 5; mj.resampling = FRA_RESAMPLE_AVERAGE;
+    mj.dst = out; mj.dst_band_stride = 15; mj.dst_row_stride = 5; mj.dst_col_stride = 1;
+    { auto j = kj; j.factor = 3; j.dtype = 8; EXPECT(says(fra_decimate(ctx, &j), "decimation factor"), "decimate: factor 3 and dtype 8: %s", g_msg.c_str()); }
+    { auto j = kj; j.dtype = 8; j.height = 0; EXPECT(says(fra_decimate(ctx, &j), "bad dtype"), "decimate: dtype 8 and zero height: %s", g_msg.c_str()); }
+    { auto j = kj; j.factor = 3; EXPECT(says(fra_decimate_masked(ctx, &j, 0.5, filled), "decimation factor"), "masked decimate: factor 3 and nodata 0.5: %s", g_msg.c_str()); }
+    { auto j = kj; j.dtype = 8; EXPECT(says(fra_decimate_masked(ctx, &j, 0.5, filled), "bad dtype"), "masked decimate: dtype 8 and nodata 0.5: %s", g_msg.c_str()); }
+    { auto j = kj; j.dst_row_stride = -1; EXPECT(says(fra_decimate_masked(ctx, &j, 0.5, filled), "bad raster layout"), "masked decimate: negative stride and nodata 0.5: %s", g_msg.c_str()); }
+    { auto j = mj; j.dtype = 8; j.width = 0; EXPECT(says(fra_resample(ctx, &j), "bad dtype"), "resample: dtype 8 and zero width: %s", g_msg.c_str()); }
+    { auto j = mj; j.src_col_stride = -1; j.out_width = 0; EXPECT(says(fra_resample(ctx, &j), "bad raster layout"), "resample: negative stride and out width 0: %s", g_msg.c_str()); }
+    { auto j = mj; j.out_height = 0; EXPECT(says(fra_resample_masked(ctx, &j, 0.5, filled), "output size"), "masked resample: out height 0 and nodata 0.5: %s", g_msg.c_str()); }
+    { auto j = mj; j.dst_row_stride = -1; EXPECT(says(fra_resample_masked(ctx, &j, 0.5, filled), "bad raster layout"), "masked resample: negative stride and nodata 0.5: %s", g_msg.c_str()); }
+    { auto j = mj; j.dst_row_stride = -1; j.out_height = 0; EXPECT(says(fra_resample_masked(ctx, &j, 0.0, filled), "bad raster layout"), "masked resample: negative stride and out height 0: %s", g_msg.c_str()); }
+    EXPECT(says(fra_decode_device_resampled(ctx, &dj, &r40, 0, 5, 1, inf), "output size"), "resampled read: zero-width roi and out height 0: %s", g_msg.c_str());
+    EXPECT(says(fra_decode_device_resampled_masked(ctx, &dj, &r40, 0, 5, 1, inf, 0.0, filled), "output size"), "masked resampled read: zero-width roi and out height 0: %s", g_msg.c_str());
+    EXPECT(says(fra_decode_device_resampled_masked(ctx, &dj, &r40, 3, 5, 1, inf, 0.5, filled), "region of interest"), "masked resampled read: zero-width roi and nodata 0.5: %s", g_msg.c_str());
+    EXPECT(says(fra_decode_device_resampled_masked(ctx, &dj, &r48, 0, 5, 1, inf, 0.5, filled), "output size"), "masked resampled read: out height 0 and nodata 0.5: %s", g_msg.c_str());
+    { fra_window r = r48; r.height = 5; EXPECT(says(fra_decode_device_resampled_masked(ctx, &dj, &r, 3, 5, 1, inf, 0.5, filled), "nodata"), "masked resampled read: uncovered row and nodata 0.5: %s", g_msg.c_str()); }
+    EXPECT(says(fra_decode_device_decimated(ctx, &dj, &r40, 3, 1, inf), "decimation factor"), "decimated read: factor 3 and zero-width roi: %s", g_msg.c_str());
+    EXPECT(says(fra_decode_device_decimated_masked(ctx, &dj, &r40, 3, 1, inf, 0.0, filled), "decimation factor"), "masked decimated read: factor 3 and zero-width roi: %s", g_msg.c_str());
+    EXPECT(says(fra_decode_device_decimated_masked(ctx, &dj, &r40, 2, 1, inf, 0.5, filled), "region of interest"), "masked decimated read: zero-width roi and nodata 0.5: %s", g_msg.c_str());
+    { fra_window r = r48; r.height = 5; EXPECT(says(fra_decode_device_decimated_masked(ctx, &dj, &r, 2, 1, inf, 0.5, filled), "nodata"), "masked decimated read: uncovered row and nodata 0.5: %s", g_msg.c_str()); }
+    fra_stats_band sbands[1];
+    fra_stats_opts eight{};
+    eight.bins = 8; eight.hist_lo = 0.0; eight.hist_hi = 1.0;
+    { auto o = eight; o.bins = -1; EXPECT(says(fra_decode_device_stats(ctx, &dj, &r40, &o, sbands, hist, inf), "bins"), "statistics read: bins -1 and zero-width roi: %s", g_msg.c_str()); }
+    { fra_window r{0, 0, 65537, 65536}; auto j = dj; j.nitems = 0; EXPECT(says(fra_decode_device_stats(ctx, &j, &r, &eight, sbands, hist, inf), "2^32 pixels"), "statistics read: 2^32 pixels and no items: %s", g_msg.c_str()); }
+    fra_stats_job sj{};
+    sj.src = dst; sj.dtype = FRA_I32; sj.channels = 1; sj.height = 8; sj.width = 8;
+    sj.band_stride = 64; sj.row_stride = 8; sj.col_stride = 1;
+    { auto j = sj; j.dtype = 8; j.width = 0; EXPECT(says(fra_stats(ctx, &j, sbands, hist), "bad dtype"), "statistics: dtype 8 and zero width: %s", g_msg.c_str()); }
+    { auto j = sj; j.row_stride = -8; j.opts = eight; j.opts.bins = -1; EXPECT(says(fra_stats(ctx, &j, sbands, hist), "bad raster layout"), "statistics: negative stride and bins -1: %s", g_msg.c_str()); }
+    { auto j = sj; j.height = 65537; j.width = 65536; j.opts = eight; j.opts.bins = -1; EXPECT(says(fra_stats(ctx, &j, sbands, hist), "2^32 pixels"), "statistics: 2^32 pixels and bins -1: %s", g_msg.c_str()); }
+    fra_compare_band cbands[1];
+    EXPECT(says(fra_decode_device_compare(ctx, &dj, &r40, ref, 0, 32, -8, 1, cbands, inf), "bad reference layout"), "compared read: negative reference stride and zero-width roi: %s", g_msg.c_str());
+    { fra_window r{0, 0, 65537, 65536}; auto j = dj; j.nitems = 0; EXPECT(says(fra_decode_device_compare(ctx, &j, &r, ref, 0, 32, 8, 1, cbands, inf), "2^32 pixels"), "compared read: 2^32 pixels and no items: %s", g_msg.c_str()); }
+    fra_compare_job cj{};
+    cj.a = dst; cj.b = ref; cj.dtype = FRA_I32; cj.channels = 1; cj.height = 8; cj.width = 8;
+    cj.a_band_stride = cj.b_band_stride = 64; cj.a_row_stride = cj.b_row_stride = 8; cj.a_col_stride = cj.b_col_stride = 1;
+    { auto j = cj; j.dtype = 8; j.b_row_stride = -8; EXPECT(says(fra_compare(ctx, &j, cbands), "bad dtype"), "compare: dtype 8 and negative stride: %s", g_msg.c_str()); }
+    { auto j = cj; j.height = 65537; j.width = 65536; j.a_col_stride = -1; EXPECT(says(fra_compare(ctx, &j, cbands), "bad raster layout"), "compare: negative stride and 2^32 pixels: %s", g_msg.c_str()); }
   }
   printf("argument validation checked\n");
 #endif
