@@ -29,6 +29,15 @@
 // k_dec_verify in k_dec_scatter's place: same grid and transpose, but it loads the source raster element instead of
 // storing to it, normalises it anew and compares.  Nothing is written but a mismatch count and the first mismatch.
 //
+// On the host the three entries are one scaffold (struct Decode) and what is particular to each.  Shared: the call's
+// stream and arena, the host's view of a device-resident input, opening an item (the parameters beside its frame
+// offsets, or STREAMINFO and the candidate search), the layout (DecItem, groups of 64 frames, scratch, the slots'
+// byte positions), staging and uploads, the launches with their five events, the infos, the copy back and the scan of
+// the failure flags.  An entry adds its own refusals, where a host input lies on the device (fra_decode_device
+// uploads it whole; the windowed read uploads the spans of the selected frames, so its slots are positions of that
+// upload and its messages carry item-relative bytes; the verify entry takes device memory), its candidates and its
+// chain: chain_stream with concatenation and capacity windows, chain_window, or the verify entry's position check.
+//
 // Not covered (refused, never decoded differently): 33-bit samples (side channel of a 32-bps stream); by the
 // windowed read also FRA_DECODE_CONCAT, capacity windows and variable-blocksize streams.
 #include <hip/hip_runtime.h>
@@ -46,8 +55,6 @@
 #include "fra_device.h"
 #include "fra_host.h"
 #include "fra_verify.h"
-
-extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
 
 namespace {
 
@@ -579,8 +586,11 @@ struct ItemPlan {
   StreamParams sp;
   uint64_t audio = 0;           // item-relative first audio byte (search path)
   std::vector<HostCand> cand;   // sorted by start
-  int32_t first_group = 0, ngroups = 0;
+  size_t n = 0;                 // frames laid out: slots first_group * 64 + [0, n)
+  int32_t first_group = 0;
 };
+struct Range { uint64_t at, bytes; };             // of the input
+struct Rect { int64_t row0, col0, rows, cols; };  // of the destination, from its origin
 
 thread_local float g_last_ms[4] = {0, 0, 0, 0};
 
@@ -596,43 +606,7 @@ void keep_times(const hipEvent_t* ev) {
   memcpy(g_last_ms, ms, sizeof(ms));
 }
 
-// k_dec_parse over every slot, the frame table back to the host (ev[0], ev[1] around the kernel); synchronises
-int parse_candidates(const DecArgs& a, size_t ng, FrameOut* h_fout, const hipEvent_t* ev, hipStream_t s) {
-  HIPCHK(hipEventRecord(ev[0], s));
-  if (ng) {
-    hipLaunchKernelGGL(k_dec_parse, dim3((unsigned)ng), dim3(kLanes), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(ev[1], s));
-  if (ng) HIPCHK(hipMemcpyAsync(h_fout, a.fout, sizeof(FrameOut) * ng * kLanes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return FRA_OK;
-}
-
-// the chain's first samples to the device, k_dec_restore and k_dec_scatter over the chained frames (ev[2..4]), the
-// failure flags back; enqueues only
-template <bool kClip>
-int restore_and_scatter(const DecArgs& a, size_t ng, int channels, int bs_max, const int64_t* h_samp0, uint32_t* h_fail,
-                        const hipEvent_t* ev, hipStream_t s) {
-  const size_t nslots = ng * kLanes;
-  if (ng) {
-    HIPCHK(hipMemcpyAsync((void*)a.samp0, h_samp0, sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(k_dec_restore<kClip>, dim3((unsigned)ng, (unsigned)channels), dim3(kLanes), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  else HIPCHK(hipEventRecord(ev[2], s));
-  HIPCHK(hipEventRecord(ev[3], s));
-  if (ng) {
-    hipLaunchKernelGGL(k_dec_scatter<kClip>, dim3((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes)), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(ev[4], s));
-  if (ng) HIPCHK(hipMemcpyAsync(h_fail, a.fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
-  return FRA_OK;
-}
-
-// what both entries check of a job and of its items before any GPU work
+// what both decode entries check of a job before any GPU work
 int check_job(const fra_ctx* ctx, const fra_decode_job* job, const fra_decoded* infos) {
   if (!ctx || !job || !infos) return fra_internal_set_error(FRA_E_INVALID, "null argument");
   const int ni = job->nitems;
@@ -649,9 +623,9 @@ int check_job(const fra_ctx* ctx, const fra_decode_job* job, const fra_decoded* 
   return FRA_OK;
 }
 
-int check_item(const fra_decode_job* job, int i) {
-  const fra_decode_item& it = job->items[i];
-  if (it.offset > job->len || it.bytes > job->len - it.offset)
+// ... and all three entries of item i of `len` bytes of data
+int check_item(const fra_decode_item& it, int i, uint64_t len) {
+  if (it.offset > len || it.bytes > len - it.offset)
     return fra_internal_set_error(FRA_E_INVALID, "item %d lies outside the data", i);
   const fra_window& w = it.window;
   if (w.row_off < 0 || w.col_off < 0 || w.width < 0 || (w.height < 0 && w.width != 1) || w.height == INT32_MIN)
@@ -670,6 +644,27 @@ int check_item(const fra_decode_job* job, int i) {
       return fra_internal_set_error(FRA_E_INVALID, "item %d: frame offsets run past the item", i);
   }
   return FRA_OK;
+}
+
+// what both decode entries refuse of an opened item: its channel count, then 32-bps samples into FRA_I16
+int check_stream(const fra_decode_job* job, int i, const StreamParams& sp) {
+  if (sp.channels != job->channels)
+    return fra_internal_set_error(FRA_E_INVALID, "item %d has %d channels, the destination %d", i, sp.channels,
+                                  job->channels);
+  if (job->denorm == FRA_DENORM_NONE && job->dst_dtype == FRA_I16 && sp.bps > 16)
+    return fra_internal_set_error(FRA_E_INVALID, "item %d: a %d-bps stream needs dst_dtype FRA_I32", i, sp.bps);
+  return FRA_OK;
+}
+
+void fill_info(fra_decoded& inf, const ItemPlan& ip, int64_t nframes, uint64_t nsamples, int nstreams) {
+  inf.sample_rate = ip.sp.sample_rate;
+  inf.channels = ip.sp.channels;
+  inf.bps = ip.sp.bps;
+  inf.blocksize = ip.sp.max_bs;
+  inf.nframes = nframes;
+  inf.nsamples = nsamples;
+  inf.nstreams = nstreams;
+  inf.audio_offset = ip.audio;
 }
 
 // the per-group and per-slot tables and the scratch of one call, owned by `sc`
@@ -714,6 +709,235 @@ void launch_verify(int dtype, dim3 grid, hipStream_t s, const DecArgs& a, const 
   }
 }
 
+// One call of any of the three entries: its stream and arena (Call), the five events of keep_times, the host's view
+// of the input, and the tables the kernels read, on the host and on the device (`a`).  The members are the steps the
+// entries share, in the order they take them; between them an entry puts its own checks, candidates and chain, and it
+// sets a.data itself: where the input lies on the device differs from entry to entry.
+struct Decode : Call {
+  hipEvent_t ev[5] = {};
+  const uint8_t* hdata = nullptr;  // the input as the host reads it (search path)
+  std::unique_ptr<uint8_t[]> hcopy;
+  std::vector<ItemPlan> plan;
+  std::vector<fra_dec::ScanUnit> units;
+  std::vector<DecItem> h_items;  // (an item that is not laid out stays zeroed and has no groups)
+  std::vector<DecGroup> h_groups;
+  std::vector<uint64_t> h_starts;
+  std::vector<FrameOut> h_fout;
+  std::vector<int64_t> h_samp0;
+  std::vector<uint32_t> h_fail;
+  uint64_t scratch_elems = 0;
+  int bs_max = 1;
+  size_t ng = 0, nslots = 0;
+  DecArgs a{};
+  size_t dst_bytes = 0;
+  bool by_window = false;  // a host destination comes back rectangle by rectangle
+
+  Decode(fra_ctx* ctx, int ni) : Call(ctx), plan((size_t)ni), h_items((size_t)ni) {}
+
+  // the host's view of the input: host memory as it is; of device memory a copy of `read` (the candidate search and
+  // the chain read the bytes on the host), none when `read` is empty
+  int host_view(const fra_decode_job* job, const std::vector<Range>& read) {
+    hdata = job->data_on_device ? nullptr : job->data;
+    if (read.empty() || !job->data_on_device) return FRA_OK;
+    hcopy.reset(new (std::nothrow) uint8_t[(size_t)job->len + 1]);  // (only the ranges copied below are touched)
+    if (!hcopy) return fra_internal_set_error(FRA_E_NOMEM, "out of host memory");
+    for (const Range& r : read)
+      if (r.bytes) HIPCHK(hipMemcpy(hcopy.get() + r.at, job->data + r.at, (size_t)r.bytes, hipMemcpyDeviceToHost));
+    hdata = hcopy.get();
+    return FRA_OK;
+  }
+
+  // item i's stream parameters: from the item beside its frame offsets, else from its STREAMINFO, and then its bytes
+  // from the first audio byte on are queued for the candidate search in units of 1 MiB
+  int open_item(const fra_decode_item& it, int i) {
+    ItemPlan& ip = plan[(size_t)i];
+    if (it.frame_offsets) {
+      ip.sp.sample_rate = 0;
+      ip.sp.channels = it.channels;
+      ip.sp.bps = it.bps;
+      ip.sp.max_bs = it.blocksize;
+      return FRA_OK;
+    }
+    ip.search = true;
+    const uint8_t* d = hdata + it.offset;
+    const size_t at = fra_dec::skip_id3(d, (size_t)it.bytes);
+    if (at == SIZE_MAX) return fra_internal_set_error(FRA_E_INVALID, "item %d: ID3v2 tag runs past the end of the data", i);
+    ip.audio = fra_dec::parse_metadata(d, (size_t)it.bytes, at, ip.sp);
+    if (!ip.audio) return fra_internal_set_error(FRA_E_INVALID, "item %d: not a FLAC stream (bad fLaC/STREAMINFO)", i);
+    if (ip.sp.channels < 1 || ip.sp.channels > 8 || ip.sp.bps < 4 || ip.sp.bps > 32)
+      return fra_internal_set_error(FRA_E_INVALID, "unsupported STREAMINFO (channels %d, bps %d)", ip.sp.channels,
+                                    ip.sp.bps);
+    for (uint64_t b = ip.audio; b < it.bytes; b += (1u << 20))
+      units.push_back({i, d, it.bytes, b, std::min<uint64_t>(it.bytes, b + (1u << 20)), &ip.sp, {}});
+    return FRA_OK;
+  }
+
+  // the queued search: every candidate of a searched item in its `cand`; true when anything was queued
+  bool scan() {
+    if (units.empty()) return false;
+    fra_dec::scan_units(units);
+    for (auto& u : units) {
+      auto& c = plan[(size_t)u.item].cand;
+      c.insert(c.end(), u.found.begin(), u.found.end());  // units are in byte order
+    }
+    return true;
+  }
+
+  // item i as the kernels see it: its bytes end at `end` of a.data and its tile lies at `at` of the destination;
+  // n candidate frames in groups of 64 (a group never spans items), `stride` scratch samples per frame and channel
+  void lay_out(int i, size_t n, int stride, uint64_t end, const fra_window& at, double dmin, double span) {
+    ItemPlan& ip = plan[(size_t)i];
+    bs_max = std::max(bs_max, stride);
+    DecItem& di = h_items[(size_t)i];
+    di.end = end;
+    di.channels = ip.sp.channels;
+    di.bps = ip.sp.bps;
+    di.sample_rate = ip.sp.sample_rate;
+    di.bs_stride = stride;
+    di.row_off = at.row_off;
+    di.col_off = at.col_off;
+    di.width = at.width;
+    di.height = at.height;
+    di.dmin = dmin;
+    di.span = span;
+    ip.first_group = (int32_t)h_groups.size();
+    ip.n = n;
+    for (size_t k = 0; k < n; k += kLanes) {
+      h_groups.push_back({scratch_elems, i, (int32_t)std::min<size_t>(kLanes, n - k)});
+      scratch_elems += (uint64_t)ip.sp.channels * (uint64_t)stride * kLanes;
+    }
+  }
+
+  // the slots of the groups laid out: start_of(i, k) is where frame k of item i starts in a.data
+  template <typename StartOf>
+  int slots(const char* too_many, StartOf&& start_of) {
+    ng = h_groups.size();
+    if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "%s", too_many);
+    nslots = ng * kLanes;
+    h_starts.assign(std::max<size_t>(1, nslots), kNoFrame);
+    for (size_t i = 0; i < plan.size(); i++)
+      for (size_t k = 0; k < plan[i].n; k++) h_starts[(size_t)plan[i].first_group * kLanes + k] = start_of((int)i, k);
+    return FRA_OK;
+  }
+
+  // the device side of the tables (and of `clips`, a windowed read's), the job's destination (none: the verify
+  // entry) -- device memory as it is; host memory staged, and copied in unless it comes back by_window, so that
+  // elements between the windows keep the caller's values either way -- the events, the uploads, cleared failure flags
+  int stage(const fra_decode_job* job, int64_t extent, const std::vector<DecClip>* clips) {
+    const size_t ni = h_items.size();
+    if (const int rc = alloc_tables(sc, a, ni, ng, scratch_elems)) return rc;
+    void* d_clips = nullptr;
+    if (clips) {
+      HIPCHK(sc.alloc(&d_clips, sizeof(DecClip) * ni));
+      a.clips = (const DecClip*)d_clips;
+    }
+    if (job) {
+      a.band_stride = job->band_stride;
+      a.row_stride = job->row_stride;
+      a.col_stride = job->col_stride;
+      a.dst_dtype = job->dst_dtype;
+      a.denorm = job->denorm;
+      dst_bytes = (size_t)extent * (size_t)elem_size(job->dst_dtype);
+      by_window = !job->dst_on_device && job->col_stride == 1;
+      a.dst = job->dst;
+      if (!job->dst_on_device) {
+        HIPCHK(sc.alloc(&a.dst, dst_bytes));
+        if (dst_bytes && !by_window) HIPCHK(hipMemcpyAsync(a.dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
+      }
+    }
+    for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
+    HIPCHK(hipMemcpyAsync((void*)a.items, h_items.data(), sizeof(DecItem) * ni, hipMemcpyHostToDevice, s));
+    if (clips) HIPCHK(hipMemcpyAsync(d_clips, clips->data(), sizeof(DecClip) * ni, hipMemcpyHostToDevice, s));
+    if (ng) {
+      HIPCHK(hipMemcpyAsync((void*)a.groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync((void*)a.starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemsetAsync(a.fail, 0, sizeof(uint32_t) * nslots, s));
+    }
+    return FRA_OK;
+  }
+
+  // k_dec_parse over every slot, the frame table back to the host in h_fout (ev[0], ev[1] around the kernel);
+  // synchronises.  h_samp0 is then the entry's chain to fill: the first sample of every chained frame
+  int parse_candidates() {
+    h_fout.resize(std::max<size_t>(1, nslots));
+    HIPCHK(hipEventRecord(ev[0], s));
+    if (ng) {
+      hipLaunchKernelGGL(k_dec_parse, dim3((unsigned)ng), dim3(kLanes), 0, s, a);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ev[1], s));
+    if (ng) HIPCHK(hipMemcpyAsync(h_fout.data(), a.fout, sizeof(FrameOut) * nslots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    h_samp0.assign(std::max<size_t>(1, nslots), -1);
+    return FRA_OK;
+  }
+
+  // k_dec_scatter's grid: (group, 64 samples of the largest block)
+  dim3 grid() const { return dim3((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes)); }
+
+  // the chain's first samples to the device, `restore` (an instance of k_dec_restore) over the chained frames, then
+  // second(): the kernel that consumes them, over grid() (ev[2..4]), the failure flags back; enqueues only
+  template <typename Second>
+  int restore_and(void (*restore)(DecArgs), int channels, Second&& second) {
+    h_fail.assign(std::max<size_t>(1, nslots), 0);
+    if (ng) {
+      HIPCHK(hipMemcpyAsync((void*)a.samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
+      HIPCHK(hipEventRecord(ev[2], s));
+      hipLaunchKernelGGL(restore, dim3((unsigned)ng, (unsigned)channels), dim3(kLanes), 0, s, a);
+      HIPCHK(hipGetLastError());
+    }
+    else HIPCHK(hipEventRecord(ev[2], s));
+    HIPCHK(hipEventRecord(ev[3], s));
+    if (ng) {
+      second();
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ev[4], s));
+    if (ng) HIPCHK(hipMemcpyAsync(h_fail.data(), a.fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
+    return FRA_OK;
+  }
+  template <bool kClip>
+  int restore_and_scatter(int channels) {
+    void (*const restore)(DecArgs) = k_dec_restore<kClip>;  // (named before k_dec_scatter: the code object's order)
+    return restore_and(restore, channels, [&] { hipLaunchKernelGGL(k_dec_scatter<kClip>, grid(), dim3(256), 0, s, a); });
+  }
+
+  // the stream waited for; FRA_E_INVALID for the first frame with a failure flag, named by its byte in `bytes`
+  int wait_and_check(const uint64_t* bytes) {
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t k = 0; k < nslots; k++)
+      if (h_fail[k])
+        return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
+                                                     "(frame at byte %llu)", (unsigned long long)bytes[k]);
+    return FRA_OK;
+  }
+
+  // the end of a decode: a host destination back -- by_window the rectangles of every band, else the whole extent --
+  // then wait_and_check, and the kernel times kept on success
+  int finish(const fra_decode_job* job, const std::vector<Rect>& rects, const uint64_t* bytes) {
+    if (by_window) {
+      const size_t es = (size_t)elem_size(job->dst_dtype);
+      for (const Rect& r : rects)
+        for (int c = 0; c < job->channels; c++) {
+          const size_t off = ((size_t)c * (size_t)job->band_stride + (size_t)r.row0 * (size_t)job->row_stride +
+                              (size_t)r.col0) * es;
+          if (job->row_stride == 0 || r.rows == 1)
+            HIPCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)a.dst + off, (size_t)r.cols * es,
+                                  hipMemcpyDeviceToHost, s));
+          else
+            HIPCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)a.dst + off,
+                                    (size_t)job->row_stride * es, (size_t)r.cols * es, (size_t)r.rows,
+                                    hipMemcpyDeviceToHost, s));
+        }
+    } else if (!job->dst_on_device && dst_bytes) {
+      HIPCHK(hipMemcpyAsync(job->dst, a.dst, dst_bytes, hipMemcpyDeviceToHost, s));
+    }
+    if (const int rc = wait_and_check(bytes)) return rc;
+    keep_times(ev);
+    return FRA_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -730,181 +954,80 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
   memset(infos, 0, sizeof(fra_decoded) * (size_t)ni);
   if (ni == 0) return FRA_OK;
 
-  bool any_search = false;
-  int64_t extent = 0;  // elements of dst addressed, from element 0
+  std::vector<Range> read;  // what the host reads of the input: all of it when any item is searched
+  int64_t extent = 0;       // elements of dst addressed, from element 0
   for (int i = 0; i < ni; i++) {
-    if (const int rc = check_item(job, i)) return rc;
     const fra_decode_item& it = job->items[i];
+    if (const int rc = check_item(it, i, job->len)) return rc;
     const fra_window& w = it.window;
-    if (!it.frame_offsets) any_search = true;
+    if (!it.frame_offsets && read.empty()) read.push_back({0, job->len});
     if (w.height != 0 && w.width > 0)
       extent = std::max<int64_t>(extent, (int64_t)(job->channels - 1) * job->band_stride +
                                              ((int64_t)w.row_off + std::abs(w.height) - 1) * job->row_stride +
                                              ((int64_t)w.col_off + w.width - 1) * job->col_stride + 1);
   }
 
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // device buffers and events of this call, released on every path
-  hipEvent_t ev[5] = {};
-
-  // ---- the input on both sides where needed
-  const uint8_t* hdata = job->data_on_device ? nullptr : job->data;
-  std::unique_ptr<uint8_t[]> hcopy;
-  if (any_search && job->data_on_device) {  // the candidate search and the chain read the bytes on the host
-    hcopy.reset(new (std::nothrow) uint8_t[(size_t)job->len + 1]);
-    if (!hcopy) return fra_internal_set_error(FRA_E_NOMEM, "out of host memory");
-    if (job->len) HIPCHK(hipMemcpy(hcopy.get(), job->data, (size_t)job->len, hipMemcpyDeviceToHost));
-    hdata = hcopy.get();
-  }
-  const uint8_t* ddata = job->data;
+  Decode c(ctx, ni);
+  if (const int rc = c.host_view(job, read)) return rc;
+  c.a.data = job->data;  // a host input is uploaded whole, so every entry of h_starts is a byte of job->data
   if (!job->data_on_device) {
     void* p = nullptr;
-    HIPCHK(sc.alloc(&p, (size_t)job->len));
-    if (job->len) HIPCHK(hipMemcpyAsync(p, job->data, (size_t)job->len, hipMemcpyHostToDevice, s));
-    ddata = (const uint8_t*)p;
+    HIPCHK(c.sc.alloc(&p, (size_t)job->len));
+    if (job->len) HIPCHK(hipMemcpyAsync(p, job->data, (size_t)job->len, hipMemcpyHostToDevice, c.s));
+    c.a.data = (const uint8_t*)p;
   }
 
-  // ---- candidates
-  std::vector<ItemPlan> plan((size_t)ni);
-  std::vector<fra_dec::ScanUnit> units;
+  // ---- candidates: every frame of the offsets, every sync position of a searched stream
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = job->items[i];
-    ItemPlan& ip = plan[(size_t)i];
-    if (it.frame_offsets) {
-      ip.sp.sample_rate = 0;
-      ip.sp.channels = it.channels;
-      ip.sp.bps = it.bps;
-      ip.sp.max_bs = it.blocksize;
-      ip.cand.reserve((size_t)it.nframes);
-      for (int f = 0; f < it.nframes; f++) ip.cand.push_back({it.frame_offsets[f], it.blocksize});
-      continue;
-    }
-    ip.search = true;
-    const uint8_t* d = hdata + it.offset;
-    const size_t at = fra_dec::skip_id3(d, (size_t)it.bytes);
-    if (at == SIZE_MAX) return fra_internal_set_error(FRA_E_INVALID, "item %d: ID3v2 tag runs past the end of the data", i);
-    ip.audio = fra_dec::parse_metadata(d, (size_t)it.bytes, at, ip.sp);
-    if (!ip.audio) return fra_internal_set_error(FRA_E_INVALID, "item %d: not a FLAC stream (bad fLaC/STREAMINFO)", i);
-    if (ip.sp.channels < 1 || ip.sp.channels > 8 || ip.sp.bps < 4 || ip.sp.bps > 32)
-      return fra_internal_set_error(FRA_E_INVALID, "unsupported STREAMINFO (channels %d, bps %d)", ip.sp.channels,
-                                    ip.sp.bps);
-    for (uint64_t b = ip.audio; b < it.bytes; b += (1u << 20))
-      units.push_back({i, d, it.bytes, b, std::min<uint64_t>(it.bytes, b + (1u << 20)), &ip.sp, {}});
+    if (const int rc = c.open_item(it, i)) return rc;
+    if (!it.frame_offsets) continue;
+    auto& cand = c.plan[(size_t)i].cand;
+    cand.reserve((size_t)it.nframes);
+    for (int f = 0; f < it.nframes; f++) cand.push_back({it.frame_offsets[f], it.blocksize});
   }
-  if (!units.empty()) {
-    fra_dec::scan_units(units);
-    for (auto& u : units) {
-      auto& c = plan[(size_t)u.item].cand;
-      c.insert(c.end(), u.found.begin(), u.found.end());  // units are in byte order
-    }
-  }
+  c.scan();
 
-  // ---- groups of 64 candidate frames (a group never spans items), scratch layout
-  std::vector<DecItem> h_items((size_t)ni);
-  std::vector<DecGroup> h_groups;
-  uint64_t scratch_elems = 0;
-  int bs_max = 1;
+  // ---- scratch of the largest candidate block size per frame; a capacity window is rows of one sample
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = job->items[i];
-    ItemPlan& ip = plan[(size_t)i];
-    if (ip.sp.channels != job->channels)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d has %d channels, the destination %d", i, ip.sp.channels,
-                                    job->channels);
-    if (job->denorm == FRA_DENORM_NONE && job->dst_dtype == FRA_I16 && ip.sp.bps > 16)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d: a %d-bps stream needs dst_dtype FRA_I32", i, ip.sp.bps);
+    const ItemPlan& ip = c.plan[(size_t)i];
+    if (const int rc = check_stream(job, i, ip.sp)) return rc;
     int stride = 1;
-    for (const HostCand& c : ip.cand) stride = std::max(stride, c.bs);
-    bs_max = std::max(bs_max, stride);
-    DecItem& di = h_items[(size_t)i];
-    di.end = it.offset + it.bytes;
-    di.channels = ip.sp.channels;
-    di.bps = ip.sp.bps;
-    di.sample_rate = ip.sp.sample_rate;
-    di.bs_stride = stride;
-    di.row_off = it.window.row_off;
-    di.col_off = it.window.col_off;
-    di.width = it.window.width;
-    di.height = std::abs(it.window.height);  // (< 0: a capacity in rows of one sample)
-    di.dmin = it.data_min;
-    di.span = it.data_max - it.data_min;
-    ip.first_group = (int32_t)h_groups.size();
-    ip.ngroups = (int32_t)((ip.cand.size() + kLanes - 1) / kLanes);
-    for (int g = 0; g < ip.ngroups; g++) {
-      const int cnt = (int)std::min<size_t>(kLanes, ip.cand.size() - (size_t)g * kLanes);
-      h_groups.push_back({scratch_elems, i, cnt});
-      scratch_elems += (uint64_t)ip.sp.channels * (uint64_t)stride * kLanes;
-    }
+    for (const HostCand& k : ip.cand) stride = std::max(stride, k.bs);
+    c.lay_out(i, ip.cand.size(), stride, it.offset + it.bytes,
+              {it.window.row_off, it.window.col_off, std::abs(it.window.height), it.window.width}, it.data_min,
+              it.data_max - it.data_min);
   }
-  const size_t ng = h_groups.size();
-  if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "too many candidate frames");
-  const size_t nslots = ng * kLanes;
-  std::vector<uint64_t> h_starts(std::max<size_t>(1, nslots), kNoFrame);
-  for (int i = 0; i < ni; i++) {
-    const ItemPlan& ip = plan[(size_t)i];
-    for (size_t k = 0; k < ip.cand.size(); k++)
-      h_starts[(size_t)ip.first_group * kLanes + k] = job->items[i].offset + ip.cand[k].start;
-  }
-
-  DecArgs a{};
-  a.data = ddata;
-  a.band_stride = job->band_stride;
-  a.row_stride = job->row_stride;
-  a.col_stride = job->col_stride;
-  a.dst_dtype = job->dst_dtype;
-  a.denorm = job->denorm;
-  void* d_dst = nullptr;
-  if (const int rc = alloc_tables(sc, a, (size_t)ni, ng, scratch_elems)) return rc;
-  void *d_items = (void*)a.items, *d_groups = (void*)a.groups, *d_starts = (void*)a.starts, *d_fail = a.fail;
-  const size_t dst_bytes = (size_t)extent * (size_t)elem_size(job->dst_dtype);
-  // a host destination with contiguous rows comes back window by window; any other layout is staged whole, so
-  // that elements between the windows keep the caller's values either way
-  const bool by_window = !job->dst_on_device && job->col_stride == 1;
-  if (job->dst_on_device) {
-    d_dst = job->dst;
-  } else {
-    HIPCHK(sc.alloc(&d_dst, dst_bytes));
-    if (dst_bytes && !by_window) HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
-  }
-  a.dst = d_dst;
-  for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
-  HIPCHK(hipMemcpyAsync(d_items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
-  if (ng) {
-    HIPCHK(hipMemcpyAsync(d_groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(uint32_t) * nslots, s));
-  }
-
-  // ---- parse every candidate
-  std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
-  if (const int rc = parse_candidates(a, ng, h_fout.data(), ev, s)) return rc;
+  if (const int rc = c.slots("too many candidate frames",
+                             [&](int i, size_t k) { return job->items[i].offset + c.plan[(size_t)i].cand[k].start; }))
+    return rc;
+  if (const int rc = c.stage(job, extent, nullptr)) return rc;
+  if (const int rc = c.parse_candidates()) return rc;
 
   // ---- chain (item-relative byte positions, the host decoder's wording)
-  std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = job->items[i];
-    const ItemPlan& ip = plan[(size_t)i];
+    const ItemPlan& ip = c.plan[(size_t)i];
     const size_t s0 = (size_t)ip.first_group * kLanes;
     uint64_t nsamp = 0;
     int64_t nframes = 0;
     int nstreams = 1;
     if (!ip.search) {
       for (size_t k = 0; k < ip.cand.size(); k++) {
-        const FrameOut& fo = h_fout[s0 + k];
+        const FrameOut& fo = c.h_fout[s0 + k];
         if (fo.status == ST_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
         if (fo.status != ST_OK || fo.len != it.frame_offsets[k + 1] - it.frame_offsets[k])
           return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
                                         (unsigned long long)it.frame_offsets[k]);
-        h_samp0[s0 + k] = (int64_t)nsamp;
+        c.h_samp0[s0 + k] = (int64_t)nsamp;
         nsamp += (uint64_t)fo.n;
         nframes++;
       }
     } else {
-      const fra_dec::ChainResult cr = fra_dec::chain_stream(hdata + it.offset, it.bytes, ip.audio, ip.sp,
+      const fra_dec::ChainResult cr = fra_dec::chain_stream(c.hdata + it.offset, it.bytes, ip.audio, ip.sp,
                                                             (job->flags & FRA_DECODE_CONCAT) != 0, ip.cand,
-                                                            h_fout.data() + s0, h_samp0.data() + s0);
+                                                            c.h_fout.data() + s0, c.h_samp0.data() + s0);
       if (cr.code == fra_dec::CHAIN_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
       if (cr.code == fra_dec::CHAIN_CONCAT_FORMAT)
         return fra_internal_set_error(FRA_E_INVALID, "concatenated stream at byte %llu has a different format",
@@ -927,49 +1050,18 @@ FRA_API int fra_decode_device(fra_ctx* ctx, const fra_decode_job* job, fra_decod
     } else if (nsamp != (uint64_t)it.window.height * (uint64_t)it.window.width)
       return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream has %llu samples per channel, its window %d x %d",
                                     i, (unsigned long long)nsamp, it.window.height, it.window.width);
-    fra_decoded& inf = infos[i];
-    inf.sample_rate = ip.sp.sample_rate;
-    inf.channels = ip.sp.channels;
-    inf.bps = ip.sp.bps;
-    inf.blocksize = ip.sp.max_bs;
-    inf.nframes = nframes;
-    inf.nsamples = nsamp;
-    inf.nstreams = nstreams;
-    inf.audio_offset = ip.audio;
+    fill_info(infos[i], ip, nframes, nsamp, nstreams);
   }
 
-  // ---- restore and scatter the chained frames
-  std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
-  if (const int rc = restore_and_scatter<false>(a, ng, job->channels, bs_max, h_samp0.data(), h_fail.data(), ev, s))
-    return rc;
-  if (by_window) {
-    const size_t es = (size_t)elem_size(job->dst_dtype);
-    for (int i = 0; i < ni; i++) {
-      const fra_window& w = job->items[i].window;
-      const int64_t rows = w.height < 0 ? (int64_t)infos[i].nsamples : w.height;
-      if (rows <= 0 || w.width <= 0) continue;
-      for (int c = 0; c < job->channels; c++) {
-        const size_t off = ((size_t)c * (size_t)job->band_stride + (size_t)w.row_off * (size_t)job->row_stride +
-                            (size_t)w.col_off) * es;
-        if (job->row_stride == 0 || rows == 1)
-          HIPCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)d_dst + off, (size_t)w.width * es,
-                              hipMemcpyDeviceToHost, s));
-        else
-          HIPCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)d_dst + off,
-                                (size_t)job->row_stride * es, (size_t)w.width * es, (size_t)rows,
-                                hipMemcpyDeviceToHost, s));
-      }
-    }
-  } else if (!job->dst_on_device && dst_bytes) {
-    HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
+  // ---- restore and scatter the chained frames; a host destination with contiguous rows comes back window by window
+  if (const int rc = c.restore_and_scatter<false>(job->channels)) return rc;
+  std::vector<Rect> rects;
+  for (int i = 0; c.by_window && i < ni; i++) {
+    const fra_window& w = job->items[i].window;
+    const int64_t rows = w.height < 0 ? (int64_t)infos[i].nsamples : w.height;
+    if (rows > 0 && w.width > 0) rects.push_back({w.row_off, w.col_off, rows, w.width});
   }
-  HIPCHK(hipStreamSynchronize(s));
-  for (size_t k = 0; k < nslots; k++)
-    if (h_fail[k])
-      return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
-                                                   "(frame at byte %llu)", (unsigned long long)h_starts[k]);
-  keep_times(ev);
-  return FRA_OK;
+  return c.finish(job, rects, c.h_starts.data());
 }
 
 // The windowed read: as fra_decode_device, for the frames that hold samples of `roi` only.  Tables, scratch and
@@ -991,11 +1083,11 @@ FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, co
   if (ni == 0) return FRA_OK;
 
   std::vector<fra_dec::FrameSel> sel((size_t)ni);
-  bool any_search = false;
-  int64_t extent = 0;  // elements of dst addressed, from element 0 (= the region's first pixel)
+  std::vector<Range> read;  // what the host reads of the input: the searched items that the region hits
+  int64_t extent = 0;       // elements of dst addressed, from element 0 (= the region's first pixel)
   for (int i = 0; i < ni; i++) {
-    if (const int rc = check_item(job, i)) return rc;
     const fra_decode_item& it = job->items[i];
+    if (const int rc = check_item(it, i, job->len)) return rc;
     const fra_window& w = it.window;
     if (w.height < 0)
       return fra_internal_set_error(FRA_E_INVALID, "item %d: a capacity window (height < 0) is not supported by the "
@@ -1005,109 +1097,59 @@ FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, co
                                  roi->width);
     if (!sl.hit) continue;
     if (it.frame_offsets) sl.set_blocksize(it.blocksize);
-    else any_search = true;
+    else read.push_back({it.offset, it.bytes});
     extent = std::max<int64_t>(extent, (int64_t)(job->channels - 1) * job->band_stride +
                                            ((int64_t)sl.rb - 1 - roi->row_off) * job->row_stride +
                                            ((int64_t)sl.cb - 1 - roi->col_off) * job->col_stride + 1);
   }
 
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;
-  hipEvent_t ev[5] = {};
-
-  // ---- the bytes of the intersecting search items on the host
-  const uint8_t* hdata = job->data_on_device ? nullptr : job->data;
-  std::unique_ptr<uint8_t[]> hcopy;
-  if (any_search && job->data_on_device) {
-    hcopy.reset(new (std::nothrow) uint8_t[(size_t)job->len + 1]);  // (only the ranges copied below are touched)
-    if (!hcopy) return fra_internal_set_error(FRA_E_NOMEM, "out of host memory");
-    for (int i = 0; i < ni; i++) {
-      const fra_decode_item& it = job->items[i];
-      if (sel[(size_t)i].hit && !it.frame_offsets && it.bytes)
-        HIPCHK(hipMemcpy(hcopy.get() + it.offset, job->data + it.offset, (size_t)it.bytes, hipMemcpyDeviceToHost));
-    }
-    hdata = hcopy.get();
-  }
+  Decode c(ctx, ni);
+  if (const int rc = c.host_view(job, read)) return rc;
 
   // ---- candidates of the selected frames
-  std::vector<ItemPlan> plan((size_t)ni);
-  std::vector<std::vector<HostCand>> all((size_t)ni);  // search path: every candidate of the stream
-  std::vector<fra_dec::ScanUnit> units;
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = job->items[i];
-    ItemPlan& ip = plan[(size_t)i];
+    ItemPlan& ip = c.plan[(size_t)i];
     fra_dec::FrameSel& sl = sel[(size_t)i];
     if (!sl.hit) continue;
+    if (const int rc = c.open_item(it, i)) return rc;
     if (it.frame_offsets) {
-      ip.sp.sample_rate = 0;
-      ip.sp.channels = it.channels;
-      ip.sp.bps = it.bps;
-      ip.sp.max_bs = it.blocksize;
       if (sl.f_hi >= it.nframes) return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
       // frame f is entry f of the offsets and starts at sample f * blocksize (header numbers are not consulted)
       for (int64_t f = sl.f_lo; f <= sl.f_hi; f++) ip.cand.push_back({it.frame_offsets[f], it.blocksize, 0, (uint64_t)f});
       continue;
     }
-    ip.search = true;
-    const uint8_t* d = hdata + it.offset;
-    const size_t at = fra_dec::skip_id3(d, (size_t)it.bytes);
-    if (at == SIZE_MAX) return fra_internal_set_error(FRA_E_INVALID, "item %d: ID3v2 tag runs past the end of the data", i);
-    ip.audio = fra_dec::parse_metadata(d, (size_t)it.bytes, at, ip.sp);
-    if (!ip.audio) return fra_internal_set_error(FRA_E_INVALID, "item %d: not a FLAC stream (bad fLaC/STREAMINFO)", i);
-    if (ip.sp.channels < 1 || ip.sp.channels > 8 || ip.sp.bps < 4 || ip.sp.bps > 32)
-      return fra_internal_set_error(FRA_E_INVALID, "unsupported STREAMINFO (channels %d, bps %d)", ip.sp.channels,
-                                    ip.sp.bps);
     if (ip.sp.min_bs != ip.sp.max_bs || ip.sp.max_bs < 1)
       return fra_internal_set_error(FRA_E_INVALID, "item %d: the windowed read needs a fixed-blocksize stream "
                                                    "(STREAMINFO block sizes %d .. %d)", i, ip.sp.min_bs, ip.sp.max_bs);
     sl.set_blocksize(ip.sp.max_bs);
     if (ip.sp.total_samples && (uint64_t)sl.p_hi > ip.sp.total_samples)
       return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
-    for (uint64_t b = ip.audio; b < it.bytes; b += (1u << 20))
-      units.push_back({i, d, it.bytes, b, std::min<uint64_t>(it.bytes, b + (1u << 20)), &ip.sp, {}});
   }
-  if (!units.empty()) {
-    fra_dec::scan_units(units);
-    for (auto& u : units) {
-      auto& c = all[(size_t)u.item];
-      c.insert(c.end(), u.found.begin(), u.found.end());  // units are in byte order
-    }
+  std::vector<std::vector<HostCand>> all((size_t)ni);  // search path: every candidate of the stream
+  if (c.scan())
     for (int i = 0; i < ni; i++) {
-      ItemPlan& ip = plan[(size_t)i];
+      ItemPlan& ip = c.plan[(size_t)i];
       if (!ip.search) continue;
-      const auto& c = all[(size_t)i];
-      if (!c.empty() && c.front().start == ip.audio && c.front().variable)
+      all[(size_t)i].swap(ip.cand);
+      const auto& found = all[(size_t)i];
+      if (!found.empty() && found.front().start == ip.audio && found.front().variable)
         return fra_internal_set_error(FRA_E_INVALID, "item %d: the windowed read needs a fixed-blocksize stream "
                                                      "(variable-blocksize frame header)", i);
-      fra_dec::filter_candidates(c, sel[(size_t)i].f_lo, sel[(size_t)i].f_hi, ip.cand);
+      fra_dec::filter_candidates(found, sel[(size_t)i].f_lo, sel[(size_t)i].f_hi, ip.cand);
     }
-  }
 
-  // ---- groups of 64 selected candidates, scratch layout, and where each item's bytes lie on the device: a host
-  //      input is uploaded as the spans that hold the selected frames, one after the other
-  std::vector<DecItem> h_items((size_t)ni);
+  // ---- where each item's bytes lie on the device: a host input is uploaded as the spans that hold the selected
+  //      frames, one after the other; scratch of the stream's block size per frame; the tile relative to the region
   std::vector<DecClip> h_clips((size_t)ni);
-  std::vector<DecGroup> h_groups;
   std::vector<uint64_t> dev_base((size_t)ni, 0), span_a((size_t)ni, 0), span_b((size_t)ni, 0);
-  uint64_t scratch_elems = 0, upload = 0;
-  int bs_max = 1;
+  uint64_t upload = 0;
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = job->items[i];
-    ItemPlan& ip = plan[(size_t)i];
+    const ItemPlan& ip = c.plan[(size_t)i];
     const fra_dec::FrameSel& sl = sel[(size_t)i];
-    DecItem& di = h_items[(size_t)i];
-    memset(&di, 0, sizeof(di));
     if (!sl.hit) continue;
-    if (ip.sp.channels != job->channels)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d has %d channels, the destination %d", i, ip.sp.channels,
-                                    job->channels);
-    if (job->denorm == FRA_DENORM_NONE && job->dst_dtype == FRA_I16 && ip.sp.bps > 16)
-      return fra_internal_set_error(FRA_E_INVALID, "item %d: a %d-bps stream needs dst_dtype FRA_I32", i, ip.sp.bps);
-    const int stride = ip.sp.max_bs;
-    bs_max = std::max(bs_max, stride);
+    if (const int rc = check_stream(job, i, ip.sp)) return rc;
     if (!ip.cand.empty()) {
       span_a[(size_t)i] = ip.cand.front().start;
       span_b[(size_t)i] = ip.search ? it.bytes : it.frame_offsets[sl.f_hi + 1];
@@ -1119,92 +1161,38 @@ FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, co
       dev_base[(size_t)i] = upload - span_a[(size_t)i];  // (modulo 2^64; only dev_base + [span_a, span_b) is addressed)
       upload += span_b[(size_t)i] - span_a[(size_t)i];
     }
-    di.end = dev_base[(size_t)i] + span_b[(size_t)i];
-    di.channels = ip.sp.channels;
-    di.bps = ip.sp.bps;
-    di.sample_rate = ip.sp.sample_rate;
-    di.bs_stride = stride;
-    di.row_off = it.window.row_off - roi->row_off;
-    di.col_off = it.window.col_off - roi->col_off;
-    di.width = it.window.width;
-    di.height = it.window.height;
+    c.lay_out(i, ip.cand.size(), ip.sp.max_bs, dev_base[(size_t)i] + span_b[(size_t)i],
+              {it.window.row_off - roi->row_off, it.window.col_off - roi->col_off, it.window.height, it.window.width},
+              it.data_min, it.data_max - it.data_min);
     h_clips[(size_t)i] = {sl.ra - it.window.row_off, sl.rb - it.window.row_off, sl.ca - it.window.col_off,
                           sl.cb - it.window.col_off, sl.p_lo, sl.p_hi};
-    di.dmin = it.data_min;
-    di.span = it.data_max - it.data_min;
-    ip.first_group = (int32_t)h_groups.size();
-    ip.ngroups = (int32_t)((ip.cand.size() + kLanes - 1) / kLanes);
-    for (int g = 0; g < ip.ngroups; g++) {
-      const int cnt = (int)std::min<size_t>(kLanes, ip.cand.size() - (size_t)g * kLanes);
-      h_groups.push_back({scratch_elems, i, cnt});
-      scratch_elems += (uint64_t)ip.sp.channels * (uint64_t)stride * kLanes;
-    }
   }
-  const size_t ng = h_groups.size();
-  if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "too many candidate frames");
-  const size_t nslots = ng * kLanes;
-  std::vector<uint64_t> h_starts(std::max<size_t>(1, nslots), kNoFrame);
-  std::vector<uint64_t> h_rel(std::max<size_t>(1, nslots), 0);  // item-relative, for messages
+  if (const int rc = c.slots("too many candidate frames",
+                             [&](int i, size_t k) { return dev_base[(size_t)i] + c.plan[(size_t)i].cand[k].start; }))
+    return rc;
+  std::vector<uint64_t> h_rel(std::max<size_t>(1, c.nslots), 0);  // item-relative, for messages
   for (int i = 0; i < ni; i++) {
-    const ItemPlan& ip = plan[(size_t)i];
-    for (size_t k = 0; k < ip.cand.size(); k++) {
-      h_starts[(size_t)ip.first_group * kLanes + k] = dev_base[(size_t)i] + ip.cand[k].start;
-      h_rel[(size_t)ip.first_group * kLanes + k] = ip.cand[k].start;
-    }
+    const ItemPlan& ip = c.plan[(size_t)i];
+    for (size_t k = 0; k < ip.cand.size(); k++) h_rel[(size_t)ip.first_group * kLanes + k] = ip.cand[k].start;
   }
-
-  DecArgs a{};
-  a.band_stride = job->band_stride;
-  a.row_stride = job->row_stride;
-  a.col_stride = job->col_stride;
-  a.dst_dtype = job->dst_dtype;
-  a.denorm = job->denorm;
-  if (job->data_on_device) {
-    a.data = job->data;
-  } else {
+  c.a.data = job->data;
+  if (!job->data_on_device) {
     void* p = nullptr;
-    HIPCHK(sc.alloc(&p, (size_t)upload));
+    HIPCHK(c.sc.alloc(&p, (size_t)upload));
     for (int i = 0; i < ni; i++)
       if (span_b[(size_t)i] > span_a[(size_t)i])
         HIPCHK(hipMemcpyAsync((uint8_t*)p + (dev_base[(size_t)i] + span_a[(size_t)i]),
                               job->data + job->items[i].offset + span_a[(size_t)i],
-                              (size_t)(span_b[(size_t)i] - span_a[(size_t)i]), hipMemcpyHostToDevice, s));
-    a.data = (const uint8_t*)p;
+                              (size_t)(span_b[(size_t)i] - span_a[(size_t)i]), hipMemcpyHostToDevice, c.s));
+    c.a.data = (const uint8_t*)p;
   }
-  if (const int rc = alloc_tables(sc, a, (size_t)ni, ng, scratch_elems)) return rc;
-  void* d_clips = nullptr;
-  HIPCHK(sc.alloc(&d_clips, sizeof(DecClip) * (size_t)ni));
-  a.clips = (const DecClip*)d_clips;
-  void* d_dst = nullptr;
-  const size_t es = (size_t)elem_size(job->dst_dtype);
-  const size_t dst_bytes = (size_t)extent * es;
-  // as fra_decode_device: contiguous rows come back intersection by intersection, any other layout is staged whole
-  const bool by_window = !job->dst_on_device && job->col_stride == 1;
-  if (job->dst_on_device) {
-    d_dst = job->dst;
-  } else {
-    HIPCHK(sc.alloc(&d_dst, dst_bytes));
-    if (dst_bytes && !by_window) HIPCHK(hipMemcpyAsync(d_dst, job->dst, dst_bytes, hipMemcpyHostToDevice, s));
-  }
-  a.dst = d_dst;
-  for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
-  HIPCHK(hipMemcpyAsync((void*)a.items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_clips, h_clips.data(), sizeof(DecClip) * (size_t)ni, hipMemcpyHostToDevice, s));
-  if (ng) {
-    HIPCHK(hipMemcpyAsync((void*)a.groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync((void*)a.starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(a.fail, 0, sizeof(uint32_t) * nslots, s));
-  }
-
-  // ---- parse the selected candidates
-  std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
-  if (const int rc = parse_candidates(a, ng, h_fout.data(), ev, s)) return rc;
+  if (const int rc = c.stage(job, extent, &h_clips)) return rc;
+  if (const int rc = c.parse_candidates()) return rc;
 
   // ---- the selected frames: CRC-16 (status), byte-contiguous, full blocks, reaching the last needed sample
-  std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = job->items[i];
-    const ItemPlan& ip = plan[(size_t)i];
+    const ItemPlan& ip = c.plan[(size_t)i];
     const fra_dec::FrameSel& sl = sel[(size_t)i];
     if (!sl.hit) continue;
     const size_t s0 = (size_t)ip.first_group * kLanes;
@@ -1212,21 +1200,21 @@ FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, co
     int64_t nframes = 0;
     if (!ip.search) {
       for (size_t k = 0; k < ip.cand.size(); k++) {
-        const FrameOut& fo = h_fout[s0 + k];
+        const FrameOut& fo = c.h_fout[s0 + k];
         const int64_t f = sl.f_lo + (int64_t)k;
         if (fo.status == ST_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
         if (fo.status != ST_OK || fo.len != it.frame_offsets[f + 1] - it.frame_offsets[f] ||
             (fo.n != bs && f != it.nframes - 1))
           return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
                                         (unsigned long long)it.frame_offsets[f]);
-        h_samp0[s0 + k] = f * bs;
+        c.h_samp0[s0 + k] = f * bs;
         nframes++;
       }
-      if (sl.f_hi * bs + h_fout[s0 + ip.cand.size() - 1].n < sl.p_hi)
+      if (sl.f_hi * bs + c.h_fout[s0 + ip.cand.size() - 1].n < sl.p_hi)
         return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
     } else {
       const fra_dec::ChainResult cr = fra_dec::chain_window(it.bytes, ip.audio, bs, sl, all[(size_t)i], ip.cand,
-                                                            h_fout.data() + s0, h_samp0.data() + s0);
+                                                            c.h_fout.data() + s0, c.h_samp0.data() + s0);
       if (cr.code == fra_dec::CHAIN_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
       if (cr.code == fra_dec::CHAIN_ENDS_EARLY)
         return fra_internal_set_error(FRA_E_INVALID, "item %d: the stream ends before the window", i);
@@ -1235,46 +1223,17 @@ FRA_API int fra_decode_device_window(fra_ctx* ctx, const fra_decode_job* job, co
                                       (unsigned long long)cr.byte);
       nframes = cr.nframes;
     }
-    fra_decoded& inf = infos[i];
-    inf.sample_rate = ip.sp.sample_rate;
-    inf.channels = ip.sp.channels;
-    inf.bps = ip.sp.bps;
-    inf.blocksize = ip.sp.max_bs;
-    inf.nframes = nframes;
-    inf.nsamples = (uint64_t)(sl.rb - sl.ra) * (uint64_t)(sl.cb - sl.ca);
-    inf.nstreams = 1;
-    inf.audio_offset = ip.audio;
+    fill_info(infos[i], ip, nframes, (uint64_t)(sl.rb - sl.ra) * (uint64_t)(sl.cb - sl.ca), 1);
   }
 
-  // ---- restore and scatter
-  std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
-  if (const int rc = restore_and_scatter<true>(a, ng, job->channels, bs_max, h_samp0.data(), h_fail.data(), ev, s))
-    return rc;
-  if (by_window) {
-    for (int i = 0; i < ni; i++) {
-      const fra_dec::FrameSel& sl = sel[(size_t)i];
-      if (!sl.hit) continue;
-      const size_t rows = (size_t)(sl.rb - sl.ra), cols = (size_t)(sl.cb - sl.ca);
-      for (int c = 0; c < job->channels; c++) {
-        const size_t off = ((size_t)c * (size_t)job->band_stride +
-                            (size_t)(sl.ra - roi->row_off) * (size_t)job->row_stride + (size_t)(sl.ca - roi->col_off)) * es;
-        if (job->row_stride == 0 || rows == 1)
-          HIPCHK(hipMemcpyAsync((uint8_t*)job->dst + off, (const uint8_t*)d_dst + off, cols * es, hipMemcpyDeviceToHost, s));
-        else
-          HIPCHK(hipMemcpy2DAsync((uint8_t*)job->dst + off, (size_t)job->row_stride * es, (const uint8_t*)d_dst + off,
-                                  (size_t)job->row_stride * es, cols * es, rows, hipMemcpyDeviceToHost, s));
-      }
-    }
-  } else if (!job->dst_on_device && dst_bytes) {
-    HIPCHK(hipMemcpyAsync(job->dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
+  // ---- restore and scatter; a host destination with contiguous rows comes back intersection by intersection
+  if (const int rc = c.restore_and_scatter<true>(job->channels)) return rc;
+  std::vector<Rect> rects;
+  for (int i = 0; c.by_window && i < ni; i++) {
+    const fra_dec::FrameSel& sl = sel[(size_t)i];
+    if (sl.hit) rects.push_back({sl.ra - roi->row_off, sl.ca - roi->col_off, sl.rb - sl.ra, sl.cb - sl.ca});
   }
-  HIPCHK(hipStreamSynchronize(s));
-  for (size_t k = 0; k < nslots; k++)
-    if (h_fail[k])
-      return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
-                                                   "(frame at byte %llu)", (unsigned long long)h_rel[k]);
-  keep_times(ev);
-  return FRA_OK;
+  return c.finish(job, rects, h_rel.data());
 }
 
 // The verify entry (fra_verify.h): fra_decode_device's offsets path up to k_dec_restore, then k_dec_verify against
@@ -1293,14 +1252,9 @@ int fra_internal_verify_device(fra_ctx* ctx, const uint8_t* data, uint64_t len, 
   if (channels < 1 || channels > 8 || src->band_stride < 0 || src->row_stride < 0 || src->col_stride < 0)
     return fra_internal_set_error(FRA_E_INVALID, "bad source layout (channels %d)", channels);
   const int ni = nitems;
-  fra_decode_job job{};  // (what check_item reads)
-  job.data = data;
-  job.len = len;
-  job.items = items;
-  job.nitems = ni;
   for (int i = 0; i < ni; i++) {
-    if (const int rc = check_item(&job, i)) return rc;
     const fra_decode_item& it = items[i];
+    if (const int rc = check_item(it, i, len)) return rc;
     if (!it.frame_offsets) return fra_internal_set_error(FRA_E_INVALID, "item %d: verify needs frame offsets", i);
     if (it.window.height < 0) return fra_internal_set_error(FRA_E_INVALID, "item %d: bad window", i);
     if (it.channels != channels)
@@ -1320,128 +1274,72 @@ int fra_internal_verify_device(fra_ctx* ctx, const uint8_t* data, uint64_t len, 
   *bad_windows = 0;
   if (ni == 0) return FRA_OK;
 
-  int device = 0;
-  hipStream_t s = nullptr;
-  fra_internal_ctx_stream(ctx, &device, &s);
-  (void)hipSetDevice(device);
-  HipArena sc;  // device buffers and events of this call, released on every path
-  hipEvent_t ev[5] = {};
-
-  // ---- groups of 64 frames (a group never spans items), scratch layout
-  std::vector<DecItem> h_items((size_t)ni);
-  std::vector<DecGroup> h_groups;
-  std::vector<int32_t> first_group((size_t)ni);
-  uint64_t scratch_elems = 0;
-  int bs_max = 1;
+  // ---- every frame of the offsets, scratch of the item's block size per frame; the source stands where a decode has
+  //      its destination
+  Decode c(ctx, ni);
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = items[i];
-    bs_max = std::max(bs_max, it.blocksize);
-    DecItem& di = h_items[(size_t)i];
-    di.end = it.offset + it.bytes;
-    di.channels = it.channels;
-    di.bps = it.bps;
-    di.sample_rate = 0;
-    di.bs_stride = it.blocksize;
-    di.row_off = it.window.row_off;
-    di.col_off = it.window.col_off;
-    di.width = it.window.width;
-    di.height = it.window.height;
-    di.dmin = 0.0;
-    di.span = 0.0;
-    first_group[(size_t)i] = (int32_t)h_groups.size();
-    for (int f = 0; f < it.nframes; f += kLanes) {
-      h_groups.push_back({scratch_elems, i, std::min(kLanes, it.nframes - f)});
-      scratch_elems += (uint64_t)it.channels * (uint64_t)it.blocksize * kLanes;
-    }
+    (void)c.open_item(it, i);  // (the offsets branch: it refuses nothing)
+    c.lay_out(i, (size_t)it.nframes, it.blocksize, it.offset + it.bytes, it.window, 0.0, 0.0);
   }
-  const size_t ng = h_groups.size();
-  if (ng > (size_t)INT32_MAX / kLanes) return fra_internal_set_error(FRA_E_INVALID, "too many frames");
-  const size_t nslots = ng * kLanes;
-  std::vector<uint64_t> h_starts(std::max<size_t>(1, nslots), kNoFrame);
-  for (int i = 0; i < ni; i++)
-    for (int f = 0; f < items[i].nframes; f++)
-      h_starts[(size_t)first_group[(size_t)i] * kLanes + (size_t)f] = items[i].offset + items[i].frame_offsets[f];
-
-  DecArgs a{};
-  a.data = data;
-  a.band_stride = src->band_stride;
-  a.row_stride = src->row_stride;
-  a.col_stride = src->col_stride;
-  if (const int rc = alloc_tables(sc, a, (size_t)ni, ng, scratch_elems)) return rc;
+  if (const int rc = c.slots("too many frames",
+                             [&](int i, size_t k) { return items[i].offset + items[i].frame_offsets[k]; }))
+    return rc;
+  c.a.data = data;
+  c.a.band_stride = src->band_stride;
+  c.a.row_stride = src->row_stride;
+  c.a.col_stride = src->col_stride;
+  if (const int rc = c.stage(nullptr, 0, nullptr)) return rc;
   VerArgs v{};
   v.src = src->raster;
   v.nd = (const fra::NormDev*)src->norm_rows;
   v.norm = src->norm;
-  HIPCHK(sc.alloc(&v.res, sizeof(unsigned long long) * 2 * (size_t)ni));
-  HIPCHK(sc.alloc(&v.vals, sizeof(int32_t) * 2 * (size_t)ni));
-  for (auto& e : ev) HIPCHK(sc.event(&e, hipEventDefault));
+  HIPCHK(c.sc.alloc(&v.res, sizeof(unsigned long long) * 2 * (size_t)ni));
+  HIPCHK(c.sc.alloc(&v.vals, sizeof(int32_t) * 2 * (size_t)ni));
   std::vector<unsigned long long> h_res(2 * (size_t)ni);
   for (int i = 0; i < ni; i++) {
     h_res[2 * (size_t)i] = 0;
     h_res[2 * (size_t)i + 1] = ~0ull;
   }
-  HIPCHK(hipMemcpyAsync((void*)a.items, h_items.data(), sizeof(DecItem) * (size_t)ni, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(v.res, h_res.data(), sizeof(unsigned long long) * 2 * (size_t)ni, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(v.vals, 0, sizeof(int32_t) * 2 * (size_t)ni, s));
-  if (ng) {
-    HIPCHK(hipMemcpyAsync((void*)a.groups, h_groups.data(), sizeof(DecGroup) * ng, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync((void*)a.starts, h_starts.data(), sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(a.fail, 0, sizeof(uint32_t) * nslots, s));
-  }
+  HIPCHK(hipMemcpyAsync(v.res, h_res.data(), sizeof(unsigned long long) * 2 * (size_t)ni, hipMemcpyHostToDevice, c.s));
+  HIPCHK(hipMemsetAsync(v.vals, 0, sizeof(int32_t) * 2 * (size_t)ni, c.s));
 
   // ---- parse every frame; each must be one, of its offsets' length and of its position's sample count
-  std::vector<FrameOut> h_fout(std::max<size_t>(1, nslots));
-  if (const int rc = parse_candidates(a, ng, h_fout.data(), ev, s)) return rc;
-  std::vector<int64_t> h_samp0(std::max<size_t>(1, nslots), -1);
+  if (const int rc = c.parse_candidates()) return rc;
   for (int i = 0; i < ni; i++) {
     const fra_decode_item& it = items[i];
-    const size_t g0 = (size_t)first_group[(size_t)i] * kLanes;
+    const size_t g0 = (size_t)c.plan[(size_t)i].first_group * kLanes;
     const int64_t nsamp = (int64_t)it.window.height * it.window.width;
     int64_t at = (int64_t)(first_frames ? first_frames[i] : 0) * it.blocksize;
     for (int f = 0; f < it.nframes; f++) {
-      const FrameOut& fo = h_fout[g0 + (size_t)f];
+      const FrameOut& fo = c.h_fout[g0 + (size_t)f];
       if (fo.status == ST_UNSUPPORTED) return fra_internal_set_error(FRA_E_INVALID, "item %d: %s", i, kUnsupported);
       if (fo.status != ST_OK || fo.len != it.frame_offsets[f + 1] - it.frame_offsets[f] ||
           fo.n != std::min<int64_t>(it.blocksize, nsamp - at))
         return fra_internal_set_error(FRA_E_INVALID, "lost sync / corrupt frame at byte %llu",
                                       (unsigned long long)it.frame_offsets[f]);
-      h_samp0[g0 + (size_t)f] = at;
+      c.h_samp0[g0 + (size_t)f] = at;
       at += fo.n;
     }
     reports[i].nframes = it.nframes;
   }
 
   // ---- restore, compare
-  std::vector<uint32_t> h_fail(std::max<size_t>(1, nslots), 0);
-  const dim3 grid((unsigned)ng, (unsigned)((bs_max + kLanes - 1) / kLanes));
-  if (ng) {
-    HIPCHK(hipMemcpyAsync((void*)a.samp0, h_samp0.data(), sizeof(int64_t) * nslots, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(k_dec_restore<false>, dim3((unsigned)ng, (unsigned)channels), dim3(kLanes), 0, s, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[3], s));
-    launch_verify(src->dtype, grid, s, a, v);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[4], s));
-    HIPCHK(hipMemcpyAsync(h_fail.data(), a.fail, sizeof(uint32_t) * nslots, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_res.data(), v.res, sizeof(unsigned long long) * 2 * (size_t)ni, hipMemcpyDeviceToHost, s));
-  } else {
-    for (int k = 2; k < 5; k++) HIPCHK(hipEventRecord(ev[k], s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  for (size_t k = 0; k < nslots; k++)
-    if (h_fail[k])
-      return fra_internal_set_error(FRA_E_INVALID, "frame decode failed: a reconstructed sample leaves the sample range "
-                                                   "(frame at byte %llu)", (unsigned long long)h_starts[k]);
+  if (const int rc = c.restore_and(k_dec_restore<false>, channels,
+                                   [&] { launch_verify(src->dtype, c.grid(), c.s, c.a, v); }))
+    return rc;
+  if (c.ng)
+    HIPCHK(hipMemcpyAsync(h_res.data(), v.res, sizeof(unsigned long long) * 2 * (size_t)ni, hipMemcpyDeviceToHost, c.s));
+  if (const int rc = c.wait_and_check(c.h_starts.data())) return rc;
   int bad = 0;
   for (int i = 0; i < ni; i++) bad += h_res[2 * (size_t)i] != 0;
   if (bad) {  // the rare path: both samples at every bad item's first mismatch
     std::vector<int32_t> h_vals(2 * (size_t)ni);
     v.pass = 1;
-    launch_verify(src->dtype, grid, s, a, v);
+    launch_verify(src->dtype, c.grid(), c.s, c.a, v);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_vals.data(), v.vals, sizeof(int32_t) * 2 * (size_t)ni, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(h_vals.data(), v.vals, sizeof(int32_t) * 2 * (size_t)ni, hipMemcpyDeviceToHost, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
     for (int i = 0; i < ni; i++) {
       if (!h_res[2 * (size_t)i]) continue;
       fra_verify_report& r = reports[i];
@@ -1453,7 +1351,7 @@ int fra_internal_verify_device(fra_ctx* ctx, const uint8_t* data, uint64_t len, 
     }
   }
   *bad_windows = bad;
-  keep_times(ev);
+  keep_times(c.ev);
   return FRA_OK;
 }
 

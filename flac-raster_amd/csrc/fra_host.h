@@ -1,7 +1,8 @@
-// fra_host.h -- host-only helpers shared by the plan / execute / host-path code and fra_decode_dev.hip: the error
-// setter, HIPCHK, elem_size and one owner of HIP resources.  Compiled by g++ (no HIP) it offers the first and the
-// third only (fra_layout.h); nothing here needs more of the library than fra_internal_set_error, which the
-// stand-alone check programs under tools/ define themselves.
+// fra_host.h -- host-only helpers shared by the plan / execute / host-path code, fra_decode_dev.hip and the units over
+// fra_region.h: the error setter, HIPCHK, elem_size, one owner of HIP resources (HipArena) and a call's stream and
+// arena (Call).  Compiled by g++ (no HIP) it offers the first and the third only (fra_layout.h); nothing here needs
+// more of the library than fra_internal_set_error and, for Call, fra_internal_ctx_stream, which the stand-alone check
+// programs under tools/ define themselves.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -91,5 +92,20 @@ struct HipArena {
   std::vector<void*> dev_, pinned_;
   std::vector<hipStream_t> streams_;
   std::vector<hipEvent_t> events_;
+};
+
+// the context's device and stream (fra_api.hip)
+extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
+
+// A call's stream, on its context's device, and the owner of what the call makes: staging buffers, tables, partials,
+// reports and events are released on every path.
+struct Call {
+  hipStream_t s = nullptr;
+  HipArena sc;
+  explicit Call(fra_ctx* ctx) {
+    int device = 0;
+    fra_internal_ctx_stream(ctx, &device, &s);
+    (void)hipSetDevice(device);
+  }
 };
 #endif  // __HIPCC__

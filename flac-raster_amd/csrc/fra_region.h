@@ -5,10 +5,11 @@
 //     (left_to_window_read, left_to_window_read_no_dst, refer_to_window_read);
 //   * the dtype dispatch (with_dtype), the extent of a strided raster (extent_of) and the test for aligned 16-byte
 //     row loads (aligned16);
-//   * a call's stream and arena (Call), the staging of host buffers (stage_in, stage_out, copy_back), the kernels'
-//     time between two events (timed), and the two frames around a unit's kernels: a raster job (run_raster) and a
-//     region decoded by the windowed read (fra_decode_device_window, called as any caller would: same kernels,
-//     refusals and messages) into a per-call device buffer (decode, run_region).
+//   * a call's stream and arena (Call: it lives in fra_host.h, where the device decoder finds it too), the staging
+//     of host buffers (stage_in, stage_out, copy_back), the kernels' time between two events (timed), and the two
+//     frames around a unit's kernels: a raster job (run_raster) and a region decoded by the windowed read
+//     (fra_decode_device_window, called as any caller would: same kernels, refusals and messages) into a per-call
+//     device buffer (decode, run_region).
 // Every function is inline: the units are separate translation units of one library and of one check program.
 #pragma once
 #include <algorithm>
@@ -16,11 +17,6 @@
 
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
-
-#ifdef __HIPCC__
-// the context's device and stream (fra_api.hip)
-extern "C" void fra_internal_ctx_stream(fra_ctx* ctx, int* device, hipStream_t* stream);
-#endif
 
 namespace fra_region {
 
@@ -123,17 +119,7 @@ inline int refer_to_window_read(fra_ctx* ctx, const fra_decode_job* job, const f
 }
 
 #ifdef __HIPCC__
-// A call's stream, on its context's device, and the owner of what the call makes: staging buffers, partials, reports
-// and events are released on every path.
-struct Call {
-  hipStream_t s = nullptr;
-  HipArena sc;
-  explicit Call(fra_ctx* ctx) {
-    int device = 0;
-    fra_internal_ctx_stream(ctx, &device, &s);
-    (void)hipSetDevice(device);
-  }
-};
+using ::Call;  // (fra_host.h)
 
 // a host raster copied to the device from its element 0 to the last one addressed; a device raster as it is
 inline int stage_in(Call& c, const void* p, int on_device, size_t bytes, const void** d) {

@@ -335,6 +335,11 @@ def _masked_args(nodata, filled, dtype, channels: int):
     return nd, filled.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
+def _window_ref(w):
+    """A ``fra_window`` argument from (row_off, col_off, height, width)."""
+    return C.byref(Window(*[int(v) for v in w]))
+
+
 def device_count() -> int:
     n = C.c_int(0)
     load().fra_device_count(C.byref(n))
@@ -531,26 +536,10 @@ class Context:
                                     omax, out.ctypes.data_as(C.c_void_p), C.byref(mn), C.byref(mx)))
         return out, mn.value, mx.value
 
-    def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
-                      denorm: int = DENORM_NONE, concat: bool = False, roi=None, decimate=None,
-                      compare=None, stats=None, resample=None, masked=None) -> List[Decoded]:
-        """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
-
-        ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
-        length)``.  ``items``: one dict per stream with ``offset``, ``bytes``, ``window`` (row_off, col_off, height,
-        width) and optionally ``data_min`` / ``data_max`` (denormalisation) and ``frame_offsets`` (uint64 array of
-        nframes + 1 offsets relative to ``offset``; then also ``channels``, ``bps``, ``blocksize``: nothing is
-        searched).  ``dst``: a numpy array (copied to the device and back, so elements outside the windows keep
-        their values) or a device pointer (int); sample p of channel c of a stream lands at element
-        ``c * strides[0] + (row_off + p // width) * strides[1] + (col_off + p % width) * strides[2]``.
-        Returns the per-stream :class:`Decoded` infos.  Anything the device path does not cover raises
-        :class:`NativeError`; there is no fallback to the host decoder.  (``roi``: see
-        :meth:`decode_device_window`; ``decimate`` = (factor, resampling code): see
-        :meth:`decode_device_decimated`; ``compare`` = (ref pointer, on device, element strides, reports array): see
-        :meth:`decode_device_compare`, ``dst`` is then ``None``; ``stats`` = (options, reports array, histogram
-        pointer): see :meth:`decode_device_stats`, ``dst`` is then ``None`` too; ``resample`` = (out_height, out_width,
-        resampling code): see :meth:`decode_device_resampled`; ``masked`` = (nodata, fill counts pointer or ``None``) beside
-        ``resample`` or ``decimate``: their nodata-aware entries.)"""
+    def _decode_job(self, data, items, dst, dst_dtype, denorm: int, channels: int, strides, concat: bool = False):
+        """The ``DecodeJob`` of a decode call (arguments as :meth:`decode_device`; ``dst`` may be ``None`` for an entry
+        that ignores it).  Returns ``(job, infos, keep)``: the per-stream :class:`Decoded` array the entry fills and
+        what the job points into, which must outlive the call."""
         keep = []
         job = DecodeJob()
         if isinstance(data, tuple):
@@ -585,38 +574,32 @@ class Context:
         job.denorm = denorm
         job.channels = channels
         job.band_stride, job.row_stride, job.col_stride = (int(v) for v in strides)
-        infos = (Decoded * max(1, len(items)))()
-        if stats is not None:
-            opts, bands, hist = stats
-            rc = load().fra_decode_device_stats(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
-                                                C.byref(opts), bands, hist, infos)
-        elif compare is not None:
-            ref, ref_on_device, rst, bands = compare
-            rc = load().fra_decode_device_compare(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
-                                                  C.c_void_p(int(ref)), 1 if ref_on_device else 0, int(rst[0]),
-                                                  int(rst[1]), int(rst[2]), bands, infos)
-        elif resample is not None and masked is not None:
-            rc = load().fra_decode_device_resampled_masked(
-                self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), int(resample[0]), int(resample[1]),
-                int(resample[2]), infos, float(masked[0]), masked[1])
-        elif resample is not None:
-            rc = load().fra_decode_device_resampled(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
-                                                    int(resample[0]), int(resample[1]), int(resample[2]), infos)
-        elif decimate is not None and masked is not None:
-            rc = load().fra_decode_device_decimated_masked(
-                self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), int(decimate[0]), int(decimate[1]), infos,
-                float(masked[0]), masked[1])
-        elif decimate is not None:
-            rc = load().fra_decode_device_decimated(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])),
-                                                    int(decimate[0]), int(decimate[1]), infos)
-        elif roi is not None:
-            rc = load().fra_decode_device_window(self.h, C.byref(job), C.byref(Window(*[int(v) for v in roi])), infos)
-        else:
-            rc = load().fra_decode_device(self.h, C.byref(job), infos)
+        return job, (Decoded * max(1, len(items)))(), keep
+
+    def _decode_run(self, entry: str, job, infos, keep, *args) -> List[Decoded]:
+        """``entry(ctx, job, *args)`` of the library for a job of :meth:`_decode_job` (``keep`` is held until the call
+        returns); the per-stream infos."""
+        rc = getattr(load(), entry)(self.h, C.byref(job), *args)
         if rc == E_SPACE:
             raise OutputTooSmall(max(int(i.nsamples) for i in infos))
         _check(rc)
-        return list(infos)[: len(items)]
+        return list(infos)[: job.nitems]
+
+    def decode_device(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
+                      denorm: int = DENORM_NONE, concat: bool = False) -> List[Decoded]:
+        """Batched FLAC decode on this context's GPU (``fra_decode_device``): tile streams -> raster.
+
+        ``data``: the bytes holding every stream -- bytes-like / uint8 array on the host, or ``(device pointer,
+        length)``.  ``items``: one dict per stream with ``offset``, ``bytes``, ``window`` (row_off, col_off, height,
+        width) and optionally ``data_min`` / ``data_max`` (denormalisation) and ``frame_offsets`` (uint64 array of
+        nframes + 1 offsets relative to ``offset``; then also ``channels``, ``bps``, ``blocksize``: nothing is
+        searched).  ``dst``: a numpy array (copied to the device and back, so elements outside the windows keep
+        their values) or a device pointer (int); sample p of channel c of a stream lands at element
+        ``c * strides[0] + (row_off + p // width) * strides[1] + (col_off + p % width) * strides[2]``.
+        Returns the per-stream :class:`Decoded` infos.  Anything the device path does not cover raises
+        :class:`NativeError`; there is no fallback to the host decoder."""
+        job, infos, keep = self._decode_job(data, items, dst, dst_dtype, denorm, channels, strides, concat)
+        return self._decode_run("fra_decode_device", job, infos, keep, infos)
 
     def decode_device_window(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
                              denorm: int = DENORM_NONE) -> List[Decoded]:
@@ -629,7 +612,8 @@ class Context:
         result is bit-identical to cropping the full decode."""
         if roi is None:
             raise ValueError("roi is required")
-        return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi)
+        job, infos, keep = self._decode_job(data, items, dst, dst_dtype, denorm, channels, strides)
+        return self._decode_run("fra_decode_device_window", job, infos, keep, _window_ref(roi), infos)
 
     def decode_device_decimated(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int], roi,
                                 factor: int, resampling: str = "nearest", denorm: int = DENORM_NONE, nodata=None,
@@ -646,9 +630,13 @@ class Context:
 
         if roi is None:
             raise ValueError("roi is required")
-        return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi,
-                                  (check_factor(factor), resampling_code(resampling)),
-                                  masked=_masked_args(nodata, filled, dst_dtype, channels))
+        k, mode = check_factor(factor), resampling_code(resampling)
+        masked = _masked_args(nodata, filled, dst_dtype, channels)
+        job, infos, keep = self._decode_job(data, items, dst, dst_dtype, denorm, channels, strides)
+        if masked is not None:
+            return self._decode_run("fra_decode_device_decimated_masked", job, infos, keep, _window_ref(roi), k, mode,
+                                    infos, float(masked[0]), masked[1])
+        return self._decode_run("fra_decode_device_decimated", job, infos, keep, _window_ref(roi), k, mode, infos)
 
     def decimate(self, src, factor: int, resampling: str = "nearest", dst=None, *, dtype=None, shape=None,
                  strides=None, dst_strides=None, nodata=None, filled=None):
@@ -701,8 +689,12 @@ class Context:
         mode = resampling_any_code(resampling)
         if mode == RESAMPLE_AVERAGE and int(roi[2]) > 0 and int(roi[3]) > 0:
             check_average_size(int(roi[2]), int(roi[3]), oh, ow, dst_dtype)
-        return self.decode_device(data, items, dst, dst_dtype, channels, strides, denorm, False, roi,
-                                  resample=(oh, ow, mode), masked=_masked_args(nodata, filled, dst_dtype, channels))
+        masked = _masked_args(nodata, filled, dst_dtype, channels)
+        job, infos, keep = self._decode_job(data, items, dst, dst_dtype, denorm, channels, strides)
+        if masked is not None:
+            return self._decode_run("fra_decode_device_resampled_masked", job, infos, keep, _window_ref(roi), oh, ow,
+                                    mode, infos, float(masked[0]), masked[1])
+        return self._decode_run("fra_decode_device_resampled", job, infos, keep, _window_ref(roi), oh, ow, mode, infos)
 
     def resample(self, src, out_shape, resampling: str = "nearest", dst=None, *, dtype=None, shape=None,
                  strides=None, dst_strides=None, nodata=None, filled=None):
@@ -755,12 +747,14 @@ class Context:
         if isinstance(ref, np.ndarray):
             if ref.shape != (channels, h, w) or ref.dtype != dt:
                 raise ValueError(f"ref must be {(channels, h, w)} of {dt}, got {ref.shape} of {ref.dtype}")
-            where = (ref.ctypes.data, False, _element_strides(ref))
+            ptr, on_device, rst = ref.ctypes.data, 0, _element_strides(ref)
         else:
-            where = (int(ref), True, tuple(int(v) for v in ref_strides) if ref_strides is not None else (h * w, w, 1))
+            ptr, on_device = int(ref), 1
+            rst = tuple(int(v) for v in ref_strides) if ref_strides is not None else (h * w, w, 1)
         bands = (CompareBand * max(1, channels))()
-        infos = self.decode_device(data, items, None, dt, channels, (0, 0, 0), denorm, False, roi,
-                                   compare=where + (bands,))
+        job, infos, keep = self._decode_job(data, items, None, dt, denorm, channels, (0, 0, 0))
+        infos = self._decode_run("fra_decode_device_compare", job, infos, keep, _window_ref(roi), C.c_void_p(ptr),
+                                 on_device, int(rst[0]), int(rst[1]), int(rst[2]), bands, infos)
         return list(bands)[:channels], infos
 
     def compare(self, a, b, *, dtype=None, shape=None, a_strides=None, b_strides=None) -> List[CompareBand]:
@@ -835,8 +829,9 @@ class Context:
         bands = (StatsBand * max(1, channels))()
         hist = np.zeros((channels, o.bins), np.uint64) if o.bins else None
         hp = hist.ctypes.data_as(C.POINTER(C.c_uint64)) if hist is not None else None
-        infos = self.decode_device(data, items, None, np.dtype(dst_dtype), channels, (0, 0, 0), denorm, False, roi,
-                                   stats=(o, bands, hp))
+        job, infos, keep = self._decode_job(data, items, None, np.dtype(dst_dtype), denorm, channels, (0, 0, 0))
+        infos = self._decode_run("fra_decode_device_stats", job, infos, keep, _window_ref(roi), C.byref(o), bands, hp,
+                                 infos)
         return list(bands)[:channels], hist, infos
 
     def stats(self, src, bins: int = 0, hist_range=None, nodata=None, *, dtype=None, shape=None, strides=None):

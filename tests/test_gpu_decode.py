@@ -486,3 +486,124 @@ def test_32_bps_mid_side_is_decoded_or_refused():
         assert "not supported on the device" in str(e)
     else:
         assert np.array_equal(got, want)
+
+
+# ------------------------------------------------------------------------------- 9. what the entries' host code keeps
+def _verbatim_stream(samples, bps=16):
+    """A hand-built stream of VERBATIM frames of 16 samples over ``samples`` (n, channels), n a multiple of 16;
+    returns (stream, offsets of the frames and of the stream's end)."""
+    x = np.asarray(samples)
+    n, ch = x.shape
+    assert n % 16 == 0 and ch in (1, 2)
+    stream, offs = N.stream_header(ch, bps, 44100, 16), []
+    for f in range(n // 16):
+        b = Bits()
+        for c in range(ch):
+            b.put(0, 1); b.put(1, 6); b.put(0, 1)
+            for v in x[16 * f:16 * f + 16, c]:
+                b.put(int(v), bps)
+        offs.append(len(stream))
+        stream += _frame(16, ch - 1, bps, f, b)
+    return stream, np.array(offs + [len(stream)], np.uint64)
+
+
+def _out_of_range_stream():
+    b = Bits()
+    b.put(0, 1); b.put(9, 6); b.put(0, 1); b.put(32767, 16)
+    b.put(0, 2); b.put(0, 4); b.put(15, 4); b.put(17, 5)
+    for _ in range(15):
+        b.put(65535, 17)
+    return N.stream_header(1, 16, 44100, 16), _frame(16, 0, 16, 0, b)
+
+
+def _on_device(ctx, blob, run):
+    """run((device pointer, length)) with ``blob`` resident on the device."""
+    buf = np.frombuffer(blob, np.uint8)
+    dev = ctx.alloc(buf.size)
+    try:
+        ctx.h2d(dev, buf)
+        return run((dev, buf.size))
+    finally:
+        ctx.free(dev)
+
+
+def test_out_of_range_frame_of_a_second_item_is_named_by_its_byte():
+    """The frame whose reconstruction leaves the sample range, in the second of two items: the full decode names its
+    byte in ``data``, the windowed read its byte in the item."""
+    good, _ = _verbatim_stream(np.arange(16).reshape(-1, 1))
+    head, frame = _out_of_range_stream()
+    blob = b"\x00" * 5 + good + b"\x00" * 3 + head + frame
+    off = 5 + len(good) + 3
+    items = [{"offset": 5, "bytes": len(good), "window": (0, 0, 1, 16)},
+             {"offset": off, "bytes": len(head) + len(frame), "window": (1, 0, 1, 16)}]
+    ctx = _ctx()
+    dst = np.zeros((2, 16), np.int16)
+    with pytest.raises(N.NativeError, match=rf"sample range \(frame at byte {off + len(head)}\)"):
+        ctx.decode_device(blob, items, dst, np.int16, 1, (32, 16, 1))
+
+    def window(data):
+        return ctx.decode_device_window(data, items, dst, np.int16, 1, (32, 16, 1), (0, 0, 2, 16))
+
+    with pytest.raises(N.NativeError, match=rf"sample range \(frame at byte {len(head)}\)"):
+        window(blob)
+    with pytest.raises(N.NativeError, match=rf"sample range \(frame at byte {len(head)}\)"):
+        _on_device(ctx, blob, window)
+
+
+@pytest.mark.parametrize("interleaved", [False, True], ids=["rows", "interleaved"])
+@pytest.mark.parametrize("resident", [False, True], ids=["host", "device"])
+def test_window_over_an_offsets_item_a_searched_item_and_one_outside(resident, interleaved):
+    """Three 8 x 8 tiles of four frames: A through frame offsets, B searched, C outside the region and not FLAC."""
+    rng = np.random.default_rng(91)
+    sa, offs = _verbatim_stream(rng.integers(-3000, 3000, size=(64, 1)))
+    sb, _ = _verbatim_stream(rng.integers(-3000, 3000, size=(64, 1)))
+    sc = b"these bytes are no FLAC stream " * 3
+    full = np.full((16, 16), -12345, np.int32)
+    full[:8, :8] = N.decode(sa)[0].reshape(8, 8)
+    full[:8, 8:] = N.decode(sb)[0].reshape(8, 8)
+    blob = b"\x00" * 5 + sa + b"\x00" * 3 + sb + b"\x00" * 3 + sc
+    ob = 5 + len(sa) + 3
+    items = [{"offset": 5, "bytes": len(sa), "window": (0, 0, 8, 8), "frame_offsets": offs, "channels": 1, "bps": 16,
+              "blocksize": 16},
+             {"offset": ob, "bytes": len(sb), "window": (0, 8, 8, 8)},
+             {"offset": ob + len(sb) + 3, "bytes": len(sc), "window": (8, 0, 8, 8)}]
+    roi = (2, 3, 3, 10)  # tile samples 19..39 of A and 16..36 of B: frames 1 and 2 of each, cut at both ends
+    r, c, h, w = roi
+    if interleaved:  # (row, col, 2): the column stride is 2, so the destination is staged whole
+        dst = np.full((h + 1, w + 2, 2), -12345, np.int16)
+        strides, view = (1, (w + 2) * 2, 2), dst[:, :, 0]
+    else:
+        dst = np.full((h + 1, w + 3), -12345, np.int16)
+        strides, view = (dst.size, w + 3, 1), dst
+    ctx = _ctx()
+
+    def window(data):
+        return ctx.decode_device_window(data, items, dst, np.int16, 1, strides, roi)
+
+    infos = _on_device(ctx, blob, window) if resident else window(blob)
+    assert np.array_equal(view[:h, :w], full[r:r + h, c:c + w])
+    view[:h, :w] = -12345
+    assert (dst == -12345).all(), "written outside the intersections"
+    assert [(i.nframes, i.nsamples, i.channels, i.bps, i.blocksize) for i in infos[:2]] == [(2, 15, 1, 16, 16)] * 2
+    z = infos[2]
+    assert all(getattr(z, name) == 0 for name, _ in N.Decoded._fields_), "infos of an item outside the region"
+
+
+def test_channel_count_is_refused_before_the_32_bps_destination():
+    """A two-channel 32-bps stream into one int16 band breaks two rules: the channel count is named, by both entries."""
+    s, _ = _verbatim_stream(np.arange(32).reshape(-1, 2) * 100000, bps=32)
+    assert N.decode(s)[1].bps == 32
+    items = [{"offset": 0, "bytes": len(s), "window": (0, 0, 1, 16)}]
+    dst = np.zeros(16, np.int16)
+    with pytest.raises(N.NativeError, match="item 0 has 2 channels, the destination 1"):
+        _ctx().decode_device(s, items, dst, np.int16, 1, (16, 16, 1))
+    with pytest.raises(N.NativeError, match="item 0 has 2 channels, the destination 1"):
+        _ctx().decode_device_window(s, items, dst, np.int16, 1, (16, 16, 1), (0, 0, 1, 16))
+
+
+def test_capacity_window_too_small_reports_the_samples_needed():
+    s, _ = _verbatim_stream(np.arange(48).reshape(-1, 1))
+    with pytest.raises(N.OutputTooSmall) as e:
+        _ctx().decode_device(s, [{"offset": 0, "bytes": len(s), "window": (0, 0, -40, 1)}], np.zeros(40, np.int16),
+                             np.int16, 1, (40, 1, 1))
+    assert e.value.needed == 48

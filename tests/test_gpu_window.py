@@ -375,8 +375,10 @@ def test_refusals_short_streams_and_damage_on_the_search_path():
     with pytest.raises(N.NativeError):
         read(bytes(e), (0, 0, 10, 16), (2, 0, 4, 16))
     assert np.array_equal(read(bytes(e), (0, 0, 10, 16), (5, 0, 4, 16)), want[5:9])
+    # (decode_device_window has no concat argument: the flag reaches the entry through the job)
+    job, infos, keep = ctx._decode_job(s, [{"offset": 0, "bytes": len(s), "window": (0, 0, 10, 16)}],
+                                       np.zeros(160, np.int16), np.int16, N.DENORM_NONE, 1, (160, 16, 1), concat=True)
     with pytest.raises(N.NativeError, match="CONCAT|concat"):
-        ctx.decode_device(s, [{"offset": 0, "bytes": len(s), "window": (0, 0, 10, 16)}], np.zeros(160, np.int16),
-                          np.int16, 1, (160, 16, 1), N.DENORM_NONE, True, (0, 0, 2, 16))
+        ctx._decode_run("fra_decode_device_window", job, infos, keep, N._window_ref((0, 0, 2, 16)), infos)
     # the context decodes a good stream afterwards
     assert np.array_equal(read(s, (0, 0, 10, 16), (0, 0, 10, 16)), want)

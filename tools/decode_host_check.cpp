@@ -280,6 +280,24 @@ int main(int argc, char** argv) {
   { auto j = job; j.dst_dtype = 9; badw("dtype 9", j, it, &roi); }
   { auto x = it; x.offset = 60; x.bytes = 8; x.window = {100, 100, 1, 8}; badw("item past the data, outside the roi", job, x, &roi); }
   { auto j = job; j.nitems = 0; EXPECT(fra_decode_device_window(ctx, &j, &roi, inf) == FRA_OK, "window read: empty job refused"); }
+  // the order of the refusals: inputs that break two rules at once, and the message that wins
+  {
+    auto says = [&](int rc, const char* part) { return rc == FRA_E_INVALID && g_msg.find(part) != std::string::npos; };
+    auto x_past = it; x_past.offset = 60; x_past.bytes = 8;
+    { auto j = job; j.dst_dtype = 9; j.denorm = 3; EXPECT(says(fra_decode_device(ctx, &j, inf), "bad dst_dtype"), "dtype 9 with denorm 3: %s", g_msg.c_str()); }
+    { auto j = job; j.dst_dtype = FRA_F32; j.denorm = FRA_DENORM_NONE; j.channels = 9; EXPECT(says(fra_decode_device(ctx, &j, inf), "FRA_DENORM_NONE needs"), "float dst without denorm with 9 channels: %s", g_msg.c_str()); }
+    {
+      fra_decode_item two[2] = {x_past, it};
+      two[1].window.row_off = -1;
+      auto j = job; j.items = two; j.nitems = 2;
+      EXPECT(says(fra_decode_device(ctx, &j, inf), "item 0 lies outside the data"), "item 0 past the data with a bad window of item 1: %s", g_msg.c_str());
+    }
+    { auto j = job; j.dst_dtype = 9; EXPECT(says(fra_decode_device_window(ctx, &j, nullptr, inf), "null argument"), "window read: null roi with dtype 9: %s", g_msg.c_str()); }
+    { auto j = job; j.dst_dtype = 9; fra_window r = roi; r.width = 0; EXPECT(says(fra_decode_device_window(ctx, &j, &r, inf), "bad dst_dtype"), "window read: dtype 9 with a zero-width roi: %s", g_msg.c_str()); }
+    { auto j = job; j.flags = FRA_DECODE_CONCAT; fra_window r = roi; r.width = 0; EXPECT(says(fra_decode_device_window(ctx, &j, &r, inf), "region of interest"), "window read: zero-width roi with FRA_DECODE_CONCAT: %s", g_msg.c_str()); }
+    { auto j = job; j.flags = FRA_DECODE_CONCAT; j.items = &x_past; EXPECT(says(fra_decode_device_window(ctx, &j, &roi, inf), "FRA_DECODE_CONCAT is not supported"), "window read: FRA_DECODE_CONCAT with an item past the data: %s", g_msg.c_str()); }
+    { auto x = x_past; x.window = {100, 100, 1, 8}; auto j = job; j.items = &x; EXPECT(says(fra_decode_device_window(ctx, &j, &roi, inf), "item 0 lies outside the data"), "window read: item past the data, outside the roi: %s", g_msg.c_str()); }
+  }
   // ... and of the verify entry (fra_plan_verify's driver): an item over frame offsets, a source raster, reports
   {
     uint64_t vo[3] = {0, 30, 64};  // two frames of 16 samples: an 8 x 4 window
@@ -319,6 +337,9 @@ int main(int argc, char** argv) {
     for (int32_t f0 : {1, 3, -1}) EXPECT(ver(ctx, data, &vi, 1, 1, &vs, &f0, rep, &nbad) == FRA_E_INVALID, "verify: first frame %d accepted", f0);
     { auto x = vi; x.nframes = 1; x.bytes = 30; int32_t f0 = 2; EXPECT(ver(ctx, data, &x, 1, 1, &vs, &f0, rep, &nbad) == FRA_E_INVALID, "verify: one frame from frame 2 of 2 accepted"); }
     { auto x = vi; x.nframes = 1; x.bytes = 30; EXPECT(ver(ctx, data, &x, 1, 1, &vs, nullptr, rep, &nbad) == FRA_E_INVALID, "verify: 1 of 2 frames without a first frame accepted"); }
+    // two rules broken at once: the message that wins
+    { auto s2 = vs; s2.dtype = 8; s2.norm = 8; EXPECT(ver(ctx, data, &vi, 1, 1, &s2, &ff, rep, &nbad) == FRA_E_INVALID && g_msg.find("bad dtype") != std::string::npos, "verify: dtype 8 with norm 8: %s", g_msg.c_str()); }
+    { auto x = vi; x.frame_offsets = nullptr; EXPECT(ver(ctx, data, &x, 1, 2, &vs, &ff, rep, &nbad) == FRA_E_INVALID && g_msg.find("verify needs frame offsets") != std::string::npos, "verify: no frame offsets with a channel mismatch: %s", g_msg.c_str()); }
     nbad = 7;
     EXPECT(ver(ctx, data, &vi, 0, 1, &vs, &ff, rep, &nbad) == FRA_OK && nbad == 0, "verify: empty job refused");
   }
