@@ -58,6 +58,9 @@ __device__ __forceinline__ void wsync() {
 // immediate offset, 16 bytes at a time (ds_read_b128: 16 lanes per LDS cycle at a 32-byte stride, 2-way)
 constexpr int kWIterDw = 8 * 64;
 constexpr int kWinW = 3;  // apodization windows of levels 3-6
+// ... of the instance with partition cap `pcap` (level_cfg: max_porder 6 is level 6, nsub = 2, num_windows = 3;
+// max_porder 4 and 5 are levels 3-5, nsub = 1, one window)
+constexpr int wave_nwin(int pcap) { return pcap == 6 ? kWinW : 1; }
 __device__ __forceinline__ uint4 lds4(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
 // D[0..5] = the last 12 samples of chunk t - 1 (zeros before the block: t == 0), D[6..13] = chunk t (int16
 // pairs, sample 16t - 12 + 2k in the low half of D[k]) -- the layout read_d14 gives k_analyze
@@ -122,7 +125,19 @@ __device__ __forceinline__ int32_t wround16(float x, float w) {
 
 // Levinson-Durbin (op sequence of levinson_wave / oracle ora_levinson) where each lane keeps only what its
 // order lo needs: the prediction error after step lo - 1 (e, step 0's for lo = 0) and that step's row,
-// negated (lp = -lpc, the quantiser's input), so neither the rows nor the errors go through LDS
+// negated (lp = -lpc, the quantiser's input), so neither the rows nor the errors go through LDS.
+// FRA_W_LEV_STOP (default): a lane stops updating once its own step is done (step i runs on the lanes with
+// i < max(lo, 1)), so what it holds after the loop IS its row and error: eight negations and a copy, where a
+// 64-bit select per coefficient and step rebuilt the kept row inside the chain (36 selects, 36 negations, 8
+// selects of e).  An active lane executes the same f64 operations on the same operands in the same order.
+// The return value is then the LANE's own stop: the group's is that of a lane that runs every step
+// (lo >= max_order, e.g. lane 15 of the group), which the caller reads.  A lane whose order lies past an early exit
+// (lo > the group's result) holds the row of the exit step, not its own: the caller's `on` (lo <= nord) excludes
+// exactly those lanes, and a lane with lo <= result has completed step lo - 1 before the exit (result >= i at an
+// exit in step i, and step lo - 1 <= i ran under i < lo)
+#ifndef FRA_W_LEV_STOP
+#define FRA_W_LEV_STOP 1
+#endif
 template <int MAXLAG>
 __device__ inline int levinson_keep(const double (&ac)[MAXLAG + 1], int max_order, double& e, double (&lp)[MAXLAG],
                                     int lo) {
@@ -133,9 +148,10 @@ __device__ inline int levinson_keep(const double (&ac)[MAXLAG + 1], int max_orde
   double err = ac[0];
   int result = max_order;
   bool done = false;
+  const int last = FRA_W_LEV_STOP ? (lo > 1 ? lo : 1) : MAXLAG;  // this lane's steps: i < last
 #pragma unroll
   for (int i = 0; i < MAXLAG; i++) {
-    if (!done && i < max_order) {
+    if (!done && i < max_order && i < last) {
       double r = -ac[i + 1];
 #pragma unroll
       for (int j = 0; j < i; j++) r = r - lpc[j] * ac[i - j];
@@ -149,15 +165,22 @@ __device__ inline int levinson_keep(const double (&ac)[MAXLAG + 1], int max_orde
       }
       if (i & 1) lpc[i >> 1] = lpc[i >> 1] + lpc[i >> 1] * r;
       err = err * (1.0 - r * r);
-      const bool mine = lo == i + 1;
+      if (!FRA_W_LEV_STOP) {
+        const bool mine = lo == i + 1;
 #pragma unroll
-      for (int j = 0; j <= i; j++) lp[j] = mine ? -lpc[j] : lp[j];
-      e = (mine || (i == 0 && lo == 0)) ? err : e;
+        for (int j = 0; j <= i; j++) lp[j] = mine ? -lpc[j] : lp[j];
+        e = (mine || (i == 0 && lo == 0)) ? err : e;
+      }
       if (!(err > 0.0)) {
         result = (err == 0.0) ? i + 1 : i;
         done = true;
       }
     }
+  }
+  if (FRA_W_LEV_STOP) {
+#pragma unroll
+    for (int j = 0; j < MAXLAG; j++) lp[j] = -lpc[j];  // (past the lane's order: -0.0, never read)
+    e = err;
   }
   return result;
 }
@@ -216,6 +239,10 @@ __device__ __forceinline__ void fixed_guess2_w(const uint32_t (&ps)[5], int P, i
 #ifndef FRA_W_ARITH
 #define FRA_W_ARITH 0
 #endif
+// FRA_W_SROW (A/B knob): 1 the row walk on scalar registers where the geometry allows it (below), 0 always per lane
+#ifndef FRA_W_SROW
+#define FRA_W_SROW 1
+#endif
 struct WNorm {
   double two_mn, range, rcp;  // (-2 mn: the exact 2 (x - mn) as one fma)
   uint32_t flip;               // 0x8000 / 0x80: signed raster (raw bits -> value by (r ^ flip) - flip)
@@ -243,20 +270,34 @@ __device__ __forceinline__ void wload_lut(const void* base, const WaveDev& wd, i
   const char* b0 = (const char*)((const T*)base + wd.off0 + (int64_t)c * wd.band_stride);
   const uint32_t rsb = wd.row_stride * (uint32_t)sizeof(T);
   const uint32_t qs = step / w, rs = step - qs * w, rstep = qs * rsb;  // uniform
-  uint32_t col = wd.col0 + (uint32_t)lane * V;
-  uint32_t roff = 0;
-  if (col >= w) {
-    const uint32_t q = col / w;
-    col -= q * w;
-    roff = q * rsb;
-  }
   VT x[NV];
+  if (FRA_W_SROW && w % step == 0 && wd.col0 % step == 0) {  // (uniform)
+    // the width and the frame's first column are multiples of the 64 vectors of one load: every lane of a load
+    // lies in one row (col0 < w, so col0 + step <= w), and the walk is the same for all of them -- the column and
+    // the row offset on scalar registers, one byte offset per lane
+    const uint32_t lb = (uint32_t)lane * 8u;
+    uint32_t scol = wd.col0, sroff = 0;
 #pragma unroll
-  for (int kv = 0; kv < NV; kv++) {
-    x[kv] = *(const VT*)(b0 + (roff + col * (uint32_t)sizeof(T)));
-    col += rs;
-    roff += rstep;
-    if (col >= w) { col -= w; roff += rsb; }
+    for (int kv = 0; kv < NV; kv++) {
+      x[kv] = *(const VT*)(b0 + (sroff + scol * (uint32_t)sizeof(T)) + lb);
+      scol += step;
+      if (scol >= w) { scol = 0; sroff += rsb; }  // (exactly w)
+    }
+  } else {
+    uint32_t col = wd.col0 + (uint32_t)lane * V;
+    uint32_t roff = 0;
+    if (col >= w) {
+      const uint32_t q = col / w;
+      col -= q * w;
+      roff = q * rsb;
+    }
+#pragma unroll
+    for (int kv = 0; kv < NV; kv++) {
+      x[kv] = *(const VT*)(b0 + (roff + col * (uint32_t)sizeof(T)));
+      col += rs;
+      roff += rstep;
+      if (col >= w) { col -= w; roff += rsb; }
+    }
   }
   if (stamp) FRA_WSTAMP_WAIT(11)
   // OR and AND of the packed pairs: the OR gives the wasted bits, and the frame is CONSTANT exactly when the AND of
@@ -455,6 +496,11 @@ template <int MAXLAG, int PCAP, bool K17>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FRA_W_WAVES, FRA_W_WAVES_MAX)))
 k_analyze_w(JobArgs a, int src) {
   static_assert(MAXLAG == 8 && PCAP >= 4 && PCAP <= 6, "levels 3-6");
+  // the level's apodization windows, from the partition cap like everything else the instance fixes: levels 3-5
+  // (PCAP 4, 5) have nsub = 1 and one window, so their instances carry no window loop, no window index in mv, no
+  // choice of a keep window and none of the eight non-keep LPC sum bodies -- the only usable window is the keep
+  // window.  Level 6 (three windows) keeps the runtime count.  launch_analyze_w refuses any other JobArgs::nwin
+  constexpr int NWIN = wave_nwin(PCAP);
   __shared__ WaveSmem S;
   uint32_t* const sw = S.sw;
   const int lane = (int)threadIdx.x;
@@ -677,15 +723,16 @@ k_analyze_w(JobArgs a, int src) {
   uint32_t mv = 0;
   if constexpr (MAXLAG > 0) {
     if (cfg.nsub > 0 && lmax > 0) {
-      nlpc = a.nwin;
-      const int nwin = a.nwin;
+      // (NWIN == 1: the loop, the window index and the lane-group clamp below fold to constants)
+      const int nwin = NWIN == 1 ? 1 : a.nwin;
+      nlpc = nwin;
       constexpr int NL = MAXLAG + 1;
       double acl[NL];
       for (int wi = 0; wi < nwin; wi++) {
-        const int32_t* wr = a.wrange + 2 * ((size_t)wd.win * a.nwin + wi);
-        const int32_t* wp = a.wplat + 2 * ((size_t)wd.win * a.nwin + wi);
+        const int32_t* wr = a.wrange + 2 * ((size_t)wd.win * nwin + wi);
+        const int32_t* wp = a.wplat + 2 * ((size_t)wd.win * nwin + wi);
         const int lo = wr[0], hi = wr[1], plo = wp[0], phi = wp[1];
-        const float* win = a.win + ((size_t)wd.win * a.nwin + wi) * a.blocksize;
+        const float* win = a.win + ((size_t)wd.win * nwin + wi) * a.blocksize;
         // FRA-1 3.5b on the matrix cores.  The windowed integer samples v (|v| < 2^15) as a 256 x 16 matrix
         // Y[k][i] = v[16 k + i] (k = 16 g + e per 1024-sample block: lane 16 g + i holds rows k of its group in
         // its 16 bytes, e = 0..15, and the next row k + 1 for the shifted copy): C0 = Y^T Y and C1 = Y^T Y'
@@ -810,6 +857,11 @@ k_analyze_w(JobArgs a, int src) {
       double lpo[MAXLAG], e = 0.0;
       int nord = 0;
       if (gon && acl[0] != 0.0) nord = levinson_keep<MAXLAG>(acl, lmax, e, lpo, lo);
+      if (FRA_W_LEV_STOP) {
+        // the group's stop is that of its lane 15, which runs every step (lo = 15 >= lmax); one group: a readlane
+        if constexpr (NWIN == 1) nord = gon ? __builtin_amdgcn_readlane(nord, 15) : 0;
+        else nord = __shfl(nord, lane | 15, 64);
+      }
       const bool on = nord > 0 && lo >= 1 && lo <= nord;
       const uint64_t key = on ? (uint64_t)__double_as_longlong(order_bits(e, n, lo, prec + sbps)) : ~0ull;
       uint64_t rk = min(key, dpp64_old<DPP_SHR1, 0xF>(key, ~0ull));
@@ -829,19 +881,32 @@ k_analyze_w(JobArgs a, int src) {
       const int o_l = nord > 0 ? (int)__builtin_ctz(rowbits | 0x10000u) : 0;
       // each window's model (lane 16 wi + o_wi) gathered into mv (o = 0: none): lane l < 24 takes coefficient
       // l & 7 of window l >> 3, lane 24 + wi the shift and usable order (every ds_bpermute on all 64 lanes)
-      const int dwi = lane < 24 ? lane >> 3 : (lane - 24) & 3;
-      const int ow = (int)bperm32((uint32_t)o_l, 16 * dwi);
-      const int L = 16 * dwi + ow;
       // (computed at the SOURCE lane 16 wi + o_wi from its own values: its order o_l == lo there)
       const uint32_t info = (uint32_t)qsh | ((o_l > 0 && ok) ? (uint32_t)o_l << 8 : 0u);
-      const uint32_t vinfo = bperm32(info, L);
+      if constexpr (NWIN == 1) {
+        // one window: its model is lane o_0 of group 0 (o_l is the same on the group's 16 lanes), a uniform lane
+        // index -- nine v_readlane, no ds_bpermute round trips; lanes 0-7 and 24 of mv, the others stay 0
+        const int L = __builtin_amdgcn_readfirstlane(o_l);
+        const uint32_t vinfo = (uint32_t)__builtin_amdgcn_readlane((int)info, L);
 #pragma unroll
-      for (int jx = 0; jx < 8; jx++) {
-        const uint32_t vq = bperm32((uint32_t)q[jx], L);
-        mv = (lane & 7) == jx ? vq : mv;
+        for (int jx = 0; jx < 8; jx++) {
+          const uint32_t vq = (uint32_t)__builtin_amdgcn_readlane(q[jx], L);
+          mv = lane == jx ? vq : mv;
+        }
+        mv = lane == 24 ? vinfo : mv;
+      } else {
+        const int dwi = lane < 24 ? lane >> 3 : (lane - 24) & 3;
+        const int ow = (int)bperm32((uint32_t)o_l, 16 * dwi);
+        const int L = 16 * dwi + ow;
+        const uint32_t vinfo = bperm32(info, L);
+#pragma unroll
+        for (int jx = 0; jx < 8; jx++) {
+          const uint32_t vq = bperm32((uint32_t)q[jx], L);
+          mv = (lane & 7) == jx ? vq : mv;
+        }
+        mv = lane >= 24 ? vinfo : mv;
+        mv = (lane < 24 ? dwi : lane - 24) < nwin && lane < 27 ? mv : 0u;
       }
-      mv = lane >= 24 ? vinfo : mv;
-      mv = (lane < 24 ? dwi : lane - 24) < nwin && lane < 27 ? mv : 0u;
     }
   }
   FRA_WSTAMP(5)
@@ -860,13 +925,15 @@ k_analyze_w(JobArgs a, int src) {
   // the chunk's zig-zag residuals (int16 pairs), which the exact pass and the encoder then read instead of
   // recomputing the predictor twice (fallback: the samples are loaded again)
   // windows with a usable model (lanes 24 + wi of mv with an order)
-  const uint32_t okm = (uint32_t)(__ballot(lane >= 24 && lane < 24 + kWinW && (mv >> 8) != 0) >> 24);
+  // (one window: bit 0 alone, from lane 24's order; keep_wi is then 0 or -1 and every `wi` below the constant 0)
+  const uint32_t okm = NWIN == 1 ? (((uint32_t)__builtin_amdgcn_readlane((int)mv, 24) >> 8) != 0 ? 1u : 0u)
+                                 : (uint32_t)(__ballot(lane >= 24 && lane < 24 + kWinW && (mv >> 8) != 0) >> 24);
   // the window whose residuals are kept: the first usable one (FRA_W_KEEP=0; window 0, the whole-block tukey,
   // is the likeliest winner) or the last (FRA_W_KEEP=1); its sum pass runs last, after the other windows' passes
 #ifndef FRA_W_KEEP
 #define FRA_W_KEEP 0
 #endif
-  const int keep_wi = okm ? (FRA_W_KEEP ? 31 - __clz((int)okm) : __builtin_ctz(okm)) : -1;
+  const int keep_wi = okm ? (NWIN == 1 ? 0 : FRA_W_KEEP ? 31 - __clz((int)okm) : __builtin_ctz(okm)) : -1;
   bool kept_fit = false;
   uint64_t hk = 0;  // bit 16 of the kept residuals: bit 16 j + jj = chunk 64 j + lane's residual jj
   bool hk_any = false;  // (wave-uniform) some kept residual has bit 16
@@ -882,8 +949,10 @@ k_analyze_w(JobArgs a, int src) {
       if (o < 0 || (lpcT != ~0ull && (ci == nlpc ? gt1 : gt2) >= lpcT)) continue;
       psum = ci == nlpc ? pf1 : pf2;
     } else {
-      const int wi = (ci + keep_wi + 1) % nlpc;  // the keep window last (nlpc >= 1 here)
+      const int wi = NWIN == 1 ? 0 : (ci + keep_wi + 1) % nlpc;  // the keep window last (nlpc >= 1 here)
       if (!((okm >> wi) & 1u)) continue;  // no order / not quantisable
+      // (one window: a usable window is the keep window, the other windows' sum pass is not compiled)
+      const bool keep_pass = NWIN == 1 || wi == keep_wi;
       const uint32_t inf = (uint32_t)__builtin_amdgcn_readlane((int)mv, 24 + wi);
       o = (int)(inf >> 8);
       m = 5 + wi;
@@ -891,7 +960,7 @@ k_analyze_w(JobArgs a, int src) {
       sh = (int)(inf & 0xFFu);
 #pragma unroll
       for (int jx = 0; jx < 8; jx++) qm[jx] = __builtin_amdgcn_readlane((int)mv, 8 * wi + jx);
-      if (wi == keep_wi) {
+      if (keep_pass) {
         uint32_t um = 0, carry[6] = {0, 0, 0, 0, 0, 0};
         // iteration 0 (the only one holding the warm-up samples, lane 0) peeled: the others are compiled with head
         // false, without the warm-up selects (r05)
@@ -936,7 +1005,7 @@ k_analyze_w(JobArgs a, int src) {
         } else {
           kept_fit = !__any(um > 0xFFFFu);
         }
-      } else {
+      } else if constexpr (NWIN > 1) {
 #pragma unroll 1
         for (int j = 0; j < kWIters; j++) {
           const int t = 64 * j + lane;
@@ -984,8 +1053,10 @@ k_analyze_w(JobArgs a, int src) {
   const int type = wtype, o = wo, sh = wsh, ps = wps;
   int32_t wq[8];
 #pragma unroll
-  for (int jq = 0; jq < 8; jq++) wq[jq] = type == 3 ? __builtin_amdgcn_readlane((int)mv, 8 * (wm - 5) + jq) : 0;
-  const bool kept_w = type == 3 && wm == 5 + keep_wi && kept_fit;
+  for (int jq = 0; jq < 8; jq++)
+    wq[jq] = type == 3 ? __builtin_amdgcn_readlane((int)mv, (NWIN == 1 ? 0 : 8 * (wm - 5)) + jq) : 0;
+  // (one window: an LPC winner is model 5, the keep window's)
+  const bool kept_w = type == 3 && (NWIN == 1 || wm == 5 + keep_wi) && kept_fit;
   FRA_WSTAMP_VAL(9, kept_w ? 0 : (type != 3 ? 3 : (wm != 5 + keep_wi ? 4 : 5)))  // why the sample path
   auto reload = [&]() {  // the keep pass replaced the samples: load them once more
     wsync();
@@ -1367,6 +1438,8 @@ hipError_t launch_analyze_w(int src, int level, const JobArgs& a, int cw, hipStr
   const LevelCfg cfg = level_cfg(level);
   if (cfg.nsub == 0 || cfg.max_lpc > 8) return hipErrorInvalidValue;  // levels 3-6 only
   if (!a.wave) return hipErrorInvalidValue;  // the plan's per-frame descriptors (wave-path plans)
+  // the instances fix their window count (levels 3-5: 1, level 6: 3 == num_windows(cfg.nsub))
+  if (a.nwin != wave_nwin(cfg.max_porder >= 6 ? 6 : cfg.max_porder)) return hipErrorInvalidValue;
   switch (cfg.max_porder) {
     case 4: k17 ? k_analyze_w<8, 4, true><<<grid, 64, 0, s>>>(a, src) : k_analyze_w<8, 4, false><<<grid, 64, 0, s>>>(a, src); break;
     case 5: k17 ? k_analyze_w<8, 5, true><<<grid, 64, 0, s>>>(a, src) : k_analyze_w<8, 5, false><<<grid, 64, 0, s>>>(a, src); break;
