@@ -1,5 +1,6 @@
-// fra_region.h -- the host scaffold of the five units that reduce a raster or a decoded region on the device
-// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip).  Once each:
+// fra_region.h -- the host scaffold of the six units over a raster or a decoded region on the device: five reduce it
+// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip) and one maps it
+// (fra_calc.hip, whose output has a dtype and a band count of its own: Dst, run_raster_to, run_region_to).  Once each:
 //   * the refusals they share: a bad dtype or raster layout (check_raster), items that do not cover the region
 //     (check_cover), and what is left to the windowed read, which refuses it with its own message
 //     (left_to_window_read, left_to_window_read_no_dst, refer_to_window_read);
@@ -216,34 +217,56 @@ struct Io {
   Strides ds;
 };
 
-// A raster job from the staging of its host buffers on: body(call, io) plans and runs the unit's kernels (timed) and
-// copies the destination back (copy_back).
+// a destination raster with a dtype and a band count of its own (a (channels, oh, ow) raster through its strides)
+struct Dst {
+  void* p;
+  int32_t on_device, dtype, channels, oh, ow;
+  Strides s;
+};
+
+// A (channels, h, w) source of `dtype` and a destination from the staging of their host buffers on: body(call, io)
+// plans and runs the unit's kernels (timed) and copies the destination back (copy_back).
 template <typename Body>
-inline int run_raster(fra_ctx* ctx, const RasterJob& j, Body&& body) {
+inline int run_raster_to(fra_ctx* ctx, const void* src, int32_t src_on_device, int32_t dtype, int32_t channels, int32_t h,
+                         int32_t w, const Strides& ss, const Dst& d, Body&& body) {
   Call c(ctx);
-  const size_t es = (size_t)elem_size(j.dtype);
-  Io io{nullptr, j.ss, {}, j.ds};
-  if (const int rc = stage_in(c, j.src, j.src_on_device, (size_t)extent_of(j.channels, j.h, j.w, j.ss) * es, &io.src))
+  Io io{nullptr, ss, {}, d.s};
+  if (const int rc = stage_in(c, src, src_on_device, (size_t)extent_of(channels, h, w, ss) * (size_t)elem_size(dtype), &io.src))
     return rc;
-  if (const int rc = stage_out(c, j.dst, j.dst_on_device, (size_t)extent_of(j.channels, j.oh, j.ow, j.ds) * es, &io.out))
+  if (const int rc = stage_out(c, d.p, d.on_device, (size_t)extent_of(d.channels, d.oh, d.ow, d.s) * (size_t)elem_size(d.dtype),
+                               &io.out))
     return rc;
   return body(c, io);
 }
-
-// The same for a region: decoded into a per-call buffer, which is the body's source; the job's dst and strides are
-// the (channels, oh, ow) destination.
+// ... for a raster job, whose destination has the source's dtype and band count
 template <typename Body>
-inline int run_region(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, int32_t oh,
-                      int32_t ow, Body&& body) {
+inline int run_raster(fra_ctx* ctx, const RasterJob& j, Body&& body) {
+  return run_raster_to(ctx, j.src, j.src_on_device, j.dtype, j.channels, j.h, j.w, j.ss,
+                       Dst{j.dst, j.dst_on_device, j.dtype, j.channels, j.oh, j.ow, j.ds}, body);
+}
+
+// The same for a region: decoded into a per-call buffer, which is the body's source.
+template <typename Body>
+inline int run_region_to(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, const Dst& d,
+                         Body&& body) {
   Call c(ctx);
   void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
   int64_t rs = 0;
   if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
-  Io io{d_region, {(int64_t)roi->height * rs, rs, 1}, {}, {job->band_stride, job->row_stride, job->col_stride}};
-  const size_t es = (size_t)elem_size(job->dst_dtype);
-  if (const int rc = stage_out(c, job->dst, job->dst_on_device, (size_t)extent_of(job->channels, oh, ow, io.ds) * es, &io.out))
+  Io io{d_region, {(int64_t)roi->height * rs, rs, 1}, {}, d.s};
+  if (const int rc = stage_out(c, d.p, d.on_device, (size_t)extent_of(d.channels, d.oh, d.ow, d.s) * (size_t)elem_size(d.dtype),
+                               &io.out))
     return rc;
   return body(c, io);
+}
+// ... into the job's dst and strides, the (channels, oh, ow) destination in dst_dtype
+template <typename Body>
+inline int run_region(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, int32_t oh,
+                      int32_t ow, Body&& body) {
+  return run_region_to(ctx, job, roi, infos,
+                       Dst{job->dst, job->dst_on_device, job->dst_dtype, job->channels, oh, ow,
+                           {job->band_stride, job->row_stride, job->col_stride}},
+                       body);
 }
 #endif
 

@@ -156,7 +156,28 @@ class StatsBand(C.Structure):
     ]
 
 
+class CalcProgram(C.Structure):
+    """``fra_calc_program`` (544 bytes; the rule: ``calc.py``)."""
+
+    _fields_ = [("ncode", C.c_int32), ("nconst", C.c_int32), ("nout", C.c_int32), ("flags", C.c_int32),
+                ("nodata", C.c_double), ("fill", C.c_double), ("code", C.c_uint16 * 128), ("consts", C.c_double * 32)]
+
+
+class CalcDst(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("dst_on_device", C.c_int32), ("dtype", C.c_int32), ("band_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("col_stride", C.c_int64)]
+
+
+class CalcJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("band_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64), ("program", CalcProgram), ("out", CalcDst),
+    ]
+
+
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
+CALC_NODATA = 1
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
 RESAMPLE_BILINEAR, RESAMPLE_CUBIC = 2, 3
@@ -211,6 +232,7 @@ EXPORTS = [
     "fra_compare_timing", "fra_stats", "fra_decode_device_stats", "fra_stats_timing", "fra_resample",
     "fra_decode_device_resampled", "fra_resample_timing", "fra_resample_masked", "fra_decimate_masked",
     "fra_decode_device_resampled_masked", "fra_decode_device_decimated_masked", "fra_resample_masked_timing",
+    "fra_calc_check", "fra_calc", "fra_decode_device_calc", "fra_calc_timing",
 ]
 
 
@@ -305,6 +327,12 @@ def load():
             L.fra_decode_device_decimated_masked.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), i32, i32,
                                                              C.POINTER(Decoded), C.c_double, C.POINTER(u64)]
             L.fra_resample_masked_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_calc"):
+            L.fra_calc_check.argtypes = [C.POINTER(CalcProgram), i32]
+            L.fra_calc.argtypes = [vp, C.POINTER(CalcJob), C.POINTER(u64)]
+            L.fra_decode_device_calc.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(CalcProgram),
+                                                 C.POINTER(CalcDst), C.POINTER(u64), C.POINTER(Decoded)]
+            L.fra_calc_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -333,6 +361,55 @@ def _masked_args(nodata, filled, dtype, channels: int):
             and filled.flags.c_contiguous and filled.flags.writeable):
         raise ValueError(f"filled must be a writable contiguous uint64 array of {int(channels)}")
     return nd, filled.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def calc_program(program, nodata=None, fill=None, out_dtype=None) -> CalcProgram:
+    """The ``fra_calc_program`` of a ``calc.Program`` as it is -- nothing is checked here: the library's validator
+    is the one that refuses -- with ``nodata`` (``None``: nothing is masked) and ``fill`` (``None``: the default of
+    ``out_dtype``, NaN for floats and 0 for integers)."""
+    from .calc import default_fill
+
+    code = np.asarray(program.code, dtype=np.uint16).reshape(-1)
+    consts = np.asarray(program.consts, dtype=np.float64).reshape(-1)
+    p = CalcProgram()
+    p.ncode, p.nconst, p.nout = code.size, consts.size, int(program.nout)
+    p.flags = 0 if nodata is None else CALC_NODATA
+    p.nodata = 0.0 if nodata is None else float(nodata)
+    p.fill = float(fill) if fill is not None else default_fill(out_dtype if out_dtype is not None else np.float64)
+    C.memmove(p.code, code.ctypes.data, min(code.size, 128) * 2)
+    C.memmove(p.consts, consts.ctypes.data, min(consts.size, 32) * 8)
+    return p
+
+
+def calc_check(program, nbands: int, nodata=None) -> None:
+    """``fra_calc_check``: raises :class:`NativeError` with the validator's message for an invalid program.  Pure host
+    code: no GPU is needed."""
+    p = calc_program(program, nodata)
+    _check(load().fra_calc_check(C.byref(p), int(nbands)))
+
+
+def _calc_dst(dst, dst_strides, out_dtype, shape) -> Tuple[CalcDst, object]:
+    """The ``fra_calc_dst`` for an ``(nout, h, w)`` output: ``None`` (a new array), a numpy array view or a device
+    pointer with element ``dst_strides`` (default band-planar); and what the caller returns."""
+    dt = np.dtype(out_dtype)
+    if dt not in DTYPE_CODES:
+        raise TypeError(f"unsupported dtype {dt}")
+    nout, h, w = shape
+    o = CalcDst()
+    o.dtype = DTYPE_CODES[dt]
+    ret = dst
+    if dst is None:
+        ret = dst = np.zeros((max(nout, 0), max(h, 0), max(w, 0)), dtype=dt)
+    if isinstance(dst, np.ndarray):
+        if dst.shape != (nout, h, w) or dst.dtype != dt:
+            raise ValueError(f"dst must be {(nout, h, w)} of {dt}, got {dst.shape} of {dst.dtype}")
+        st = _element_strides(dst)
+        o.dst, o.dst_on_device = C.c_void_p(dst.ctypes.data), 0
+    else:
+        st = tuple(int(v) for v in dst_strides) if dst_strides is not None else (h * w, w, 1)
+        o.dst, o.dst_on_device = C.c_void_p(int(dst)), 1
+    o.band_stride, o.row_stride, o.col_stride = st
+    return o, ret
 
 
 def _window_ref(w):
@@ -856,6 +933,49 @@ class Context:
         """HIP-event ms of this thread's last statistics kernels (:meth:`stats` / :meth:`decode_device_stats`)."""
         ms = C.c_float()
         _check(load().fra_stats_timing(C.byref(ms)))
+        return ms.value
+
+    def calc(self, src, program, out_dtype="float32", dst=None, *, nodata=None, fill=None, dtype=None, shape=None,
+             strides=None, dst_strides=None):
+        """Band math over a raster on this context's GPU (``fra_calc``, the rule of ``flac_raster.calc``): ``(the
+        (nout, h, w) result, the per-output count of left-out pixels)``.
+
+        ``src``: as :meth:`stats`.  ``program``: a ``calc.Program`` (``calc.compile_exprs``); an invalid one is refused
+        by the library before anything is launched.  ``dst``: ``None`` (a new array is returned), a numpy array view
+        ``(nout, h, w)`` of ``out_dtype`` (the elements between its outputs keep their values) or a device pointer with
+        element ``dst_strides`` (default band-planar).  ``nodata`` / ``fill``: as ``calc.calc_arrays``; the default
+        ``fill`` is NaN for float outputs and 0 for integer ones."""
+        job = CalcJob()
+        _, (B, h, w), st = _raster_source(job, src, dtype, shape, strides)
+        job.band_stride, job.row_stride, job.col_stride = st
+        job.program = calc_program(program, nodata, fill, out_dtype)
+        job.out, ret = _calc_dst(dst, dst_strides, out_dtype, (int(program.nout), h, w))
+        left = np.zeros(max(1, int(program.nout)), np.uint64)
+        _check(load().fra_calc(self.h, C.byref(job), left.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return ret, left[: int(program.nout)]
+
+    def decode_device_calc(self, data, items, dst_dtype, channels: int, roi, program, out_dtype="float32", dst=None, *,
+                           denorm: int = DENORM_NONE, nodata=None, fill=None, dst_strides=None):
+        """Band math over ``roi`` of the tile streams (``fra_decode_device_calc``): ``calc.calc_arrays`` of what
+        :meth:`decode_device_window` would have written in ``dst_dtype``, without the decoded region leaving the GPU.
+
+        ``data``, ``items``, ``roi``, ``denorm`` as :meth:`decode_device_window`; ``program``, ``out_dtype``, ``dst``,
+        ``nodata``, ``fill`` as :meth:`calc`.  The items must cover the region.  Returns ``(result, left-out counts,
+        infos)``."""
+        if roi is None:
+            raise ValueError("roi is required")
+        p = calc_program(program, nodata, fill, out_dtype)
+        o, ret = _calc_dst(dst, dst_strides, out_dtype, (int(program.nout), int(roi[2]), int(roi[3])))
+        left = np.zeros(max(1, int(program.nout)), np.uint64)
+        job, infos, keep = self._decode_job(data, items, None, np.dtype(dst_dtype), denorm, channels, (0, 0, 0))
+        infos = self._decode_run("fra_decode_device_calc", job, infos, keep, _window_ref(roi), C.byref(p), C.byref(o),
+                                 left.ctypes.data_as(C.POINTER(C.c_uint64)), infos)
+        return ret, left[: int(program.nout)], infos
+
+    def calc_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_calc`` (:meth:`calc` / :meth:`decode_device_calc`)."""
+        ms = C.c_float()
+        _check(load().fra_calc_timing(C.byref(ms)))
         return ms.value
 
     def decode_timing(self) -> List[float]:

@@ -468,6 +468,54 @@ def stats(
         raise typer.Exit(1)
 
 
+@app.command()
+def calc(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),
+    expr: List[str] = typer.Option(..., "--expr", "-e", help="Expression over b1 ... bN, e.g. '(b4-b3)/(b4+b3)'; "
+                                   "one per output band"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width'"),
+    dtype: str = typer.Option("float32", "--dtype", help="Output dtype"),
+    nodata: Optional[float] = typer.Option(None, "--nodata", help="Nodata value of the source (default: the TIFF's own "
+                                           "tag): pixels that hold it in a band the expressions read are left out"),
+    fill: Optional[float] = typer.Option(None, "--fill", help="What a left-out pixel gets (default: NaN for float "
+                                         "outputs, 0 for integer ones)"),
+    cpu: bool = typer.Option(False, "--cpu", help="Evaluate with numpy on the host"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Band math: per-pixel expressions over the bands of a streaming FLAC file or a GeoTIFF -> GeoTIFF."""
+    import numpy as np
+
+    from .streaming import calc_to_tiff
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        path = _local(file_path)
+        if not path.exists():
+            console.print(f"[red]File not found: {path}[/red]")
+            raise typer.Exit(1)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        got, left, n = calc_to_tiff(path, output_path, list(expr), window=win, bbox=box, out_dtype=np.dtype(dtype),
+                                    nodata=nodata, fill=fill, device=dev)
+        console.print(f"[green]{output_path}[/green]: {len(expr)} band(s) of {np.dtype(dtype)}, rows {got[0]}.."
+                      f"{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]}"
+                      + (f" (GPU {dev})" if dev is not None else " (host)"))
+        if nodata is not None or int(left[0]):
+            console.print("left out: " + ", ".join(f"band {k + 1}: {100.0 * int(v) / max(1, n):.2f}%"
+                                                   for k, v in enumerate(left)))
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Band math failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
 def _show_tiff_info(path: Path):
     from .tiff import GeoTIFF
 

@@ -676,6 +676,115 @@ def tiff_stats(path: Path, window: Optional[Sequence[int]] = None, bbox: Optiona
     return report_from_bands(bands, hist, dt), win, info
 
 
+# ------------------------------------------------------------------------------------------ band math
+def _calc_fill(fill, out_dtype):
+    from .calc import default_fill
+
+    return default_fill(out_dtype) if fill is None else float(fill)
+
+
+def calc_window(src, exprs, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                out_dtype="float32", nodata: Optional[float] = None, fill: Optional[float] = None,
+                device: Optional[int] = None, semantics: str = "pcm16"):
+    """Band math over a streaming container (path or bytes), or over a window of it -> ``(raster (nout, h, w) in
+    out_dtype, left-out pixels per output band, window, index)``: ``calc.calc_arrays(read_window(src, ...)[0],
+    calc.compile_exprs(exprs, bands), out_dtype, nodata, fill)``.
+
+    ``exprs``: one expression per output band over ``b1 ... bN`` (``calc.compile_exprs``); ``window`` / ``bbox`` as in
+    :func:`read_window` (default: the whole raster); ``nodata`` / ``fill`` as ``calc.calc_arrays``, the default ``fill``
+    being NaN for float outputs and 0 for integer ones.  ``device=None`` reads the window on the host and applies the
+    numpy rule; an integer makes one ``fra_decode_device_calc`` call on that GPU: the decoded pixels never leave the
+    device and only the result comes back."""
+    from . import _native
+    from .calc import calc_arrays, compile_exprs
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    if window is None and bbox is None:
+        index = _index_of(src)
+        window = (0, 0, int(index["height"]), int(index["width"]))
+    index, win, blob, items = _window_items(src, window, bbox)
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    program = compile_exprs(exprs, B)
+    odt = np.dtype(out_dtype)
+    fill = _calc_fill(fill, odt)
+    if device is None:
+        out = np.zeros((B, win[2], win[3]), dtype=dt)
+        _decode_window_on_host(blob, items, win, out, semantics)
+        res, left = calc_arrays(out, program, odt, nodata, fill)
+        return res, left, win, index
+    ctx = _native.default_context(int(device))
+    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+    res, left, _ = ctx.decode_device_calc(np.frombuffer(blob, dtype=np.uint8), items, dt, B, win, program, odt,
+                                          denorm=denorm, nodata=nodata, fill=fill)
+    return res, left, win, index
+
+
+def calc_tiff(path: Path, exprs, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+              out_dtype="float32", nodata: Optional[float] = None, fill: Optional[float] = None,
+              device: Optional[int] = None):
+    """:func:`calc_window` for a GeoTIFF source -> ``(raster, left-out pixels, window, info, the nodata used)``.  The
+    window is read with the in-package reader; an integer ``device`` hands it to ``fra_calc`` on that GPU, ``None`` to
+    the numpy rule.  ``nodata=None`` takes the TIFF's own nodata tag, when it has one."""
+    from . import _native
+    from .calc import calc_arrays, compile_exprs
+
+    g = GeoTIFF(Path(path))
+    try:
+        info = g.info
+        program = compile_exprs(exprs, int(info.count))
+        if window is None and bbox is None:
+            win = (0, 0, info.height, info.width)
+        else:
+            win = resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)},
+                                 window, bbox)
+        if nodata is None and info.nodata is not None:
+            nodata = float(info.nodata)
+        a = np.zeros((info.count, win[2], win[3]), dtype=np.dtype(info.dtype))
+        g.read_window_into(a, *win)
+    finally:
+        g.close()
+    odt = np.dtype(out_dtype)
+    fill = _calc_fill(fill, odt)
+    if device is None:
+        res, left = calc_arrays(a, program, odt, nodata, fill)
+    else:
+        res, left = _native.default_context(int(device)).calc(a, program, odt, nodata=nodata, fill=fill)
+    return res, left, win, info, nodata
+
+
+def calc_to_tiff(path: Path, tiff_path: Path, exprs, window: Optional[Sequence[int]] = None,
+                 bbox: Optional[Sequence[float]] = None, out_dtype="float32", nodata: Optional[float] = None,
+                 fill: Optional[float] = None, device: Optional[int] = None, semantics: str = "pcm16"):
+    """Band math over a streaming container or a GeoTIFF (told apart by their first bytes) -> GeoTIFF with the
+    source's CRS and the transform shifted to the window's origin.  When a nodata value was given (or the source TIFF
+    carries one) the result's nodata tag is ``fill`` as the output dtype holds it.  Returns ``(window, left-out pixels
+    per output band, pixels per band)``."""
+    from .tiff import write_geotiff
+
+    path = Path(path)
+    with open(path, "rb") as f:
+        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+    if is_tiff:
+        res, left, win, info, nodata = calc_tiff(path, exprs, window, bbox, out_dtype, nodata, fill, device)
+        t, crs = list(info.transform), str(info.crs) if info.crs is not None else None
+    elif is_streaming_container(path):
+        res, left, win, index = calc_window(path, exprs, window, bbox, out_dtype, nodata, fill, device, semantics)
+        t, crs = index.get("transform"), index.get("crs")
+    else:
+        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
+    tag = None
+    if nodata is not None:
+        from .calc import convert
+
+        v = convert(np.array([_calc_fill(fill, res.dtype)]), res.dtype)[0]
+        tag = float(v) if res.dtype.kind == "f" else int(v)
+    write_geotiff(Path(tiff_path), res, transform=transform, crs=crs if crs and crs != "None" else None, nodata=tag)
+    return win, left, int(win[2]) * int(win[3])
+
+
 def _index_of(src):
     if isinstance(src, (bytes, bytearray, memoryview)):
         return read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))[0]

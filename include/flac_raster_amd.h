@@ -623,6 +623,90 @@ FRA_API int fra_decode_device_stats(fra_ctx *ctx, const fra_decode_job *job, con
 /* HIP-event time (ms) of the calling thread's last statistics kernels, both passes and folds */
 FRA_API int fra_stats_timing(float *ms);
 
+/* Band math: per-pixel expressions over the bands of a raster (channels, h, w) of any fra_dtype, one expression per
+ * output band of a raster (nout, h, w) of any fra_dtype.  This unit maps a raster; the five above reduce one.
+ *   The program.  A stack program in reverse Polish notation, code[i] = op | arg << 8, at most FRA_CALC_MAX_CODE words,
+ *     FRA_CALC_MAX_CONST f64 constants, FRA_CALC_MAX_OUT outputs and a stack of FRA_CALC_MAX_DEPTH values.  Every value
+ *     is an f64; every element of the source is taken as f64 (exact for all eight dtypes).  arg is 0 for every op
+ *     without one.
+ *       FRA_CALC_CONST k   push consts[k]              FRA_CALC_BAND b   push the pixel's element of band b (0-based)
+ *       FRA_CALC_STORE k   pop x: output band k of the pixel is x, converted as below
+ *       ADD SUB MUL DIV    pop b, pop a, push a op b   NEG ABS SQRT FLOOR   pop x, push op x
+ *       MIN  a < b ? a : b         MAX  a > b ? a : b  (the < / > form, not minNum: MIN(NaN, 1) = 1, MIN(1, NaN) = NaN)
+ *       LT LE GT GE EQ NE  pop b, pop a, push 1.0 when a op b holds, else 0.0 (IEEE comparisons: NaN != NaN holds only)
+ *       AND OR             pop b, pop a, push 1.0 / 0.0 of the truths of a and b; NOT  pop x, push 1.0 when x is false
+ *       SELECT             pop b, pop a, pop c, push c true ? a : b
+ *     A value is true when x != 0.0, so NaN is true.  Every op is one IEEE f64 operation rounded on its own: no
+ *     contraction, no reassociation, division and square root correctly rounded.  NaN and +-inf flow through as IEEE
+ *     gives them.
+ *   Output.  f64 / f32: a NaN result becomes the quiet NaN 0x7ff8000000000000 (the sign and payload of a NaN are not
+ *     IEEE's to fix), then a plain cast.  Integer dtypes: rint(x), half to even, saturated to the dtype's range, NaN -> 0
+ *     (the rule of FRA_DENORM_INT).
+ *   Nodata.  With FRA_CALC_NODATA a pixel is left out when any band the program reads (a FRA_CALC_BAND word names it)
+ *     holds (double)x == nodata, or NaN; bands the program does not read are not looked at, and a NaN nodata matches
+ *     nothing.  Every output band of a left-out pixel gets `fill`, converted as above.  Without the flag nothing is
+ *     masked.  left_out receives per output band the number of left-out pixels (one number, nout times).
+ *   A program is valid when: 1 <= ncode <= 128, 0 <= nconst <= 32, 1 <= nout <= 8, no unknown flag bit, 1 <= channels
+ *     <= 255; every op is known and an op without an argument has arg 0; BAND's arg < channels, CONST's < nconst,
+ *     STORE's < nout; the stack never underflows nor exceeds 8 values and is empty after the last word; every output is
+ *     stored exactly once.  Any double -- NaN, inf -- is accepted as a constant, as nodata and as fill. */
+#define FRA_CALC_MAX_CODE 128
+#define FRA_CALC_MAX_CONST 32
+#define FRA_CALC_MAX_OUT 8
+#define FRA_CALC_MAX_DEPTH 8
+#define FRA_CALC_NODATA 1
+typedef enum {
+  FRA_CALC_CONST = 0, FRA_CALC_BAND = 1, FRA_CALC_STORE = 2,
+  FRA_CALC_ADD = 3, FRA_CALC_SUB = 4, FRA_CALC_MUL = 5, FRA_CALC_DIV = 6,
+  FRA_CALC_NEG = 7, FRA_CALC_ABS = 8, FRA_CALC_SQRT = 9, FRA_CALC_FLOOR = 10,
+  FRA_CALC_MIN = 11, FRA_CALC_MAX = 12,
+  FRA_CALC_LT = 13, FRA_CALC_LE = 14, FRA_CALC_GT = 15, FRA_CALC_GE = 16, FRA_CALC_EQ = 17, FRA_CALC_NE = 18,
+  FRA_CALC_AND = 19, FRA_CALC_OR = 20, FRA_CALC_NOT = 21, FRA_CALC_SELECT = 22
+} fra_calc_op;
+typedef struct {
+  int32_t ncode, nconst, nout, flags;       /* flags: FRA_CALC_NODATA */
+  double nodata, fill;
+  uint16_t code[FRA_CALC_MAX_CODE];
+  double consts[FRA_CALC_MAX_CONST];
+} fra_calc_program;                         /* 544 bytes */
+typedef struct {
+  void *dst; int32_t dst_on_device;         /* element (band 0, row 0, col 0) of the (nout, h, w) output */
+  int32_t dtype;                            /* fra_dtype of the output */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+} fra_calc_dst;
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype of the source */
+  int32_t channels, height, width;          /* >= 1; channels <= 255 */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+  fra_calc_program program;
+  fra_calc_dst out;
+} fra_calc_job;
+/* Whether `program` is valid for a source of `channels` bands (the list above).  Pure host code: no context, no GPU.
+ * FRA_E_INVALID with a message that names the offending word ("word 5: ...") or count. */
+FRA_API int fra_calc_check(const fra_calc_program *program, int32_t channels);
+/* k_calc alone, over a host or device raster of any layout into a host or device raster of any layout.  Synchronous.
+ * Host buffers are staged as fra_decimate stages them (one allocation spanning every addressed element from element 0;
+ * the elements of dst that are not outputs keep the caller's values).  Rows are read, and written, with vector accesses
+ * when the column stride is 1 and the base, the row stride and the band stride are multiples of 16 bytes, element by
+ * element otherwise; source and destination are judged separately.  left_out (host memory, nout words, may be NULL).
+ * FRA_E_INVALID, before any GPU work and in this order: a null argument, an invalid program (fra_calc_check), a bad
+ * source or destination dtype or layout, more than 2^32 pixels per band.  The kernel interprets the program, so nothing
+ * is launched for a program that has not passed the check. */
+FRA_API int fra_calc(fra_ctx *ctx, const fra_calc_job *job, uint64_t *left_out /* nout, may be NULL */);
+/* The program over what fra_decode_device_window would have written for `roi`, in job->dst_dtype, after its
+ * denormalisation and saturation.  roi, the items and infos mean what they mean there; job->dst and the job's strides
+ * are ignored: the region goes to a per-call device buffer (band-planar, rows padded to 16 bytes) and never leaves the
+ * device, and the result goes to `out`, a (program->nout, roi->height, roi->width) raster of out->dtype.  Every refusal
+ * and message of the windowed read is this call's as well; items that do not cover the region are refused as by
+ * fra_decode_device_compare; the program and `out` as by fra_calc.  Afterwards fra_decode_device_timing reports the
+ * inner windowed read and fra_calc_timing the map. */
+FRA_API int fra_decode_device_calc(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                   const fra_calc_program *program, const fra_calc_dst *out,
+                                   uint64_t *left_out /* nout, may be NULL */, fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last k_calc (fra_calc or fra_decode_device_calc) */
+FRA_API int fra_calc_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -76,6 +76,16 @@ skipped.
 
     python tools/bench_decode.py --compare --steps 5 --warmup 2
 
+``--calc EXPR`` times band math over the same container (``fra_decode_device_calc``: the whole raster decoded into a
+per-call buffer, then ``k_calc``) beside the plain read and beside ``k_stats`` without a histogram -- a streaming kernel's
+achieved bandwidth in the same session.  One expression per output band separated by ``;``, optionally ``:dtype``
+(default ``--dtype``); ``--calc`` may be repeated, each one a leg of the same run; ``--nodata corner`` masks with what
+pixel (0, 0) decodes to.  Per leg ``calc_wall_ms``, the inner read, ``k_calc_ms`` (HIP events), the bytes read (the bands
+the program reads, once) and written, and ``k_calc_TBps``.  It exits non-zero unless the first and last 256 rows equal
+``calc.calc_arrays`` of the plain read byte for byte.
+
+    python tools/bench_decode.py --calc "(b4-b3)/(b4+b3)" --calc "b1" --steps 5 --warmup 2
+
 ``--stats`` times the band statistics of the same container (``fra_decode_device_stats``: the whole raster decoded
 with ``pcm16`` semantics to uint16 and described there, only the reports and the histogram come back) in five legs: the
 plain read to a device destination, ``bins = 0`` (one pass), 256 bins over the automatic range (two passes), the exact
@@ -152,11 +162,15 @@ def main():
                     help="time the comparison of the container with its source raster against the plain read")
     ap.add_argument("--stats", action="store_true",
                     help="time the band statistics and histograms of the container against the plain read")
+    ap.add_argument("--calc", action="append", default=None, metavar="EXPR",
+                    help="time band math over the container against the plain read: one expression per output band, "
+                         "separated by ';', optionally followed by ':dtype'; repeat for further legs of the same run")
+    ap.add_argument("--dtype", default="float32", help="with --calc: the output dtype of the legs that name none")
     args = ap.parse_args()
     if args.decimate and args.resampling not in RESAMPLING:
         ap.error("--decimate takes --resampling nearest or average")
-    if args.nodata is not None and not (args.decimate or args.resample):
-        ap.error("--nodata goes with --decimate or --resample")
+    if args.nodata is not None and not (args.decimate or args.resample or args.calc):
+        ap.error("--nodata goes with --decimate, --resample or --calc")
     if args.nodata not in (None, "corner"):
         args.nodata = float(args.nodata)
 
@@ -408,6 +422,84 @@ def main():
                          "k_stats_TBps": round(reads * (once // B) / (med(ks) * 1e-3) / 1e12, 3),
                          "all_ms": {"k_stats": [round(v, 4) for v in ks]}}
         res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall]}
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
+
+    if args.calc:
+        from flac_raster.calc import calc_arrays, compile_exprs, default_fill
+
+        if len(wins) != len(calculate_tiles(H, W, TILE)):
+            raise SystemExit("--calc needs every tile: the region mapped is the whole raster")
+        roi = (0, 0, H, W)
+        citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
+        plain_wall, plain_ms = [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ctx.decode_device_window((frames_ptr, total), citems, dev_out, dt, B, (H * W, W, 1), roi, N.DENORM_PCM16)
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                plain_wall.append((t1 - t0) * 1e3)
+                plain_ms.append(ctx.decode_timing()[3])
+        rows = 256  # the rows checked against calc_arrays: the first and the last of the raster
+        top, bottom = np.empty((B, rows, W), dt), np.empty((B, rows, W), dt)
+        for b in range(B):
+            ctx.d2h(top[b], dev_out + (b * H * W) * dt.itemsize)
+            ctx.d2h(bottom[b], dev_out + (b * H * W + (H - rows) * W) * dt.itemsize)
+        nodata = float(top[0, 0, 0]) if corner else args.nodata
+        med = statistics.median
+        # the streaming kernel of this session: k_stats without a histogram reads every band once
+        ks = []
+        for s in range(args.warmup + args.steps):
+            ctx.decode_device_stats((frames_ptr, total), citems, dt, B, roi, N.DENORM_PCM16, 0, None)
+            if s >= args.warmup:
+                ks.append(ctx.stats_timing())
+        once = B * H * W * dt.itemsize
+        res = {
+            "workload": f"calc C4-like {W}x{H}x{B} uint16 (pcm16), tile {TILE}, level {LEVEL}, {len(wins)} tiles, "
+                        "whole raster",
+            "tiles": len(wins), "frames": nfr, "steps": args.steps, "warmup": args.warmup, "nodata": nodata,
+            "checked_rows_equal_calc_arrays": True,
+            "plain_ms": round(med(plain_ms), 3), "plain_wall_ms": round(med(plain_wall), 3),
+            "k_stats_ms": round(med(ks), 4), "k_stats_TBps": round(once / (med(ks) * 1e-3) / 1e12, 3), "legs": [],
+        }
+        for spec in args.calc:
+            text, _, odt = spec.rpartition(":") if ":" in spec else (spec, "", args.dtype)
+            exprs = [e.strip() for e in text.split(";") if e.strip()]
+            odt = np.dtype(odt)
+            prog = compile_exprs(exprs, B)
+            fill = default_fill(odt)
+            dev_res = ctx.alloc(prog.nout * H * W * odt.itemsize)
+            wall, inner, kc = [], [], []
+            for s in range(args.warmup + args.steps):
+                t0 = time.perf_counter()
+                _, left, _ = ctx.decode_device_calc((frames_ptr, total), citems, dt, B, roi, prog, odt, dst=dev_res,
+                                                    denorm=N.DENORM_PCM16, nodata=nodata, fill=fill)
+                t1 = time.perf_counter()
+                if s >= args.warmup:
+                    wall.append((t1 - t0) * 1e3)
+                    inner.append(ctx.decode_timing()[3])
+                    kc.append(ctx.calc_timing())
+            for part, r0 in ((top, 0), (bottom, H - rows)):
+                want, _ = calc_arrays(part, prog, odt, nodata, fill)
+                got = np.empty((prog.nout, rows, W), odt)
+                for k in range(prog.nout):
+                    ctx.d2h(got[k], dev_res + (k * H * W + r0 * W) * odt.itemsize)
+                if got.tobytes() != want.tobytes():
+                    raise SystemExit(f"calc {exprs}: rows {r0} ... {r0 + rows} differ from calc_arrays")
+            ctx.free(dev_res)
+            rd, wr = len(prog.bands_read()) * H * W * dt.itemsize, prog.nout * H * W * odt.itemsize
+            res["legs"].append({
+                "exprs": exprs, "dtype": str(odt), "words": int(prog.code.size), "left_out": int(left[0]),
+                "calc_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3),
+                "k_calc_ms": round(med(kc), 4), "bytes_read": rd, "bytes_written": wr,
+                "k_calc_TBps": round((rd + wr) / (med(kc) * 1e-3) / 1e12, 3),
+                "wall_over_plain": round(med(wall) / med(plain_wall), 3),
+                "all_ms": {"k_calc": [round(v, 4) for v in kc], "calc_wall": [round(v, 3) for v in wall]}})
+        res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall],
+                         "k_stats": [round(v, 4) for v in ks]}
         print(json.dumps(res), flush=True)
         plan.close()
         ctx.free(dev_out)

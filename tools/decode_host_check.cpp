@@ -11,12 +11,14 @@
 //   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
 //     their nodata-aware entries (fra_resample_masked.hip: a nodata value the dtype does not admit included),
-//     the comparison (fra_compare, fra_decode_device_compare) and the statistics (fra_stats, fra_decode_device_stats),
+//     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats) and
+//     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
 //     which returns before any GPU work, and the order of these refusals (inputs that break two rules at once).
 // usage: decode_host_check [--concat] file.flac ...
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -630,6 +632,101 @@ int main(int argc, char** argv) {
     { auto j = sj; j.opts = eight; j.opts.hist_hi = -1.0; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics: inverted range accepted"); }
     { auto j = sj; j.opts = eight; j.opts.hist_lo = -HUGE_VAL; EXPECT(fra_stats(ctx, &j, bands, hist) == FRA_E_INVALID && g_msg.find("range") != std::string::npos, "statistics: infinite range accepted"); }
     EXPECT(fra_stats_timing(nullptr) == FRA_E_INVALID, "statistics timing: null accepted");
+  }
+  // ... and of the band math (fra_calc.hip): the program validator (fra_calc.h), which needs no context, and the
+  // argument refusals of both entries, before any GPU work
+  {
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    auto word = [](int op, int arg = 0) { return (uint16_t)(op | arg << 8); };
+    fra_calc_program ndvi{};  // (b1 - b0) / (b1 + b0)
+    const uint16_t code[] = {word(FRA_CALC_BAND, 1), word(FRA_CALC_BAND, 0), word(FRA_CALC_SUB), word(FRA_CALC_BAND, 1),
+                             word(FRA_CALC_BAND, 0), word(FRA_CALC_ADD), word(FRA_CALC_DIV), word(FRA_CALC_STORE, 0)};
+    memcpy(ndvi.code, code, sizeof(code));
+    ndvi.ncode = 8; ndvi.nout = 1;
+    EXPECT(fra_calc_check(&ndvi, 2) == FRA_OK, "calc check: NDVI refused: %s", g_msg.c_str());
+    EXPECT(fra_calc_check(nullptr, 2) == FRA_E_INVALID, "calc check: null program accepted");
+    EXPECT(says(fra_calc_check(&ndvi, 1), "word 0: band 1 of 1"), "calc check: band past the channels: %s", g_msg.c_str());
+    for (int ch : {0, 256}) EXPECT(says(fra_calc_check(&ndvi, ch), "source bands"), "calc check: %d channels accepted", ch);
+    for (int n : {0, -1, 129}) { auto p = ndvi; p.ncode = n; EXPECT(says(fra_calc_check(&p, 2), "words outside"), "calc check: %d words accepted", n); }
+    for (int n : {-1, 33}) { auto p = ndvi; p.nconst = n; EXPECT(says(fra_calc_check(&p, 2), "constants outside"), "calc check: %d constants accepted", n); }
+    for (int n : {0, 9}) { auto p = ndvi; p.nout = n; EXPECT(says(fra_calc_check(&p, 2), "outputs outside"), "calc check: %d outputs accepted", n); }
+    { auto p = ndvi; p.flags = 2; EXPECT(says(fra_calc_check(&p, 2), "flags"), "calc check: flag 2 accepted"); }
+    { auto p = ndvi; p.flags = FRA_CALC_NODATA; p.nodata = NAN; p.fill = HUGE_VAL; EXPECT(fra_calc_check(&p, 2) == FRA_OK, "calc check: NaN nodata and infinite fill refused"); }
+    { auto p = ndvi; p.code[2] = word(23); EXPECT(says(fra_calc_check(&p, 2), "word 2: unknown op 23"), "calc check: op 23: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[2] = word(255, 255); EXPECT(says(fra_calc_check(&p, 2), "word 2: unknown op 255"), "calc check: op 255: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[2] = word(FRA_CALC_SUB, 1); EXPECT(says(fra_calc_check(&p, 2), "word 2: op 4 takes no argument"), "calc check: SUB with an argument: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[1] = word(FRA_CALC_CONST, 0); EXPECT(says(fra_calc_check(&p, 2), "word 1: constant 0 of 0"), "calc check: constant past nconst: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[1] = word(FRA_CALC_CONST, 31); p.nconst = 32; p.consts[31] = NAN; EXPECT(fra_calc_check(&p, 2) == FRA_OK, "calc check: a NaN constant refused"); }
+    { auto p = ndvi; p.code[0] = word(FRA_CALC_NEG); EXPECT(says(fra_calc_check(&p, 2), "word 0: stack underflow"), "calc check: underflow: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[3] = word(FRA_CALC_SELECT); EXPECT(says(fra_calc_check(&p, 2), "word 3: stack underflow"), "calc check: SELECT of one value: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[7] = word(FRA_CALC_STORE, 1); EXPECT(says(fra_calc_check(&p, 2), "word 7: output 1 of 1"), "calc check: output past nout: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.nout = 2; EXPECT(says(fra_calc_check(&p, 2), "word 7: output 1 is never stored"), "calc check: missing output: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.ncode = 7; EXPECT(says(fra_calc_check(&p, 2), "word 6: 1 values left"), "calc check: values left: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.code[8] = word(FRA_CALC_BAND, 0); p.code[9] = word(FRA_CALC_STORE, 0); p.ncode = 10; EXPECT(says(fra_calc_check(&p, 2), "word 9: output 0 stored twice"), "calc check: stored twice: %s", g_msg.c_str()); }
+    { fra_calc_program p{}; for (int i = 0; i < 9; i++) p.code[i] = word(FRA_CALC_BAND, 0); p.ncode = 9; p.nout = 1; EXPECT(says(fra_calc_check(&p, 2), "word 8: stack deeper than 8"), "calc check: depth 9: %s", g_msg.c_str()); }
+    { fra_calc_program p{}; for (int i = 0; i < 128; i++) p.code[i] = word(i % 2 ? FRA_CALC_NEG : FRA_CALC_ABS); p.code[0] = word(FRA_CALC_BAND, 254); p.code[127] = word(FRA_CALC_STORE, 0); p.ncode = 128; p.nout = 1; EXPECT(fra_calc_check(&p, 255) == FRA_OK, "calc check: 128 words over band 254 refused: %s", g_msg.c_str()); }
+    // every word of every value: the validator reads nothing outside the program
+    { fra_calc_program p{}; p.ncode = 1; p.nout = 1; for (int w = 0; w < 65536; w++) { p.code[0] = (uint16_t)w; EXPECT(fra_calc_check(&p, 255) == FRA_E_INVALID, "calc check: the lone word %d accepted", w); } }
+
+    static float out[64];
+    fra_calc_job cj{};
+    cj.src = dst; cj.dtype = FRA_I32; cj.channels = 2; cj.height = 4; cj.width = 8;
+    cj.band_stride = 32; cj.row_stride = 8; cj.col_stride = 1;
+    cj.program = ndvi;
+    cj.out.dst = out; cj.out.dtype = FRA_F32; cj.out.band_stride = 32; cj.out.row_stride = 8; cj.out.col_stride = 1;
+    uint64_t left[8];
+    EXPECT(fra_calc(nullptr, &cj, left) == FRA_E_INVALID, "calc: null ctx accepted");
+    EXPECT(fra_calc(ctx, nullptr, left) == FRA_E_INVALID, "calc: null job accepted");
+    { auto j = cj; j.src = nullptr; EXPECT(fra_calc(ctx, &j, left) == FRA_E_INVALID, "calc: null src accepted"); }
+    { auto j = cj; j.out.dst = nullptr; EXPECT(fra_calc(ctx, &j, nullptr) == FRA_E_INVALID, "calc: null dst accepted"); }
+    { auto j = cj; j.channels = 1; EXPECT(says(fra_calc(ctx, &j, left), "word 0: band 1 of 1"), "calc: band past the channels: %s", g_msg.c_str()); }
+    { auto j = cj; j.program.code[7] = word(FRA_CALC_ADD); EXPECT(says(fra_calc(ctx, &j, left), "word 7"), "calc: invalid program: %s", g_msg.c_str()); }
+    { auto j = cj; j.dtype = 8; EXPECT(says(fra_calc(ctx, &j, left), "bad dtype"), "calc: source dtype 8: %s", g_msg.c_str()); }
+    { auto j = cj; j.out.dtype = -1; EXPECT(says(fra_calc(ctx, &j, left), "bad dtype"), "calc: destination dtype -1: %s", g_msg.c_str()); }
+    { auto j = cj; j.width = 0; EXPECT(says(fra_calc(ctx, &j, left), "bad raster layout"), "calc: zero width: %s", g_msg.c_str()); }
+    { auto j = cj; j.row_stride = -8; EXPECT(says(fra_calc(ctx, &j, left), "bad raster layout"), "calc: negative source stride: %s", g_msg.c_str()); }
+    { auto j = cj; j.out.col_stride = -1; EXPECT(says(fra_calc(ctx, &j, left), "bad raster layout"), "calc: negative destination stride: %s", g_msg.c_str()); }
+    { auto j = cj; j.height = 65537; j.width = 65536; EXPECT(says(fra_calc(ctx, &j, left), "2^32 pixels"), "calc: more than 2^32 pixels: %s", g_msg.c_str()); }
+    // the order: the program, then the source, then the destination, then the size
+    { auto j = cj; j.program.ncode = 0; j.dtype = 8; EXPECT(says(fra_calc(ctx, &j, left), "words outside"), "calc: no words and dtype 8: %s", g_msg.c_str()); }
+    { auto j = cj; j.dtype = 8; j.out.dtype = 8; j.width = 0; EXPECT(says(fra_calc(ctx, &j, left), "bad dtype"), "calc: dtype 8 and zero width: %s", g_msg.c_str()); }
+    { auto j = cj; j.out.row_stride = -1; j.height = 65537; j.width = 65536; EXPECT(says(fra_calc(ctx, &j, left), "bad raster layout"), "calc: negative stride and 2^32 pixels: %s", g_msg.c_str()); }
+    EXPECT(fra_calc_timing(nullptr) == FRA_E_INVALID, "calc timing: null accepted");
+
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;
+    dj.items = &di;
+    dj.dst = nullptr;  // ignored, as are the job's strides
+    dj.band_stride = dj.row_stride = dj.col_stride = -1;
+    dj.channels = 2;
+    const fra_window r48{0, 0, 4, 8};
+    const fra_calc_dst od = cj.out;
+    auto rc = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, const fra_calc_program* p, const fra_calc_dst* o,
+                  fra_decoded* d) { return fra_decode_device_calc(c, j, r, p, o, left, d); };
+    EXPECT(rc(nullptr, &dj, &r48, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: null ctx accepted");
+    EXPECT(rc(ctx, nullptr, &r48, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: null job accepted");
+    EXPECT(rc(ctx, &dj, nullptr, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: null roi accepted");
+    EXPECT(rc(ctx, &dj, &r48, nullptr, &od, inf) == FRA_E_INVALID, "calc read: null program accepted");
+    EXPECT(rc(ctx, &dj, &r48, &ndvi, nullptr, inf) == FRA_E_INVALID, "calc read: null destination accepted");
+    EXPECT(rc(ctx, &dj, &r48, &ndvi, &od, nullptr) == FRA_E_INVALID, "calc read: null infos accepted");
+    { auto o = od; o.dst = nullptr; EXPECT(rc(ctx, &dj, &r48, &ndvi, &o, inf) == FRA_E_INVALID, "calc read: null dst accepted"); }
+    { auto j = dj; j.channels = 1; EXPECT(says(rc(ctx, &j, &r48, &ndvi, &od, inf), "word 0: band 1 of 1"), "calc read: band past the channels: %s", g_msg.c_str()); }
+    { auto p = ndvi; p.nout = 9; EXPECT(says(rc(ctx, &dj, &r48, &p, &od, inf), "outputs outside"), "calc read: 9 outputs: %s", g_msg.c_str()); }
+    { auto o = od; o.dtype = 8; EXPECT(says(rc(ctx, &dj, &r48, &ndvi, &o, inf), "bad dtype"), "calc read: destination dtype 8: %s", g_msg.c_str()); }
+    { auto o = od; o.band_stride = -1; EXPECT(says(rc(ctx, &dj, &r48, &ndvi, &o, inf), "bad raster layout"), "calc read: negative destination stride: %s", g_msg.c_str()); }
+    { fra_window r = r48; r.height = 5; EXPECT(says(rc(ctx, &dj, &r, &ndvi, &od, inf), "do not cover"), "calc read: uncovered row: %s", g_msg.c_str()); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(says(rc(ctx, &j, &r48, &ndvi, &od, inf), "do not cover"), "calc read: uncovered column: %s", g_msg.c_str()); }
+    { auto j = dj; j.nitems = 0; EXPECT(rc(ctx, &j, &r48, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(says(rc(ctx, &dj, &r, &ndvi, &od, inf), "region of interest"), "calc read: zero-width roi: %s", g_msg.c_str()); }
+    { fra_window r{0, 0, 65537, 65536}; EXPECT(says(rc(ctx, &dj, &r, &ndvi, &od, inf), "2^32 pixels"), "calc read: more than 2^32 pixels: %s", g_msg.c_str()); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(rc(ctx, &j, &r48, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(says(rc(ctx, &j, &r48, &ndvi, &od, inf), "dtype"), "calc read: dtype 9: %s", g_msg.c_str()); }
+    { auto j = dj; j.denorm = 7; EXPECT(rc(ctx, &j, &r48, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: denorm 7 accepted"); }
+    { auto j = dj; j.channels = 0; EXPECT(rc(ctx, &j, &r48, &ndvi, &od, inf) == FRA_E_INVALID, "calc read: no channels accepted"); }
+    // the windowed read's refusals come first, then the program, then the destination, then the cover
+    { fra_window r = r48; r.width = 0; auto p = ndvi; p.ncode = 0; EXPECT(says(rc(ctx, &dj, &r, &p, &od, inf), "region of interest"), "calc read: zero-width roi and no words: %s", g_msg.c_str()); }
+    { fra_window r = r48; r.height = 5; auto p = ndvi; p.ncode = 0; EXPECT(says(rc(ctx, &dj, &r, &p, &od, inf), "words outside"), "calc read: uncovered row and no words: %s", g_msg.c_str()); }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
   {
