@@ -70,9 +70,6 @@ struct CalcArgs {
   double consts[FRA_CALC_MAX_CONST];
 };
 
-template <typename T, int P>
-struct alignas(sizeof(T) * P < 16 ? sizeof(T) * P : 16) VecOf { T v[P]; };
-
 // elements [0, n) of a slot as f64 (the others 0.0)
 template <typename S, int P>
 __device__ inline void load_slot(const S* p, int64_t cs, bool vec, int n, double* x) {
@@ -83,18 +80,6 @@ __device__ inline void load_slot(const S* p, int64_t cs, bool vec, int n, double
   } else {
 #pragma unroll
     for (int i = 0; i < P; i++) x[i] = i < n ? (double)p[(int64_t)i * cs] : 0.0;
-  }
-}
-
-__device__ inline double sat(double x, double lo, double hi) { return x != x ? 0.0 : (x < lo ? lo : (x > hi ? hi : x)); }
-
-// the rule's conversion of a result
-template <typename D>
-__device__ inline D to_out(double x) {
-  if constexpr (std::is_floating_point<D>::value) {
-    return (D)(x != x ? __longlong_as_double(0x7ff8000000000000ll) : x);
-  } else {
-    return (D)sat(rint(x), (double)std::numeric_limits<D>::lowest(), (double)std::numeric_limits<D>::max());
   }
 }
 

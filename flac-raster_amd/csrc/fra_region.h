@@ -1,6 +1,7 @@
-// fra_region.h -- the host scaffold of the six units over a raster or a decoded region on the device: five reduce it
-// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip) and one maps it
-// (fra_calc.hip, whose output has a dtype and a band count of its own: Dst, run_raster_to, run_region_to).  Once each:
+// fra_region.h -- the host scaffold of the seven units over a raster or a decoded region on the device: five reduce it
+// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip) and two map it
+// (fra_calc.hip and fra_focal.hip, whose output has a dtype, a size or a band count of its own: Dst, run_raster_to,
+// run_region_to).  Once each:
 //   * the refusals they share: a bad dtype or raster layout (check_raster), items that do not cover the region
 //     (check_cover), and what is left to the windowed read, which refuses it with its own message
 //     (left_to_window_read, left_to_window_read_no_dst, refer_to_window_read);
@@ -15,6 +16,8 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <limits>
+#include <type_traits>
 
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
@@ -267,6 +270,22 @@ inline int run_region(fra_ctx* ctx, const fra_decode_job* job, const fra_window*
                        Dst{job->dst, job->dst_on_device, job->dst_dtype, job->channels, oh, ow,
                            {job->band_stride, job->row_stride, job->col_stride}},
                        body);
+}
+
+// Device code the mapping units (fra_calc.hip, fra_focal.hip) share: P neighbouring elements as one vector access,
+// and the rule's conversion of an f64 result (include/flac_raster_amd.h, band math: Output).
+template <typename T, int P>
+struct alignas(sizeof(T) * P < 16 ? sizeof(T) * P : 16) VecOf { T v[P]; };
+
+__device__ inline double sat(double x, double lo, double hi) { return x != x ? 0.0 : (x < lo ? lo : (x > hi ? hi : x)); }
+
+template <typename D>
+__device__ inline D to_out(double x) {
+  if constexpr (std::is_floating_point<D>::value) {
+    return (D)(x != x ? __longlong_as_double(0x7ff8000000000000ll) : x);
+  } else {
+    return (D)sat(rint(x), (double)std::numeric_limits<D>::lowest(), (double)std::numeric_limits<D>::max());
+  }
 }
 #endif
 

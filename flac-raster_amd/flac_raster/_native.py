@@ -176,6 +176,21 @@ class CalcJob(C.Structure):
     ]
 
 
+class FocalSpec(C.Structure):
+    """``fra_focal_spec`` (1904 bytes; the rule: ``focal.py``)."""
+
+    _fields_ = [("op", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32), ("edge", C.c_int32), ("flags", C.c_int32),
+                ("nodata", C.c_double), ("fill", C.c_double), ("params", C.c_double * 8), ("weights", C.c_double * 225)]
+
+
+class FocalJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("band_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64), ("rect", Window), ("spec", FocalSpec), ("out", CalcDst),
+    ]
+
+
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 CALC_NODATA = 1
 DECODE_CONCAT = 1
@@ -233,6 +248,7 @@ EXPORTS = [
     "fra_decode_device_resampled", "fra_resample_timing", "fra_resample_masked", "fra_decimate_masked",
     "fra_decode_device_resampled_masked", "fra_decode_device_decimated_masked", "fra_resample_masked_timing",
     "fra_calc_check", "fra_calc", "fra_decode_device_calc", "fra_calc_timing",
+    "fra_focal_check", "fra_focal", "fra_decode_device_focal", "fra_focal_timing",
 ]
 
 
@@ -333,6 +349,13 @@ def load():
             L.fra_decode_device_calc.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(CalcProgram),
                                                  C.POINTER(CalcDst), C.POINTER(u64), C.POINTER(Decoded)]
             L.fra_calc_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_focal"):
+            L.fra_focal_check.argtypes = [C.POINTER(FocalSpec)]
+            L.fra_focal.argtypes = [vp, C.POINTER(FocalJob), C.POINTER(u64)]
+            L.fra_decode_device_focal.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(FocalSpec),
+                                                  C.POINTER(Window), C.POINTER(CalcDst), C.POINTER(u64),
+                                                  C.POINTER(Decoded)]
+            L.fra_focal_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -386,6 +409,31 @@ def calc_check(program, nbands: int, nodata=None) -> None:
     code: no GPU is needed."""
     p = calc_program(program, nodata)
     _check(load().fra_calc_check(C.byref(p), int(nbands)))
+
+
+def focal_spec(spec, out_dtype=None) -> FocalSpec:
+    """The ``fra_focal_spec`` of a ``focal.Spec`` as it is -- nothing is checked here: the library's validator is the
+    one that refuses -- with the default ``fill`` of ``out_dtype`` (NaN for floats, 0 for integers) when the spec has
+    none."""
+    from .calc import default_fill
+
+    s = FocalSpec()
+    s.op, s.kh, s.kw, s.edge, s.flags = int(spec.op), int(spec.kh), int(spec.kw), int(spec.edge), spec.flag_bits()
+    s.nodata = 0.0 if spec.nodata is None else float(spec.nodata)
+    s.fill = float(spec.fill) if spec.fill is not None else default_fill(out_dtype if out_dtype is not None else np.float64)
+    for k, v in enumerate(spec.params):
+        s.params[k] = v
+    if spec.weights is not None:
+        w = np.ascontiguousarray(spec.weights, dtype=np.float64).reshape(-1)
+        C.memmove(s.weights, w.ctypes.data, min(w.size, 225) * 8)
+    return s
+
+
+def focal_check(spec) -> None:
+    """``fra_focal_check``: raises :class:`NativeError` with the validator's message for an invalid spec.  Pure host
+    code: no GPU is needed."""
+    s = focal_spec(spec)
+    _check(load().fra_focal_check(C.byref(s)))
 
 
 def _calc_dst(dst, dst_strides, out_dtype, shape) -> Tuple[CalcDst, object]:
@@ -976,6 +1024,51 @@ class Context:
         """HIP-event ms of this thread's last ``k_calc`` (:meth:`calc` / :meth:`decode_device_calc`)."""
         ms = C.c_float()
         _check(load().fra_calc_timing(C.byref(ms)))
+        return ms.value
+
+    def focal(self, src, spec, out_dtype="float32", dst=None, *, out_window=None, dtype=None, shape=None, strides=None,
+              dst_strides=None):
+        """A focal operation over a raster on this context's GPU (``fra_focal``, the rule of ``flac_raster.focal``):
+        ``(the (B, out_h, out_w) result, the per-band count of pixels that got fill)``.
+
+        ``src``, ``dst``, ``dst_strides``: as :meth:`calc`.  ``spec``: a ``focal.Spec``; an invalid one is refused by the
+        library before anything is launched.  ``out_window`` = (row_off, col_off, out_h, out_w) inside the source,
+        default all of it: neighbours outside it are read."""
+        job = FocalJob()
+        _, (B, h, w), st = _raster_source(job, src, dtype, shape, strides)
+        job.band_stride, job.row_stride, job.col_stride = st
+        win = (0, 0, h, w) if out_window is None else tuple(int(v) for v in out_window)
+        job.rect = Window(*win)
+        job.spec = focal_spec(spec, out_dtype)
+        job.out, ret = _calc_dst(dst, dst_strides, out_dtype, (B, win[2], win[3]))
+        left = np.zeros(max(1, B), np.uint64)
+        _check(load().fra_focal(self.h, C.byref(job), left.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return ret, left[:B]
+
+    def decode_device_focal(self, data, items, dst_dtype, channels: int, roi, spec, inner, out_dtype="float32", dst=None,
+                            *, denorm: int = DENORM_NONE, dst_strides=None):
+        """A focal operation over the tile streams (``fra_decode_device_focal``): ``focal.focal_arrays`` of what
+        :meth:`decode_device_window` would have written for ``roi`` in ``dst_dtype``, over the rectangle ``inner`` of
+        it, without the decoded region leaving the GPU.
+
+        ``data``, ``items``, ``roi``, ``denorm`` as :meth:`decode_device_window`; ``roi`` is the wanted rectangle grown
+        by the window's radius and clipped to the raster, ``inner`` = (row_off, col_off, h, w) the wanted rectangle
+        relative to it.  ``spec``, ``out_dtype``, ``dst`` as :meth:`focal`.  The items must cover ``roi``.  Returns
+        ``(result, fill counts, infos)``."""
+        if roi is None or inner is None:
+            raise ValueError("roi and inner are required")
+        s = focal_spec(spec, out_dtype)
+        o, ret = _calc_dst(dst, dst_strides, out_dtype, (int(channels), int(inner[2]), int(inner[3])))
+        left = np.zeros(max(1, int(channels)), np.uint64)
+        job, infos, keep = self._decode_job(data, items, None, np.dtype(dst_dtype), denorm, channels, (0, 0, 0))
+        infos = self._decode_run("fra_decode_device_focal", job, infos, keep, _window_ref(roi), C.byref(s),
+                                 _window_ref(inner), C.byref(o), left.ctypes.data_as(C.POINTER(C.c_uint64)), infos)
+        return ret, left[: int(channels)], infos
+
+    def focal_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_focal`` (:meth:`focal` / :meth:`decode_device_focal`)."""
+        ms = C.c_float()
+        _check(load().fra_focal_timing(C.byref(ms)))
         return ms.value
 
     def decode_timing(self) -> List[float]:

@@ -516,6 +516,132 @@ def calc(
         raise typer.Exit(1)
 
 
+def _run_focal(what: str, file_path: str, output_path: Path, spec, bbox, pixels, dtype: str, cpu: bool, device):
+    """The three focal commands from their spec (a ``focal.Spec`` or a function of the pixel sizes) on."""
+    import numpy as np
+
+    from .streaming import focal_to_tiff
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        path = _local(file_path)
+        if not path.exists():
+            console.print(f"[red]File not found: {path}[/red]")
+            raise typer.Exit(1)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        got, left, n = focal_to_tiff(path, output_path, spec(), window=win, bbox=box, out_dtype=np.dtype(dtype), device=dev)
+        console.print(f"[green]{output_path}[/green]: {what}, {len(left)} band(s) of {np.dtype(dtype)}, rows {got[0]}.."
+                      f"{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]}"
+                      + (f" (GPU {dev})" if dev is not None else " (host)"))
+        console.print("left out: " + ", ".join(f"band {k + 1}: {100.0 * int(v) / max(1, n):.2f}%"
+                                               for k, v in enumerate(left)))
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Focal operation failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
+_F_BBOX = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'")
+_F_WINDOW = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width' (neighbours "
+                         "outside it are still read)")
+_F_EDGE = typer.Option("skip", "--edge", help="Taps outside the raster: skip (left out) or clamp (the nearest pixel)")
+_F_NODATA = typer.Option(None, "--nodata", help="Nodata value of the source (default: the TIFF's own tag): taps that "
+                         "hold it are left out")
+_F_FILL = typer.Option(None, "--fill", help="What a pixel without a result gets (default: NaN for float outputs, 0 for "
+                       "integer ones)")
+_F_KEEP = typer.Option(False, "--keep-mask", help="A pixel that is itself nodata or NaN gets the fill")
+_F_CPU = typer.Option(False, "--cpu", help="Evaluate with numpy on the host")
+_F_DEVICE = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)")
+
+
+@app.command()
+def focal(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),
+    op: Optional[str] = typer.Option(None, "--op", help="mean, sum, min, max, count or median over the window"),
+    size: str = typer.Option("3", "--size", help="Window: one odd number 1 ... 15, or 'HEIGHTxWIDTH' (median: at most "
+                             "25 pixels)"),
+    kernel: Optional[str] = typer.Option(None, "--kernel", help="Convolution weights, rows separated by ';': "
+                                         "'0,-1,0;-1,4,-1;0,-1,0'"),
+    normalize: bool = typer.Option(False, "--normalize", help="Divide a convolution by the sum of the weights used"),
+    bbox: Optional[str] = _F_BBOX, pixels: Optional[str] = _F_WINDOW, edge: str = _F_EDGE,
+    nodata: Optional[float] = _F_NODATA, fill: Optional[float] = _F_FILL, keep_mask: bool = _F_KEEP,
+    dtype: str = typer.Option("float32", "--dtype", help="Output dtype"),
+    cpu: bool = _F_CPU, device: Optional[int] = _F_DEVICE,
+):
+    """Focal statistics (--op) or a convolution (--kernel) over a streaming FLAC file or a GeoTIFF -> GeoTIFF."""
+    from .focal import Spec
+
+    def spec():
+        if (op is None) == (kernel is None):
+            raise ValueError("give exactly one of --op and --kernel")
+        if kernel is not None:
+            rows = [[float(v) for v in row.split(",")] for row in kernel.split(";")]
+            if len({len(r) for r in rows}) != 1:
+                raise ValueError("--kernel: every row needs the same number of weights")
+            return Spec("convolve", (len(rows), len(rows[0])), edge, nodata, fill, normalize, keep_mask, rows)
+        if op.lower() not in ("mean", "sum", "min", "max", "count", "median"):
+            raise ValueError(f"--op: {op!r} is none of mean, sum, min, max, count, median")
+        kh, _, kw = size.lower().partition("x")
+        return Spec(op, (int(kh), int(kw or kh)), edge, nodata, fill, normalize, keep_mask)
+
+    _run_focal(f"{op or 'convolution'} {size if kernel is None else ''}".strip(), file_path, output_path, spec, bbox,
+               pixels, dtype, cpu, device)
+
+
+@app.command()
+def hillshade(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF holding elevations"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),
+    azimuth: float = typer.Option(315.0, "--azimuth", help="Direction of the light, degrees clockwise from north"),
+    altitude: float = typer.Option(45.0, "--altitude", help="Height of the light above the horizon, degrees"),
+    z_factor: float = typer.Option(1.0, "--z-factor", help="Vertical exaggeration"),
+    scale_xy: float = typer.Option(1.0, "--scale-xy", help="Ground units per elevation unit (111120 for degrees and "
+                                   "metres)"),
+    scale: float = typer.Option(255.0, "--scale", help="Value of a fully lit pixel"),
+    bbox: Optional[str] = _F_BBOX, pixels: Optional[str] = _F_WINDOW, edge: str = _F_EDGE,
+    nodata: Optional[float] = _F_NODATA, fill: Optional[float] = _F_FILL, keep_mask: bool = _F_KEEP,
+    dtype: str = typer.Option("uint8", "--dtype", help="Output dtype"),
+    cpu: bool = _F_CPU, device: Optional[int] = _F_DEVICE,
+):
+    """Hillshade (Horn's gradient) of a streaming FLAC file or a GeoTIFF -> GeoTIFF."""
+    from .focal import Spec, hillshade_params
+
+    def spec():
+        return lambda dx, dy: Spec("hillshade", 3, edge, nodata, fill, False, keep_mask, None,
+                                   hillshade_params(azimuth, altitude, z_factor, dx * scale_xy, dy * scale_xy, scale))
+
+    _run_focal("hillshade", file_path, output_path, spec, bbox, pixels, dtype, cpu, device)
+
+
+@app.command()
+def slope(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF holding elevations"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),
+    percent: bool = typer.Option(False, "--percent", help="Percent instead of rise over run"),
+    z_factor: float = typer.Option(1.0, "--z-factor", help="Vertical exaggeration"),
+    scale_xy: float = typer.Option(1.0, "--scale-xy", help="Ground units per elevation unit"),
+    bbox: Optional[str] = _F_BBOX, pixels: Optional[str] = _F_WINDOW, edge: str = _F_EDGE,
+    nodata: Optional[float] = _F_NODATA, fill: Optional[float] = _F_FILL, keep_mask: bool = _F_KEEP,
+    dtype: str = typer.Option("float32", "--dtype", help="Output dtype"),
+    cpu: bool = _F_CPU, device: Optional[int] = _F_DEVICE,
+):
+    """Slope (Horn's gradient, rise over run or percent) of a streaming FLAC file or a GeoTIFF -> GeoTIFF."""
+    from .focal import Spec, slope_params
+
+    def spec():
+        return lambda dx, dy: Spec("slope", 3, edge, nodata, fill, False, keep_mask, None,
+                                   slope_params(z_factor, dx * scale_xy, dy * scale_xy, 100.0 if percent else 1.0))
+
+    _run_focal("slope", file_path, output_path, spec, bbox, pixels, dtype, cpu, device)
+
+
 def _show_tiff_info(path: Path):
     from .tiff import GeoTIFF
 

@@ -785,6 +785,137 @@ def calc_to_tiff(path: Path, tiff_path: Path, exprs, window: Optional[Sequence[i
     return win, left, int(win[2]) * int(win[3])
 
 
+# ------------------------------------------------------------------------------------------ focal operations
+def _pixel_sizes(transform) -> Tuple[float, float]:
+    """``(dx, dy)`` = ``(|a|, |e|)`` of a transform; ``ValueError`` without one or with rotation terms."""
+    if not transform:
+        raise ValueError("the terrain ops need a transform (the pixel sizes)")
+    a, b, _, d, e, _ = (float(v) for v in list(transform)[:6])
+    if b != 0.0 or d != 0.0 or a == 0.0 or e == 0.0:
+        raise ValueError("the terrain ops need an axis-aligned transform (no rotation terms)")
+    return abs(a), abs(e)
+
+
+def _focal_spec(spec, transform):
+    """``spec`` itself, or ``spec(dx, dy)`` for a function of the pixel sizes (the terrain ops)."""
+    return spec(*_pixel_sizes(transform)) if callable(spec) else spec
+
+
+def _grown(win, spec, H: int, W: int):
+    """``win`` grown by the radius of ``spec``'s window and clipped to an ``H x W`` raster, and ``win`` relative to it."""
+    r, c, h, w = win
+    ry, rx = spec.kh // 2, spec.kw // 2
+    r0, c0, r1, c1 = max(r - ry, 0), max(c - rx, 0), min(r + h + ry, H), min(c + w + rx, W)
+    return (r0, c0, r1 - r0, c1 - c0), (r - r0, c - c0, h, w)
+
+
+def focal_window(src, spec, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                 out_dtype="float32", device: Optional[int] = None, semantics: str = "pcm16"):
+    """A focal operation over a streaming container (path or bytes), or over a window of it -> ``(raster (B, h, w) in
+    out_dtype, pixels that got fill per band, window, index)``: the crop of ``focal.focal_arrays`` over the whole
+    raster.
+
+    ``spec``: a ``focal.Spec``, or a function ``(dx, dy) -> Spec`` that receives the pixel sizes ``|a|`` and ``|e|`` of
+    the container's transform (the terrain ops; a transform with rotation terms is then refused).  ``window`` / ``bbox``
+    as in :func:`read_window` (default: the whole raster).  The window is grown by the radius of the spec's window and
+    clipped to the raster, and the tiles of the grown window are selected: ``device=None`` reads it on the host and
+    applies the numpy rule; an integer makes one ``fra_decode_device_focal`` call on that GPU: the decoded pixels never
+    leave the device and only the result comes back."""
+    from . import _native
+    from .focal import focal_arrays, validate
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    index = _index_of(src)
+    H, W = int(index["height"]), int(index["width"])
+    spec = _focal_spec(spec, index.get("transform"))
+    validate(spec)
+    win = (0, 0, H, W) if window is None and bbox is None else resolve_window(index, window, bbox)
+    grown, inner = _grown(win, spec, H, W)
+    index, gwin, blob, items = _window_items(src, grown, None)
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    odt = np.dtype(out_dtype)
+    if device is None:
+        out = np.zeros((B, gwin[2], gwin[3]), dtype=dt)
+        _decode_window_on_host(blob, items, gwin, out, semantics)
+        res, left = focal_arrays(out, spec, odt, inner)
+        return res, left, win, index
+    ctx = _native.default_context(int(device))
+    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+    res, left, _ = ctx.decode_device_focal(np.frombuffer(blob, dtype=np.uint8), items, dt, B, gwin, spec, inner, odt,
+                                           denorm=denorm)
+    return res, left, win, index
+
+
+def focal_tiff(path: Path, spec, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+               out_dtype="float32", device: Optional[int] = None):
+    """:func:`focal_window` for a GeoTIFF source -> ``(raster, pixels that got fill, window, info, the spec used)``.
+    The grown window is read with the in-package reader; an integer ``device`` hands it to ``fra_focal`` on that GPU,
+    ``None`` to the numpy rule.  A spec without a nodata value takes the TIFF's own nodata tag, when it has one."""
+    import dataclasses
+
+    from . import _native
+    from .focal import focal_arrays, validate
+
+    g = GeoTIFF(Path(path))
+    try:
+        info = g.info
+        spec = _focal_spec(spec, list(info.transform) if info.transform is not None else None)
+        if spec.nodata is None and info.nodata is not None:
+            spec = dataclasses.replace(spec, nodata=float(info.nodata))
+        validate(spec)
+        if window is None and bbox is None:
+            win = (0, 0, info.height, info.width)
+        else:
+            win = resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)},
+                                 window, bbox)
+        grown, inner = _grown(win, spec, info.height, info.width)
+        a = np.zeros((info.count, grown[2], grown[3]), dtype=np.dtype(info.dtype))
+        g.read_window_into(a, *grown)
+    finally:
+        g.close()
+    odt = np.dtype(out_dtype)
+    if device is None:
+        res, left = focal_arrays(a, spec, odt, inner)
+    else:
+        res, left = _native.default_context(int(device)).focal(a, spec, odt, out_window=inner)
+    return res, left, win, info, spec
+
+
+def focal_to_tiff(path: Path, tiff_path: Path, spec, window: Optional[Sequence[int]] = None,
+                  bbox: Optional[Sequence[float]] = None, out_dtype="float32", device: Optional[int] = None,
+                  semantics: str = "pcm16"):
+    """A focal operation over a streaming container or a GeoTIFF (told apart by their first bytes) -> GeoTIFF with the
+    source's CRS and the transform shifted to the window's origin.  When the spec used has a nodata value (its own or
+    the source TIFF's) the result's nodata tag is ``fill`` as the output dtype holds it.  Returns ``(window, pixels that
+    got fill per band, pixels per band)``."""
+    from .tiff import write_geotiff
+
+    path = Path(path)
+    with open(path, "rb") as f:
+        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+    if is_tiff:
+        res, left, win, info, spec = focal_tiff(path, spec, window, bbox, out_dtype, device)
+        t, crs = list(info.transform), str(info.crs) if info.crs is not None else None
+    elif is_streaming_container(path):
+        t = open_streaming(path).index.get("transform")
+        spec = _focal_spec(spec, t)
+        res, left, win, index = focal_window(path, spec, window, bbox, out_dtype, device, semantics)
+        crs = index.get("crs")
+    else:
+        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
+    tag = None
+    if spec.nodata is not None:
+        from .calc import convert
+
+        v = convert(np.array([_calc_fill(spec.fill, res.dtype)]), res.dtype)[0]
+        tag = float(v) if res.dtype.kind == "f" else int(v)
+    write_geotiff(Path(tiff_path), res, transform=transform, crs=crs if crs and crs != "None" else None, nodata=tag)
+    return win, left, int(win[2]) * int(win[3])
+
+
 def _index_of(src):
     if isinstance(src, (bytes, bytearray, memoryview)):
         return read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))[0]

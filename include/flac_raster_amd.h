@@ -707,6 +707,91 @@ FRA_API int fra_decode_device_calc(fra_ctx *ctx, const fra_decode_job *job, cons
 /* HIP-event time (ms) of the calling thread's last k_calc (fra_calc or fra_decode_device_calc) */
 FRA_API int fra_calc_timing(float *ms);
 
+/* Focal operations: every band of a raster (channels, h, w) of any fra_dtype on its own, a window of kh x kw pixels
+ * around each pixel, into a raster (channels, out_h, out_w) of any fra_dtype.  The result covers an output rectangle
+ * (row_off, col_off, out_h, out_w) inside the source; neighbours inside the source but outside the rectangle are read,
+ * so a rectangle of the result is the crop of the whole-raster result.  This unit maps a raster, like the band math.
+ *   Values.  Every value is an f64; every element of the source is taken as f64 (exact for all eight dtypes).  Every
+ *     arithmetic step is one IEEE f64 operation rounded on its own: no contraction, no reassociation, division and
+ *     square root correctly rounded.  A result is converted as the band math converts one (Output, above).
+ *   Window.  kh x kw, both odd, 1 ... 15, centred on the pixel.  Taps are visited in row-major order.
+ *   A tap is left out when it is NaN; when FRA_FOCAL_NODATA is set and (double)x == nodata (a NaN nodata matches
+ *     nothing); when it lies outside the source and edge is FRA_FOCAL_EDGE_SKIP.  With FRA_FOCAL_EDGE_CLAMP a tap outside
+ *     the source is the nearest source pixel (coordinates clamped per axis), left out when that pixel is.  The other
+ *     taps are the valid ones; n is their number.
+ *   Ops.
+ *     SUM       the valid taps added in tap order, starting from the first valid one.
+ *     MEAN      that sum / (double)n.
+ *     MIN, MAX  m = the first valid tap, then m = x < m ? x : m (MAX: x > m) in tap order.
+ *     COUNT     (double)n.
+ *     MEDIAN    the lower median, no averaging: the valid taps ordered by value, equal values (-0.0 == 0.0) by tap
+ *               order; the one of rank (n - 1) / 2.  kh * kw <= 25.
+ *     CONVOLVE  acc = the products (double)x * weights[tap], each rounded, added in tap order starting from the first
+ *               valid one; weights is row-major, any double.  With FRA_FOCAL_NORMALIZE the result is acc / ws, ws the
+ *               valid taps' weights added the same way; ws == 0.0 gives fill.
+ *     SLOPE, HILLSHADE  3 x 3 only, Horn's gradient; the taps are a b c / d e f / g h i, row 0 to the north.
+ *               zx = ((c + (f + f)) + i) - ((a + (d + d)) + g),  zy = ((a + (b + b)) + c) - ((g + (h + h)) + i),
+ *               p = zx * params[0], q = zy * params[1]; the caller passes params[0] = zfactor / (8 dx) and params[1] =
+ *               zfactor / (8 dy).  SLOPE = sqrt(p * p + q * q) * params[2] (1: rise / run, 100: percent).  HILLSHADE,
+ *               with the light vector (lx, ly, lz) = params[2 .. 4] (east, north, up): s = ((lz - p * lx) - q * ly) /
+ *               sqrt((1.0 + p * p) + q * q), s = s > 0 ? s : 0, result = s * params[5].  No trigonometry: the caller
+ *               turns azimuth and altitude into the light vector.  Any of the nine taps left out: fill.
+ *   Fill.  A pixel gets `fill` when no tap is valid (COUNT gives 0 instead), when an op above says so, and, with
+ *     FRA_FOCAL_KEEP_MASK, when the centre pixel itself is left out.  left_out receives per band the number of output
+ *     pixels that got fill.
+ *   A spec is valid when: the op, the edge mode and every flag bit are known; kh and kw are odd and in 1 ... 15; MEDIAN
+ *     has at most 25 taps; SLOPE and HILLSHADE have a 3 x 3 window; FRA_FOCAL_NORMALIZE comes with CONVOLVE alone.  Any
+ *     double is accepted as a weight, a parameter, nodata and fill. */
+#define FRA_FOCAL_MAX_SIZE 15
+#define FRA_FOCAL_MAX_MEDIAN 25
+#define FRA_FOCAL_NODATA 1
+#define FRA_FOCAL_NORMALIZE 2
+#define FRA_FOCAL_KEEP_MASK 4
+typedef enum {
+  FRA_FOCAL_SUM = 0, FRA_FOCAL_MEAN = 1, FRA_FOCAL_MIN = 2, FRA_FOCAL_MAX = 3, FRA_FOCAL_COUNT = 4,
+  FRA_FOCAL_MEDIAN = 5, FRA_FOCAL_CONVOLVE = 6, FRA_FOCAL_SLOPE = 7, FRA_FOCAL_HILLSHADE = 8
+} fra_focal_op;
+typedef enum { FRA_FOCAL_EDGE_SKIP = 0, FRA_FOCAL_EDGE_CLAMP = 1 } fra_focal_edge;
+typedef struct {
+  int32_t op, kh, kw, edge, flags;          /* fra_focal_op, the window, fra_focal_edge, FRA_FOCAL_* flags */
+  double nodata, fill;
+  double params[8];                         /* SLOPE, HILLSHADE */
+  double weights[225];                      /* CONVOLVE: kh * kw, row-major */
+} fra_focal_spec;                           /* 1904 bytes */
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype of the source */
+  int32_t channels, height, width;          /* >= 1; channels <= 255 */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+  fra_window rect;                          /* the output rectangle, inside the source */
+  fra_focal_spec spec;
+  fra_calc_dst out;                         /* the (channels, rect.height, rect.width) output */
+} fra_focal_job;
+/* Whether `spec` is valid (the list above).  Pure host code: no context, no GPU.  FRA_E_INVALID with a message that
+ * names the offending field. */
+FRA_API int fra_focal_check(const fra_focal_spec *spec);
+/* k_focal alone, over a host or device raster of any layout into a host or device raster of any layout.  Synchronous.
+ * Host buffers are staged as fra_calc stages them (the elements of dst that are not outputs keep the caller's values);
+ * the source is read with 16-byte loads and the destination written with vector stores under fra_calc's conditions,
+ * judged separately.  left_out (host memory, `channels` words, may be NULL).
+ * FRA_E_INVALID, before any GPU work and in this order: a null argument, an invalid spec (fra_focal_check), a bad
+ * source or destination dtype or layout (more than 255 bands), an output rectangle that is empty or not inside the
+ * source, more than 2^32 pixels per band. */
+FRA_API int fra_focal(fra_ctx *ctx, const fra_focal_job *job, uint64_t *left_out /* channels, may be NULL */);
+/* The focal operation over what fra_decode_device_window would have written for `roi`, in job->dst_dtype.  roi is the
+ * region to decode: the caller has grown the rectangle it wants by the window's radius and clipped it to the raster;
+ * `inner` is the output rectangle relative to roi, and the edge mode acts at roi's borders (where the caller's growth
+ * was clipped those are the raster's own).  The region never leaves the device; the result goes to `out`, a
+ * (job->channels, inner->height, inner->width) raster.  Every refusal and message of the windowed read is this call's as
+ * well; items that do not cover roi are refused as by fra_decode_device_compare; the spec and `out` as by fra_focal; an
+ * `inner` that is empty or not inside roi is refused.  Afterwards fra_decode_device_timing reports the inner windowed
+ * read and fra_focal_timing the map. */
+FRA_API int fra_decode_device_focal(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                    const fra_focal_spec *spec, const fra_window *inner, const fra_calc_dst *out,
+                                    uint64_t *left_out /* channels, may be NULL */, fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last k_focal (fra_focal or fra_decode_device_focal) */
+FRA_API int fra_focal_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -86,6 +86,17 @@ the program reads, once) and written, and ``k_calc_TBps``.  It exits non-zero un
 
     python tools/bench_decode.py --calc "(b4-b3)/(b4+b3)" --calc "b1" --steps 5 --warmup 2
 
+``--focal OP[:SIZE]`` times a focal operation over the same container (``fra_decode_device_focal``: the whole raster
+decoded into a per-call buffer, then ``k_focal`` over all four bands) in the same run, beside the plain read and the
+``--calc`` legs: with ``--calc b1`` every focal leg also reports ``over_calc_copy_per_band``, its time per band over
+``k_calc``'s one-band copy, which moves the same bytes per band and shares nothing between pixels.  It exits non-zero
+unless the top left and the bottom right 1024-column corners of the result equal ``focal.focal_arrays`` of the plain read
+byte for byte.  ``--dem`` runs the focal legs over a synthetic 16384 x 16384 int16 DEM on the device instead
+(``fra_focal``: ``k_focal`` alone).
+
+    python tools/bench_decode.py --focal mean:3 --focal mean:15 --focal median:5 --calc b1 --steps 5 --warmup 2
+    python tools/bench_decode.py --focal hillshade --dtype uint8 --dem --steps 5 --warmup 2
+
 ``--stats`` times the band statistics of the same container (``fra_decode_device_stats``: the whole raster decoded
 with ``pcm16`` semantics to uint16 and described there, only the reports and the histogram come back) in five legs: the
 plain read to a device destination, ``bins = 0`` (one pass), 256 bins over the automatic range (two passes), the exact
@@ -138,6 +149,63 @@ def host_decode_all(streams) -> int:
     return total
 
 
+def focal_spec_of(text, nodata=None):
+    """The ``focal.Spec`` of a ``--focal`` leg: ``OP[:SIZE]``; the terrain ops with 10 m pixels."""
+    from flac_raster.focal import Spec, hillshade_params, slope_params
+
+    op, _, size = text.partition(":")
+    kh, _, kw = (size or "3").lower().partition("x")
+    size = (int(kh), int(kw or kh))
+    if op == "laplace":
+        return Spec("convolve", nodata=nodata, weights=[[0, -1, 0], [-1, 4, -1], [0, -1, 0]])
+    if op == "hillshade":
+        return Spec(op, 3, nodata=nodata, params=hillshade_params(315.0, 45.0, 1.0, 10.0, 10.0, 255.0))
+    if op == "slope":
+        return Spec(op, 3, nodata=nodata, params=slope_params(1.0, 10.0, 10.0, 100.0))
+    return Spec(op, size, nodata=nodata)
+
+
+def focal_over_dem(ctx, args):
+    """``--focal ... --dem``: k_focal alone (``fra_focal``) over a synthetic DEM resident on the device."""
+    from flac_raster.focal import focal_arrays
+
+    n, dt, odt = 16384, np.dtype(np.int16), np.dtype(args.dtype)
+    dem = ctx.alloc(n * n * dt.itemsize)
+    ctx.synth(3, SEED, 1, n, n, dem)
+    out = ctx.alloc(n * n * odt.itemsize)
+    rows, cw = 128, 1024
+    top = np.empty((rows, n), dt)
+    ctx.d2h(top, dem)
+    res = {"workload": f"focal over a C3-like {n}x{n}x1 int16 DEM on the device, k_focal alone", "steps": args.steps,
+           "warmup": args.warmup, "checked_windows_equal_focal_arrays": True, "legs": []}
+    for text in args.focal:
+        spec = focal_spec_of(text, None if args.nodata in (None, "corner") else args.nodata)
+        kf, wall = [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            _, left = ctx.focal(dem, spec, odt, dst=out, dtype=dt, shape=(1, n, n))
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                kf.append(ctx.focal_timing())
+                wall.append((t1 - t0) * 1e3)
+        ry, rx = spec.kh // 2, spec.kw // 2
+        want, _ = focal_arrays(top[None, :, :cw + rx], spec, odt, (0, 0, rows - ry, cw))
+        got = np.empty((1, rows - ry, cw), odt)
+        for r in range(rows - ry):
+            ctx.d2h(got[0, r], out + r * n * odt.itemsize)
+        if got.tobytes() != want.tobytes():
+            raise SystemExit(f"focal {text}: the top left window differs from focal_arrays")
+        med = statistics.median
+        rd, wr = n * n * dt.itemsize, n * n * odt.itemsize
+        res["legs"].append({"focal": text, "window": [spec.kh, spec.kw], "dtype": str(odt), "left_out": int(left[0]),
+                            "k_focal_ms": round(med(kf), 4), "focal_wall_ms": round(med(wall), 3),
+                            "k_focal_TBps": round((rd + wr) / (med(kf) * 1e-3) / 1e12, 3),
+                            "all_ms": {"k_focal": [round(v, 4) for v in kf]}})
+    print(json.dumps(res), flush=True)
+    ctx.free(out)
+    ctx.free(dem)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tiles", type=int, default=0, help="first N tiles of the scene (0: all 121)")
@@ -165,16 +233,27 @@ def main():
     ap.add_argument("--calc", action="append", default=None, metavar="EXPR",
                     help="time band math over the container against the plain read: one expression per output band, "
                          "separated by ';', optionally followed by ':dtype'; repeat for further legs of the same run")
-    ap.add_argument("--dtype", default="float32", help="with --calc: the output dtype of the legs that name none")
+    ap.add_argument("--focal", action="append", default=None, metavar="OP[:SIZE]",
+                    help="time a focal operation over the container against the plain read (and against the --calc legs "
+                         "of the same run): mean, sum, min, max, count, median, laplace (a 3 x 3 convolution), slope or "
+                         "hillshade, SIZE one odd number or HxW (default 3); repeat for further legs")
+    ap.add_argument("--dem", action="store_true",
+                    help="with --focal: k_focal alone over a synthetic 16384 x 16384 int16 DEM on the device instead")
+    ap.add_argument("--dtype", default="float32", help="with --calc or --focal: the output dtype of the legs that name none")
     args = ap.parse_args()
     if args.decimate and args.resampling not in RESAMPLING:
         ap.error("--decimate takes --resampling nearest or average")
-    if args.nodata is not None and not (args.decimate or args.resample or args.calc):
-        ap.error("--nodata goes with --decimate, --resample or --calc")
+    if args.nodata is not None and not (args.decimate or args.resample or args.calc or args.focal):
+        ap.error("--nodata goes with --decimate, --resample, --calc or --focal")
+    if args.dem and not args.focal:
+        ap.error("--dem goes with --focal")
     if args.nodata not in (None, "corner"):
         args.nodata = float(args.nodata)
 
     ctx = N.Context(0)
+    if args.dem:
+        focal_over_dem(ctx, args)
+        return
     dt = np.dtype(np.uint16)
     dev_raster = ctx.alloc(B * H * W * dt.itemsize)
     ctx.synth(4, SEED, B, H, W, dev_raster)
@@ -428,11 +507,11 @@ def main():
         ctx.free(dev_raster)
         return
 
-    if args.calc:
+    if args.calc or args.focal:
         from flac_raster.calc import calc_arrays, compile_exprs, default_fill
 
         if len(wins) != len(calculate_tiles(H, W, TILE)):
-            raise SystemExit("--calc needs every tile: the region mapped is the whole raster")
+            raise SystemExit("--calc and --focal need every tile: the region mapped is the whole raster")
         roi = (0, 0, H, W)
         citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
         plain_wall, plain_ms = [], []
@@ -461,11 +540,11 @@ def main():
             "workload": f"calc C4-like {W}x{H}x{B} uint16 (pcm16), tile {TILE}, level {LEVEL}, {len(wins)} tiles, "
                         "whole raster",
             "tiles": len(wins), "frames": nfr, "steps": args.steps, "warmup": args.warmup, "nodata": nodata,
-            "checked_rows_equal_calc_arrays": True,
+            "checked_rows_equal_calc_arrays": bool(args.calc), "checked_windows_equal_focal_arrays": bool(args.focal),
             "plain_ms": round(med(plain_ms), 3), "plain_wall_ms": round(med(plain_wall), 3),
             "k_stats_ms": round(med(ks), 4), "k_stats_TBps": round(once / (med(ks) * 1e-3) / 1e12, 3), "legs": [],
         }
-        for spec in args.calc:
+        for spec in args.calc or []:
             text, _, odt = spec.rpartition(":") if ":" in spec else (spec, "", args.dtype)
             exprs = [e.strip() for e in text.split(";") if e.strip()]
             odt = np.dtype(odt)
@@ -498,6 +577,47 @@ def main():
                 "k_calc_TBps": round((rd + wr) / (med(kc) * 1e-3) / 1e12, 3),
                 "wall_over_plain": round(med(wall) / med(plain_wall), 3),
                 "all_ms": {"k_calc": [round(v, 4) for v in kc], "calc_wall": [round(v, 3) for v in wall]}})
+        for text in args.focal or []:
+            from flac_raster.focal import focal_arrays
+
+            spec = focal_spec_of(text, nodata)
+            odt = np.dtype(args.dtype)
+            dev_res = ctx.alloc(B * H * W * odt.itemsize)
+            wall, inner, kf = [], [], []
+            for s in range(args.warmup + args.steps):
+                t0 = time.perf_counter()
+                _, left, _ = ctx.decode_device_focal((frames_ptr, total), citems, dt, B, roi, spec, roi, odt, dst=dev_res,
+                                                     denorm=N.DENORM_PCM16)
+                t1 = time.perf_counter()
+                if s >= args.warmup:
+                    wall.append((t1 - t0) * 1e3)
+                    inner.append(ctx.decode_timing()[3])
+                    kf.append(ctx.focal_timing())
+            # the top left and the bottom right corner of the result against the rule over the rows read back: the
+            # windows stay the radius away from the rows and columns that were not
+            ry, rx, cw = spec.kh // 2, spec.kw // 2, 1024
+            for part, r0, c0, win in ((top[:, :, :cw + rx], 0, 0, (0, 0, rows - ry, cw)),
+                                      (bottom[:, :, W - cw - rx:], H - rows + ry, W - cw, (ry, rx, rows - ry, cw))):
+                want, _ = focal_arrays(part, spec, odt, win)
+                got = np.empty((B, rows - ry, cw), odt)
+                for k in range(B):
+                    for r in range(rows - ry):
+                        ctx.d2h(got[k, r], dev_res + ((k * H + r0 + r) * W + c0) * odt.itemsize)
+                if got.tobytes() != want.tobytes():
+                    raise SystemExit(f"focal {text}: the window at ({r0}, {c0}) differs from focal_arrays")
+            ctx.free(dev_res)
+            rd, wr = B * H * W * dt.itemsize, B * H * W * odt.itemsize
+            res["legs"].append({
+                "focal": text, "window": [spec.kh, spec.kw], "dtype": str(odt), "left_out": [int(v) for v in left],
+                "focal_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3),
+                "k_focal_ms": round(med(kf), 4), "bytes_read": rd, "bytes_written": wr,
+                "k_focal_TBps": round((rd + wr) / (med(kf) * 1e-3) / 1e12, 3),
+                "wall_over_plain": round(med(wall) / med(plain_wall), 3),
+                "all_ms": {"k_focal": [round(v, 4) for v in kf], "focal_wall": [round(v, 3) for v in wall]}})
+        copies = [leg["k_calc_ms"] for leg in res["legs"] if leg.get("exprs") == ["b1"]]
+        for leg in res["legs"]:
+            if "focal" in leg and copies:  # against k_calc's one-band copy of this run, band for band
+                leg["over_calc_copy_per_band"] = round(leg["k_focal_ms"] / B / copies[0], 3)
         res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall],
                          "k_stats": [round(v, 4) for v in ks]}
         print(json.dumps(res), flush=True)

@@ -11,9 +11,10 @@
 //   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
 //     their nodata-aware entries (fra_resample_masked.hip: a nodata value the dtype does not admit included),
-//     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats) and
-//     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
-//     which returns before any GPU work, and the order of these refusals (inputs that break two rules at once).
+//     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats),
+//     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check) and
+//     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
+//     fra_focal_check), which returns before any GPU work, and the order of these refusals (inputs that break two rules at once).
 // usage: decode_host_check [--concat] file.flac ...
 #include <cmath>
 #include <cstdarg>
@@ -727,6 +728,76 @@ int main(int argc, char** argv) {
     // the windowed read's refusals come first, then the program, then the destination, then the cover
     { fra_window r = r48; r.width = 0; auto p = ndvi; p.ncode = 0; EXPECT(says(rc(ctx, &dj, &r, &p, &od, inf), "region of interest"), "calc read: zero-width roi and no words: %s", g_msg.c_str()); }
     { fra_window r = r48; r.height = 5; auto p = ndvi; p.ncode = 0; EXPECT(says(rc(ctx, &dj, &r, &p, &od, inf), "words outside"), "calc read: uncovered row and no words: %s", g_msg.c_str()); }
+
+    // ... and of the focal operations (fra_focal.hip): the spec validator, which needs no context, and the two entries
+    fra_focal_spec mean3{};
+    mean3.op = FRA_FOCAL_MEAN; mean3.kh = 3; mean3.kw = 3; mean3.edge = FRA_FOCAL_EDGE_SKIP;
+    EXPECT(fra_focal_check(&mean3) == FRA_OK, "focal check: a 3 x 3 mean refused: %s", g_msg.c_str());
+    EXPECT(fra_focal_check(nullptr) == FRA_E_INVALID, "focal check: null spec accepted");
+    for (int op : {-1, 9}) { auto s = mean3; s.op = op; EXPECT(says(fra_focal_check(&s), "op: unknown focal op"), "focal check: op %d: %s", op, g_msg.c_str()); }
+    for (int e : {-1, 2}) { auto s = mean3; s.edge = e; EXPECT(says(fra_focal_check(&s), "edge: unknown edge mode"), "focal check: edge %d: %s", e, g_msg.c_str()); }
+    { auto s = mean3; s.flags = 8; EXPECT(says(fra_focal_check(&s), "flags: unknown focal flags"), "focal check: flag 8: %s", g_msg.c_str()); }
+    for (int k : {0, 2, 17, -3}) { auto s = mean3; s.kh = k; EXPECT(says(fra_focal_check(&s), "kh: window height"), "focal check: kh %d: %s", k, g_msg.c_str()); }
+    for (int k : {0, 4, 17, -1}) { auto s = mean3; s.kw = k; EXPECT(says(fra_focal_check(&s), "kw: window width"), "focal check: kw %d: %s", k, g_msg.c_str()); }
+    { auto s = mean3; s.kh = s.kw = 15; s.flags = FRA_FOCAL_NODATA | FRA_FOCAL_KEEP_MASK; s.nodata = NAN; s.fill = HUGE_VAL; EXPECT(fra_focal_check(&s) == FRA_OK, "focal check: 15 x 15, NaN nodata and infinite fill refused: %s", g_msg.c_str()); }
+    { auto s = mean3; s.op = FRA_FOCAL_MEDIAN; s.kh = 5; s.kw = 5; EXPECT(fra_focal_check(&s) == FRA_OK, "focal check: a 5 x 5 median refused"); s.kw = 7; EXPECT(says(fra_focal_check(&s), "a median of 5 x 7 taps"), "focal check: a 5 x 7 median: %s", g_msg.c_str()); }
+    for (int op : {FRA_FOCAL_SLOPE, FRA_FOCAL_HILLSHADE}) { auto s = mean3; s.op = op; EXPECT(fra_focal_check(&s) == FRA_OK, "focal check: 3 x 3 terrain op refused"); s.kh = 5; EXPECT(says(fra_focal_check(&s), "take a 3 x 3 window"), "focal check: 5 x 3 terrain op: %s", g_msg.c_str()); }
+    { auto s = mean3; s.flags = FRA_FOCAL_NORMALIZE; EXPECT(says(fra_focal_check(&s), "FRA_FOCAL_NORMALIZE goes with"), "focal check: a normalised mean: %s", g_msg.c_str()); s.op = FRA_FOCAL_CONVOLVE; s.weights[4] = NAN; EXPECT(fra_focal_check(&s) == FRA_OK, "focal check: a normalised convolution with a NaN weight refused"); }
+
+    fra_focal_job fj{};
+    fj.src = dst; fj.dtype = FRA_I32; fj.channels = 2; fj.height = 4; fj.width = 8;
+    fj.band_stride = 32; fj.row_stride = 8; fj.col_stride = 1;
+    fj.rect = {0, 0, 4, 8};
+    fj.spec = mean3;
+    fj.out = cj.out;
+    EXPECT(fra_focal(nullptr, &fj, left) == FRA_E_INVALID, "focal: null ctx accepted");
+    EXPECT(fra_focal(ctx, nullptr, left) == FRA_E_INVALID, "focal: null job accepted");
+    { auto j = fj; j.src = nullptr; EXPECT(fra_focal(ctx, &j, left) == FRA_E_INVALID, "focal: null src accepted"); }
+    { auto j = fj; j.out.dst = nullptr; EXPECT(fra_focal(ctx, &j, nullptr) == FRA_E_INVALID, "focal: null dst accepted"); }
+    { auto j = fj; j.spec.kw = 2; EXPECT(says(fra_focal(ctx, &j, left), "kw: window width"), "focal: even window: %s", g_msg.c_str()); }
+    { auto j = fj; j.dtype = 8; EXPECT(says(fra_focal(ctx, &j, left), "bad dtype"), "focal: source dtype 8: %s", g_msg.c_str()); }
+    { auto j = fj; j.out.dtype = -1; EXPECT(says(fra_focal(ctx, &j, left), "bad dtype"), "focal: destination dtype -1: %s", g_msg.c_str()); }
+    { auto j = fj; j.width = 0; EXPECT(says(fra_focal(ctx, &j, left), "bad raster layout"), "focal: zero width: %s", g_msg.c_str()); }
+    { auto j = fj; j.row_stride = -8; EXPECT(says(fra_focal(ctx, &j, left), "bad raster layout"), "focal: negative source stride: %s", g_msg.c_str()); }
+    { auto j = fj; j.out.col_stride = -1; EXPECT(says(fra_focal(ctx, &j, left), "bad raster layout"), "focal: negative destination stride: %s", g_msg.c_str()); }
+    { auto j = fj; j.channels = 256; EXPECT(says(fra_focal(ctx, &j, left), "more than 255"), "focal: 256 bands: %s", g_msg.c_str()); }
+    for (fra_window r : {fra_window{0, 0, 0, 8}, fra_window{0, 0, 4, 0}, fra_window{-1, 0, 4, 8}, fra_window{0, -1, 4, 8}, fra_window{1, 0, 4, 8}, fra_window{0, 1, 4, 8}, fra_window{0, 0, 2147483647, 8}, fra_window{2147483647, 0, 1, 8}}) {
+      auto j = fj; j.rect = r; EXPECT(says(fra_focal(ctx, &j, left), "the output rectangle"), "focal: rectangle (%d, %d, %d x %d): %s", r.row_off, r.col_off, r.height, r.width, g_msg.c_str());
+    }
+    { auto j = fj; j.height = 65537; j.width = 65536; EXPECT(says(fra_focal(ctx, &j, left), "2^32 pixels"), "focal: more than 2^32 pixels: %s", g_msg.c_str()); }
+    // the order: the spec, then the layouts, then the rectangle, then the size
+    { auto j = fj; j.spec.op = 9; j.dtype = 8; EXPECT(says(fra_focal(ctx, &j, left), "op: unknown"), "focal: op 9 and dtype 8: %s", g_msg.c_str()); }
+    { auto j = fj; j.out.dtype = 8; j.rect.width = 9; EXPECT(says(fra_focal(ctx, &j, left), "bad dtype"), "focal: dtype 8 and a wide rectangle: %s", g_msg.c_str()); }
+    { auto j = fj; j.rect.width = 0; j.height = 65537; j.width = 65536; EXPECT(says(fra_focal(ctx, &j, left), "the output rectangle"), "focal: empty rectangle and 2^32 pixels: %s", g_msg.c_str()); }
+    EXPECT(fra_focal_timing(nullptr) == FRA_E_INVALID, "focal timing: null accepted");
+
+    const fra_window in48{0, 0, 4, 8};
+    auto rf = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, const fra_focal_spec* s, const fra_window* in,
+                  const fra_calc_dst* o, fra_decoded* d) { return fra_decode_device_focal(c, j, r, s, in, o, left, d); };
+    EXPECT(rf(nullptr, &dj, &r48, &mean3, &in48, &od, inf) == FRA_E_INVALID, "focal read: null ctx accepted");
+    EXPECT(rf(ctx, nullptr, &r48, &mean3, &in48, &od, inf) == FRA_E_INVALID, "focal read: null job accepted");
+    EXPECT(rf(ctx, &dj, nullptr, &mean3, &in48, &od, inf) == FRA_E_INVALID, "focal read: null roi accepted");
+    EXPECT(rf(ctx, &dj, &r48, nullptr, &in48, &od, inf) == FRA_E_INVALID, "focal read: null spec accepted");
+    EXPECT(rf(ctx, &dj, &r48, &mean3, nullptr, &od, inf) == FRA_E_INVALID, "focal read: null inner rectangle accepted");
+    EXPECT(rf(ctx, &dj, &r48, &mean3, &in48, nullptr, inf) == FRA_E_INVALID, "focal read: null destination accepted");
+    EXPECT(rf(ctx, &dj, &r48, &mean3, &in48, &od, nullptr) == FRA_E_INVALID, "focal read: null infos accepted");
+    { auto o = od; o.dst = nullptr; EXPECT(rf(ctx, &dj, &r48, &mean3, &in48, &o, inf) == FRA_E_INVALID, "focal read: null dst accepted"); }
+    { auto s = mean3; s.kh = 4; EXPECT(says(rf(ctx, &dj, &r48, &s, &in48, &od, inf), "kh: window height"), "focal read: even window: %s", g_msg.c_str()); }
+    { auto o = od; o.dtype = 8; EXPECT(says(rf(ctx, &dj, &r48, &mean3, &in48, &o, inf), "bad dtype"), "focal read: destination dtype 8: %s", g_msg.c_str()); }
+    { auto o = od; o.band_stride = -1; EXPECT(says(rf(ctx, &dj, &r48, &mean3, &in48, &o, inf), "bad raster layout"), "focal read: negative destination stride: %s", g_msg.c_str()); }
+    for (fra_window in : {fra_window{0, 0, 0, 8}, fra_window{0, 0, 5, 8}, fra_window{0, 1, 4, 8}, fra_window{-1, 0, 2, 2}}) {
+      EXPECT(says(rf(ctx, &dj, &r48, &mean3, &in, &od, inf), "the inner rectangle"), "focal read: inner (%d, %d, %d x %d): %s", in.row_off, in.col_off, in.height, in.width, g_msg.c_str());
+    }
+    { fra_window r = r48; r.height = 5; EXPECT(says(rf(ctx, &dj, &r, &mean3, &in48, &od, inf), "do not cover"), "focal read: uncovered row: %s", g_msg.c_str()); }
+    { auto j = dj; j.nitems = 0; EXPECT(rf(ctx, &j, &r48, &mean3, &in48, &od, inf) == FRA_E_INVALID, "focal read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(says(rf(ctx, &dj, &r, &mean3, &in48, &od, inf), "region of interest"), "focal read: zero-width roi: %s", g_msg.c_str()); }
+    { fra_window r{0, 0, 65537, 65536}; EXPECT(says(rf(ctx, &dj, &r, &mean3, &in48, &od, inf), "2^32 pixels"), "focal read: more than 2^32 pixels: %s", g_msg.c_str()); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(rf(ctx, &j, &r48, &mean3, &in48, &od, inf) == FRA_E_INVALID, "focal read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(says(rf(ctx, &j, &r48, &mean3, &in48, &od, inf), "dtype"), "focal read: dtype 9: %s", g_msg.c_str()); }
+    { auto j = dj; j.channels = 0; EXPECT(rf(ctx, &j, &r48, &mean3, &in48, &od, inf) == FRA_E_INVALID, "focal read: no channels accepted"); }
+    // the windowed read's refusals come first, then the spec, then the destination, then the inner rectangle, then the cover
+    { fra_window r = r48; r.width = 0; auto s = mean3; s.op = 9; EXPECT(says(rf(ctx, &dj, &r, &s, &in48, &od, inf), "region of interest"), "focal read: zero-width roi and op 9: %s", g_msg.c_str()); }
+    { fra_window r = r48; r.height = 5; fra_window in{0, 0, 6, 8}; EXPECT(says(rf(ctx, &dj, &r, &mean3, &in, &od, inf), "the inner rectangle"), "focal read: uncovered row and a tall inner rectangle: %s", g_msg.c_str()); }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
   {
