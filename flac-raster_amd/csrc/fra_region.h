@@ -1,5 +1,5 @@
-// fra_region.h -- the host scaffold of the seven units over a raster or a decoded region on the device: five reduce it
-// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip) and two map it
+// fra_region.h -- the host scaffold of the eight units over a raster or a decoded region on the device: six reduce it
+// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip, fra_zonal.hip) and two map it
 // (fra_calc.hip and fra_focal.hip, whose output has a dtype, a size or a band count of its own: Dst, run_raster_to,
 // run_region_to).  Once each:
 //   * the refusals they share: a bad dtype or raster layout (check_raster), items that do not cover the region
@@ -58,6 +58,20 @@ inline void with_dtype(int dtype, F&& f) {
     case FRA_I32: f(int32_t{}); break;
     case FRA_F32: f(float{}); break;
     case FRA_F64: f(double{}); break;
+  }
+}
+
+// a second, read-only raster of labels beside the values (fra_zonal.hip): the integer dtypes, and f(Z{}) for one
+inline bool is_int_dtype(int dtype) { return dtype >= FRA_U8 && dtype <= FRA_I32; }
+template <typename F>
+inline void with_int_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case FRA_U8: f(uint8_t{}); break;
+    case FRA_I8: f(int8_t{}); break;
+    case FRA_U16: f(uint16_t{}); break;
+    case FRA_I16: f(int16_t{}); break;
+    case FRA_U32: f(uint32_t{}); break;
+    case FRA_I32: f(int32_t{}); break;
   }
 }
 

@@ -191,7 +191,35 @@ class FocalJob(C.Structure):
     ]
 
 
+class ZonalOpts(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("nzones", C.c_int32), ("zone_lo", C.c_int64), ("ignore_zone", C.c_int64),
+                ("nodata", C.c_double)]
+
+
+class ZonalJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("band_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64), ("zones", C.c_void_p), ("zones_on_device", C.c_int32), ("zone_dtype", C.c_int32),
+        ("zone_row_stride", C.c_int64), ("zone_col_stride", C.c_int64), ("opts", ZonalOpts),
+    ]
+
+
+class ZonalRec(C.Structure):
+    """One (band, zone) record of ``fra_zonal`` / ``fra_decode_device_zonal`` (112 bytes; the rule: ``zonal.py``)."""
+
+    _fields_ = [
+        ("count", C.c_uint64), ("valid", C.c_uint64), ("nan", C.c_uint64), ("nodata", C.c_uint64),
+        ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("sq_lo", C.c_uint64), ("sq_hi", C.c_uint64),
+        ("min", C.c_double), ("max", C.c_double), ("fsum", C.c_double), ("mean", C.c_double), ("fm2", C.c_double),
+        ("reserved", C.c_uint64),
+    ]
+
+
+assert C.sizeof(ZonalRec) == 112 and C.sizeof(ZonalOpts) == 32 and C.sizeof(ZonalJob) == 120
+
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
+ZONAL_NODATA, ZONAL_IGNORE = 1, 2
 CALC_NODATA = 1
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
@@ -249,6 +277,7 @@ EXPORTS = [
     "fra_decode_device_resampled_masked", "fra_decode_device_decimated_masked", "fra_resample_masked_timing",
     "fra_calc_check", "fra_calc", "fra_decode_device_calc", "fra_calc_timing",
     "fra_focal_check", "fra_focal", "fra_decode_device_focal", "fra_focal_timing",
+    "fra_zonal", "fra_decode_device_zonal", "fra_zonal_timing",
 ]
 
 
@@ -356,6 +385,12 @@ def load():
                                                   C.POINTER(Window), C.POINTER(CalcDst), C.POINTER(u64),
                                                   C.POINTER(Decoded)]
             L.fra_focal_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_zonal"):
+            L.fra_zonal.argtypes = [vp, C.POINTER(ZonalJob), vp, C.POINTER(u64)]
+            L.fra_decode_device_zonal.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), vp, i32, i32, C.c_int64,
+                                                  C.c_int64, C.POINTER(ZonalOpts), vp, C.POINTER(u64),
+                                                  C.POINTER(Decoded)]
+            L.fra_zonal_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -981,6 +1016,91 @@ class Context:
         """HIP-event ms of this thread's last statistics kernels (:meth:`stats` / :meth:`decode_device_stats`)."""
         ms = C.c_float()
         _check(load().fra_stats_timing(C.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _zonal_opts(zone_lo, nzones, nodata, ignore):
+        from .zonal import flags_of
+
+        o = ZonalOpts()
+        o.flags, o.nzones, o.zone_lo = flags_of(nodata, ignore), int(nzones), int(zone_lo)
+        o.ignore_zone = 0 if ignore is None else int(ignore)
+        o.nodata = 0.0 if nodata is None else float(nodata)
+        return o
+
+    @staticmethod
+    def _zone_raster(zones, zone_dtype, zone_strides, h: int, w: int):
+        """``(pointer, on_device, dtype code, row stride, column stride, keepalive)`` of a zone raster given as a
+        numpy array ``(h, w)`` of an integer dtype (any non-negative strides) or as a device pointer (int) with
+        ``zone_dtype`` and element ``zone_strides`` = (row, column), default ``(w, 1)``."""
+        if isinstance(zones, np.ndarray):
+            if zones.shape != (h, w):
+                raise ValueError(f"the zone raster must be {(h, w)}, got {zones.shape}")
+            zdt = zones.dtype
+            if any(st % zdt.itemsize for st in zones.strides):
+                raise ValueError("the zone raster's strides must be whole elements")
+            ptr, on_device, zst = zones.ctypes.data, 0, tuple(st // zdt.itemsize for st in zones.strides)
+        else:
+            zdt = np.dtype(zone_dtype)
+            ptr, on_device = int(zones), 1
+            zst = tuple(int(v) for v in zone_strides) if zone_strides is not None else (w, 1)
+        if zdt not in DTYPE_CODES:
+            raise TypeError(f"unsupported zone dtype {zdt}")
+        return C.c_void_p(ptr), on_device, DTYPE_CODES[zdt], int(zst[0]), int(zst[1]), zones
+
+    def zonal(self, src, zones, zone_lo: int = 0, nzones: int = 1, nodata=None, ignore=None, *, dtype=None, shape=None,
+              strides=None, zone_dtype=None, zone_strides=None):
+        """Zonal statistics of a raster on this context's GPU (``fra_zonal``, the rule of ``flac_raster.zonal``):
+        ``(records (B, nzones) of zonal.REC_DTYPE, outside)``.
+
+        ``src``: a numpy array ``(B, h, w)`` / ``(h, w)`` of one of the eight raster dtypes with any non-negative
+        strides, or a device pointer (int) with ``dtype``, ``shape`` = (B, h, w) and element ``strides`` (default
+        band-planar).  ``zones``: a numpy array ``(h, w)`` of an integer dtype of at most 32 bits with any
+        non-negative strides, or a device pointer with ``zone_dtype`` and element ``zone_strides`` = (row, column).
+        Neither is written.  ``zone_lo``, ``nzones``, ``nodata``, ``ignore`` as ``zonal.zonal_arrays``."""
+        from .zonal import REC_DTYPE
+
+        job = ZonalJob()
+        _, (B, h, w), st = _raster_source(job, src, dtype, shape, strides)
+        job.band_stride, job.row_stride, job.col_stride = st
+        (job.zones, job.zones_on_device, job.zone_dtype, job.zone_row_stride, job.zone_col_stride,
+         _keep) = self._zone_raster(zones, zone_dtype, zone_strides, h, w)
+        job.opts = self._zonal_opts(zone_lo, nzones, nodata, ignore)
+        recs = np.zeros((max(1, B), max(1, min(int(nzones), 65536))), REC_DTYPE)
+        outside = C.c_uint64()
+        _check(load().fra_zonal(self.h, C.byref(job), C.c_void_p(recs.ctypes.data), C.byref(outside)))
+        return recs[:B], int(outside.value)
+
+    def decode_device_zonal(self, data, items, zones, dst_dtype, channels: int, roi, denorm: int = DENORM_NONE,
+                            zone_lo: int = 0, nzones: int = 1, nodata=None, ignore=None, *, zone_dtype=None,
+                            zone_strides=None):
+        """The zonal statistics of ``roi`` of the tile streams (``fra_decode_device_zonal``): the records of
+        ``zonal.zonal_arrays(what decode_device_window would have written, zones, ...)`` without the decoded region
+        leaving the GPU.
+
+        ``data``, ``items``, ``roi``, ``denorm`` as :meth:`decode_device_window`.  ``zones`` is addressed relative to
+        the region: a numpy array ``(h, w)`` of the region's size (a strided crop of a larger array is fine: it is
+        copied to the device from its first element to its last), or a device pointer with ``zone_dtype`` and
+        ``zone_strides``.  The items must cover the region.  Returns ``(records (channels, nzones), outside,
+        infos)``."""
+        from .zonal import REC_DTYPE
+
+        if roi is None:
+            raise ValueError("roi is required")
+        h, w = int(roi[2]), int(roi[3])
+        zp, z_on_device, zcode, zrs, zcs, _keep = self._zone_raster(zones, zone_dtype, zone_strides, h, w)
+        o = self._zonal_opts(zone_lo, nzones, nodata, ignore)
+        recs = np.zeros((max(1, channels), max(1, min(int(nzones), 65536))), REC_DTYPE)
+        outside = C.c_uint64()
+        job, infos, keep = self._decode_job(data, items, None, np.dtype(dst_dtype), denorm, channels, (0, 0, 0))
+        infos = self._decode_run("fra_decode_device_zonal", job, infos, keep, _window_ref(roi), zp, z_on_device, zcode,
+                                 zrs, zcs, C.byref(o), C.c_void_p(recs.ctypes.data), C.byref(outside), infos)
+        return recs[:channels], int(outside.value), infos
+
+    def zonal_timing(self) -> float:
+        """HIP-event ms of this thread's last zonal kernels (:meth:`zonal` / :meth:`decode_device_zonal`)."""
+        ms = C.c_float()
+        _check(load().fra_zonal_timing(C.byref(ms)))
         return ms.value
 
     def calc(self, src, program, out_dtype="float32", dst=None, *, nodata=None, fill=None, dtype=None, shape=None,

@@ -469,6 +469,53 @@ def stats(
 
 
 @app.command()
+def zonal(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    zones: Path = typer.Option(..., "--zones", "-z", help="Single-band integer GeoTIFF of the same shape: the zones"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width'"),
+    nodata: Optional[float] = typer.Option(None, "--nodata", help="Nodata value (default: a source TIFF's own tag)"),
+    ignore: Optional[int] = typer.Option(None, "--ignore", help="Zone label to leave out (default: the zones TIFF's "
+                                         "nodata tag)"),
+    semantics: str = typer.Option("pcm16", "--semantics", help="Container pixels: pcm16 (what convert back gives) or int"),
+    export: Optional[Path] = typer.Option(None, "--export", "-e", help="Export the full report to .json or .csv"),
+    cpu: bool = typer.Option(False, "--cpu", help="Decode and reduce on the host (numpy)"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Per-zone band statistics of a streaming FLAC file or a GeoTIFF over the zones of a GeoTIFF."""
+    from .streaming import zonal_with_tiff
+    from .zonal import display_zonal_table, export_report
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        path = _local(file_path)
+        for p in (path, zones):
+            if not p.exists():
+                console.print(f"[red]File not found: {p}[/red]")
+                raise typer.Exit(1)
+        if export is not None and export.suffix.lower() not in (".json", ".csv"):
+            console.print("[red]Error: --export takes a .json or a .csv file[/red]")
+            raise typer.Exit(1)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        report, got, _ = zonal_with_tiff(path, zones, window=win, bbox=box, nodata=nodata, ignore=ignore, device=dev,
+                                         semantics=semantics)
+        display_zonal_table(report, title=f"{path.name} by {zones.name}: rows {got[0]}..{got[0] + got[2]}, columns "
+                                          f"{got[1]}..{got[1] + got[3]}")
+        if export is not None:
+            export_report(export, report, {"file": path.name, "zones": zones.name, "window": list(got), "device": dev})
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Zonal statistics failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
+@app.command()
 def calc(
     file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
     output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),

@@ -676,6 +676,177 @@ def tiff_stats(path: Path, window: Optional[Sequence[int]] = None, bbox: Optiona
     return report_from_bands(bands, hist, dt), win, info
 
 
+# ------------------------------------------------------------------------------------------ zonal statistics
+def _zone_crop(zones, shape, win) -> np.ndarray:
+    """The whole zone raster ``(H, W)`` checked against the raster's shape and cropped to ``win`` (a view)."""
+    zones = np.asarray(zones)
+    if zones.dtype.kind not in "iu":
+        raise TypeError(f"the zone raster must have an integer dtype, got {zones.dtype}")
+    if zones.shape != tuple(shape):
+        raise ValueError(f"the zone raster must be {tuple(shape)} like the raster, got {zones.shape}")
+    r, c, h, w = win
+    return zones[r:r + h, c:c + w]
+
+
+def _zonal_on_device(run, crop: np.ndarray, dt, nodata, ignore):
+    """The report of one GPU call over the cropped zone raster: ``run(zones, zone_lo, nzones, ignore)`` returns the
+    records and the outside count.  Labels spread too far for one call are relabelled first (``zonal.dense_zones``),
+    and 64-bit labels go as int32 offsets from the smallest."""
+    from .zonal import ZONE_DTYPES, dense_zones, report_from_recs
+
+    zones, zone_lo, nzones, labels = dense_zones(crop, ignore)
+    if labels is not None:
+        ignore = None  # the ignored pixels carry id -1, outside the range
+    first = zone_lo  # the label of zone 0 when there is no label table
+    if zones.dtype not in ZONE_DTYPES:
+        with np.errstate(over="ignore"):
+            k = (zones - zones.dtype.type(zone_lo)).astype(np.int64)  # (an ignored label may wrap: it is replaced)
+        zones = (k if ignore is None else np.where(zones == ignore, -1, k)).astype(np.int32)
+        zone_lo, ignore = 0, None
+    elif not zones.dtype.isnative or any(st < 0 for st in zones.strides):
+        zones = np.ascontiguousarray(zones, dtype=zones.dtype.newbyteorder("="))
+    recs, outside = run(zones, zone_lo, nzones, ignore)
+    return report_from_recs(recs, outside, dt, first, labels)
+
+
+def _whole_window(src):
+    """The window of the whole raster of a container (path or bytes)."""
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        mv = memoryview(src)
+        index, _ = read_index_bytes(bytes(mv[:4 + struct.unpack(">I", mv[:4])[0]]))
+    else:
+        index = open_streaming(Path(src)).index
+    return 0, 0, int(index["height"]), int(index["width"])
+
+
+def _container_zonal(index, win, blob, items, crop: np.ndarray, nodata, ignore, device, semantics: str):
+    """The report of the window ``win`` of the tiles of ``_window_items`` over ``crop``, the zones of that window."""
+    from . import _native
+    from .zonal import zonal_arrays
+
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    if device is None:
+        out = np.zeros((B, win[2], win[3]), dtype=dt)
+        _decode_window_on_host(blob, items, win, out, semantics)
+        return zonal_arrays(out, crop, nodata=nodata, ignore=ignore)
+    ctx = _native.default_context(int(device))
+    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+    data = np.frombuffer(blob, dtype=np.uint8)
+
+    def run(z, zone_lo, nzones, ign):
+        recs, outside, _ = ctx.decode_device_zonal(data, items, z, dt, B, win, denorm, zone_lo, nzones, nodata, ign)
+        return recs, outside
+
+    return _zonal_on_device(run, crop, dt, nodata, ignore)
+
+
+def container_zonal(src, zones, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                    nodata: Optional[float] = None, ignore: Optional[int] = None, device: Optional[int] = None,
+                    semantics: str = "pcm16"):
+    """Zonal statistics of a streaming container (path or bytes), or of a window of it -> ``(report, window, index)``:
+    ``zonal.zonal_arrays(read_window(src, ...)[0], zones cropped to the window, nodata=nodata, ignore=ignore)``.
+
+    ``zones`` is the whole ``(H, W)`` zone raster of the container's raster (``ValueError`` otherwise), of an integer
+    dtype; ``window`` / ``bbox`` as in :func:`read_window` (default: the whole raster).  ``device=None`` reads the
+    window on the host and applies the numpy rule; an integer makes one ``fra_decode_device_zonal`` call on that GPU:
+    the decoded pixels never leave the device, the cropped zone raster goes there, and only the records come back."""
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    if window is None and bbox is None:
+        window = _whole_window(src)
+    index, win, blob, items = _window_items(src, window, bbox)
+    crop = _zone_crop(zones, (int(index["height"]), int(index["width"])), win)
+    return _container_zonal(index, win, blob, items, crop, nodata, ignore, device, semantics), win, index
+
+
+def _tiff_window(g: GeoTIFF, window, bbox):
+    info = g.info
+    if window is None and bbox is None:
+        return 0, 0, info.height, info.width
+    return resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)}, window, bbox)
+
+
+def _array_zonal(a: np.ndarray, crop: np.ndarray, nodata, ignore, device):
+    """The report of a raster in host memory over its zones: the numpy rule, or ``fra_zonal`` on a GPU."""
+    from . import _native
+    from .zonal import zonal_arrays
+
+    if device is None:
+        return zonal_arrays(a, crop, nodata=nodata, ignore=ignore)
+    ctx = _native.default_context(int(device))
+    return _zonal_on_device(lambda z, lo, n, ign: ctx.zonal(a, z, lo, n, nodata, ign), crop, a.dtype, nodata, ignore)
+
+
+def tiff_zonal(path: Path, zones, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+               nodata: Optional[float] = None, ignore: Optional[int] = None, device: Optional[int] = None):
+    """Zonal statistics of a GeoTIFF, or of a window of it, over the whole ``(H, W)`` zone raster ``zones`` ->
+    ``(report, window, info)``.  The window is read with the in-package reader; an integer ``device`` hands it to
+    ``fra_zonal`` on that GPU, ``None`` to the numpy rule.  ``nodata=None`` takes the TIFF's own nodata tag, when it
+    has one."""
+    g = GeoTIFF(Path(path))
+    try:
+        info = g.info
+        win = _tiff_window(g, window, bbox)
+        if nodata is None and info.nodata is not None:
+            nodata = float(info.nodata)
+        crop = _zone_crop(zones, (info.height, info.width), win)
+        a = np.zeros((info.count, win[2], win[3]), dtype=np.dtype(info.dtype))
+        g.read_window_into(a, *win)
+    finally:
+        g.close()
+    return _array_zonal(a, crop, nodata, ignore, device), win, info
+
+
+def zonal_with_tiff(source: Path, zones_tiff: Path, window: Optional[Sequence[int]] = None,
+                    bbox: Optional[Sequence[float]] = None, nodata: Optional[float] = None,
+                    ignore: Optional[int] = None, device: Optional[int] = None, semantics: str = "pcm16"):
+    """Zonal statistics of ``source`` -- a streaming container or a GeoTIFF -- over the zones of a single-band integer
+    GeoTIFF of the same shape -> ``(report, window, index or info)``.  Only the window of the zones TIFF is read
+    (in-package reader).  ``ignore=None`` takes the zones TIFF's nodata tag, when it has one; ``nodata=None`` a source
+    TIFF's."""
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    source, zones_tiff = Path(source), Path(zones_tiff)
+    with open(source, "rb") as f:
+        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+    a = blob = items = None
+    if is_tiff:
+        g = GeoTIFF(source)
+        try:
+            meta = g.info
+            shape = (meta.height, meta.width)
+            win = _tiff_window(g, window, bbox)
+            if nodata is None and meta.nodata is not None:
+                nodata = float(meta.nodata)
+            a = np.zeros((meta.count, win[2], win[3]), dtype=np.dtype(meta.dtype))
+            g.read_window_into(a, *win)
+        finally:
+            g.close()
+    else:
+        if window is None and bbox is None:
+            window = _whole_window(source)
+        meta, win, blob, items = _window_items(source, window, bbox)
+        shape = (int(meta["height"]), int(meta["width"]))
+    z = GeoTIFF(zones_tiff)
+    try:
+        zi = z.info
+        zdt = np.dtype(zi.dtype)
+        if zi.count != 1 or zdt.kind not in "iu":
+            raise ValueError(f"{zones_tiff.name} must be a single-band integer raster, it has {zi.count} band(s) of {zdt}")
+        if (zi.height, zi.width) != shape:
+            raise ValueError(f"{zones_tiff.name} is {(zi.height, zi.width)}, {source.name} is {shape}")
+        if ignore is None and zi.nodata is not None and float(zi.nodata) == int(float(zi.nodata)):
+            ignore = int(float(zi.nodata))
+        crop = np.zeros((1, win[2], win[3]), dtype=zdt)
+        z.read_window_into(crop, *win)
+    finally:
+        z.close()
+    if is_tiff:
+        return _array_zonal(a, crop[0], nodata, ignore, device), win, meta
+    return _container_zonal(meta, win, blob, items, crop[0], nodata, ignore, device, semantics), win, meta
+
+
 # ------------------------------------------------------------------------------------------ band math
 def _calc_fill(fill, out_dtype):
     from .calc import default_fill

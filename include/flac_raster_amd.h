@@ -792,6 +792,80 @@ FRA_API int fra_decode_device_focal(fra_ctx *ctx, const fra_decode_job *job, con
 /* HIP-event time (ms) of the calling thread's last k_focal (fra_focal or fra_decode_device_focal) */
 FRA_API int fra_focal_timing(float *ms);
 
+/* Zonal statistics: the band statistics of a value raster (channels, h, w) of any fra_dtype, separately for every zone of
+ * a zone raster (h, w) of an integer dtype (FRA_U8, FRA_I8, FRA_U16, FRA_I16, FRA_U32 or FRA_I32) with row and column
+ * strides of its own: one record per (band, zone).  The fourth classical map-algebra member beside the global
+ * (fra_stats, fra_compare), local (fra_calc) and focal (fra_focal) ones.  The reference has no counterpart: its users do
+ * this with rasterio + numpy on the host.
+ *   Which zone a pixel belongs to.  z = (int64) the zone raster's pixel.  With FRA_ZONAL_IGNORE and z == opts.ignore_zone
+ *     the pixel is outside.  Otherwise k = z - opts.zone_lo (exact), and the pixel is outside unless 0 <= k < opts.nzones;
+ *     nzones lies in 1 ... 65536.  *outside = the number of pixels of the raster that are outside, one count per call (not
+ *     per band).
+ *   The record of (band, zone k) is recs[band * nzones + k].  count = the pixels of the zone.  nan, nodata and valid mean
+ *     exactly what they mean in fra_stats: every element is taken as f64, nan = the NaN pixels (floats only), nodata = the
+ *     pixels with (double)x == opts.nodata, counted only with FRA_ZONAL_NODATA (a NaN nodata matches nothing), valid = the
+ *     rest, +-inf are valid numbers; count = valid + nan + nodata.  min, max over the valid pixels, exact doubles, NaN when
+ *     valid == 0.
+ *   Integer dtypes.  sum (sum_lo uint64, sum_hi int64) and sq (sq_lo, sq_hi) are the exact 128-bit sums of x and x^2 of
+ *     fra_stats, in its encoding.  fsum = mean = fm2 = 0.0.  More than 2^32 pixels per band are refused.
+ *   f32 / f64.  fsum = the f64 sum of x; mean = fsum / (double)valid, one IEEE division (0 / 0 = NaN for a zone without a
+ *     valid pixel); fm2 = the f64 sum of (x - mean) * (x - mean) with that zone's mean of the first pass, read on the device.
+ *     Plain IEEE arithmetic: +-inf propagate.  The integer sums are 0.
+ *     No summation order is implied, and unlike fra_stats this unit adds fsum and fm2 with f64 atomics (in LDS, then in
+ *     device memory): the two of two calls on the same inputs may differ in their last bits.  Everything else in a
+ *     record -- the counts, the extremes, mean's relation to fsum, the integer sums -- and `outside` is exact and does not
+ *     depend on any order.
+ *   A zone without pixels has all counts 0, sums 0, min = max = NaN and, for floats, mean = NaN. */
+#define FRA_ZONAL_NODATA 1
+#define FRA_ZONAL_IGNORE 2
+typedef struct {
+  int32_t flags, nzones;
+  int64_t zone_lo, ignore_zone;
+  double nodata;
+} fra_zonal_opts;     /* 32 bytes */
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype */
+  int32_t channels, height, width;          /* >= 1 */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+  const void *zones; int32_t zones_on_device;   /* element (row 0, col 0) of the zone raster */
+  int32_t zone_dtype;                       /* an integer fra_dtype */
+  int64_t zone_row_stride, zone_col_stride; /* elements, >= 0 */
+  fra_zonal_opts opts;
+} fra_zonal_job;
+typedef struct {
+  uint64_t count, valid, nan, nodata;
+  uint64_t sum_lo; int64_t sum_hi; uint64_t sq_lo, sq_hi;
+  double   min, max, fsum, mean, fm2;
+  uint64_t reserved;  /* 0 */
+} fra_zonal_rec;      /* 112 bytes */
+/* k_zonal and its small kernels alone, over host or device rasters of any non-negative strides.  Synchronous; recs (host
+ * memory) receives channels x nzones records and *outside (host memory) the count.  Host rasters are staged as fra_stats
+ * and fra_compare stage theirs (each one allocation spanning every addressed element from element 0); neither raster is
+ * written.  Each raster is read with vector loads when its column stride is 1 and its base, row stride (and, for the
+ * values, band stride) are multiples of 16 bytes, element by element otherwise, judged separately.  The reference has no
+ * counterpart.  FRA_E_INVALID, before any GPU work and in this order: a null argument, a bad value dtype or layout, a zone
+ * dtype outside the six, a negative zone stride, nzones outside 1 ... 65536, unknown flag bits, more than 2^32 pixels per
+ * band, more than 2^24 records (channels x nzones). */
+FRA_API int fra_zonal(fra_ctx *ctx, const fra_zonal_job *job, fra_zonal_rec *recs /* channels x nzones */,
+                      uint64_t *outside);
+/* The zonal statistics of what fra_decode_device_window would have written for `roi`, in job->dst_dtype.  roi, the items
+ * and infos mean what they mean there; job->dst and the job's strides are ignored.  The zone raster (host or device) is
+ * addressed relative to the region, exactly as `ref` is in fra_decode_device_compare: the label of pixel (R, C) at
+ * (R - roi.row_off)*zone_row_stride + (C - roi.col_off)*zone_col_stride.  The region goes to a per-call device buffer,
+ * never leaves the device and is released on every path.  Every refusal and message of the windowed read is this call's
+ * as well; items that do not cover the region are refused as by fra_decode_device_compare; the zone raster and the
+ * options as by fra_zonal.  The reference has no counterpart.  Afterwards fra_decode_device_timing reports the inner
+ * windowed read and fra_zonal_timing the statistics. */
+FRA_API int fra_decode_device_zonal(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi, const void *zones,
+                                    int32_t zones_on_device, int32_t zone_dtype, int64_t zone_row_stride,
+                                    int64_t zone_col_stride, const fra_zonal_opts *opts,
+                                    fra_zonal_rec *recs /* channels x nzones */, uint64_t *outside,
+                                    fra_decoded *infos /* nitems */);
+/* HIP-event time (ms) of the calling thread's last zonal kernels (fra_zonal or fra_decode_device_zonal); the reference
+ * has no counterpart */
+FRA_API int fra_zonal_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -107,6 +107,18 @@ that time; ``band_reads`` counts them: a band is read once per pass and once mor
 its values reach (the launches of the other windows leave without reading).  It exits non-zero unless band 0 of every leg equals ``stats.stats_arrays`` of the plain read.
 
     python tools/bench_decode.py --stats --steps 5 --warmup 2
+
+``--zonal PATTERN`` times the zonal statistics of the same container (``fra_decode_device_zonal``: the whole raster
+decoded to uint16 and reduced per zone there, only the records come back) over a uint16 zone raster synthesised on the
+host and resident on the device: ``blocks:N`` (squares of N x N pixels, ``blocks:256`` = 43 x 43 = 1849 zones),
+``const`` (one zone: every update to one address) or ``random:N`` (a label in 0 ... N - 1 per pixel: no runs).  Beside
+it, in the same session, the plain read and ``k_stats`` without a histogram.  ``k_zonal_ms`` is ``fra_zonal_timing``
+(HIP events over every launch).  A workgroup's chunk of rows is read once per window of 512 zones between the smallest
+and the largest zone that occurs in it: ``launches`` is that count for the widest chunk, ``bytes_moved`` the sum over
+the chunks of (the values + the zone raster once per band), plus the zone raster once for the range pass, and
+``k_zonal_TBps`` their quotient.  It exits non-zero unless the counts and sums of band 0 equal ``np.bincount`` over the plain read.
+
+    python tools/bench_decode.py --zonal blocks:256 --steps 5 --warmup 2
 """
 from __future__ import annotations
 
@@ -230,6 +242,8 @@ def main():
                     help="time the comparison of the container with its source raster against the plain read")
     ap.add_argument("--stats", action="store_true",
                     help="time the band statistics and histograms of the container against the plain read")
+    ap.add_argument("--zonal", default=None, metavar="PATTERN",
+                    help="time fra_decode_device_zonal over a synthetic zone raster: blocks:N, const or random:N")
     ap.add_argument("--calc", action="append", default=None, metavar="EXPR",
                     help="time band math over the container against the plain read: one expression per output band, "
                          "separated by ';', optionally followed by ':dtype'; repeat for further legs of the same run")
@@ -503,6 +517,95 @@ def main():
         res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall]}
         print(json.dumps(res), flush=True)
         plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
+
+    if args.zonal:
+        from flac_raster.zonal import report_from_recs
+
+        if len(wins) != len(calculate_tiles(H, W, TILE)):
+            raise SystemExit("--zonal needs every tile: the region reduced is the whole raster")
+        kind, _, arg = args.zonal.partition(":")
+        if kind == "blocks":
+            n = int(arg or 256)
+            per_row = -(-W // n)
+            zones = ((np.arange(H, dtype=np.uint32)[:, None] // n) * per_row + np.arange(W, dtype=np.uint32)[None, :] // n)
+            nzones = per_row * -(-H // n)
+        elif kind == "const":
+            zones, nzones = np.zeros((H, W), np.uint32), 1
+        elif kind == "random":
+            nzones = int(arg or 16)
+            zones = np.random.default_rng(SEED).integers(0, nzones, (H, W), dtype=np.uint32)
+        else:
+            raise SystemExit("--zonal takes blocks:N, const or random:N")
+        if not 1 <= nzones <= 65536:
+            raise SystemExit(f"--zonal {args.zonal}: {nzones} zones, 1 ... 65536 go into one call")
+        zones = zones.astype(np.uint16)
+        dev_zones = ctx.alloc(zones.nbytes)
+        ctx.h2d(dev_zones, zones)
+        roi = (0, 0, H, W)
+        citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
+        med = statistics.median
+        plain_wall, plain_ms, ks = [], [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ctx.decode_device_window((frames_ptr, total), citems, dev_out, dt, B, (H * W, W, 1), roi, N.DENORM_PCM16)
+            t1 = time.perf_counter()
+            ctx.decode_device_stats((frames_ptr, total), citems, dt, B, roi, N.DENORM_PCM16, 0, None)
+            if s >= args.warmup:
+                plain_wall.append((t1 - t0) * 1e3)
+                plain_ms.append(ctx.decode_timing()[3])
+                ks.append(ctx.stats_timing())
+        wall, inner, kz = [], [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            recs, outside, _ = ctx.decode_device_zonal((frames_ptr, total), citems, dev_zones, dt, B, roi, N.DENORM_PCM16,
+                                                       0, nzones, zone_dtype=np.uint16, zone_strides=(W, 1))
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                wall.append((t1 - t0) * 1e3)
+                inner.append(ctx.decode_timing()[3])
+                kz.append(ctx.zonal_timing())
+        band0 = np.empty((H, W), dt)
+        ctx.d2h(band0, dev_out)
+        flat = zones.ravel()
+        counts = np.bincount(flat, minlength=nzones)
+        sums = np.bincount(flat, weights=band0.ravel().astype(np.float64), minlength=nzones)  # < 2^53: exact
+        if (outside != 0 or not np.array_equal(recs["count"][0], counts.astype(np.uint64))
+                or not np.array_equal(recs["sum_lo"][0], sums.astype(np.uint64)) or recs["sum_hi"].any()
+                or not np.array_equal(recs["valid"], recs["count"])):
+            raise SystemExit(f"zonal {args.zonal}: band 0 differs from np.bincount over the plain read")
+        first = report_from_recs(recs[:1], outside, dt)[0]["zones"][0]
+        once = B * H * W * dt.itemsize
+        # the chunks of rows of fra_zonal.hip's launch (8 uint16 per slot, 4096 workgroups aimed at, 1024 slots at least)
+        nvec = -(-W // 8)
+        rpb = min(H, max(-(-H * B // 4096), -(-1024 // nvec)))
+        moved, launches = zones.nbytes, 0
+        for r0 in range(0, H, rpb):
+            z = zones[r0:r0 + rpb]
+            reads = -(-(int(z.max()) - int(z.min()) + 1) // 512)
+            launches = max(launches, reads)
+            moved += reads * z.shape[0] * W * B * (dt.itemsize + zones.itemsize)
+        res = {
+            "workload": f"zonal C4-like {W}x{H}x{B} uint16 (pcm16), tile {TILE}, level {LEVEL}, {len(wins)} tiles, whole "
+                        f"raster, zones {args.zonal}",
+            "tiles": len(wins), "frames": nfr, "steps": args.steps, "warmup": args.warmup, "pattern": args.zonal,
+            "nzones": nzones, "band0_counts_and_sums_equal_bincount": True,
+            "plain_ms": round(med(plain_ms), 3), "plain_wall_ms": round(med(plain_wall), 3), "raster_bytes": once,
+            "zone_raster_bytes": zones.nbytes, "k_stats_ms": round(med(ks), 4),
+            "k_stats_TBps": round(once / (med(ks) * 1e-3) / 1e12, 3),
+            "zonal_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3), "k_zonal_ms": round(med(kz), 4),
+            "launches": launches, "chunk_rows": rpb, "bytes_moved": moved, "k_zonal_TBps": round(moved / (med(kz) * 1e-3) / 1e12, 3),
+            "k_zonal_over_scaled_k_stats": round(med(kz) / (med(ks) * moved / once), 3),
+            "wall_over_plain": round(med(wall) / med(plain_wall), 3),
+            "first_zone": {k: first[k] for k in ("zone", "valid", "min", "max", "mean", "std")},
+            "all_ms": {"k_zonal": [round(v, 4) for v in kz], "zonal_wall": [round(v, 3) for v in wall],
+                       "k_stats": [round(v, 4) for v in ks], "plain": [round(v, 3) for v in plain_ms]},
+        }
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_zones)
         ctx.free(dev_out)
         ctx.free(dev_raster)
         return

@@ -12,9 +12,10 @@
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
 //     their nodata-aware entries (fra_resample_masked.hip: a nodata value the dtype does not admit included),
 //     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats),
-//     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check) and
+//     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
 //     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
-//     fra_focal_check), which returns before any GPU work, and the order of these refusals (inputs that break two rules at once).
+//     fra_focal_check) and the zonal statistics (fra_zonal, fra_decode_device_zonal), which returns before any GPU
+//     work, and the order of these refusals (inputs that break two rules at once).
 // usage: decode_host_check [--concat] file.flac ...
 #include <cmath>
 #include <cstdarg>
@@ -798,6 +799,76 @@ int main(int argc, char** argv) {
     // the windowed read's refusals come first, then the spec, then the destination, then the inner rectangle, then the cover
     { fra_window r = r48; r.width = 0; auto s = mean3; s.op = 9; EXPECT(says(rf(ctx, &dj, &r, &s, &in48, &od, inf), "region of interest"), "focal read: zero-width roi and op 9: %s", g_msg.c_str()); }
     { fra_window r = r48; r.height = 5; fra_window in{0, 0, 6, 8}; EXPECT(says(rf(ctx, &dj, &r, &mean3, &in, &od, inf), "the inner rectangle"), "focal read: uncovered row and a tall inner rectangle: %s", g_msg.c_str()); }
+  }
+  // ... and of the zonal statistics (fra_zonal.hip): refused before any GPU work, in the order the header gives
+  {
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;
+    dj.items = &di;
+    dj.dst = nullptr;  // ignored, as are the job's strides
+    dj.band_stride = dj.row_stride = dj.col_stride = -1;
+    const fra_window r48{0, 0, 4, 8};
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    static uint16_t zones[64];
+    fra_zonal_rec recs[4];
+    uint64_t outside = 0;
+    fra_zonal_opts four{};
+    four.nzones = 4;
+    fra_zonal_job zj{};
+    zj.src = dst; zj.dtype = FRA_I32; zj.channels = 1; zj.height = 8; zj.width = 8;
+    zj.band_stride = 64; zj.row_stride = 8; zj.col_stride = 1;
+    zj.zones = zones; zj.zone_dtype = FRA_U16; zj.zone_row_stride = 8; zj.zone_col_stride = 1;
+    zj.opts = four;
+    EXPECT(fra_zonal(nullptr, &zj, recs, &outside) == FRA_E_INVALID, "zonal: null ctx accepted");
+    EXPECT(fra_zonal(ctx, nullptr, recs, &outside) == FRA_E_INVALID, "zonal: null job accepted");
+    EXPECT(fra_zonal(ctx, &zj, nullptr, &outside) == FRA_E_INVALID, "zonal: null records accepted");
+    EXPECT(fra_zonal(ctx, &zj, recs, nullptr) == FRA_E_INVALID, "zonal: null outside accepted");
+    { auto j = zj; j.src = nullptr; EXPECT(fra_zonal(ctx, &j, recs, &outside) == FRA_E_INVALID, "zonal: null src accepted"); }
+    { auto j = zj; j.zones = nullptr; EXPECT(fra_zonal(ctx, &j, recs, &outside) == FRA_E_INVALID, "zonal: null zones accepted"); }
+    { auto j = zj; j.dtype = 8; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad dtype"), "zonal: dtype 8: %s", g_msg.c_str()); }
+    { auto j = zj; j.width = 0; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad raster layout"), "zonal: zero width: %s", g_msg.c_str()); }
+    { auto j = zj; j.row_stride = -8; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad raster layout"), "zonal: negative stride: %s", g_msg.c_str()); }
+    for (int z : {-1, (int)FRA_F32, (int)FRA_F64, 8}) { auto j = zj; j.zone_dtype = z; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad zone dtype"), "zonal: zone dtype %d: %s", z, g_msg.c_str()); }
+    { auto j = zj; j.zone_row_stride = -8; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad zone layout"), "zonal: negative zone row stride: %s", g_msg.c_str()); }
+    { auto j = zj; j.zone_col_stride = -1; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad zone layout"), "zonal: negative zone column stride: %s", g_msg.c_str()); }
+    for (int n : {0, -1, 65537}) { auto j = zj; j.opts.nzones = n; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "nzones"), "zonal: nzones %d: %s", n, g_msg.c_str()); }
+    { auto j = zj; j.opts.flags = 4; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "unknown zonal flags"), "zonal: flag 4: %s", g_msg.c_str()); }
+    { auto j = zj; j.height = 65537; j.width = 65536; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "2^32 pixels"), "zonal: more than 2^32 pixels: %s", g_msg.c_str()); }
+    { auto j = zj; j.channels = 257; j.opts.nzones = 65536; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "2^24 records"), "zonal: 257 bands x 65536 zones: %s", g_msg.c_str()); }
+    // ... the order: the first broken rule speaks
+    { auto j = zj; j.dtype = 8; j.zone_dtype = 7; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad dtype"), "zonal: dtype 8 and zone dtype 7: %s", g_msg.c_str()); }
+    { auto j = zj; j.zone_dtype = 7; j.zone_row_stride = -1; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad zone dtype"), "zonal: zone dtype 7 and a negative zone stride: %s", g_msg.c_str()); }
+    { auto j = zj; j.zone_col_stride = -1; j.opts.nzones = 0; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "bad zone layout"), "zonal: negative zone stride and no zones: %s", g_msg.c_str()); }
+    { auto j = zj; j.opts.nzones = 0; j.opts.flags = 4; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "nzones"), "zonal: no zones and flag 4: %s", g_msg.c_str()); }
+    { auto j = zj; j.opts.flags = 4; j.height = 65537; j.width = 65536; EXPECT(says(fra_zonal(ctx, &j, recs, &outside), "unknown zonal flags"), "zonal: flag 4 and 2^32 pixels: %s", g_msg.c_str()); }
+    EXPECT(fra_zonal_timing(nullptr) == FRA_E_INVALID, "zonal timing: null accepted");
+    auto zr = [&](fra_ctx* c, const fra_decode_job* j, const fra_window* r, const void* z, int zd, int64_t zrs, int64_t zcs,
+                  const fra_zonal_opts* o, fra_zonal_rec* rc, uint64_t* out, fra_decoded* d) {
+      return fra_decode_device_zonal(c, j, r, z, 0, zd, zrs, zcs, o, rc, out, d);
+    };
+    EXPECT(zr(nullptr, &dj, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: null ctx accepted");
+    EXPECT(zr(ctx, nullptr, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: null job accepted");
+    EXPECT(zr(ctx, &dj, nullptr, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: null roi accepted");
+    EXPECT(zr(ctx, &dj, &r48, nullptr, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: null zones accepted");
+    EXPECT(zr(ctx, &dj, &r48, zones, FRA_U16, 8, 1, nullptr, recs, &outside, inf) == FRA_E_INVALID, "zonal read: null options accepted");
+    EXPECT(zr(ctx, &dj, &r48, zones, FRA_U16, 8, 1, &four, nullptr, &outside, inf) == FRA_E_INVALID, "zonal read: null records accepted");
+    EXPECT(zr(ctx, &dj, &r48, zones, FRA_U16, 8, 1, &four, recs, nullptr, inf) == FRA_E_INVALID, "zonal read: null outside accepted");
+    EXPECT(zr(ctx, &dj, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, nullptr) == FRA_E_INVALID, "zonal read: null infos accepted");
+    for (int z : {-1, (int)FRA_F32, 8}) EXPECT(says(zr(ctx, &dj, &r48, zones, z, 8, 1, &four, recs, &outside, inf), "bad zone dtype"), "zonal read: zone dtype %d: %s", z, g_msg.c_str());
+    EXPECT(says(zr(ctx, &dj, &r48, zones, FRA_U16, -8, 1, &four, recs, &outside, inf), "bad zone layout"), "zonal read: negative zone stride: %s", g_msg.c_str());
+    for (int n : {0, 65537}) { auto o = four; o.nzones = n; EXPECT(says(zr(ctx, &dj, &r48, zones, FRA_U16, 8, 1, &o, recs, &outside, inf), "nzones"), "zonal read: nzones %d: %s", n, g_msg.c_str()); }
+    { auto o = four; o.flags = 8; EXPECT(says(zr(ctx, &dj, &r48, zones, FRA_U16, 8, 1, &o, recs, &outside, inf), "unknown zonal flags"), "zonal read: flag 8: %s", g_msg.c_str()); }
+    { fra_window r = r48; r.height = 5; EXPECT(says(zr(ctx, &dj, &r, zones, FRA_U16, 8, 1, &four, recs, &outside, inf), "do not cover"), "zonal read: uncovered row: %s", g_msg.c_str()); }
+    { auto x = di; x.window.width = 7; auto j = dj; j.items = &x; EXPECT(says(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf), "do not cover"), "zonal read: uncovered column: %s", g_msg.c_str()); }
+    { auto j = dj; j.nitems = 0; EXPECT(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: empty job accepted"); }
+    { fra_window r = r48; r.width = 0; EXPECT(says(zr(ctx, &dj, &r, zones, FRA_U16, 8, 1, &four, recs, &outside, inf), "region of interest"), "zonal read: zero-width roi: %s", g_msg.c_str()); }
+    { fra_window r{0, 0, 65537, 65536}; EXPECT(says(zr(ctx, &dj, &r, zones, FRA_U16, 8, 1, &four, recs, &outside, inf), "2^32 pixels"), "zonal read: more than 2^32 pixels: %s", g_msg.c_str()); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.dst_dtype = 9; EXPECT(says(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf), "dtype"), "zonal read: dtype 9: %s", g_msg.c_str()); }
+    { auto j = dj; j.denorm = 7; EXPECT(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: denorm 7 accepted"); }
+    { auto j = dj; j.channels = 0; EXPECT(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: no channels accepted"); }
+    { fra_window r = r48; r.width = 0; auto o = four; o.nzones = 0; EXPECT(says(zr(ctx, &dj, &r, zones, FRA_U16, 8, 1, &o, recs, &outside, inf), "nzones"), "zonal read: no zones and zero-width roi: %s", g_msg.c_str()); }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
   {
