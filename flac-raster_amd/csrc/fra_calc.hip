@@ -9,7 +9,8 @@
 // dispatch on its op and the stack pointer are scalar loads, scalar branches and a scalar register: the program is the
 // same for every lane.  A lane evaluates P = 8 or 4 neighbouring pixels of a row (a slot) per word, which spreads a
 // word's dispatch, and the latency of a BAND word's load, over the wave's 512 or 256 pixels (P = 8: 21 - 38 % less time
-// than P = 4 on the measured expressions; the host picks it while the LDS below stays within 32 KiB).  Grid and tail as k_stats: a workgroup is a chunk of rows, thread t owns slots
+// than P = 4 on the measured expressions; the host picks it while the LDS below stays within 32 KiB).
+// Grid, slots and cursor of fra_scan.h, with no band in the grid: a workgroup is a chunk of rows, thread t owns slots
 // t, t + 256, ... of it, and the loop over a chunk's slots has one trip count for the whole workgroup (lanes past the
 // end evaluate nothing they load or store), so no branch of the interpreter diverges.
 //   The stack.  A per-lane array indexed by the stack pointer would live in private memory.  Instead the top of the
@@ -37,6 +38,7 @@
 #include "fra_calc.h"
 #include "fra_host.h"
 #include "fra_region.h"
+#include "fra_scan.h"
 
 static_assert(sizeof(fra_calc_program) == 544, "fra_calc_program is 544 bytes");
 
@@ -59,10 +61,7 @@ struct CalcArgs {
   unsigned long long* left;  // the left-out pixels, zeroed by the host
   double nodata, fill;
   int32_t h, w;
-  uint32_t nvec;       // slots per row: ceil(w / P), P the instance's
-  uint32_t rpb;        // rows per workgroup
-  uint32_t step_rows;  // 256 / nvec and 256 % nvec: a thread's way from one of its slots to the next
-  uint32_t step_vecs;
+  ChunkPlan plan;      // for slots of P pixels, P the instance's; one band
   int32_t svec, dvec;  // vector accesses are aligned (column stride 1; base, row and band strides multiples of 16 bytes)
   int32_t use_nd;      // FRA_CALC_NODATA with a nodata that is not NaN ... (1) or that is (2: NaN pixels alone are left out)
   int32_t ncode;
@@ -72,15 +71,14 @@ struct CalcArgs {
 
 // elements [0, n) of a slot as f64 (the others 0.0)
 template <typename S, int P>
-__device__ inline void load_slot(const S* p, int64_t cs, bool vec, int n, double* x) {
-  if (vec && n == P) {
-    const VecOf<S, P> v = *(const VecOf<S, P>*)p;
+__device__ inline void load_f64(const S* p, int64_t cs, bool vec, int n, double* x) {
+  auto widen = [&](const VecOf<S, P>& v) {
 #pragma unroll
     for (int i = 0; i < P; i++) x[i] = (double)v.v[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < P; i++) x[i] = i < n ? (double)p[(int64_t)i * cs] : 0.0;
-  }
+  };
+  // (each path converts what it loaded: one conversion after the paths have met costs the interpreter more branches)
+  if (vec && n == P) widen(load_slot<S, P>(p, cs, true, P));
+  else widen(load_slot<S, P>(p, cs, false, n));
 }
 
 template <typename D, int P>
@@ -102,28 +100,28 @@ __global__ void __launch_bounds__(256) k_calc(CalcArgs g) {
   static_assert(P == 4 || P == 8, "a slot's left-out bits and vector accesses are written for 4 or 8 pixels");
   extern __shared__ double s_stack[];  // (deepest - 1) x P x 256 values: what lies below the top of the stack
   const uint32_t tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * g.rpb;
-  const uint32_t rows = (uint32_t)min((int64_t)g.rpb, (int64_t)g.h - row0);
-  const uint32_t nslots = rows * g.nvec;  // (the host keeps a chunk's slots inside 31 bits)
+  const Chunk c = chunk_at(g.plan, g.h, blockIdx.x);
+  const uint32_t rows = c.rows;
+  const uint32_t nslots = rows * g.plan.nvec;  // (the host keeps a chunk's slots inside 31 bits)
   const uint32_t niter = (nslots + 255u) / 256u;
-  const S* __restrict__ const ps = (const S*)g.src + row0 * g.srs;
-  D* __restrict__ const pd = (D*)g.dst + row0 * g.drs;
+  const S* __restrict__ const ps = (const S*)g.src + c.row0 * g.srs;
+  D* __restrict__ const pd = (D*)g.dst + c.row0 * g.drs;
   const bool svec = g.svec != 0, dvec = g.dvec != 0;
-  uint32_t row = tid / g.nvec, cv = tid % g.nvec;
+  Cursor at(g.plan, tid);
   uint32_t nleft = 0;  // (a thread's slots x P stay far below 2^32)
 
   for (uint32_t it = 0; it < niter; it++) {
-    const bool active = row < rows;
-    const int n = active ? (int)min((int64_t)P, (int64_t)g.w - (int64_t)cv * P) : 0;
-    const int64_t soff = (int64_t)row * g.srs + (int64_t)cv * P * g.scs;
-    const int64_t doff = (int64_t)row * g.drs + (int64_t)cv * P * g.dcs;
+    const bool active = at.row < rows;
+    const int n = active ? slot_count<P>(g.w, at.cv) : 0;
+    const int64_t soff = (int64_t)at.row * g.srs + (int64_t)at.cv * P * g.scs;
+    const int64_t doff = (int64_t)at.row * g.drs + (int64_t)at.cv * P * g.dcs;
     uint32_t mask = 0;  // bit i: pixel i of the slot is left out
     if (g.use_nd) {
       for (int pc = 0; pc < g.ncode; pc++) {
         const uint32_t word = g.code[pc];
         if ((word & 0xffu) != FRA_CALC_BAND) continue;
         double x[P];
-        load_slot<S, P>(ps + ((int64_t)(word >> 8) * g.sbs + soff), g.scs, svec, n, x);
+        load_f64<S, P>(ps + ((int64_t)(word >> 8) * g.sbs + soff), g.scs, svec, n, x);
 #pragma unroll
         for (int i = 0; i < P; i++) mask |= (uint32_t)(x[i] != x[i] || (g.use_nd == 1 && x[i] == g.nodata)) << i;
       }
@@ -154,7 +152,7 @@ __global__ void __launch_bounds__(256) k_calc(CalcArgs g) {
         for (int i = 0; i < P; i++) tos[i] = c;
       } else if (op == FRA_CALC_BAND) {
         push();
-        load_slot<S, P>(ps + ((int64_t)arg * g.sbs + soff), g.scs, svec, n, tos);
+        load_f64<S, P>(ps + ((int64_t)arg * g.sbs + soff), g.scs, svec, n, tos);
       } else if (op == FRA_CALC_STORE) {
         double x[P];
 #pragma unroll
@@ -219,8 +217,7 @@ __global__ void __launch_bounds__(256) k_calc(CalcArgs g) {
         }
       }
     }
-    row += g.step_rows, cv += g.step_vecs;
-    if (cv >= g.nvec) cv -= g.nvec, row++;
+    at.next(g.plan);
   }
 
   if (g.use_nd) {
@@ -233,9 +230,7 @@ __global__ void __launch_bounds__(256) k_calc(CalcArgs g) {
 
 thread_local float g_calc_ms = 0.f;
 
-constexpr int64_t kMaxPixels = (int64_t)1 << 32;  // per band
-constexpr int64_t kBlocks = 4096;                 // workgroups aimed at: 16 per CU
-constexpr int64_t kMinSlots = 1024;               // slots of a workgroup, at least (4 per thread), rows permitting
+constexpr const char* kNot = "mapped in one call";  // (too_many_pixels)
 
 // k_calc over a (channels, h, w) device raster into a device raster, timed; the left-out count to `left_out` (nout words)
 int run_calc(Call& c, const fra_calc_program& p, int deepest, int sdtype, int32_t h, int32_t w, const Io& io, int ddtype,
@@ -254,13 +249,9 @@ int run_calc(Call& c, const fra_calc_program& p, int deepest, int sdtype, int32_
   std::memcpy(g.consts, p.consts, sizeof(g.consts));
   const int below = std::max(0, deepest - 1);  // the values the LDS holds per pixel
   const int P = (int64_t)below * 8 * 256 * (int64_t)sizeof(double) <= kWideLds ? 8 : 4;
-  const int64_t nvec = ((int64_t)w + P - 1) / P;
-  int64_t rpb = std::max<int64_t>(((int64_t)h + kBlocks - 1) / kBlocks, (kMinSlots + nvec - 1) / nvec);
-  rpb = std::min<int64_t>(rpb, std::max<int64_t>(1, ((int64_t)1 << 29) / nvec));  // a chunk's pixels are counted in 32 bits
-  rpb = std::min<int64_t>(rpb, h);
-  const int64_t grid = ((int64_t)h + rpb - 1) / rpb;
-  g.nvec = (uint32_t)nvec, g.rpb = (uint32_t)rpb;
-  g.step_rows = (uint32_t)(256 / nvec), g.step_vecs = (uint32_t)(256 % nvec);
+  // (a chunk's pixels are counted in 32 bits: 2^29 slots of 8)
+  if (const int rc = plan_chunks(&g.plan, P, h, w, 1, (int64_t)1 << 29, 0, "band math call")) return rc;
+  const unsigned grid = g.plan.grid;
   const size_t lds = (size_t)below * P * 256 * sizeof(double);
   HIPCHK(c.sc.alloc(&g.left, sizeof(unsigned long long)));
   HIPCHK(hipMemsetAsync(g.left, 0, sizeof(unsigned long long), c.s));
@@ -270,8 +261,8 @@ int run_calc(Call& c, const fra_calc_program& p, int deepest, int sdtype, int32_
       [&]() -> int {
         with_dtype(sdtype, [&](auto s) {
           with_dtype(ddtype, [&](auto d) {
-            if (P == 8) hipLaunchKernelGGL((k_calc<decltype(s), decltype(d), 8>), dim3((unsigned)grid), dim3(256), lds, c.s, g);
-            else hipLaunchKernelGGL((k_calc<decltype(s), decltype(d), 4>), dim3((unsigned)grid), dim3(256), lds, c.s, g);
+            if (P == 8) hipLaunchKernelGGL((k_calc<decltype(s), decltype(d), 8>), dim3(grid), dim3(256), lds, c.s, g);
+            else hipLaunchKernelGGL((k_calc<decltype(s), decltype(d), 4>), dim3(grid), dim3(256), lds, c.s, g);
           });
         });
         HIPCHK(hipGetLastError());
@@ -285,12 +276,6 @@ int run_calc(Call& c, const fra_calc_program& p, int deepest, int sdtype, int32_
   if (left_out)
     for (int k = 0; k < p.nout; k++) left_out[k] = (uint64_t)left;
   return FRA_OK;
-}
-
-int too_many_pixels(int64_t h, int64_t w) {
-  if (h * w <= kMaxPixels) return FRA_OK;
-  return fra_internal_set_error(FRA_E_INVALID, "more than 2^32 pixels per band (%lld x %lld) are not mapped in one call",
-                                (long long)h, (long long)w);
 }
 
 // the destination's dtype and layout, for an output of p's bands
@@ -322,7 +307,7 @@ FRA_API int fra_calc(fra_ctx* ctx, const fra_calc_job* job, uint64_t* left_out) 
   const int32_t h = job->height, w = job->width;
   if (const int rc = check_raster(job->dtype, job->channels, h, w, ss, ss)) return rc;
   if (const int rc = check_dst(&p, &job->out, h, w)) return rc;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   const fra_calc_dst& o = job->out;
   return run_raster_to(ctx, job->src, job->src_on_device, job->dtype, job->channels, h, w, ss,
                        Dst{o.dst, o.dst_on_device, o.dtype, p.nout, h, w, {o.band_stride, o.row_stride, o.col_stride}},
@@ -339,7 +324,7 @@ FRA_API int fra_decode_device_calc(fra_ctx* ctx, const fra_decode_job* job, cons
   if (const int rc = fra_calcp::check_program(program, job->channels, &deepest)) return rc;
   const int32_t h = roi->height, w = roi->width;
   if (const int rc = check_dst(program, out, h, w)) return rc;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   if (const int rc = check_cover(job, roi)) return rc;
   return run_region_to(
       ctx, job, roi, infos,

@@ -39,6 +39,7 @@
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
 #include "fra_region.h"
+#include "fra_scan.h"
 
 static_assert(sizeof(fra_focal_spec) == 1904, "fra_focal_spec is 1904 bytes");
 
@@ -333,7 +334,7 @@ __global__ void __launch_bounds__(256) k_focal(FocalArgs g) {
 
 thread_local float g_focal_ms = 0.f;
 
-constexpr int64_t kMaxPixels = (int64_t)1 << 32;  // per band
+constexpr const char* kNot = "mapped in one call";  // (too_many_pixels)
 
 // the smallest b >= bytes with b % mod == mod / 2
 int64_t half_odd(int64_t bytes, int64_t mod) { return (bytes + mod / 2 - 1) / mod * mod + mod / 2; }
@@ -431,12 +432,6 @@ int check_rect(const fra_window& r, int32_t h, int32_t w, const char* what, cons
   return FRA_OK;
 }
 
-int too_many_pixels(int64_t h, int64_t w) {
-  if (h * w <= kMaxPixels) return FRA_OK;
-  return fra_internal_set_error(FRA_E_INVALID, "more than 2^32 pixels per band (%lld x %lld) are not mapped in one call",
-                                (long long)h, (long long)w);
-}
-
 }  // namespace
 
 extern "C" {
@@ -457,7 +452,7 @@ FRA_API int fra_focal(fra_ctx* ctx, const fra_focal_job* job, uint64_t* left_out
   const fra_calc_dst& o = job->out;
   if (const int rc = check_layouts(job->dtype, job->channels, h, w, ss, &o)) return rc;
   if (const int rc = check_rect(job->rect, h, w, "the output rectangle", "the source")) return rc;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   return run_raster_to(ctx, job->src, job->src_on_device, job->dtype, job->channels, h, w, ss,
                        Dst{o.dst, o.dst_on_device, o.dtype, job->channels, job->rect.height, job->rect.width,
                            {o.band_stride, o.row_stride, o.col_stride}},
@@ -475,7 +470,7 @@ FRA_API int fra_decode_device_focal(fra_ctx* ctx, const fra_decode_job* job, con
   const int32_t h = roi->height, w = roi->width;
   if (const int rc = check_layouts(job->dst_dtype, job->channels, h, w, Strides{0, 0, 1}, out)) return rc;
   if (const int rc = check_rect(*inner, h, w, "the inner rectangle", "the region")) return rc;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   if (const int rc = check_cover(job, roi)) return rc;
   return run_region_to(ctx, job, roi, infos,
                        Dst{out->dst, out->dst_on_device, out->dtype, job->channels, inner->height, inner->width,

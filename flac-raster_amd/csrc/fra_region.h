@@ -11,7 +11,8 @@
 //     of host buffers (stage_in, stage_out, copy_back), the kernels' time between two events (timed), and the two
 //     frames around a unit's kernels: a raster job (run_raster) and a region decoded by the windowed read
 //     (fra_decode_device_window, called as any caller would: same kernels, refusals and messages) into a per-call
-//     device buffer (decode, run_region).
+//     device buffer (decode; run_region_src without a destination, run_region_to and run_region with one).
+// The scan of a raster in chunks of rows and slots, which four of the units share, is in fra_scan.h.
 // Every function is inline: the units are separate translation units of one library and of one check program.
 #pragma once
 #include <algorithm>
@@ -262,19 +263,26 @@ inline int run_raster(fra_ctx* ctx, const RasterJob& j, Body&& body) {
                        Dst{j.dst, j.dst_on_device, j.dtype, j.channels, j.oh, j.ow, j.ds}, body);
 }
 
-// The same for a region: decoded into a per-call buffer, which is the body's source.
+// A region without a destination (the reducing units): decoded into a per-call buffer, body(call, d_region, strides).
 template <typename Body>
-inline int run_region_to(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, const Dst& d,
-                         Body&& body) {
+inline int run_region_src(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, Body&& body) {
   Call c(ctx);
   void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
   int64_t rs = 0;
   if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
-  Io io{d_region, {(int64_t)roi->height * rs, rs, 1}, {}, d.s};
-  if (const int rc = stage_out(c, d.p, d.on_device, (size_t)extent_of(d.channels, d.oh, d.ow, d.s) * (size_t)elem_size(d.dtype),
-                               &io.out))
-    return rc;
-  return body(c, io);
+  return body(c, (const void*)d_region, Strides{(int64_t)roi->height * rs, rs, 1});
+}
+// The same as run_raster_to for a region: the decoded region is the body's source.
+template <typename Body>
+inline int run_region_to(fra_ctx* ctx, const fra_decode_job* job, const fra_window* roi, fra_decoded* infos, const Dst& d,
+                         Body&& body) {
+  return run_region_src(ctx, job, roi, infos, [&](Call& c, const void* d_region, const Strides& ss) -> int {
+    Io io{d_region, ss, {}, d.s};
+    if (const int rc = stage_out(c, d.p, d.on_device,
+                                 (size_t)extent_of(d.channels, d.oh, d.ow, d.s) * (size_t)elem_size(d.dtype), &io.out))
+      return rc;
+    return body(c, io);
+  });
 }
 // ... into the job's dst and strides, the (channels, oh, ow) destination in dst_dtype
 template <typename Body>

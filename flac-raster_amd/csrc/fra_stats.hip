@@ -7,8 +7,8 @@
 // first pass; a histogram of `bins` bins over an explicit range or over [fin_min, fin_max] of the band, with the pixels
 // outside it counted in below / above.
 //
-// k_stats<T, PASS, HMODE>: the thread-to-slot mapping, the load choice and the pipelined loads of k_compare, over one
-// raster: a workgroup is one (band, chunk of rows), thread t owns slots t, t + 256, ... of V = 16 / sizeof(T) elements.
+// k_stats<T, PASS, HMODE>: the row-chunk scan of fra_scan.h over one raster, slots of V = 16 / sizeof(T) elements, the
+// pipelined row-major walk (scan_row_major).
 //   PASS 1 accumulates the counts, extremes and sums; PASS 2 reads the band's record (mean, histogram range and scale)
 //   from device memory -- no host round trip -- and accumulates fm2 (floats) and the histogram.  Pass 2 runs for floats,
 //   and for integers only for a histogram over the automatic range; integers with an explicit range count their
@@ -21,8 +21,7 @@
 //   raster per window (at most 8): pixels of other windows are skipped, and the partials of these launches are not
 //   folded.  (Global atomics per pixel run were measured first: 50 ms for the 65536-bin histogram of a 964 MB uint16
 //   scene and 354 ms for a constant one, against 0.5 - 0.8 ms per LDS window.)
-//   The thread's record goes through a fixed wave tree (__shfl_down) and, through LDS, the block's four waves in order,
-//   to one partial per workgroup.
+//   The thread's record goes through the fixed tree of block_reduce to one partial per workgroup.
 // k_stats_fold / k_stats_fold2: one workgroup per band.  Counts, extremes and the integer sums by the same tree, the f64
 // sum strictly in partial order; the band's record is written to (pass 1) and completed in (pass 2) device memory.
 //
@@ -30,9 +29,9 @@
 // waves), which a bandwidth-bound loop needs; a uint32 bin per 4-byte bank, so lanes that hit different bins conflict
 // only on equal banks and lanes that hit one bin serialise -- which the merge above bounds per slot.
 //
-// This unit holds the kernels, their launch and the refusals of the options and of 2^32 pixels.  Shared with the other
-// region-reducing units (fra_region.h): the dtype and layout refusal, what is left to the windowed read (the variant
-// that ignores the job's destination), the staging of a host raster, the decoded region and the timed launch.
+// This unit holds the kernels, their launch and the refusals of the options.  Shared with the other units over a region
+// (fra_region.h): the dtype and layout refusal, what is left to the windowed read (the variant that ignores the job's
+// destination), the staging of a host raster, the decoded region and the timed launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +44,7 @@
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
 #include "fra_region.h"
+#include "fra_scan.h"
 
 static_assert(sizeof(fra_stats_band) == 160, "fra_stats_band is 160 bytes");
 
@@ -70,11 +70,7 @@ struct StatsArgs {
   double lo, hi, scale;    // the explicit range (pass 1 with a histogram)
   double nodata;
   int32_t h, w;
-  uint32_t nvec;       // slots per row: ceil(w / V)
-  uint32_t rpb;        // rows per workgroup
-  uint32_t nchunks;    // workgroups per band: ceil(h / rpb)
-  uint32_t step_rows;  // 256 / nvec and 256 % nvec: a thread's way from one of its slots to the next
-  uint32_t step_vecs;
+  ChunkPlan plan;
   int32_t vec;  // 16-byte loads are aligned (column stride 1; base, row and band strides multiples of 16 bytes)
   int32_t bins, flags;
   int32_t bin0, nbins;  // the window of bins this launch counts (HMODE 1)
@@ -97,30 +93,6 @@ __device__ inline Partial empty_partial() {
   p.valid = p.nan = p.nodata = p.below = p.above = p.sum_lo = p.sum_hi = p.sq_lo = p.sq_hi = 0;
   p.mn = p.fmn = HUGE_VAL, p.mx = p.fmx = -HUGE_VAL;
   p.fsum = 0.0;
-  return p;
-}
-
-__device__ inline uint64_t down(uint64_t v, int off) { return (uint64_t)__shfl_down((unsigned long long)v, off, 64); }
-__device__ inline double down(double v, int off) { return __shfl_down(v, off, 64); }
-
-// the block's record in thread 0: lane tree inside each wave, then the waves in order
-__device__ inline Partial block_reduce(Partial p, Partial* sh /* [4] */) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    Partial q;
-    q.valid = down(p.valid, off), q.nan = down(p.nan, off), q.nodata = down(p.nodata, off);
-    q.below = down(p.below, off), q.above = down(p.above, off);
-    q.sum_lo = down(p.sum_lo, off), q.sum_hi = down(p.sum_hi, off), q.sq_lo = down(p.sq_lo, off), q.sq_hi = down(p.sq_hi, off);
-    q.mn = down(p.mn, off), q.mx = down(p.mx, off), q.fmn = down(p.fmn, off), q.fmx = down(p.fmx, off);
-    q.fsum = down(p.fsum, off);
-    combine(p, q);  // (lanes past 64 - off fold their own value in; lane 0 never reads them)
-  }
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = p;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    p = sh[0];
-    for (int k = 1; k < 4; k++) combine(p, sh[k]);
-  }
   return p;
 }
 
@@ -199,20 +171,9 @@ struct Acc {
   S sum = 0;  // integers: |x| <= 2^31 over fewer than 2^32 / 256 + V pixels; floats: sum x (pass 1), sum (x - mean)^2 (pass 2)
   M mn = FLT ? (M)HUGE_VAL : std::numeric_limits<M>::max(), mx = FLT ? (M)-HUGE_VAL : std::numeric_limits<M>::lowest();
   double fmn = HUGE_VAL, fmx = -HUGE_VAL;  // floats
-  M nd = 0;
-  bool use_nd = false;
+  Nodata<T> nodata_of;
   double mean = 0.0;
   Hist<HMODE> hist;
-
-  __device__ inline void set_nodata(int flags, double v) {
-    if (!(flags & FRA_STATS_NODATA)) return;
-    if constexpr (FLT) {
-      use_nd = v == v, nd = v;
-    } else {  // (double)x == v only for an integral v inside T's range
-      use_nd = v >= (double)std::numeric_limits<T>::lowest() && v <= (double)std::numeric_limits<T>::max() && v == floor(v);
-      nd = use_nd ? (T)v : (T)0;
-    }
-  }
 
   template <bool FULL>
   __device__ inline void slot(const T* v, int n) {
@@ -228,7 +189,7 @@ struct Acc {
             continue;
           }
         }
-        if (use_nd && x == nd) {
+        if (nodata_of.is(x)) {
           nodata++;
           continue;
         }
@@ -290,19 +251,16 @@ struct Acc {
 template <typename T, int PASS, int HMODE>
 __global__ void __launch_bounds__(256) k_stats(StatsArgs g) {
   constexpr int V = 16 / (int)sizeof(T);
-  struct alignas(16) Vec { T v[V]; };
   extern __shared__ uint32_t s_hist[];  // HMODE 1: the workgroup's bins (nbins x 4 bytes of dynamic LDS)
   __shared__ Partial sh[4];
-  const uint32_t chunk = blockIdx.x % g.nchunks;
-  const int64_t band = (int64_t)(blockIdx.x / g.nchunks);
-  const int64_t row0 = (int64_t)chunk * g.rpb;
-  const uint32_t rows = (uint32_t)min((int64_t)g.rpb, (int64_t)g.h - row0);
-  const T* __restrict__ ps = (const T*)g.src + (band * g.bs + row0 * g.rs);
+  const Chunk c = chunk_of(g.plan, g.h, blockIdx.x);
+  const int64_t band = c.band;
+  const T* __restrict__ ps = (const T*)g.src + (band * g.bs + c.row0 * g.rs);
   const bool vec = g.vec != 0;
   unsigned long long* const band_hist = HMODE != 0 ? g.hist + (band * (int64_t)g.bins + g.bin0) : nullptr;
 
   Acc<T, PASS, HMODE> acc;
-  acc.set_nodata(g.flags, g.nodata);
+  acc.nodata_of.set((g.flags & FRA_STATS_NODATA) != 0, g.nodata);
   if constexpr (HMODE != 0) {
     if constexpr (PASS == 1) {
       acc.hist.set_range(g.lo, g.hi, g.scale, g.bins);
@@ -330,40 +288,16 @@ __global__ void __launch_bounds__(256) k_stats(StatsArgs g) {
     __syncthreads();
   }
 
-  // slot (row, cv) of the chunk: elements [cv V, cv V + n) of its row
-  auto count = [&](uint32_t cv) { return (int)min((int64_t)V, (int64_t)g.w - (int64_t)cv * V); };
-  auto load = [&](const T* p, int n) {
-    Vec v;
-    if (vec && n == V) {
-      v = *(const Vec*)p;
-    } else {
-#pragma unroll
-      for (int i = 0; i < V; i++) v.v[i] = i < n ? p[(int64_t)i * g.cs] : (T)0;
-    }
-    return v;
-  };
-  uint32_t row = threadIdx.x / g.nvec, cv = threadIdx.x % g.nvec;
-  Vec nx{};
-  int nn = 0;
-  bool have = row < rows;
-  if (have) {
-    nn = count(cv);
-    nx = load(ps + ((int64_t)row * g.rs + (int64_t)cv * V * g.cs), nn);
-  }
-  while (have) {
-    const Vec cx = nx;
-    const int cn = nn;
-    row += g.step_rows, cv += g.step_vecs;
-    if (cv >= g.nvec) cv -= g.nvec, row++;
-    have = row < rows;
-    if (have) {  // in flight while the current slot is accumulated
-      nn = count(cv);
-      nx = load(ps + ((int64_t)row * g.rs + (int64_t)cv * V * g.cs), nn);
-    }
-    if (cn == V) acc.template slot<true>(cx.v, cn);
-    else acc.template slot<false>(cx.v, cn);
-  }
-  const Partial p = block_reduce(acc.partial(), sh);  // (its barrier also ends the workgroup's LDS counting)
+  scan_row_major<V>(
+      g.plan, c.rows, g.w,
+      [&](uint32_t row, uint32_t cv, int n) {
+        return load_slot<T, V>(ps + ((int64_t)row * g.rs + (int64_t)cv * V * g.cs), g.cs, vec, n);
+      },
+      [&](const VecOf<T, V>& x, int n, uint32_t, uint32_t) {
+        if (n == V) acc.template slot<true>(x.v, n);
+        else acc.template slot<false>(x.v, n);
+      });
+  const Partial p = block_reduce(acc.partial(), sh, combine);  // (its barrier also ends the workgroup's LDS counting)
   if (threadIdx.x == 0) g.partials[blockIdx.x] = p;
   if constexpr (HMODE == 1) {
     for (int i = threadIdx.x; i < g.nbins; i += 256) {
@@ -374,30 +308,22 @@ __global__ void __launch_bounds__(256) k_stats(StatsArgs g) {
 }
 
 // a band's partials folded into thread 0's record; the f64 sum, added strictly in partial order, into *fsum
-__device__ inline Partial fold_partials(const Partial* p, uint32_t nchunks, Partial* sh, double* s_f /* [256] */,
+__device__ inline Partial fold_partials(const Partial* p, uint32_t nchunks, Partial* sh, double (&s_f)[1][256],
                                         double* fsum) {
   Partial acc = empty_partial();
   for (uint32_t i = threadIdx.x; i < nchunks; i += 256) combine(acc, p[i]);
-  acc = block_reduce(acc, sh);  // everything but the f64 sum, which follows in partial order
-  double f = 0.0;
-  for (uint32_t base = 0; base < nchunks; base += 256) {
-    const uint32_t i = base + threadIdx.x;
-    __syncthreads();
-    s_f[threadIdx.x] = i < nchunks ? p[i].fsum : 0.0;
-    __syncthreads();
-    const uint32_t n = min(256u, nchunks - base);
-    if (threadIdx.x == 0)
-      for (uint32_t j = 0; j < n; j++) f = f + s_f[j];
-  }
-  *fsum = f;
+  acc = block_reduce(acc, sh, combine);  // everything but the f64 sum, which follows in partial order
+  double f[1];
+  sum_in_order(p, nchunks, {&Partial::fsum}, s_f, f);
+  *fsum = f[0];
   return acc;
 }
 
 __global__ void __launch_bounds__(256) k_stats_fold(StatsArgs g, int32_t is_float, int32_t fused_hist) {
   __shared__ Partial sh[4];
-  __shared__ double s_f[256];
+  __shared__ double s_f[1][256];
   double fsum = 0.0;
-  const Partial a = fold_partials(g.partials + (size_t)blockIdx.x * g.nchunks, g.nchunks, sh, s_f, &fsum);
+  const Partial a = fold_partials(g.partials + (size_t)blockIdx.x * g.plan.nchunks, g.plan.nchunks, sh, s_f, &fsum);
   if (threadIdx.x != 0) return;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   fra_stats_band r;
@@ -429,9 +355,9 @@ __global__ void __launch_bounds__(256) k_stats_fold(StatsArgs g, int32_t is_floa
 
 __global__ void __launch_bounds__(256) k_stats_fold2(StatsArgs g, int32_t is_float) {
   __shared__ Partial sh[4];
-  __shared__ double s_f[256];
+  __shared__ double s_f[1][256];
   double fsum = 0.0;
-  const Partial a = fold_partials(g.partials + (size_t)blockIdx.x * g.nchunks, g.nchunks, sh, s_f, &fsum);
+  const Partial a = fold_partials(g.partials + (size_t)blockIdx.x * g.plan.nchunks, g.plan.nchunks, sh, s_f, &fsum);
   if (threadIdx.x != 0) return;
   fra_stats_band* r = g.bands + blockIdx.x;
   r->below = a.below, r->above = a.above;
@@ -440,9 +366,7 @@ __global__ void __launch_bounds__(256) k_stats_fold2(StatsArgs g, int32_t is_flo
 
 thread_local float g_stats_ms = 0.f;
 
-constexpr int64_t kMaxPixels = (int64_t)1 << 32;  // per band: the integer sums stay inside 65 and 96 bits
-constexpr int64_t kBlocks = 4096;                 // workgroups aimed at: 16 per CU
-constexpr int64_t kMinSlots = 1024;               // slots of a workgroup, at least (4 per thread), rows permitting
+constexpr const char* kNot = "described in one call";  // (too_many_pixels)
 
 template <typename T, int PASS, int HMODE>
 void launch_one(unsigned grid, size_t lds, hipStream_t s, const StatsArgs& g) {
@@ -492,16 +416,10 @@ int run_stats(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
     g.scale = g.hi > g.lo ? (double)o.bins / span : 0.0;
     if (!std::isfinite(g.scale)) g.scale = 0.0;
   }
-  const int64_t nvec = ((int64_t)g.w + V - 1) / V;
-  int64_t rpb = std::max<int64_t>(((int64_t)g.h * channels + kBlocks - 1) / kBlocks, (kMinSlots + nvec - 1) / nvec);
-  rpb = std::min<int64_t>(rpb, std::max<int64_t>(1, ((int64_t)1 << 31) / nvec));  // a chunk's slots are counted in 32 bits
-  rpb = std::min<int64_t>(rpb, std::max<int64_t>(1, (((int64_t)1 << 32) - 1) / g.w));  // ... and its pixels, in an LDS bin
-  rpb = std::min<int64_t>(rpb, g.h);
-  const int64_t nchunks = ((int64_t)g.h + rpb - 1) / rpb;
-  const int64_t grid = nchunks * channels;
-  if (grid > INT32_MAX) return fra_internal_set_error(FRA_E_INVALID, "the raster is too large for one statistics call");
-  g.nvec = (uint32_t)nvec, g.rpb = (uint32_t)rpb, g.nchunks = (uint32_t)nchunks;
-  g.step_rows = (uint32_t)(256 / nvec), g.step_vecs = (uint32_t)(256 % nvec);
+  // (a chunk's slots are counted in 32 bits, and its pixels in an LDS bin)
+  if (const int rc = plan_chunks(&g.plan, V, h, w, channels, (int64_t)1 << 31, ((int64_t)1 << 32) - 1, "statistics call"))
+    return rc;
+  const unsigned grid = g.plan.grid;
   HIPCHK(sc.alloc(&g.partials, (size_t)grid * sizeof(Partial)));
   HIPCHK(sc.alloc(&g.bands, (size_t)channels * sizeof(fra_stats_band)));
   const size_t hist_bytes = (size_t)channels * (size_t)o.bins * sizeof(uint64_t);
@@ -523,7 +441,7 @@ int run_stats(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
       [&]() -> int {
         {
           const size_t lds = fused ? window(0) : 0;
-          launch_dtype(dtype, 1, fused ? hmode : 0, (unsigned)grid, lds, s, g);
+          launch_dtype(dtype, 1, fused ? hmode : 0, grid, lds, s, g);
           HIPCHK(hipGetLastError());
         }
         hipLaunchKernelGGL(k_stats_fold, dim3((unsigned)channels), dim3(256), 0, s, g, (int32_t)is_float, (int32_t)fused);
@@ -532,7 +450,7 @@ int run_stats(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
         // and once more per further window of bins, for its counts alone
         for (int bin0 = fused ? kLdsBins : 0; bin0 == 0 ? second : bin0 < o.bins; bin0 += kLdsBins) {
           const size_t lds = hmode ? window(bin0) : 0;
-          launch_dtype(dtype, 2, hmode, (unsigned)grid, lds, s, g);
+          launch_dtype(dtype, 2, hmode, grid, lds, s, g);
           HIPCHK(hipGetLastError());
           if (bin0 == 0) {
             hipLaunchKernelGGL(k_stats_fold2, dim3((unsigned)channels), dim3(256), 0, s, g, (int32_t)is_float);
@@ -547,13 +465,6 @@ int run_stats(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
         if (o.bins > 0) HIPCHK(hipMemcpyAsync(hist, g.hist, hist_bytes, hipMemcpyDeviceToHost, s));
         return FRA_OK;
       });
-}
-
-int too_many_pixels(int64_t h, int64_t w) {
-  if (h * w <= kMaxPixels) return FRA_OK;
-  return fra_internal_set_error(FRA_E_INVALID,
-                                "more than 2^32 pixels per band (%lld x %lld) are not described in one call", (long long)h,
-                                (long long)w);
 }
 
 int check_opts(const fra_stats_opts* o, const uint64_t* hist) {
@@ -584,7 +495,7 @@ FRA_API int fra_stats(fra_ctx* ctx, const fra_stats_job* job, fra_stats_band* ba
   const Strides ss{job->band_stride, job->row_stride, job->col_stride};
   const int32_t ch = job->channels, h = job->height, w = job->width;
   if (const int rc = check_raster(job->dtype, ch, h, w, ss, ss)) return rc;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   if (const int rc = check_opts(&job->opts, hist)) return rc;
   Call c(ctx);
   const void* d_src = nullptr;
@@ -601,13 +512,11 @@ FRA_API int fra_decode_device_stats(fra_ctx* ctx, const fra_decode_job* job, con
   if (const int rc = check_opts(opts, hist)) return rc;
   if (left_to_window_read_no_dst(job, roi)) return refer_to_window_read(ctx, job, roi, infos, true);
   const int32_t h = roi->height, w = roi->width;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   if (const int rc = check_cover(job, roi)) return rc;
-  Call c(ctx);
-  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
-  int64_t rs = 0;
-  if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
-  return run_stats(c, job->dst_dtype, job->channels, h, w, d_region, Strides{(int64_t)h * rs, rs, 1}, *opts, bands, hist);
+  return run_region_src(ctx, job, roi, infos, [&](Call& c, const void* d_region, const Strides& ss) {
+    return run_stats(c, job->dst_dtype, job->channels, h, w, d_region, ss, *opts, bands, hist);
+  });
 }
 
 }  // extern "C"

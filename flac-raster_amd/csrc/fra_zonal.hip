@@ -5,13 +5,13 @@
 // integer dtype; a pixel belongs to zone k = z - zone_lo when 0 <= k < nzones (and z is not the ignored label), else it
 // is outside; one record per (band, zone) with the counts, extremes and sums of fra_stats over the zone's pixels.
 //
-// k_zonal<T, Z, PASS>: the chunks, the load choice (for each raster separately) and the pipelined loads of k_stats: a
+// k_zonal<T, Z, PASS>: the chunks and the slot loads of fra_scan.h (the load choice for each raster separately): a
 // workgroup is one (band, chunk of rows), a slot is V = 16 / sizeof(T) pixels, the values as one 16-byte load and their
 // V zone labels as one load of V * sizeof(Z) bytes (in 16-byte pieces) where the raster allows it, element by element
 // otherwise, the next slot in flight while this one is accumulated.  The threads lie on neighbouring slots of a row
 // (256 of them, or on several rows of a narrow raster), and each walks down the chunk's rows in its column of slots
-// before it moves 256 slots on: unlike k_stats' row-major walk this keeps a thread inside one zone for as long as the
-// zone goes on downwards.  The zone raster is read once per (band, chunk) workgroup, so `channels` times per launch; a
+// before it moves 256 slots on: unlike the row-major walk of fra_scan.h this keeps a thread inside one zone for as long
+// as the zone goes on downwards.  The zone raster is read once per (band, chunk) workgroup, so `channels` times per launch; a
 // workgroup over all bands of a chunk would need channels tables in LDS.
 //   Runs.  A thread merges the neighbouring pixels of one zone in registers (counts, sum, sq, min, max) and touches
 //   shared state once per run; a run goes on from one slot of the thread to its next, so a constant zone raster costs
@@ -57,6 +57,7 @@
 #include "../../include/flac_raster_amd.h"
 #include "fra_host.h"
 #include "fra_region.h"
+#include "fra_scan.h"
 
 static_assert(sizeof(fra_zonal_rec) == 112, "fra_zonal_rec is 112 bytes");
 static_assert(sizeof(fra_zonal_opts) == 32, "fra_zonal_opts is 32 bytes");
@@ -85,7 +86,7 @@ struct ZonalArgs {
   int64_t zone_lo, ignore_zone;
   double nodata;
   int32_t h, w;
-  uint32_t nvec, rpb, nchunks;  // slots per row, rows per workgroup, workgroups per band: as k_stats
+  ChunkPlan plan;               // (its row-major steps are not used: the column walk below)
   uint32_t cols, rstep;         // a workgroup's threads lie on `rstep` rows of `cols` neighbouring slots: cols x rstep <= 256
   int32_t vec, zvec;  // aligned 16-byte loads of the values / aligned vector loads of the zones
   int32_t flags, nzones;
@@ -120,18 +121,7 @@ struct Run {
   u64 sqa = 0, sqb = 0;
   M mn = 0, mx = 0;    // of the valid pixels (set by the first)
   double mean = 0.0;   // pass 2
-  M nd = 0;
-  bool use_nd = false;
-
-  __device__ inline void set_nodata(int flags, double v) {
-    if (!(flags & FRA_ZONAL_NODATA)) return;
-    if constexpr (FLT) {
-      use_nd = v == v, nd = v;
-    } else {  // (double)x == v only for an integral v inside T's range
-      use_nd = v >= (double)std::numeric_limits<T>::lowest() && v <= (double)std::numeric_limits<T>::max() && v == floor(v);
-      nd = use_nd ? (M)v : (M)0;
-    }
-  }
+  Nodata<T> nodata_of;
 
   __device__ inline void flush() {
     if (cur == ~0u) return;
@@ -172,7 +162,7 @@ struct Run {
         return;
       }
     }
-    if (use_nd && x == nd) {
+    if (nodata_of.is(x)) {
       nodata++;
       return;
     }
@@ -200,15 +190,14 @@ __global__ void __launch_bounds__(256) k_zonal(ZonalArgs g) {
   constexpr int V = 16 / (int)sizeof(T);
   constexpr bool FLT = std::is_floating_point<T>::value;
   static_assert(PASS == 1 || FLT, "the second pass is the floats'");
-  struct alignas(16) Vec { T v[V]; };
+  using Vec = VecOf<T, V>;
   using ZVec = VecOf<Z, V>;
   extern __shared__ u64 s_tab[];  // pass 1: kWords x nwin; pass 2: fm2 and the mean, 2 x nwin
-  const uint32_t chunk = blockIdx.x % g.nchunks;
-  const int64_t band = (int64_t)(blockIdx.x / g.nchunks);
-  const int64_t row0 = (int64_t)chunk * g.rpb;
-  const uint32_t rows = (uint32_t)min((int64_t)g.rpb, (int64_t)g.h - row0);
-  const T* __restrict__ ps = (const T*)g.src + (band * g.bs + row0 * g.rs);
-  const Z* __restrict__ pz = (const Z*)g.zones + row0 * g.zrs;
+  const Chunk c = chunk_of(g.plan, g.h, blockIdx.x);
+  const int64_t band = c.band;
+  const uint32_t chunk = c.chunk, rows = c.rows;
+  const T* __restrict__ ps = (const T*)g.src + (band * g.bs + c.row0 * g.rs);
+  const Z* __restrict__ pz = (const Z*)g.zones + c.row0 * g.zrs;
   const bool vec = g.vec != 0, zvec = g.zvec != 0;
   // the window of this launch: `wcap` zones from the chunk's smallest zone on, cut at its largest.  A window that no
   // zone of the chunk reaches has nothing to add: the whole workgroup leaves before it reads a pixel
@@ -227,31 +216,9 @@ __global__ void __launch_bounds__(256) k_zonal(ZonalArgs g) {
 
   Run<T, PASS> run;
   run.tab = s_tab, run.nwin = nwin;
-  run.set_nodata(g.flags, g.nodata);
+  run.nodata_of.set((g.flags & FRA_ZONAL_NODATA) != 0, g.nodata);
   const bool ignore = (g.flags & FRA_ZONAL_IGNORE) != 0;
 
-  // slot (row, cv) of the chunk: pixels [cv V, cv V + n) of its row
-  auto count = [&](uint32_t cv) { return (int)min((int64_t)V, (int64_t)g.w - (int64_t)cv * V); };
-  auto load = [&](const T* p, int n) {
-    Vec v;
-    if (vec && n == V) {
-      v = *(const Vec*)p;
-    } else {
-#pragma unroll
-      for (int i = 0; i < V; i++) v.v[i] = i < n ? p[(int64_t)i * g.cs] : (T)0;
-    }
-    return v;
-  };
-  auto loadz = [&](const Z* p, int n) {
-    ZVec v;
-    if (zvec && n == V) {
-      v = *(const ZVec*)p;
-    } else {
-#pragma unroll
-      for (int i = 0; i < V; i++) v.v[i] = i < n ? p[(int64_t)i * g.zcs] : (Z)0;
-    }
-    return v;
-  };
   auto slot = [&](const Vec& x, const ZVec& z, int n) {
 #pragma unroll
     for (int i = 0; i < V; i++) {
@@ -273,24 +240,21 @@ __global__ void __launch_bounds__(256) k_zonal(ZonalArgs g) {
   Vec nx{};
   ZVec nz{};
   int nn = 0;
+  auto issue = [&]() {  // the loads of slot (row, cv) of the chunk: pixels [cv V, cv V + nn) of its row
+    nn = slot_count<V>(g.w, cv);
+    nx = load_slot<T, V>(ps + ((int64_t)row * g.rs + (int64_t)cv * V * g.cs), g.cs, vec, nn);
+    nz = load_slot<Z, V>(pz + ((int64_t)row * g.zrs + (int64_t)cv * V * g.zcs), g.zcs, zvec, nn);
+  };
   bool have = rl < g.rstep && rl < rows;
-  if (have) {
-    nn = count(cv);
-    nx = load(ps + ((int64_t)row * g.rs + (int64_t)cv * V * g.cs), nn);
-    nz = loadz(pz + ((int64_t)row * g.zrs + (int64_t)cv * V * g.zcs), nn);
-  }
+  if (have) issue();
   while (have) {
     const Vec cx = nx;
     const ZVec cz = nz;
     const int cn = nn;
     row += g.rstep;
     if (row >= rows) row = rl, cv += g.cols;
-    have = cv < g.nvec;
-    if (have) {  // in flight while the current slot is accumulated
-      nn = count(cv);
-      nx = load(ps + ((int64_t)row * g.rs + (int64_t)cv * V * g.cs), nn);
-      nz = loadz(pz + ((int64_t)row * g.zrs + (int64_t)cv * V * g.zcs), nn);
-    }
+    have = cv < g.plan.nvec;
+    if (have) issue();  // in flight while the current slot is accumulated
     slot(cx, cz, cn);
   }
   run.flush();      // a run goes on from one slot of the thread to its next: a constant zone raster, one update per thread
@@ -330,9 +294,9 @@ __global__ void __launch_bounds__(256) k_zonal_range(ZonalArgs g, uint2* ranges,
   __shared__ uint32_t s_min, s_max;
   __shared__ u64 s_out;
   const uint32_t chunk = blockIdx.x / parts, part = blockIdx.x % parts;
-  const int64_t row0 = (int64_t)chunk * g.rpb;
-  const uint32_t rows = (uint32_t)min((int64_t)g.rpb, (int64_t)g.h - row0);
-  const Z* __restrict__ pz = (const Z*)g.zones + row0 * g.zrs;
+  const Chunk c = chunk_at(g.plan, g.h, chunk);
+  const uint32_t rows = c.rows;
+  const Z* __restrict__ pz = (const Z*)g.zones + c.row0 * g.zrs;
   const bool ignore = (g.flags & FRA_ZONAL_IGNORE) != 0, zvec = g.zvec != 0;
   if (threadIdx.x == 0) s_min = ~0u, s_max = 0, s_out = 0;
   __syncthreads();
@@ -341,15 +305,8 @@ __global__ void __launch_bounds__(256) k_zonal_range(ZonalArgs g, uint2* ranges,
   u64 out = 0;
   for (u64 idx = (u64)part * 256 + threadIdx.x; idx < total; idx += (u64)parts * 256) {
     const u64 r = idx / nvz, cv = idx % nvz;
-    const int n = (int)min((int64_t)VZ, (int64_t)g.w - (int64_t)cv * VZ);
-    const Z* p = pz + ((int64_t)r * g.zrs + (int64_t)cv * VZ * g.zcs);
-    ZVec v;
-    if (zvec && n == VZ) {
-      v = *(const ZVec*)p;
-    } else {
-#pragma unroll
-      for (int i = 0; i < VZ; i++) v.v[i] = i < n ? p[(int64_t)i * g.zcs] : (Z)0;
-    }
+    const int n = slot_count<VZ>(g.w, (uint32_t)cv);
+    const ZVec v = load_slot<Z, VZ>(pz + ((int64_t)r * g.zrs + (int64_t)cv * VZ * g.zcs), g.zcs, zvec, n);
 #pragma unroll
     for (int i = 0; i < VZ; i++) {
       if (i < n) {
@@ -419,9 +376,7 @@ __global__ void __launch_bounds__(256) k_zonal_finish(const u64* table, const u6
 
 thread_local float g_zonal_ms = 0.f;
 
-constexpr int64_t kMaxPixels = (int64_t)1 << 32;  // per band: the integer sums stay inside 64 and 96 bits
-constexpr int64_t kBlocks = 4096;                 // workgroups aimed at: 16 per CU
-constexpr int64_t kMinSlots = 1024;               // slots of a workgroup, at least (4 per thread), rows permitting
+constexpr const char* kNot = "described in one zonal call";  // (too_many_pixels)
 constexpr int64_t kMaxRecords = (int64_t)1 << 24;  // (band, zone) records of a call: a table of 1 GiB
 
 template <typename T, typename Z>
@@ -457,15 +412,11 @@ int run_zonal(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
   const bool is_signed = dtype == FRA_I8 || dtype == FRA_I16 || dtype == FRA_I32;
   g.vec = aligned16(d_src, ss, es);
   g.zvec = aligned16(d_zones, Strides{0, zrs, zcs}, zes);
-  const int64_t nvec = ((int64_t)g.w + V - 1) / V;
-  int64_t rpb = std::max<int64_t>(((int64_t)g.h * channels + kBlocks - 1) / kBlocks, (kMinSlots + nvec - 1) / nvec);
-  rpb = std::min<int64_t>(rpb, std::max<int64_t>(1, ((int64_t)1 << 31) / nvec));  // a chunk's slots are counted in 32 bits
-  rpb = std::min<int64_t>(rpb, g.h);
-  const int64_t nchunks = ((int64_t)g.h + rpb - 1) / rpb;
-  const int64_t grid = nchunks * channels;
-  if (grid > INT32_MAX) return fra_internal_set_error(FRA_E_INVALID, "the raster is too large for one zonal call");
-  g.nvec = (uint32_t)nvec, g.rpb = (uint32_t)rpb, g.nchunks = (uint32_t)nchunks;
-  g.cols = (uint32_t)std::min<int64_t>(nvec, 256), g.rstep = 256 / g.cols;
+  // (a chunk's slots are counted in 32 bits)
+  if (const int rc = plan_chunks(&g.plan, V, h, w, channels, (int64_t)1 << 31, 0, "zonal call")) return rc;
+  const unsigned grid = g.plan.grid;
+  const int64_t nchunks = g.plan.nchunks;
+  g.cols = std::min<uint32_t>(g.plan.nvec, 256), g.rstep = 256 / g.cols;
   const uint32_t entries = (uint32_t)channels * (uint32_t)o.nzones;  // (checked: too_many_records)
   HIPCHK(sc.alloc(&g.table, (size_t)entries * kWords * sizeof(u64)));
   u64* d_misc = nullptr;  // the pixels outside every zone
@@ -494,7 +445,7 @@ int run_zonal(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
         // widest chunk could need; in the others its workgroups leave at once
         g.wcap = std::min(kLdsZones, o.nzones);
         for (g.wini = 0; g.wini * kLdsZones < o.nzones; g.wini++) {
-          launch_dtypes(dtype, zdtype, 1, (unsigned)grid, (size_t)g.wcap * kWords * sizeof(u64), s, g);
+          launch_dtypes(dtype, zdtype, 1, grid, (size_t)g.wcap * kWords * sizeof(u64), s, g);
           HIPCHK(hipGetLastError());
         }
         if (is_float) {
@@ -502,7 +453,7 @@ int run_zonal(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
           HIPCHK(hipGetLastError());
           g.wcap = std::min(kLdsZones2, o.nzones);
           for (g.wini = 0; g.wini * kLdsZones2 < o.nzones; g.wini++) {
-            launch_dtypes(dtype, zdtype, 2, (unsigned)grid, (size_t)g.wcap * 2 * sizeof(u64), s, g);
+            launch_dtypes(dtype, zdtype, 2, grid, (size_t)g.wcap * 2 * sizeof(u64), s, g);
             HIPCHK(hipGetLastError());
           }
         }
@@ -516,13 +467,6 @@ int run_zonal(Call& c, int dtype, int channels, int32_t h, int32_t w, const void
         HIPCHK(hipMemcpyAsync(outside, d_outside, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         return FRA_OK;
       });
-}
-
-int too_many_pixels(int64_t h, int64_t w) {
-  if (h * w <= kMaxPixels) return FRA_OK;
-  return fra_internal_set_error(FRA_E_INVALID,
-                                "more than 2^32 pixels per band (%lld x %lld) are not described in one zonal call",
-                                (long long)h, (long long)w);
 }
 
 int too_many_records(int64_t channels, int64_t nzones) {
@@ -565,7 +509,7 @@ FRA_API int fra_zonal(fra_ctx* ctx, const fra_zonal_job* job, fra_zonal_rec* rec
   if (const int rc = check_raster(job->dtype, ch, h, w, ss, ss)) return rc;
   if (const int rc = check_zones(job->zone_dtype, job->zone_row_stride, job->zone_col_stride)) return rc;
   if (const int rc = check_opts(&job->opts)) return rc;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   if (const int rc = too_many_records(ch, job->opts.nzones)) return rc;
   Call c(ctx);
   const void *d_src = nullptr, *d_zones = nullptr;
@@ -589,19 +533,17 @@ FRA_API int fra_decode_device_zonal(fra_ctx* ctx, const fra_decode_job* job, con
   if (const int rc = check_opts(opts)) return rc;
   if (left_to_window_read_no_dst(job, roi)) return refer_to_window_read(ctx, job, roi, infos, true);
   const int32_t h = roi->height, w = roi->width;
-  if (const int rc = too_many_pixels(h, w)) return rc;
+  if (const int rc = too_many_pixels(h, w, kNot)) return rc;
   if (const int rc = check_cover(job, roi)) return rc;
-  Call c(ctx);
-  void* d_region = nullptr;  // the region at full resolution: band-planar, in dst_dtype, rows on 16-byte boundaries
-  int64_t rs = 0;
-  if (const int rc = decode(ctx, job, roi, infos, c.sc, &d_region, &rs)) return rc;
-  const Strides zs{0, zone_row_stride, zone_col_stride};
-  const void* d_zones = nullptr;
-  if (const int rc = stage_in(c, zones, zones_on_device, (size_t)extent_of(1, h, w, zs) * (size_t)elem_size(zone_dtype),
-                              &d_zones))
-    return rc;
-  return run_zonal(c, job->dst_dtype, job->channels, h, w, d_region, Strides{(int64_t)h * rs, rs, 1}, zone_dtype, d_zones,
-                   zs.row, zs.col, *opts, recs, outside);
+  return run_region_src(ctx, job, roi, infos, [&](Call& c, const void* d_region, const Strides& ss) -> int {
+    const Strides zs{0, zone_row_stride, zone_col_stride};
+    const void* d_zones = nullptr;
+    if (const int rc = stage_in(c, zones, zones_on_device, (size_t)extent_of(1, h, w, zs) * (size_t)elem_size(zone_dtype),
+                                &d_zones))
+      return rc;
+    return run_zonal(c, job->dst_dtype, job->channels, h, w, d_region, ss, zone_dtype, d_zones, zs.row, zs.col, *opts, recs,
+                     outside);
+  });
 }
 
 }  // extern "C"

@@ -131,6 +131,28 @@ def test_programs_shapes_and_output_dtypes(dt):
         assert ctx.calc_timing() >= 0.0
 
 
+# A thread's way from one of its slots to the next, 256 slots on in row-major order, at its two corners.  (3, 4113): more
+# than 256 slots of 8 pixels per row (no whole row in a step), the last slot of a row holds 1 pixel.  (5, 511): 64 slots
+# per row (a step is four rows, no slots) and a short last slot.
+CURSOR_SHAPES = [(3, 4113), (5, 511)]
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
+def test_rows_of_more_than_256_slots_and_whole_row_steps(dt):
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(350 + dt.num)
+    ctx = _ctx()
+    prog = compile_exprs(["b1", "b1 + b2"], B)
+    for (h, w) in CURSOR_SHAPES:
+        a = _raster(dt, (B, h, w), rng)
+        av = _padded(a, 6)[1]  # rows of an odd number of elements: element loads
+        assert av.strides[1] % 16
+        for odt in (dt, np.float64):
+            want, _ = calc_arrays(a, prog, odt)
+            _same(ctx.calc(a, prog, odt)[0], want, f"{dt} {(h, w)} -> {np.dtype(odt)}")  # contiguous
+            _same(ctx.calc(av, prog, odt)[0], want, f"{dt} {(h, w)} padded -> {np.dtype(odt)}")
+
+
 def test_ndvi_with_zero_denominators():
     ctx = _ctx()
     rng = np.random.default_rng(5)

@@ -160,6 +160,29 @@ def test_kernel_alone_equals_the_numpy_rule(dt):
             ctx.free(d_b)
 
 
+# A thread's way from one of its slots to the next, 256 slots on in row-major order, at its two corners.  (3, 4113): more
+# than 256 slots per row for every element size (no whole row in a step), the last slot of a row holds 1 element (1 of 2
+# for f64).  (5, 511): exactly 256 slots per row for f64 (a step is one row, no slots), 128 for f32 (two rows), and a
+# short last slot for every dtype.
+CURSOR_SHAPES = [(3, 4113), (5, 511)]
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
+def test_rows_of_more_than_and_exactly_256_slots(dt):
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(250 + dt.num)
+    ctx = _ctx()
+    for (h, w) in CURSOR_SHAPES:
+        a = _raster(dt, (B, h, w), rng)
+        b = _other(a, rng)
+        if dt.kind == "f":
+            a[0, 0, 1] = b[0, 0, 1] = a[1, h - 1, 2] = b[2, h // 2, w - 1] = np.nan
+        _check(ctx.compare(a, b), a, b)  # contiguous
+        av, bv = _padded(a, 6)[1], _padded(b, 6)[1]  # rows of an odd number of elements: element loads
+        assert av.strides[1] % 16 and bv.strides[1] % 16
+        _check(ctx.compare(av, bv), a, b)
+
+
 @pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
 def test_identical_single_and_misordered_differences(dt):
     dt = np.dtype(dt)

@@ -188,6 +188,30 @@ def test_kernel_alone_equals_the_numpy_rule(dt):
             ctx.free(d_a)
 
 
+# A thread's way from one of its slots to the next, 256 slots on in row-major order, at its two corners.  (3, 4113): more
+# than 256 slots per row for every element size (no whole row in a step), the last slot of a row holds 1 element (1 of 2
+# for f64).  (5, 511): exactly 256 slots per row for f64 (a step is one row, no slots), 128 for f32 (two rows), and a
+# short last slot for every dtype.
+CURSOR_SHAPES = [(3, 4113), (5, 511)]
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
+def test_rows_of_more_than_and_exactly_256_slots(dt):
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(550 + dt.num)
+    ctx = _ctx()
+    for (h, w) in CURSOR_SHAPES:
+        a = _raster(dt, (B, h, w), rng)
+        if dt.kind == "f":
+            a[0, 0, 1] = a[1, h - 1, 2] = a[2, h // 2, w - 1] = np.nan
+        av = _padded(a, 6)[1]  # rows of an odd number of elements: element loads
+        assert av.strides[1] % 16
+        for bins, r in [(0, None)] + _ranges(a, 256)[:2]:  # no histogram; 256 bins over an explicit and the automatic range
+            want = Want(a, bins, r)
+            _check(ctx.stats(a, bins, r), want)  # contiguous
+            _check(ctx.stats(av, bins, r), want, printed_alike=False)
+
+
 # ------------------------------------------------------------------------------- 2. specials
 @pytest.mark.parametrize("dt", [np.float32, np.float64], ids=lambda d: np.dtype(d).name)
 def test_float_specials(dt):

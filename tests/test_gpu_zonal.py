@@ -172,6 +172,34 @@ def test_kernel_alone_equals_the_numpy_rule(dt):
                 assert ctx.zonal_timing() >= 0.0
 
 
+# Rows of many slots, at the two corners of the chunk arithmetic that the units over a raster share.  (3, 4113): more
+# than 256 slots per row for every element size, the last slot of a row holds 1 element (1 of 2 for f64).  (5, 511):
+# exactly 256 slots per row for f64, 128 for f32, and a short last slot for every dtype.  One value dtype per element
+# size (both of four bytes).
+CURSOR_SHAPES = [(3, 4113), (5, 511)]
+
+
+@pytest.mark.parametrize("dt", [np.uint8, np.int16, np.int32, np.float32, np.float64], ids=lambda d: np.dtype(d).name)
+def test_rows_of_more_than_and_exactly_256_slots(dt):
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(750 + dt.num)
+    ctx = _ctx()
+    lo, nz = -2, 7
+    for shape in CURSOR_SHAPES:
+        h, w = shape
+        a = _raster(dt, (B,) + shape, rng)
+        if dt.kind == "f":
+            a[0, 0, 1] = a[1, h - 1, 2] = a[2, h // 2, w - 1] = np.nan
+        nd = float(a[1, h // 2, w // 3])  # (not one of the NaNs)
+        zones = rng.integers(lo - 1, lo + nz + 1, shape).astype(np.int16)  # a label below and one above the zones
+        zones[:, w // 2:w // 2 + 300] = lo + 3                              # and a run over many slots of every row
+        want = zonal_arrays(a, zones, lo, nz, nd, lo + 5)
+        _check(ctx.zonal(a, zones, lo, nz, nd, lo + 5), a, zones, lo, nz, nd, lo + 5, want)  # contiguous
+        av, zv = _padded(a, 6, 77)[1], _padded(zones, 3, lo + 2)[1]  # rows of both that are not 16-byte aligned
+        assert av.strides[1] % 16 and zv.strides[0] % 16
+        _check(ctx.zonal(av, zv, lo, nz, nd, lo + 5), a, zones, lo, nz, nd, lo + 5, want)
+
+
 @pytest.mark.parametrize("nz", NZONES)
 def test_zone_counts_across_the_windows(nz):
     """Zone counts on both sides of the LDS window of the first pass (integers), the populated zones in every window,

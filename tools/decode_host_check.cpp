@@ -16,6 +16,7 @@
 //     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
 //     fra_focal_check) and the zonal statistics (fra_zonal, fra_decode_device_zonal), which returns before any GPU
 //     work, and the order of these refusals (inputs that break two rules at once).
+//   * the chunk arithmetic of the row-chunk scan (fra_scan.h plan_chunks): invariants and pinned values.
 // usage: decode_host_check [--concat] file.flac ...
 #include <cmath>
 #include <cstdarg>
@@ -26,6 +27,7 @@
 
 #include "../flac-raster_amd/csrc/fra_decode.cpp"  // the host decoder's frame validation (internal linkage)
 #include "../flac-raster_amd/csrc/fra_decode_host.h"
+#include "../flac-raster_amd/csrc/fra_scan.h"
 
 static std::string g_msg;
 extern "C" int fra_internal_set_error(int code, const char* fmt, ...) {
@@ -934,6 +936,53 @@ int main(int argc, char** argv) {
   }
   printf("argument validation checked\n");
 #endif
+  // the chunk arithmetic of the row-chunk scan (fra_scan.h plan_chunks): its invariants over every element size and a
+  // set of shapes (one slot, short last slots, more than 256 slots per row, one column, 2^32 pixels, the benchmark
+  // scene), as the reducing units call it (slots of 16 bytes, with and without the statistics' pixel cap) and as the
+  // band math does (slots of 4 and 8 pixels, one band), and pinned values
+  {
+    using fra_region::ChunkPlan;
+    using fra_region::plan_chunks;
+    struct Shape { int64_t h, w, bands; };
+    const Shape shapes[] = {{1, 1, 1}, {5, 511, 1}, {3, 4113, 1}, {130, 517, 1}, {(int64_t)1 << 20, 1, 1}, {65536, 65536, 1},
+                            {10980, 10980, 4}};
+    auto check = [&](int64_t V, const Shape& s, int64_t bands, int64_t slot_cap, int64_t pixel_cap) {
+      ChunkPlan p{};
+      EXPECT(plan_chunks(&p, V, s.h, s.w, bands, slot_cap, pixel_cap, "check") == FRA_OK, "plan V %lld %lld x %lld refused: %s",
+             (long long)V, (long long)s.h, (long long)s.w, g_msg.c_str());
+      const int64_t nvec = p.nvec, rpb = p.rpb, nchunks = p.nchunks;
+      const bool ok = nvec == (s.w + V - 1) / V && rpb >= 1 && (nchunks - 1) * rpb < s.h && s.h <= nchunks * rpb &&
+                      rpb * nvec <= slot_cap && (!pixel_cap || rpb * s.w <= pixel_cap) &&
+                      (int64_t)p.step_rows * nvec + p.step_vecs == 256 && (int64_t)p.step_vecs < nvec &&
+                      (int64_t)p.grid == nchunks * bands;
+      EXPECT(ok, "plan V %lld %lld x %lld x %lld cap %lld / %lld: nvec %u rpb %u nchunks %u step %u + %u grid %u", (long long)V,
+             (long long)s.h, (long long)s.w, (long long)bands, (long long)slot_cap, (long long)pixel_cap, p.nvec, p.rpb, p.nchunks,
+             p.step_rows, p.step_vecs, p.grid);
+    };
+    for (int64_t es : {1, 2, 4, 8})
+      for (const Shape& s : shapes) {
+        check(16 / es, s, s.bands, (int64_t)1 << 31, 0);
+        check(16 / es, s, s.bands, (int64_t)1 << 31, ((int64_t)1 << 32) - 1);
+      }
+    for (int64_t P : {4, 8})
+      for (const Shape& s : shapes) check(P, s, 1, (int64_t)1 << 29, 0);
+    auto pin = [&](const char* what, int64_t V, const Shape& s, int64_t slot_cap, int64_t pixel_cap, ChunkPlan want) {
+      ChunkPlan p{};
+      plan_chunks(&p, V, s.h, s.w, s.bands, slot_cap, pixel_cap, "check");
+      EXPECT(p.nvec == want.nvec && p.rpb == want.rpb && p.nchunks == want.nchunks && p.step_rows == want.step_rows &&
+                 p.step_vecs == want.step_vecs && p.grid == want.grid,
+             "plan %s: nvec %u rpb %u nchunks %u step %u + %u grid %u", what, p.nvec, p.rpb, p.nchunks, p.step_rows, p.step_vecs,
+             p.grid);
+    };
+    pin("benchmark scene, 2-byte elements", 8, {10980, 10980, 4}, (int64_t)1 << 31, 0, {1373, 11, 999, 0, 256, 3996});
+    pin("3 x 4113, 8-byte elements", 2, {3, 4113, 1}, (int64_t)1 << 31, 0, {2057, 1, 3, 0, 256, 3});
+    pin("2^20 x 1, 4-byte elements", 4, {(int64_t)1 << 20, 1, 1}, (int64_t)1 << 31, 0, {1, 1024, 1024, 256, 0, 1024});
+    pin("65536 x 65536 x 4, 1-byte elements, pixel cap", 16, {65536, 65536, 4}, (int64_t)1 << 31, ((int64_t)1 << 32) - 1,
+        {4096, 64, 1024, 0, 256, 4096});
+    pin("130 x 517, band math with 8 pixels", 8, {130, 517, 1}, (int64_t)1 << 29, 0, {65, 16, 9, 3, 61, 9});
+    { ChunkPlan p{}; EXPECT(plan_chunks(&p, 16, INT32_MAX, 1, 2, 1, 0, "check") == FRA_E_INVALID && g_msg == "the raster is too large for one check", "plan: a grid past INT32_MAX: %s", g_msg.c_str()); }
+    printf("chunk plans checked\n");
+  }
   printf(g_fail ? "%d FAILED\n" : "host check ok\n", g_fail);
   return g_fail ? 1 : 0;
 }
