@@ -1,12 +1,14 @@
 // fra_resample.h -- what the resampling kernels and their hosts share (fra_resample.hip, fra_resample_masked.hip;
 // fra_decimate.hip takes AccOf, log2_factor and check_factor): the kernels' arguments, the device helpers of the rule
 // (include/flac_raster_amd.h: centres, tap weights, the conversion of a result), the refusals of an output size, a
-// resampling code, an average the rule's exact arithmetic does not hold and a decimation factor, and the grid of a
-// launch.  The host scaffold around the kernels is fra_region.h.
+// resampling code, an average the rule's exact arithmetic does not hold, a decimation factor and a nodata value
+// (check_nodata; fra_warp.hip takes it too), and the grid of a launch.  The host scaffold around the kernels is fra_region.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <numeric>
 #include <type_traits>
@@ -114,6 +116,27 @@ inline int check_factor(int32_t h, int32_t w, int32_t factor, int32_t resampling
   a->h = h, a->w = w;
   a->oh = (int32_t)(((int64_t)h + factor - 1) / factor), a->ow = (int32_t)(((int64_t)w + factor - 1) / factor);
   a->hr = a->wr = factor, a->ohr = a->owr = 1;
+  return FRA_OK;
+}
+
+// FRA_E_INVALID unless nd is a nodata value of the dtype (the rule): an integer inside an integer dtype's range; NaN,
+// or finite and exact in a float dtype (`what`: the argument's name in the message)
+inline int check_nodata(double nd, int dtype, const char* what = "nodata") {
+  bool ok;
+  if (dtype == FRA_F64) {
+    ok = std::isnan(nd) || std::isfinite(nd);
+  } else if (dtype == FRA_F32) {
+    ok = std::isnan(nd) || (std::isfinite(nd) && std::fabs(nd) <= (double)FLT_MAX && (double)(float)nd == nd);
+  } else {
+    const int bits = 8 * elem_size(dtype);
+    const bool sgn = dtype == FRA_I8 || dtype == FRA_I16 || dtype == FRA_I32;
+    const double lo = sgn ? -std::ldexp(1.0, bits - 1) : 0.0, hi = std::ldexp(1.0, sgn ? bits - 1 : bits) - 1.0;
+    ok = std::isfinite(nd) && nd == std::floor(nd) && nd >= lo && nd <= hi;
+  }
+  if (!ok)
+    return fra_internal_set_error(FRA_E_INVALID,
+                                  "%s %.17g is not a value of the dtype (an integer in range; for floats NaN, or "
+                                  "finite and exact)", what, nd);
   return FRA_OK;
 }
 

@@ -22,10 +22,10 @@
 // The count of fill outputs per band (optional): summed within each wave by lane exchanges, then one atomicAdd per
 // workgroup into a zeroed array of `channels` 64-bit words; no atomic in a loop.  All indices are 64-bit.
 //
-// This unit holds the kernel, its launch with the fill counts, and the nodata refusal.  Shared with fra_resample.hip
-// (fra_resample.h): MaskedArgs is ResampleArgs and two fields; udiv, centre, tap_weights, from_f64, the refusals of
-// the sizes and of a factor, the grid of a launch (NARROW with the extra h' < 2^16 here only); with all five
-// region-reducing units (fra_region.h): the dtype and layout refusal, what is left to the windowed read, staging, the
+// This unit holds the kernel and its launch with the fill counts.  Shared with fra_resample.hip (fra_resample.h): the
+// nodata refusal (check_nodata, which fra_warp.hip takes too); MaskedArgs is ResampleArgs and two fields; udiv, centre,
+// tap_weights, from_f64, the refusals of the sizes and of a factor, the grid of a launch (NARROW with the extra
+// h' < 2^16 here only); with all five region-reducing units (fra_region.h): the dtype and layout refusal, what is left to the windowed read, staging, the
 // decoded region and the timed launch.
 #include <hip/hip_runtime.h>
 
@@ -318,27 +318,6 @@ void launch_t(int mode, unsigned grid, hipStream_t s, const MaskedArgs& a) {
     case FRA_RESAMPLE_BILINEAR: hipLaunchKernelGGL((k_resample_masked<T, 2>), dim3(grid), dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL((k_resample_masked<T, 3>), dim3(grid), dim3(256), 0, s, a); break;
   }
-}
-
-// FRA_E_INVALID unless nd is a nodata value of the dtype (the rule): an integer inside an integer dtype's range; NaN,
-// or finite and exact in a float dtype
-int check_nodata(double nd, int dtype) {
-  bool ok;
-  if (dtype == FRA_F64) {
-    ok = std::isnan(nd) || std::isfinite(nd);
-  } else if (dtype == FRA_F32) {
-    ok = std::isnan(nd) || (std::isfinite(nd) && std::fabs(nd) <= (double)FLT_MAX && (double)(float)nd == nd);
-  } else {
-    const int bits = 8 * elem_size(dtype);
-    const bool sgn = dtype == FRA_I8 || dtype == FRA_I16 || dtype == FRA_I32;
-    const double lo = sgn ? -std::ldexp(1.0, bits - 1) : 0.0, hi = std::ldexp(1.0, sgn ? bits - 1 : bits) - 1.0;
-    ok = std::isfinite(nd) && nd == std::floor(nd) && nd >= lo && nd <= hi;
-  }
-  if (!ok)
-    return fra_internal_set_error(FRA_E_INVALID,
-                                  "nodata %.17g is not a value of the dtype (an integer in range; for floats NaN, or "
-                                  "finite and exact)", nd);
-  return FRA_OK;
 }
 
 // k_resample_masked over `io`, timed, the fill counts into `filled` (host, channels words; may be null) and the

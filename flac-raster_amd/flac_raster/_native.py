@@ -191,6 +191,27 @@ class FocalJob(C.Structure):
     ]
 
 
+class WarpMap(C.Structure):
+    """``fra_warp_map`` (80 bytes; the rule: ``warp.py``)."""
+
+    _fields_ = [("kind", C.c_int32), ("step", C.c_int32), ("gh", C.c_int32), ("gw", C.c_int32),
+                ("affine", C.c_double * 6), ("gx", C.POINTER(C.c_double)), ("gy", C.POINTER(C.c_double))]
+
+
+class WarpJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("src_band_stride", C.c_int64), ("src_row_stride", C.c_int64),
+        ("src_col_stride", C.c_int64), ("out_height", C.c_int32), ("out_width", C.c_int32), ("resampling", C.c_int32),
+        ("flags", C.c_int32), ("dst", C.c_void_p), ("dst_on_device", C.c_int32), ("dst_band_stride", C.c_int64),
+        ("dst_row_stride", C.c_int64), ("dst_col_stride", C.c_int64), ("nodata", C.c_double), ("fill", C.c_double),
+        ("map", WarpMap),
+    ]
+
+
+assert C.sizeof(WarpMap) == 80 and C.sizeof(WarpJob) == 208
+
+
 class ZonalOpts(C.Structure):
     _fields_ = [("flags", C.c_int32), ("nzones", C.c_int32), ("zone_lo", C.c_int64), ("ignore_zone", C.c_int64),
                 ("nodata", C.c_double)]
@@ -221,6 +242,8 @@ assert C.sizeof(ZonalRec) == 112 and C.sizeof(ZonalOpts) == 32 and C.sizeof(Zona
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 ZONAL_NODATA, ZONAL_IGNORE = 1, 2
 CALC_NODATA = 1
+WARP_AFFINE, WARP_GRID = 0, 1
+WARP_NODATA = 1
 DECODE_CONCAT = 1
 RESAMPLE_NEAREST, RESAMPLE_AVERAGE = 0, 1
 RESAMPLE_BILINEAR, RESAMPLE_CUBIC = 2, 3
@@ -278,6 +301,7 @@ EXPORTS = [
     "fra_calc_check", "fra_calc", "fra_decode_device_calc", "fra_calc_timing",
     "fra_focal_check", "fra_focal", "fra_decode_device_focal", "fra_focal_timing",
     "fra_zonal", "fra_decode_device_zonal", "fra_zonal_timing",
+    "fra_warp", "fra_decode_device_warped", "fra_warp_source_window", "fra_warp_timing", "fra_warp_paths",
 ]
 
 
@@ -391,6 +415,13 @@ def load():
                                                   C.c_int64, C.POINTER(ZonalOpts), vp, C.POINTER(u64),
                                                   C.POINTER(Decoded)]
             L.fra_zonal_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_warp"):
+            L.fra_warp.argtypes = [vp, C.POINTER(WarpJob), C.POINTER(u64)]
+            L.fra_decode_device_warped.argtypes = [vp, C.POINTER(DecodeJob), i32, i32, C.POINTER(WarpMap), i32, i32, i32,
+                                                   i32, C.c_double, C.c_double, C.POINTER(Decoded), C.POINTER(u64)]
+            L.fra_warp_source_window.argtypes = [C.POINTER(WarpMap), i32, i32, i32, i32, C.POINTER(Window)]
+            L.fra_warp_timing.argtypes = [C.POINTER(C.c_float)]
+            L.fra_warp_paths.argtypes = [C.POINTER(u64)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -469,6 +500,47 @@ def focal_check(spec) -> None:
     code: no GPU is needed."""
     s = focal_spec(spec)
     _check(load().fra_focal_check(C.byref(s)))
+
+
+def warp_map(m) -> Tuple[WarpMap, list]:
+    """The ``fra_warp_map`` of a ``warp.Map`` as it is -- nothing is checked here: the library is the one that refuses
+    -- and what it points into, which must outlive the call."""
+    w = WarpMap()
+    w.kind, w.step = int(m.kind), int(m.step)
+    for k, v in enumerate(tuple(m.affine)[:6]):
+        w.affine[k] = float(v)
+    keep = []
+    if m.gx is not None and m.gy is not None:
+        gx, gy = np.ascontiguousarray(m.gx, dtype=np.float64), np.ascontiguousarray(m.gy, dtype=np.float64)
+        keep += [gx, gy]
+        w.gh, w.gw = (int(v) for v in gx.shape) if gx.ndim == 2 else (0, 0)
+        w.gx, w.gy = gx.ctypes.data_as(C.POINTER(C.c_double)), gy.ctypes.data_as(C.POINTER(C.c_double))
+    return w, keep
+
+
+def warp_source_window(m, raster_shape, out_shape):
+    """``fra_warp_source_window``: the source window ``(row_off, col_off, height, width)`` a warped read decodes, or
+    ``None`` when the map's footprint misses the raster.  Pure host code: no GPU is needed."""
+    w, keep = warp_map(m)
+    win = Window()
+    rc = load().fra_warp_source_window(C.byref(w), int(raster_shape[0]), int(raster_shape[1]), int(out_shape[0]),
+                                       int(out_shape[1]), C.byref(win))
+    if rc < 0:
+        _check(rc)
+    return (win.row_off, win.col_off, win.height, win.width) if rc == 1 else None
+
+
+def _warp_values(dtype, nodata, fill):
+    """``(flags, nodata, fill)`` of a warp entry from the Python arguments (``warp.check_values``)."""
+    from .warp import check_values
+
+    nd, fl = check_values(dtype, nodata, fill)
+    return (WARP_NODATA if nd is not None else 0), (0.0 if nd is None else nd), fl
+
+
+def _filled_out(channels: int):
+    f = np.zeros(int(channels), np.uint64)
+    return f, f.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
 def _calc_dst(dst, dst_strides, out_dtype, shape) -> Tuple[CalcDst, object]:
@@ -1190,6 +1262,63 @@ class Context:
         ms = C.c_float()
         _check(load().fra_focal_timing(C.byref(ms)))
         return ms.value
+
+    def warp(self, src, out_shape, m, resampling: str = "bilinear", dst=None, *, nodata=None, fill=None, dtype=None,
+             shape=None, strides=None, dst_strides=None):
+        """A raster warped onto ``out_shape`` = (oh, ow) through the ``warp.Map`` ``m`` on this context's GPU
+        (``fra_warp``, the rule of ``flac_raster.warp.warp_arrays``).
+
+        ``src``, ``dst`` and the layout arguments as :meth:`resample`.  ``resampling``: ``"nearest"``, ``"bilinear"`` or
+        ``"cubic"``.  ``nodata``: the nodata-aware sampling; ``fill``: what an outside pixel gets (``None``: the nodata
+        value, else NaN for floats and 0 for integers).  Returns ``(dst, filled)``: per band the number of pixels
+        written as the fill."""
+        from .resample import check_out_shape
+        from .warp import resampling_code
+
+        (oh, ow), mode = check_out_shape(out_shape), resampling_code(resampling)
+        job = WarpJob()
+        ret, dt, B = _raster_job(job, src, dst, dtype, shape, strides, dst_strides, lambda h, w: (oh, ow))
+        job.out_height, job.out_width, job.resampling = oh, ow, mode
+        job.flags, job.nodata, job.fill = _warp_values(dt, nodata, fill)
+        job.map, keep = warp_map(m)
+        filled, fp = _filled_out(B)
+        _check(load().fra_warp(self.h, C.byref(job), fp))
+        del keep
+        return ret, filled
+
+    def decode_device_warped(self, data, items, dst, dst_dtype, channels: int, strides: Tuple[int, int, int],
+                             raster_shape, out_shape, m, resampling: str = "bilinear", denorm: int = DENORM_NONE,
+                             nodata=None, fill=None):
+        """The tile streams' raster of ``raster_shape`` = (H, W) warped onto ``out_shape`` through ``m``
+        (``fra_decode_device_warped``): exactly ``warp.warp_arrays`` of the full decode, with only the source window
+        the map touches (``warp.source_window``) decoded and nothing but the output leaving the GPU.
+
+        ``data``, ``items``, ``denorm`` as :meth:`decode_device_window` (the items must cover the source window);
+        ``dst`` and ``strides`` address the ``(channels, oh, ow)`` output.  Returns ``(infos, filled)``."""
+        from .resample import check_out_shape
+        from .warp import resampling_code
+
+        (oh, ow), mode = check_out_shape(out_shape), resampling_code(resampling)
+        flags, nd, fl = _warp_values(dst_dtype, nodata, fill)
+        w, keep_map = warp_map(m)
+        job, infos, keep = self._decode_job(data, items, dst, dst_dtype, denorm, channels, strides)
+        filled, fp = _filled_out(channels)
+        infos = self._decode_run("fra_decode_device_warped", job, infos, keep, int(raster_shape[0]), int(raster_shape[1]),
+                                 C.byref(w), oh, ow, mode, flags, nd, fl, infos, fp)
+        del keep_map
+        return infos, filled
+
+    def warp_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_warp`` (:meth:`warp` / :meth:`decode_device_warped`)."""
+        ms = C.c_float()
+        _check(load().fra_warp_timing(C.byref(ms)))
+        return ms.value
+
+    def warp_paths(self) -> Tuple[int, int]:
+        """The workgroups of this thread's last ``k_warp`` that staged their footprint in LDS, and that gathered it."""
+        counts = (C.c_uint64 * 2)()
+        _check(load().fra_warp_paths(counts))
+        return int(counts[0]), int(counts[1])
 
     def decode_timing(self) -> List[float]:
         """HIP-event ms of this thread's last ``decode_device`` / ``decode_device_window``: parse, restore, scatter,

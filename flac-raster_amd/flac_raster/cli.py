@@ -689,6 +689,128 @@ def slope(
     _run_focal("slope", file_path, output_path, spec, bbox, pixels, dtype, cpu, device)
 
 
+def _source_grid(path: Path):
+    """``(transform, (H, W), crs)`` of a streaming container or a GeoTIFF."""
+    from .streaming import is_streaming_container, open_streaming
+    from .tiff import GeoTIFF
+
+    with open(path, "rb") as f:
+        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+    if is_tiff:
+        g = GeoTIFF(path)
+        try:
+            i = g.info
+            return (list(i.transform)[:6] if i.transform is not None else None, (i.height, i.width),
+                    str(i.crs) if i.crs is not None and str(i.crs) else None)
+        finally:
+            g.close()
+    if not is_streaming_container(path):
+        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    index = open_streaming(path).index
+    crs = index.get("crs")
+    t = index.get("transform")
+    return (list(t)[:6] if t else None), (int(index["height"]), int(index["width"])), (crs if crs and crs != "None" else None)
+
+
+def _numbers(text: str, n: int, what: str, kind=float):
+    try:
+        vals = [kind(x.strip()) for x in text.split(",")]
+    except ValueError:
+        vals = []
+    if len(vals) != n:
+        raise ValueError(f"{what} takes {n} comma-separated numbers, got {text!r}")
+    return vals
+
+
+@app.command()
+def warp(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),
+    dst_crs: Optional[str] = typer.Option(None, "--dst-crs", help="Reproject to this CRS (EPSG:4326, EPSG:3857, WGS84 UTM)"),
+    res: Optional[float] = typer.Option(None, "--res", help="With --dst-crs: the output pixel size"),
+    size: Optional[str] = typer.Option(None, "--size", help="With --dst-crs: the output size 'HEIGHT,WIDTH'"),
+    bounds: Optional[str] = typer.Option(None, "--bounds", help="With --dst-crs: 'xmin,ymin,xmax,ymax' in that CRS"),
+    like: Optional[Path] = typer.Option(None, "--like", help="Onto the grid of this GeoTIFF: its transform, shape and CRS"),
+    transform: Optional[str] = typer.Option(None, "--transform", help="Onto this geotransform 'a,b,c,d,e,f' in the "
+                                            "source's CRS, with --out-shape"),
+    out_shape: Optional[str] = typer.Option(None, "--out-shape", help="With --transform: 'HEIGHT,WIDTH'"),
+    resampling: str = typer.Option("bilinear", "--resampling", help="nearest, bilinear or cubic"),
+    nodata: Optional[float] = typer.Option(None, "--nodata", help="Nodata value of the source (default: the TIFF's own "
+                                           "tag): pixels that hold it are left out of every sample"),
+    fill: Optional[float] = typer.Option(None, "--fill", help="What a pixel outside the source gets (default: the "
+                                         "nodata value, else NaN for floats and 0 for integers)"),
+    grid_step: Optional[int] = typer.Option(None, "--grid-step", help="Across CRSs: the coordinate grid's step in output "
+                                            "pixels (default: from 16 down until the error is within 0.125 px)"),
+    cpu: bool = typer.Option(False, "--cpu", help="Evaluate with numpy on the host"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """A streaming FLAC file or a GeoTIFF onto another grid (another CRS, another raster's grid, any transform) -> GeoTIFF."""
+    from .crs import suggested_grid, transformer
+    from .geo import Affine
+    from .streaming import warp_to_tiff
+
+    try:
+        if sum(x is not None for x in (dst_crs, like, transform)) != 1:
+            console.print("[red]Error: give exactly one of --dst-crs, --like and --transform[/red]")
+            raise typer.Exit(1)
+        if (transform is None) != (out_shape is None):
+            console.print("[red]Error: --transform and --out-shape go together[/red]")
+            raise typer.Exit(1)
+        if dst_crs is None and (res is not None or size is not None or bounds is not None):
+            console.print("[red]Error: --res, --size and --bounds go with --dst-crs[/red]")
+            raise typer.Exit(1)
+        if res is not None and size is not None:
+            console.print("[red]Error: give at most one of --res and --size[/red]")
+            raise typer.Exit(1)
+        path = _local(file_path)
+        if not path.exists():
+            console.print(f"[red]File not found: {path}[/red]")
+            raise typer.Exit(1)
+        if like is not None:
+            t, shape, crs = _source_grid(like)
+            if t is None:
+                raise ValueError(f"{like} has no transform")
+        elif transform is not None:
+            t, shape, crs = _numbers(transform, 6, "--transform"), tuple(_numbers(out_shape, 2, "--out-shape", int)), None
+        else:
+            st, sshape, scrs = _source_grid(path)
+            if st is None or scrs is None:
+                raise ValueError("--dst-crs needs a source with a transform and a CRS")
+            crs = dst_crs
+            t, shape = suggested_grid(st, sshape, transformer(scrs, dst_crs))
+            if bounds is not None or res is not None or size is not None:
+                xmin, ymax = t[2], t[5]
+                xmax, ymin = xmin + t[0] * shape[1], ymax + t[4] * shape[0]
+                if bounds is not None:
+                    xmin, ymin, xmax, ymax = _numbers(bounds, 4, "--bounds")
+                if size is not None:
+                    shape = tuple(_numbers(size, 2, "--size", int))
+                else:
+                    r = float(res) if res is not None else t[0]
+                    shape = (max(1, int((ymax - ymin) / r + 0.5)), max(1, int((xmax - xmin) / r + 0.5)))
+                if size is not None:
+                    t = Affine((xmax - xmin) / shape[1], 0.0, xmin, 0.0, -(ymax - ymin) / shape[0], ymax)
+                else:
+                    t = Affine(r, 0.0, xmin, 0.0, -r, ymax)
+        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        info = warp_to_tiff(path, output_path, tuple(t)[:6], shape, crs, None, resampling, nodata, fill, dev, cpu,
+                            grid_step=grid_step)
+        console.print(f"[green]{output_path}[/green]: {len(info['filled'])} band(s) of {shape[0]} x {shape[1]}, {resampling}"
+                      + (f" (GPU {dev})" if dev is not None else " (host)"))
+        if info["grid_step"]:
+            console.print(f"coordinate grid: step {info['grid_step']}, error {info['grid_error']:.4f} px at the cell centres")
+        w = info["source_window"]
+        console.print("source window: " + (f"rows {w[0]}..{w[0] + w[2]}, columns {w[1]}..{w[1] + w[3]}" if w else
+                                           "none (the grid misses the source)"))
+        console.print("filled: " + ", ".join(f"band {k + 1}: {100.0 * v:.2f}%" for k, v in enumerate(info["shares"])))
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Warp failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
 def _show_tiff_info(path: Path):
     from .tiff import GeoTIFF
 

@@ -1087,6 +1087,152 @@ def focal_to_tiff(path: Path, tiff_path: Path, spec, window: Optional[Sequence[i
     return win, left, int(win[2]) * int(win[3])
 
 
+# ------------------------------------------------------------------------------------------ warped reads
+def _warp_map(src_transform, src_crs, dst_transform, out_shape, dst_crs, coords, grid_step, max_error):
+    """The ``warp.Map`` of an output grid onto a source: an affine map within one CRS, else a coordinate grid fitted to
+    ``coords`` (output CRS -> source CRS over arrays; default ``crs.transformer``).  Returns ``(map, step, error)``."""
+    from . import warp
+    from .crs import transformer
+
+    if not src_transform:
+        raise ValueError("the source has no transform")
+    same = dst_crs is None or not src_crs or str(dst_crs).strip().upper() == str(src_crs).strip().upper()
+    if coords is None and same:
+        return warp.affine_map(dst_transform, src_transform), 0, 0.0
+    if coords is None:
+        coords = transformer(dst_crs, src_crs)
+    da, db, dc, dd, de, df = (float(v) for v in tuple(dst_transform)[:6])
+    inv = warp.affine_map((1.0, 0.0, 0.0, 0.0, 1.0, 0.0), src_transform).affine  # source CRS -> source pixels
+
+    def pixel(cols, rows):
+        x, y = coords(da * cols + db * rows + dc, dd * cols + de * rows + df)
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return (inv[0] * x + inv[1] * y) + inv[2], (inv[3] * x + inv[4] * y) + inv[5]
+
+    if grid_step is not None:
+        m = warp.grid_map(pixel, out_shape, int(grid_step))
+        return m, m.step, warp.centre_error(m, pixel)
+    m, err = warp.fit_grid(pixel, out_shape, max_error)
+    return m, m.step, err
+
+
+def _warp_info(m, step, err, window, filled, out_shape, index=None):
+    n = int(out_shape[0]) * int(out_shape[1])
+    return {"map": m, "grid_step": step, "grid_error": err, "source_window": window, "filled": filled,
+            "shares": [int(v) / n for v in filled], "index": index}
+
+
+def warp_window(src, dst_transform, out_shape, dst_crs=None, coords=None, resampling: str = "bilinear", nodata=None,
+                fill=None, device: Optional[int] = None, cpu: bool = False, semantics: str = "pcm16",
+                grid_step: Optional[int] = None, max_error: float = 0.125):
+    """A streaming container (path or bytes) read onto another grid -> ``(raster (B, oh, ow) in the index's dtype,
+    output transform, output CRS, info)``: ``warp.warp_arrays`` of the whole raster.
+
+    The output grid is ``dst_transform`` (``geo.Affine`` or six floats) and ``out_shape`` in ``dst_crs`` (default: the
+    container's CRS, where the map is the affine ``src^-1 o dst``).  Across CRSs the map is a coordinate grid fitted to
+    ``coords`` (output CRS -> source CRS over arrays, e.g. a pyproj ``Transformer.transform``; default
+    ``crs.transformer``) by ``warp.fit_grid(max_error)``, or built at ``grid_step``.  Only the source window the map
+    touches (``warp.source_window``) is read.  An integer ``device`` makes one ``fra_decode_device_warped`` call on that
+    GPU: the decoded window never leaves it and only the output comes back; ``cpu=True`` (or ``device=None``) decodes the
+    window on the host and applies the numpy rule.  ``info``: the map, the grid step and the error reached, the source
+    window (``None``: the map misses the raster), the pixels written as fill per band and their shares."""
+    from . import _native, warp
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    oh, ow = resample.check_out_shape(out_shape)
+    warp.resampling_code(resampling)
+    index = _index_of(src)
+    H, W = int(index["height"]), int(index["width"])
+    dt = np.dtype(index["dtype"])
+    B = int(index["bands"])
+    src_crs = index.get("crs")
+    src_crs = src_crs if src_crs and src_crs != "None" else None
+    m, step, err = _warp_map(index.get("transform"), src_crs, dst_transform, (oh, ow), dst_crs, coords, grid_step, max_error)
+    warp.check_values(dt, nodata, fill)
+    win = warp.source_window(m, (H, W), (oh, ow))
+    blob, items = bytearray(), []
+    if win is not None:
+        index, win, blob, items = _window_items(src, win, None)
+    if cpu or device is None:
+        if win is None:
+            region, origin = np.zeros((B, 1, 1), dt), (0, 0)
+        else:
+            region, origin = np.zeros((B, win[2], win[3]), dtype=dt), (win[0], win[1])
+            _decode_window_on_host(blob, items, win, region, semantics)
+        out, filled = warp.warp_arrays(region, (oh, ow), m, resampling, nodata, fill, origin=origin, raster_shape=(H, W))
+    else:
+        out = np.zeros((B, oh, ow), dtype=dt)
+        ctx = _native.default_context(int(device))
+        _, filled = ctx.decode_device_warped(np.frombuffer(bytes(blob), dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1),
+                                             (H, W), (oh, ow), m, resampling,
+                                             _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT,
+                                             nodata=nodata, fill=fill)
+    return out, tuple(float(v) for v in tuple(dst_transform)[:6]), (dst_crs or src_crs), \
+        _warp_info(m, step, err, win, filled, (oh, ow), index)
+
+
+def warp_tiff(path: Path, dst_transform, out_shape, dst_crs=None, coords=None, resampling: str = "bilinear", nodata=None,
+              fill=None, device: Optional[int] = None, cpu: bool = False, grid_step: Optional[int] = None,
+              max_error: float = 0.125):
+    """:func:`warp_window` for a GeoTIFF source, read whole with the in-package reader: ``fra_warp`` on the GPU
+    ``device``, the numpy rule with ``cpu=True`` (or ``device=None``).  Without ``nodata`` the TIFF's own tag is used."""
+    from . import _native, warp
+
+    oh, ow = resample.check_out_shape(out_shape)
+    warp.resampling_code(resampling)
+    g = GeoTIFF(Path(path))
+    try:
+        info = g.info
+        if nodata is None and info.nodata is not None:
+            nodata = float(info.nodata)
+        src_crs = str(info.crs) if info.crs is not None and str(info.crs) else None
+        m, step, err = _warp_map(list(info.transform) if info.transform is not None else None, src_crs, dst_transform,
+                                 (oh, ow), dst_crs, coords, grid_step, max_error)
+        warp.check_values(np.dtype(info.dtype), nodata, fill)
+        a = np.zeros((info.count, info.height, info.width), dtype=np.dtype(info.dtype))
+        g.read_window_into(a, 0, 0, info.height, info.width)
+    finally:
+        g.close()
+    win = warp.source_window(m, a.shape[1:], (oh, ow))
+    if cpu or device is None:
+        out, filled = warp.warp_arrays(a, (oh, ow), m, resampling, nodata, fill)
+    else:
+        out, filled = _native.default_context(int(device)).warp(a, (oh, ow), m, resampling, nodata=nodata, fill=fill)
+    res = _warp_info(m, step, err, win, filled, (oh, ow))
+    res["nodata"] = nodata
+    return out, tuple(float(v) for v in tuple(dst_transform)[:6]), (dst_crs or src_crs), res
+
+
+def warp_to_tiff(path: Path, tiff_path: Path, dst_transform, out_shape, dst_crs=None, coords=None,
+                 resampling: str = "bilinear", nodata=None, fill=None, device: Optional[int] = None, cpu: bool = False,
+                 semantics: str = "pcm16", grid_step: Optional[int] = None, max_error: float = 0.125):
+    """A streaming container or a GeoTIFF (told apart by their first bytes) warped onto a grid -> GeoTIFF with the
+    grid's transform and CRS; with a nodata value (the caller's or the source TIFF's) the nodata tag is the fill.
+    Returns the ``info`` of :func:`warp_window`."""
+    from . import warp
+    from .tiff import write_geotiff
+
+    path = Path(path)
+    with open(path, "rb") as f:
+        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+    if is_tiff:
+        out, t, crs, info = warp_tiff(path, dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device, cpu,
+                                      grid_step, max_error)
+        nodata = info["nodata"]
+    elif is_streaming_container(path):
+        out, t, crs, info = warp_window(path, dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device,
+                                        cpu, semantics, grid_step, max_error)
+    else:
+        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    tag = None
+    if nodata is not None:
+        v = warp.check_values(out.dtype, nodata, fill)[1]
+        tag = float(v) if out.dtype.kind == "f" else int(v)
+    write_geotiff(Path(tiff_path), out, transform=t, crs=str(crs) if crs and str(crs) != "None" else None, nodata=tag)
+    return info
+
+
 def _index_of(src):
     if isinstance(src, (bytes, bytearray, memoryview)):
         return read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))[0]

@@ -866,6 +866,104 @@ FRA_API int fra_decode_device_zonal(fra_ctx *ctx, const fra_decode_job *job, con
  * has no counterpart */
 FRA_API int fra_zonal_timing(float *ms);
 
+/* Warped reads: a raster (channels, H, W) of any fra_dtype, or a region of a set of tile streams, onto an output grid
+ * (channels, oh, ow) of its own, 1 <= oh, ow <= 65536, in the input's dtype.  A map takes every output pixel to a source
+ * coordinate and the source is sampled there.  The rule (flac_raster/warp.py restates it in numpy: warp_arrays):
+ *   All coordinate and value arithmetic is IEEE f64, each operation rounded on its own, no contraction.  Pixel (row r,
+ *   col c) covers [c, c + 1) x [r, r + 1); its centre is (c + 0.5, r + 0.5).
+ *   Maps.  For output pixel (R, C): u = (double)C + 0.5, v = (double)R + 0.5.
+ *     FRA_WARP_AFFINE  six doubles a .. f:  x = (a*u + b*v) + c,  y = (d*u + e*v) + f  -- two products, their sum, then
+ *                      the constant, in exactly this order.
+ *     FRA_WARP_GRID    step >= 1, gw = ceil(ow / step) + 1, gh = ceil(oh / step) + 1, and two f64 planes gx, gy of shape
+ *                      (gh, gw): the source coordinates of the output-grid points (j*step, i*step) -- pixel corners, not
+ *                      centres.  cj = min(C / step, gw - 2), ci = min(R / step, gh - 2) (integer division);
+ *                      fx = (u - (double)(cj*step)) / (double)step, fy likewise; per plane g
+ *                        top = g[ci][cj] + (g[ci][cj+1] - g[ci][cj]) * fx,  bot the same on row ci + 1,
+ *                        value = top + (bot - top) * fy.
+ *                      (The bilinear coordinate grid of GDAL's approximate transformer: any CRS transform is supplied
+ *                      as data, and the kernel and the numpy rule consume the same numbers.)
+ *   Inside.  The pixel is inside when x >= 0 && x < W && y >= 0 && y < H, W and H the size of the whole source raster
+ *     (not of a decoded region).  A NaN coordinate fails the test.  An outside pixel is written as `fill` and counted
+ *     in filled[band].
+ *   Sampling an inside pixel.
+ *     nearest          in[floor(y)][floor(x)].
+ *     bilinear, cubic  px = x - 0.5, i0 = floor(px), t = px - i0, rows likewise.  Taps, weights, the clamping of the tap
+ *                      indices to [0, W - 1] / [0, H - 1], the order (vertically first, top to bottom, then left to
+ *                      right) and the conversion of the result are exactly those of the resampling rule above, except
+ *                      that a NaN result is written as the canonical quiet NaN (0x7ff8000000000000 as the dtype holds
+ *                      it), so that a float output is fixed to the last bit (the nearest copies its pixel's bits).
+ *     With FRA_WARP_NODATA the validity of a value and the renormalisation are exactly those of the nodata-aware rule's
+ *     "bilinear, cubic" paragraph and its "nearest" line: all taps valid gives the unmasked formula; otherwise the
+ *     masked bilinear of the same centre; no valid tap, or Wt <= 0, gives `fill` and the pixel is counted.  The nearest
+ *     picks its pixel, invalid or not, and counts it when it is invalid.  Without the flag NaN and +-inf propagate.
+ *     `fill` is a double the dtype admits by the nodata rule (an integer in range; for floats NaN, or finite and exact);
+ *     so is `nodata` under FRA_WARP_NODATA.  FRA_RESAMPLE_AVERAGE is refused: a warp that shrinks takes point samples
+ *     (read an overview first, then warp that).
+ *   Consequences.  Under the identity map (1, 0, 0, 0, 1, 0) the nearest returns the input bit for bit, and the bilinear
+ *     and the cubic return every finite value (t = 0: the other taps weigh 0.0, so -0.0 comes back as +0.0, and a tap
+ *     of +-inf or NaN next to a pixel makes it NaN).  An integer translation is, likewise, a shifted copy with fill.
+ *     For an axis-aligned map whose scales are powers of two and whose offsets are 0 every coordinate is exact, and the
+ *     result equals fra_resample / fra_resample_masked (nearest, bilinear, cubic) of that size bit for bit (for the
+ *     masked ones when `fill` is the nodata value; a NaN result has the sign the hardware gives it there, none here).
+ * k_warp: one 256-thread workgroup per 16 x 64 output tile of a band; every thread computes the source coordinates of
+ * its pixels and reads its taps from global memory ("gathered").  A second path that staged the tile's footprint in LDS
+ * ("staged") was measured slower and is not built; fra_warp_paths still reports both counts. */
+#define FRA_WARP_AFFINE 0
+#define FRA_WARP_GRID 1
+#define FRA_WARP_NODATA 1
+typedef struct {
+  int32_t kind;                             /* FRA_WARP_AFFINE, FRA_WARP_GRID */
+  int32_t step, gh, gw;                     /* GRID: the step and the planes' shape */
+  double affine[6];                         /* AFFINE: a .. f, finite */
+  const double *gx, *gy;                    /* GRID: host memory, gh * gw doubles each, row-major */
+} fra_warp_map;                             /* 80 bytes */
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype, of src and dst */
+  int32_t channels, height, width;          /* >= 1; channels <= 255 */
+  int64_t src_band_stride, src_row_stride, src_col_stride;  /* elements, >= 0 */
+  int32_t out_height, out_width;            /* 1 .. FRA_RESAMPLE_MAX_OUT */
+  int32_t resampling;                       /* FRA_RESAMPLE_NEAREST, _BILINEAR, _CUBIC */
+  int32_t flags;                            /* FRA_WARP_NODATA */
+  void *dst; int32_t dst_on_device;         /* (channels, out_height, out_width) through the strides below */
+  int64_t dst_band_stride, dst_row_stride, dst_col_stride;
+  double nodata, fill;
+  fra_warp_map map;
+} fra_warp_job;                             /* 208 bytes */
+/* k_warp alone, over a host or device raster of any dtype and layout.  Synchronous.  Host buffers are staged as
+ * fra_resample stages them (the elements of dst that are not outputs keep the caller's values).  filled (host memory,
+ * `channels` words, may be NULL) receives per band the number of output pixels written as the fill (and the invalid
+ * pixels the nearest picked).
+ * FRA_E_INVALID, before any GPU work: a null argument, a bad dtype or layout (more than 255 bands), an output size
+ * outside 1 .. 65536, an unknown or AVERAGE resampling, unknown flags, an unknown map kind, step < 1 or gh / gw that do
+ * not match step, a null grid, a non-finite affine coefficient, a nodata or fill the dtype does not admit. */
+FRA_API int fra_warp(fra_ctx *ctx, const fra_warp_job *job, uint64_t *filled /* channels, may be NULL */);
+/* The warp of what fra_decode_device would have written for the whole raster_h x raster_w raster the items tile, in
+ * dst_dtype.  The host computes the source window the map touches -- for an affine map from the four corner pixel
+ * centres of the output, for a grid map from the grid nodes alone (a bilinear patch has its extremes at its corners;
+ * non-finite nodes are left out) --, grows it by 3 pixels per side and clips it to the raster
+ * (fra_warp_source_window).  That window is decoded by the windowed read into a per-call device buffer (its refusals and
+ * messages are this call's; the items must cover the window), then k_warp runs with the window's origin: taps are
+ * clamped against the whole raster and indexed relative to the window.  The job's dst and strides address the out_h x
+ * out_w output.  A footprint wholly outside the raster (by more than a pixel) decodes nothing (infos are zeroed), writes the fill everywhere
+ * and returns FRA_OK with filled = out_h * out_w per band.  FRA_E_INVALID before any GPU work for everything fra_warp
+ * refuses so, and for a raster size below 1.  Afterwards fra_decode_device_timing reports the inner windowed read and
+ * fra_warp_timing the warp. */
+FRA_API int fra_decode_device_warped(fra_ctx *ctx, const fra_decode_job *job, int32_t raster_h, int32_t raster_w,
+                                     const fra_warp_map *map, int32_t out_h, int32_t out_w, int32_t resampling,
+                                     int32_t flags, double nodata, double fill, fra_decoded *infos /* nitems */,
+                                     uint64_t *filled /* channels, may be NULL */);
+/* The source window fra_decode_device_warped decodes for a checked map: *window; returns 0 when the footprint lies wholly
+ * outside the raster (nothing is decoded), 1 otherwise, FRA_E_INVALID for what fra_warp refuses in a map or a size.
+ * Pure host code: no context, no GPU. */
+FRA_API int fra_warp_source_window(const fra_warp_map *map, int32_t raster_h, int32_t raster_w, int32_t out_h,
+                                   int32_t out_w, fra_window *window);
+/* HIP-event time (ms) of the calling thread's last k_warp (fra_warp or fra_decode_device_warped) */
+FRA_API int fra_warp_timing(float *ms);
+/* The workgroups of the calling thread's last k_warp that staged their taps in LDS (counts[0]: always 0, no such path is
+ * built) and that gathered them from global memory (counts[1]: all of them) */
+FRA_API int fra_warp_paths(uint64_t counts[2]);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

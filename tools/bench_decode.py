@@ -97,6 +97,17 @@ byte for byte.  ``--dem`` runs the focal legs over a synthetic 16384 x 16384 int
     python tools/bench_decode.py --focal mean:3 --focal mean:15 --focal median:5 --calc b1 --steps 5 --warmup 2
     python tools/bench_decode.py --focal hillshade --dtype uint8 --dem --steps 5 --warmup 2
 
+``--warp KIND`` times a warped read of the same container onto a grid of the scene's own size
+(``fra_decode_device_warped``: the source window decoded into a per-call buffer, then ``k_warp`` over all four bands) in the
+same run, beside the plain read and the ``--calc`` legs, once per mode of ``--warp-resampling``: ``rotate:DEG`` about the
+centre, ``shift:DX,DY``, or ``mercator`` (UTM 33 N to EPSG:3857 through ``warp.fit_grid``).  Per leg ``k_warp_ms`` (HIP
+events), the bytes read and written, the ``staged`` / ``gathered`` workgroups and, with ``--calc b1:uint16``,
+``over_calc_copy_per_band``.  It exits non-zero unless three 64 x 512 rectangles of the result equal ``warp.warp_arrays``
+of the plain read byte for byte.  ``FRA_LIB_PATH`` set to the ``warpgather`` diagnostic build times the kernel without its
+staged path.
+
+    python tools/bench_decode.py --warp shift:0.5,0.5 --warp rotate:10 --warp mercator --calc b1:uint16 --steps 5 --warmup 2
+
 ``--stats`` times the band statistics of the same container (``fra_decode_device_stats``: the whole raster decoded
 with ``pcm16`` semantics to uint16 and described there, only the reports and the histogram come back) in five legs: the
 plain read to a device destination, ``bins = 0`` (one pass), 256 bins over the automatic range (two passes), the exact
@@ -218,6 +229,35 @@ def focal_over_dem(ctx, args):
     ctx.free(dem)
 
 
+def warp_map_of(text):
+    """The ``warp.Map`` of a ``--warp`` leg over the scene at its own size, and a word about it."""
+    import math
+
+    from flac_raster import crs
+    from flac_raster import warp as WP
+
+    kind, _, arg = text.partition(":")
+    if kind == "rotate":
+        c, s = math.cos(math.radians(float(arg))), math.sin(math.radians(float(arg)))
+        cx, cy = W / 2.0, H / 2.0
+        return WP.affine_coefficients((c, -s, cx - (c * cx - s * cy), s, c, cy - (s * cx + c * cy))), f"rotation by {arg} deg"
+    if kind == "shift":
+        dx, dy = (float(v) for v in arg.split(","))
+        return WP.affine_coefficients((1.0, 0.0, dx, 0.0, 1.0, dy)), f"shift by ({dx}, {dy})"
+    if kind == "mercator":
+        st = (10.0, 0.0, 399960.0, 0.0, -10.0, 4600020.0)  # a Sentinel-2 tile of UTM zone 33 N
+        dt_, _ = crs.suggested_grid(st, (H, W), crs.transformer("EPSG:32633", "EPSG:3857"))
+        back = crs.transformer("EPSG:3857", "EPSG:32633")
+
+        def pixel(cols, rows):
+            x, y = back(dt_.a * cols + dt_.c, dt_.e * rows + dt_.f)
+            return (x - st[2]) / st[0], (y - st[5]) / st[4]
+
+        m, err = WP.fit_grid(pixel, (H, W))
+        return m, f"UTM 33 N -> EPSG:3857, grid step {m.step}, error {err:.4f} px"
+    raise SystemExit(f"--warp {text!r}: rotate:DEG, shift:DX,DY or mercator")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tiles", type=int, default=0, help="first N tiles of the scene (0: all 121)")
@@ -251,6 +291,11 @@ def main():
                     help="time a focal operation over the container against the plain read (and against the --calc legs "
                          "of the same run): mean, sum, min, max, count, median, laplace (a 3 x 3 convolution), slope or "
                          "hillshade, SIZE one odd number or HxW (default 3); repeat for further legs")
+    ap.add_argument("--warp", action="append", default=None, metavar="KIND",
+                    help="time a warped read of the container onto a grid of the scene's own size against the plain read "
+                         "(and against the --calc legs of the same run): rotate:DEG (about the centre), shift:DX,DY or "
+                         "mercator (UTM 33 N -> EPSG:3857 through a fitted coordinate grid); may be repeated")
+    ap.add_argument("--warp-resampling", default="bilinear,nearest", help="with --warp: the modes of every leg")
     ap.add_argument("--dem", action="store_true",
                     help="with --focal: k_focal alone over a synthetic 16384 x 16384 int16 DEM on the device instead")
     ap.add_argument("--dtype", default="float32", help="with --calc or --focal: the output dtype of the legs that name none")
@@ -610,11 +655,11 @@ def main():
         ctx.free(dev_raster)
         return
 
-    if args.calc or args.focal:
+    if args.calc or args.focal or args.warp:
         from flac_raster.calc import calc_arrays, compile_exprs, default_fill
 
         if len(wins) != len(calculate_tiles(H, W, TILE)):
-            raise SystemExit("--calc and --focal need every tile: the region mapped is the whole raster")
+            raise SystemExit("--calc, --focal and --warp need every tile: the region mapped is the whole raster")
         roi = (0, 0, H, W)
         citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
         plain_wall, plain_ms = [], []
@@ -717,8 +762,59 @@ def main():
                 "k_focal_TBps": round((rd + wr) / (med(kf) * 1e-3) / 1e12, 3),
                 "wall_over_plain": round(med(wall) / med(plain_wall), 3),
                 "all_ms": {"k_focal": [round(v, 4) for v in kf], "focal_wall": [round(v, 3) for v in wall]}})
+        for text in args.warp or []:
+            from flac_raster import warp as WP
+
+            m, what = warp_map_of(text)
+            dev_res = ctx.alloc(B * H * W * dt.itemsize)
+            for mode in args.warp_resampling.split(","):
+                wall, inner, kw = [], [], []
+                for s in range(args.warmup + args.steps):
+                    t0 = time.perf_counter()
+                    _, filled = ctx.decode_device_warped((frames_ptr, total), citems, dev_res, dt, B, (H * W, W, 1), (H, W), (H, W),
+                                                         m, mode, denorm=N.DENORM_PCM16)
+                    t1 = time.perf_counter()
+                    if s >= args.warmup:
+                        wall.append((t1 - t0) * 1e3)
+                        inner.append(ctx.decode_timing()[3])
+                        kw.append(ctx.warp_timing())
+                staged, gathered = ctx.warp_paths()
+                # two rectangles of the result against the rule over the source pixels they touch, read back from the
+                # plain read of this run
+                for ow_ in ((0, 0, 64, 512), (H // 2 - 32, W // 2 - 256, 64, 512), (H - 64, W - 512, 64, 512)):
+                    x, y = WP.map_coords(m, (H, W), ow_)
+                    ok = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+                    got = np.empty((B, ow_[2], ow_[3]), dt)
+                    for k in range(B):
+                        for r in range(ow_[2]):
+                            ctx.d2h(got[k, r], dev_res + ((k * H + ow_[0] + r) * W + ow_[1]) * dt.itemsize)
+                    if not ok.any():
+                        if (got != 0).any():
+                            raise SystemExit(f"warp {text} {mode}: a rectangle outside the source is not all fill")
+                        continue
+                    r0, r1 = max(int(np.floor(y[ok].min())) - 3, 0), min(int(np.floor(y[ok].max())) + 3, H - 1)
+                    c0, c1 = max(int(np.floor(x[ok].min())) - 3, 0), min(int(np.floor(x[ok].max())) + 3, W - 1)
+                    part = np.empty((B, r1 - r0 + 1, c1 - c0 + 1), dt)
+                    for k in range(B):
+                        for r in range(part.shape[1]):
+                            ctx.d2h(part[k, r], dev_out + ((k * H + r0 + r) * W + c0) * dt.itemsize)
+                    want, _ = WP.warp_arrays(part, (H, W), m, mode, origin=(r0, c0), raster_shape=(H, W), out_window=ow_)
+                    if got.tobytes() != want.tobytes():
+                        raise SystemExit(f"warp {text} {mode}: the rectangle at {ow_[:2]} differs from warp_arrays")
+                rd = wr = B * H * W * dt.itemsize
+                res["legs"].append({
+                    "warp": text, "map": what, "resampling": mode, "filled": [int(v) for v in filled],
+                    "source_window": WP.source_window(m, (H, W), (H, W)), "staged": staged, "gathered": gathered,
+                    "warp_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3),
+                    "k_warp_ms": round(med(kw), 4), "bytes_read": rd, "bytes_written": wr,
+                    "k_warp_TBps": round((rd + wr) / (med(kw) * 1e-3) / 1e12, 3),
+                    "wall_over_plain": round(med(wall) / med(plain_wall), 3),
+                    "all_ms": {"k_warp": [round(v, 4) for v in kw], "warp_wall": [round(v, 3) for v in wall]}})
+            ctx.free(dev_res)
         copies = [leg["k_calc_ms"] for leg in res["legs"] if leg.get("exprs") == ["b1"]]
         for leg in res["legs"]:
+            if "warp" in leg and copies:  # against k_calc's one-band copy of this run, band for band
+                leg["over_calc_copy_per_band"] = round(leg["k_warp_ms"] / B / copies[0], 3)
             if "focal" in leg and copies:  # against k_calc's one-band copy of this run, band for band
                 leg["over_calc_copy_per_band"] = round(leg["k_focal_ms"] / B / copies[0], 3)
         res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall],

@@ -14,8 +14,11 @@
 //     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats),
 //     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
 //     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
-//     fra_focal_check) and the zonal statistics (fra_zonal, fra_decode_device_zonal), which returns before any GPU
-//     work, and the order of these refusals (inputs that break two rules at once).
+//     fra_focal_check), the zonal statistics (fra_zonal, fra_decode_device_zonal) and the warped reads (fra_warp,
+//     fra_decode_device_warped, fra_warp_source_window), which returns before any GPU work, and the order of these
+//     refusals (inputs that break two rules at once);
+//   * the source-window arithmetic of the warped reads (fra_warp.h source_window): pinned windows, footprints that
+//     miss the raster, non-finite grid nodes, and that every tap of every inside pixel lies in the window;
 //   * the chunk arithmetic of the row-chunk scan (fra_scan.h plan_chunks): invariants and pinned values.
 // usage: decode_host_check [--concat] file.flac ...
 #include <cmath>
@@ -28,6 +31,7 @@
 #include "../flac-raster_amd/csrc/fra_decode.cpp"  // the host decoder's frame validation (internal linkage)
 #include "../flac-raster_amd/csrc/fra_decode_host.h"
 #include "../flac-raster_amd/csrc/fra_scan.h"
+#include "../flac-raster_amd/csrc/fra_warp.h"
 
 static std::string g_msg;
 extern "C" int fra_internal_set_error(int code, const char* fmt, ...) {
@@ -871,6 +875,156 @@ int main(int argc, char** argv) {
     { auto j = dj; j.denorm = 7; EXPECT(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: denorm 7 accepted"); }
     { auto j = dj; j.channels = 0; EXPECT(zr(ctx, &j, &r48, zones, FRA_U16, 8, 1, &four, recs, &outside, inf) == FRA_E_INVALID, "zonal read: no channels accepted"); }
     { fra_window r = r48; r.width = 0; auto o = four; o.nzones = 0; EXPECT(says(zr(ctx, &dj, &r, zones, FRA_U16, 8, 1, &o, recs, &outside, inf), "nzones"), "zonal read: no zones and zero-width roi: %s", g_msg.c_str()); }
+  }
+  // ... and of the warped reads (fra_warp.hip): refused before any GPU work, in the order the header gives
+  {
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    static int32_t wsrc[64];
+    int32_t wout[15];
+    uint64_t wfilled[1];
+    fra_warp_job wj{};
+    wj.src = wsrc; wj.dtype = FRA_I32; wj.channels = 1; wj.height = 8; wj.width = 8;
+    wj.src_band_stride = 64; wj.src_row_stride = 8; wj.src_col_stride = 1;
+    wj.out_height = 3; wj.out_width = 5; wj.resampling = FRA_RESAMPLE_BILINEAR;
+    wj.dst = wout; wj.dst_band_stride = 15; wj.dst_row_stride = 5; wj.dst_col_stride = 1;
+    wj.map.kind = FRA_WARP_AFFINE;
+    wj.map.affine[0] = wj.map.affine[4] = 1.0;
+    EXPECT(fra_warp(nullptr, &wj, wfilled) == FRA_E_INVALID, "warp: null ctx accepted");
+    EXPECT(fra_warp(ctx, nullptr, wfilled) == FRA_E_INVALID, "warp: null job accepted");
+    { auto j = wj; j.src = nullptr; EXPECT(fra_warp(ctx, &j, wfilled) == FRA_E_INVALID, "warp: null src accepted"); }
+    { auto j = wj; j.dst = nullptr; EXPECT(fra_warp(ctx, &j, nullptr) == FRA_E_INVALID, "warp: null dst accepted"); }
+    { auto j = wj; j.dtype = 8; EXPECT(says(fra_warp(ctx, &j, wfilled), "bad dtype"), "warp: dtype 8: %s", g_msg.c_str()); }
+    { auto j = wj; j.height = 0; EXPECT(says(fra_warp(ctx, &j, wfilled), "bad raster layout"), "warp: zero height: %s", g_msg.c_str()); }
+    { auto j = wj; j.dst_row_stride = -5; EXPECT(says(fra_warp(ctx, &j, wfilled), "bad raster layout"), "warp: negative stride: %s", g_msg.c_str()); }
+    { auto j = wj; j.channels = 256; EXPECT(says(fra_warp(ctx, &j, wfilled), "more than 255"), "warp: 256 bands: %s", g_msg.c_str()); }
+    for (int n : {0, -1, 65537}) {
+      { auto j = wj; j.out_height = n; EXPECT(says(fra_warp(ctx, &j, wfilled), "output size"), "warp: out height %d: %s", n, g_msg.c_str()); }
+      { auto j = wj; j.out_width = n; EXPECT(says(fra_warp(ctx, &j, wfilled), "output size"), "warp: out width %d: %s", n, g_msg.c_str()); }
+    }
+    { auto j = wj; j.resampling = FRA_RESAMPLE_AVERAGE; EXPECT(says(fra_warp(ctx, &j, wfilled), "point samples"), "warp: average: %s", g_msg.c_str()); }
+    for (int r : {-1, 4}) { auto j = wj; j.resampling = r; EXPECT(says(fra_warp(ctx, &j, wfilled), "unknown resampling"), "warp: resampling %d: %s", r, g_msg.c_str()); }
+    { auto j = wj; j.flags = 2; EXPECT(says(fra_warp(ctx, &j, wfilled), "unknown warp flags"), "warp: flag 2: %s", g_msg.c_str()); }
+    for (int k : {-1, 2}) { auto j = wj; j.map.kind = k; EXPECT(says(fra_warp(ctx, &j, wfilled), "unknown map kind"), "warp: kind %d: %s", k, g_msg.c_str()); }
+    for (int k = 0; k < 6; k++)
+      for (double bad : {(double)NAN, (double)HUGE_VAL, -(double)HUGE_VAL}) {
+        auto j = wj; j.map.affine[k] = bad; EXPECT(says(fra_warp(ctx, &j, wfilled), "is not finite"), "warp: coefficient %d = %g: %s", k, bad, g_msg.c_str());
+      }
+    double plane[12] = {0};
+    fra_warp_job gj = wj;
+    gj.map.kind = FRA_WARP_GRID; gj.map.step = 2; gj.map.gh = 3; gj.map.gw = 4; gj.map.gx = gj.map.gy = plane;
+    for (int st : {0, -2}) { auto j = gj; j.map.step = st; EXPECT(says(fra_warp(ctx, &j, wfilled), "grid step"), "warp: step %d: %s", st, g_msg.c_str()); }
+    { auto j = gj; j.map.gw = 5; EXPECT(says(fra_warp(ctx, &j, wfilled), "takes a grid of 3 x 4 nodes"), "warp: gw 5: %s", g_msg.c_str()); }
+    { auto j = gj; j.map.gh = 2; EXPECT(says(fra_warp(ctx, &j, wfilled), "takes a grid of 3 x 4 nodes"), "warp: gh 2: %s", g_msg.c_str()); }
+    { auto j = gj; j.map.step = 1; EXPECT(says(fra_warp(ctx, &j, wfilled), "takes a grid of 4 x 6 nodes"), "warp: step 1 with 3 x 4 nodes: %s", g_msg.c_str()); }
+    { auto j = gj; j.map.gx = nullptr; EXPECT(says(fra_warp(ctx, &j, wfilled), "null grid"), "warp: null gx: %s", g_msg.c_str()); }
+    { auto j = gj; j.map.gy = nullptr; EXPECT(says(fra_warp(ctx, &j, wfilled), "null grid"), "warp: null gy: %s", g_msg.c_str()); }
+    { auto j = wj; j.flags = FRA_WARP_NODATA; j.nodata = 0.5; EXPECT(says(fra_warp(ctx, &j, wfilled), "nodata 0.5 is not a value"), "warp: nodata 0.5: %s", g_msg.c_str()); }
+    { auto j = wj; j.nodata = 0.5; j.fill = 0.5; EXPECT(says(fra_warp(ctx, &j, wfilled), "fill 0.5 is not a value"), "warp: fill 0.5 (and an unused nodata): %s", g_msg.c_str()); }
+    { auto j = wj; j.fill = 2147483648.0; EXPECT(says(fra_warp(ctx, &j, wfilled), "fill"), "warp: fill 2^31: %s", g_msg.c_str()); }
+    { auto j = wj; j.dtype = FRA_F32; j.fill = 0.1; EXPECT(says(fra_warp(ctx, &j, wfilled), "fill"), "warp: an inexact float32 fill: %s", g_msg.c_str()); }
+    { auto j = wj; j.dtype = FRA_F64; j.fill = HUGE_VAL; EXPECT(says(fra_warp(ctx, &j, wfilled), "fill"), "warp: an infinite fill: %s", g_msg.c_str()); }
+    // ... the order: the layout, the sizes, the resampling, the flags, the map, nodata, fill
+    { auto j = wj; j.dtype = 8; j.out_height = 0; EXPECT(says(fra_warp(ctx, &j, wfilled), "bad dtype"), "warp: dtype 8 and out height 0: %s", g_msg.c_str()); }
+    { auto j = wj; j.out_height = 0; j.resampling = 1; EXPECT(says(fra_warp(ctx, &j, wfilled), "output size"), "warp: out height 0 and the average: %s", g_msg.c_str()); }
+    { auto j = wj; j.resampling = 1; j.flags = 2; EXPECT(says(fra_warp(ctx, &j, wfilled), "point samples"), "warp: the average and flag 2: %s", g_msg.c_str()); }
+    { auto j = gj; j.flags = 2; j.map.step = 0; EXPECT(says(fra_warp(ctx, &j, wfilled), "unknown warp flags"), "warp: flag 2 and step 0: %s", g_msg.c_str()); }
+    { auto j = gj; j.map.step = 0; j.map.gx = nullptr; EXPECT(says(fra_warp(ctx, &j, wfilled), "grid step"), "warp: step 0 and a null grid: %s", g_msg.c_str()); }
+    { auto j = wj; j.map.affine[2] = NAN; j.fill = 0.5; EXPECT(says(fra_warp(ctx, &j, wfilled), "is not finite"), "warp: a NaN coefficient and fill 0.5: %s", g_msg.c_str()); }
+    { auto j = wj; j.flags = 1; j.nodata = 0.5; j.fill = 0.5; EXPECT(says(fra_warp(ctx, &j, wfilled), "nodata"), "warp: nodata 0.5 and fill 0.5: %s", g_msg.c_str()); }
+    EXPECT(fra_warp_timing(nullptr) == FRA_E_INVALID, "warp timing: null accepted");
+    EXPECT(fra_warp_paths(nullptr) == FRA_E_INVALID, "warp paths: null accepted");
+    { uint64_t c[2] = {7, 7}; EXPECT(fra_warp_paths(c) == FRA_OK && c[0] == 0 && c[1] == 0, "warp paths: not zero before any call"); }
+    // the read behind the decoder: an identity over a 4 x 8 raster of one item
+    fra_decode_item di = it;
+    di.window = {0, 0, 4, 8};
+    fra_decode_job dj = job;  // dst_dtype int32, a destination with strides
+    dj.items = &di;
+    auto rd = [&](fra_ctx* c, const fra_decode_job* j, int32_t rh, int32_t rw, const fra_warp_map* m, int32_t oh, int32_t ow, int32_t mode,
+                  int32_t flags, double nd, double fl, fra_decoded* d) {
+      return fra_decode_device_warped(c, j, rh, rw, m, oh, ow, mode, flags, nd, fl, d, wfilled);
+    };
+    const fra_warp_map& id = wj.map;
+    EXPECT(rd(nullptr, &dj, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: null ctx accepted");
+    EXPECT(rd(ctx, nullptr, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: null job accepted");
+    EXPECT(rd(ctx, &dj, 4, 8, nullptr, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: null map accepted");
+    EXPECT(rd(ctx, &dj, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.0, nullptr) == FRA_E_INVALID, "warped read: null infos accepted");
+    EXPECT(says(rd(ctx, &dj, 4, 8, &id, 0, 5, 2, 0, 0.0, 0.0, inf), "output size"), "warped read: out height 0: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 4, 8, &id, 3, 5, 1, 0, 0.0, 0.0, inf), "point samples"), "warped read: average: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 4, 8, &id, 3, 5, 2, 4, 0.0, 0.0, inf), "unknown warp flags"), "warped read: flag 4: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 4, 8, &gj.map, 3, 7, 2, 0, 0.0, 0.0, inf), "takes a grid of"), "warped read: a grid for another size: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 0, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf), "bad raster size"), "warped read: raster height 0: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 4, 8, &id, 3, 5, 2, 1, 0.5, 0.0, inf), "nodata"), "warped read: nodata 0.5: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.5, inf), "fill"), "warped read: fill 0.5: %s", g_msg.c_str());
+    EXPECT(says(rd(ctx, &dj, 9, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf), "do not cover"), "warped read: a window of six rows over an item of four: %s", g_msg.c_str());
+    { auto j = dj; j.dst_dtype = 9; EXPECT(says(rd(ctx, &j, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.5, inf), "dtype"), "warped read: dtype 9 and fill 0.5: %s", g_msg.c_str()); }
+    { auto j = dj; j.dst = nullptr; EXPECT(rd(ctx, &j, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: null dst accepted"); }
+    { auto j = dj; j.flags = FRA_DECODE_CONCAT; EXPECT(rd(ctx, &j, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: FRA_DECODE_CONCAT accepted"); }
+    { auto j = dj; j.channels = 0; EXPECT(rd(ctx, &j, 4, 8, &id, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: no channels accepted"); }
+    { auto j = dj; j.row_stride = -1; fra_warp_map out = id; out.affine[2] = 100.0;  // nothing to decode: the job is still checked
+      EXPECT(rd(ctx, &j, 4, 8, &out, 3, 5, 2, 0, 0.0, 0.0, inf) == FRA_E_INVALID, "warped read: negative stride with a map that misses the raster accepted"); }
+    // the source window
+    fra_window win{};
+    EXPECT(fra_warp_source_window(nullptr, 4, 8, 3, 5, &win) == FRA_E_INVALID, "source window: null map accepted");
+    EXPECT(fra_warp_source_window(&id, 4, 8, 3, 5, nullptr) == FRA_E_INVALID, "source window: null window accepted");
+    EXPECT(says(fra_warp_source_window(&id, 4, 8, 0, 5, &win), "output size"), "source window: out height 0: %s", g_msg.c_str());
+    EXPECT(says(fra_warp_source_window(&id, 0, 8, 3, 5, &win), "bad raster size"), "source window: raster height 0: %s", g_msg.c_str());
+    auto window_is = [&](const fra_warp_map& m, int32_t H, int32_t W, int32_t oh, int32_t ow, int r, int c, int h, int w) {
+      fra_window x{-1, -1, -1, -1};
+      return fra_warp_source_window(&m, H, W, oh, ow, &x) == 1 && x.row_off == r && x.col_off == c && x.height == h && x.width == w;
+    };
+    auto misses = [&](const fra_warp_map& m, int32_t H, int32_t W, int32_t oh, int32_t ow) {
+      fra_window x{-1, -1, -1, -1};
+      return fra_warp_source_window(&m, H, W, oh, ow, &x) == 0 && x.row_off == -1;
+    };
+    auto affine = [&](double a, double b, double c, double d, double e, double f) {
+      fra_warp_map m{};
+      m.kind = FRA_WARP_AFFINE;
+      const double k[6] = {a, b, c, d, e, f};
+      memcpy(m.affine, k, sizeof(k));
+      return m;
+    };
+    EXPECT(window_is(id, 300, 500, 300, 500, 0, 0, 300, 500), "source window: the identity is not the raster");
+    EXPECT(window_is(id, 9, 8, 3, 5, 0, 0, 6, 8), "source window: the identity of 3 x 5 over 9 x 8");
+    EXPECT(window_is(affine(1, 0, 100, 0, 1, 50), 300, 500, 10, 20, 47, 97, 16, 26), "source window: a shift by (100, 50)");
+    EXPECT(window_is(affine(1, 0, -2.5, 0, 1, 0), 300, 500, 5, 3, 0, 0, 8, 4), "source window: a shift that leaves one column inside");
+    EXPECT(misses(affine(1, 0, -4.5, 0, 1, 0), 300, 500, 5, 3), "source window: two pixels left of the raster");
+    EXPECT(window_is(affine(1, 0, 0, 0, 1, 299.75), 300, 500, 7, 7, 297, 0, 3, 10), "source window: within a pixel below the raster");
+    EXPECT(misses(affine(1, 0, 0, 0, 1, 300.5), 300, 500, 7, 7), "source window: a pixel below the raster");
+    EXPECT(misses(affine(1, 0, 600, 0, 1, 0), 300, 500, 5, 5), "source window: right of the raster");
+    EXPECT(misses(affine(1, 0, 0, 0, 1, -50), 300, 500, 9, 9), "source window: above the raster");
+    EXPECT(window_is(affine(1e6, 0, -1e9, 0, 1e6, -1e9), 300, 500, 65536, 65536, 0, 0, 300, 500), "source window: a huge footprint is clipped");
+    {  // a grid: the nodes' hull; non-finite nodes are left out; none finite misses
+      double gx[12], gy[12];
+      for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 4; k++) gx[i * 4 + k] = 10.0 + 2.5 * k, gy[i * 4 + k] = 20.0 + 1.5 * i;
+      fra_warp_map g = gj.map;
+      g.gx = gx; g.gy = gy;
+      EXPECT(window_is(g, 300, 500, 3, 5, 17, 7, 10, 14), "source window: a grid's hull");
+      gx[5] = NAN; gy[0] = HUGE_VAL; gx[11] = 4000.0; gy[11] = NAN;
+      EXPECT(window_is(g, 300, 500, 3, 5, 17, 7, 10, 14), "source window: non-finite nodes are left out");
+      for (double& v : gx) v = NAN;
+      EXPECT(misses(g, 300, 500, 3, 5), "source window: no finite node");
+    }
+    // every tap of every inside pixel lies in the window: rotations and scales about the raster, the cubic's reach
+    for (int deg = 0; deg < 360; deg += 17)
+      for (double scale : {0.3, 1.0, 1.9, 7.5}) {
+        const int H = 300, W = 500, oh = 70, ow = 300;
+        const double c = scale * std::cos(deg * M_PI / 180.0), s = scale * std::sin(deg * M_PI / 180.0);
+        const fra_warp_map m = affine(c, -s, 250.0 - (c * 150 - s * 35), s, c, 150.0 - (s * 150 + c * 35));
+        fra_window x{};
+        const int rc = fra_warp_source_window(&m, H, W, oh, ow, &x);
+        bool ok = rc == 0 || (rc == 1 && x.row_off >= 0 && x.col_off >= 0 && x.height >= 1 && x.width >= 1 && x.row_off + x.height <= H && x.col_off + x.width <= W);
+        for (int R = 0; R < oh && ok; R++)
+          for (int C = 0; C < ow && ok; C++) {
+            const double u = C + 0.5, v = R + 0.5;
+            const double px = (m.affine[0] * u + m.affine[1] * v) + m.affine[2], py = (m.affine[3] * u + m.affine[4] * v) + m.affine[5];
+            if (!(px >= 0 && px < W && py >= 0 && py < H)) continue;
+            const int i0 = (int)std::floor(px - 0.5), j0 = (int)std::floor(py - 0.5);
+            ok = rc == 1 && std::max(i0 - 1, 0) >= x.col_off && std::min(i0 + 2, W - 1) < x.col_off + x.width &&
+                 std::max(j0 - 1, 0) >= x.row_off && std::min(j0 + 2, H - 1) < x.row_off + x.height;
+          }
+        EXPECT(ok, "source window: rotation %d, scale %g: a tap lies outside (%d, %d, %d x %d)", deg, scale, x.row_off, x.col_off, x.height, x.width);
+      }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
   {
