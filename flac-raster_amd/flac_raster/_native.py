@@ -239,6 +239,21 @@ class ZonalRec(C.Structure):
 
 assert C.sizeof(ZonalRec) == 112 and C.sizeof(ZonalOpts) == 32 and C.sizeof(ZonalJob) == 120
 
+
+class RasterizeJob(C.Structure):
+    """``fra_rasterize_job`` (128 bytes; the rule: ``rasterize.py``)."""
+
+    _fields_ = [
+        ("xy", C.c_void_p), ("nverts", C.c_int64), ("ring_start", C.c_void_p), ("nrings", C.c_int64),
+        ("feature_ring_start", C.c_void_p), ("nfeatures", C.c_int32), ("values", C.c_void_p), ("dtype", C.c_int32),
+        ("row_off", C.c_int64), ("col_off", C.c_int64), ("height", C.c_int32), ("width", C.c_int32),
+        ("fill", C.c_int64), ("dst", C.c_void_p), ("dst_on_device", C.c_int32), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64),
+    ]
+
+
+assert C.sizeof(RasterizeJob) == 128
+
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 ZONAL_NODATA, ZONAL_IGNORE = 1, 2
 CALC_NODATA = 1
@@ -302,6 +317,7 @@ EXPORTS = [
     "fra_focal_check", "fra_focal", "fra_decode_device_focal", "fra_focal_timing",
     "fra_zonal", "fra_decode_device_zonal", "fra_zonal_timing",
     "fra_warp", "fra_decode_device_warped", "fra_warp_source_window", "fra_warp_timing", "fra_warp_paths",
+    "fra_rasterize", "fra_rasterize_timing",
 ]
 
 
@@ -422,6 +438,9 @@ def load():
             L.fra_warp_source_window.argtypes = [C.POINTER(WarpMap), i32, i32, i32, i32, C.POINTER(Window)]
             L.fra_warp_timing.argtypes = [C.POINTER(C.c_float)]
             L.fra_warp_paths.argtypes = [C.POINTER(u64)]
+        if hasattr(L, "fra_rasterize"):
+            L.fra_rasterize.argtypes = [vp, C.POINTER(RasterizeJob), C.POINTER(u64)]
+            L.fra_rasterize_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -1319,6 +1338,50 @@ class Context:
         counts = (C.c_uint64 * 2)()
         _check(load().fra_warp_paths(counts))
         return int(counts[0]), int(counts[1])
+
+    def rasterize(self, features, window_or_shape, values=None, fill=0, dtype=np.int32, dst=None, *, dst_strides=None):
+        """Polygon features burned into an integer raster on this context's GPU (``fra_rasterize``, the rule of
+        ``flac_raster.rasterize.rasterize_arrays``).
+
+        ``features``: a list of features, each a list of rings, each ``(n, 2)`` pixel coordinates.
+        ``window_or_shape``: ``(h, w)`` or ``(row_off, col_off, h, w)``.  ``values``: an integer per feature (default
+        ``i + 1``).  ``dst``: ``None`` (a new array), a numpy array ``(h, w)`` of ``dtype`` with any non-negative
+        strides, or a device pointer (int) with element ``dst_strides`` = (row, column), default ``(w, 1)``.  Returns
+        ``(raster, burned)``, the raster ``None`` for a device pointer."""
+        from .rasterize import burn_values, flatten, window_of
+
+        row_off, col_off, h, w = window_of(window_or_shape)
+        features = list(features)
+        xy, ring_start, feat_start = flatten(features)
+        vals, fill, dt = burn_values(values, len(features), fill, dtype)
+        job = RasterizeJob()
+        job.xy, job.nverts = C.c_void_p(xy.ctypes.data), xy.shape[0]
+        job.ring_start, job.nrings = C.c_void_p(ring_start.ctypes.data), ring_start.size - 1
+        job.feature_ring_start, job.nfeatures = C.c_void_p(feat_start.ctypes.data), feat_start.size - 1
+        job.values, job.dtype = C.c_void_p(vals.ctypes.data), DTYPE_CODES[dt]
+        job.row_off, job.col_off, job.height, job.width, job.fill = row_off, col_off, h, w, fill
+        ret = dst
+        if dst is None:
+            ret = dst = np.zeros((h, w), dtype=dt)
+        if isinstance(dst, np.ndarray):
+            if dst.shape != (h, w) or dst.dtype != dt:
+                raise ValueError(f"dst must be {(h, w)} of {dt}, got {dst.shape} of {dst.dtype}")
+            if any(st % dt.itemsize for st in dst.strides):
+                raise ValueError("dst's strides must be whole elements")
+            job.dst, job.dst_on_device = C.c_void_p(dst.ctypes.data), 0
+            job.row_stride, job.col_stride = (st // dt.itemsize for st in dst.strides)
+        else:
+            job.dst, job.dst_on_device, ret = C.c_void_p(int(dst)), 1, None
+            job.row_stride, job.col_stride = (int(v) for v in dst_strides) if dst_strides is not None else (w, 1)
+        burned = C.c_uint64()
+        _check(load().fra_rasterize(self.h, C.byref(job), C.byref(burned)))
+        return ret, int(burned.value)
+
+    def rasterize_timing(self) -> float:
+        """HIP-event ms of this thread's last ``k_rasterize`` (:meth:`rasterize`)."""
+        ms = C.c_float()
+        _check(load().fra_rasterize_timing(C.byref(ms)))
+        return ms.value
 
     def decode_timing(self) -> List[float]:
         """HIP-event ms of this thread's last ``decode_device`` / ``decode_device_window``: parse, restore, scatter,

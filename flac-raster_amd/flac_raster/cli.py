@@ -471,7 +471,10 @@ def stats(
 @app.command()
 def zonal(
     file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
-    zones: Path = typer.Option(..., "--zones", "-z", help="Single-band integer GeoTIFF of the same shape: the zones"),
+    zones: Path = typer.Option(..., "--zones", "-z", help="Single-band integer GeoTIFF of the same shape: the zones; or "
+                               "a GeoJSON file (.geojson, .json) of polygons in the source's CRS"),
+    attribute: Optional[str] = typer.Option(None, "--attribute", "-a", help="With GeoJSON zones: the integer property "
+                                            "that names a feature's zone (default: feature i is zone i + 1)"),
     bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
     pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width'"),
     nodata: Optional[float] = typer.Option(None, "--nodata", help="Nodata value (default: a source TIFF's own tag)"),
@@ -482,8 +485,9 @@ def zonal(
     cpu: bool = typer.Option(False, "--cpu", help="Decode and reduce on the host (numpy)"),
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
 ):
-    """Per-zone band statistics of a streaming FLAC file or a GeoTIFF over the zones of a GeoTIFF."""
-    from .streaming import zonal_with_tiff
+    """Per-zone band statistics of a streaming FLAC file or a GeoTIFF over the zones of a GeoTIFF or the polygons of a
+    GeoJSON file."""
+    from .streaming import zonal_with_polygons, zonal_with_tiff
     from .zonal import display_zonal_table, export_report
 
     try:
@@ -501,8 +505,19 @@ def zonal(
         box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
         win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
         dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
-        report, got, _ = zonal_with_tiff(path, zones, window=win, bbox=box, nodata=nodata, ignore=ignore, device=dev,
-                                         semantics=semantics)
+        if zones.suffix.lower() in (".geojson", ".json"):
+            if ignore is not None:
+                console.print("[red]Error: --ignore goes with a zones GeoTIFF: polygons leave the pixels outside them "
+                              "out already[/red]")
+                raise typer.Exit(1)
+            report, got, _ = zonal_with_polygons(path, zones, attribute=attribute, window=win, bbox=box, nodata=nodata,
+                                                 device=dev, semantics=semantics)
+        else:
+            if attribute is not None:
+                console.print("[red]Error: --attribute goes with GeoJSON zones[/red]")
+                raise typer.Exit(1)
+            report, got, _ = zonal_with_tiff(path, zones, window=win, bbox=box, nodata=nodata, ignore=ignore, device=dev,
+                                             semantics=semantics)
         display_zonal_table(report, title=f"{path.name} by {zones.name}: rows {got[0]}..{got[0] + got[2]}, columns "
                                           f"{got[1]}..{got[1] + got[3]}")
         if export is not None:
@@ -511,6 +526,52 @@ def zonal(
         raise
     except Exception as e:
         logger.exception("Zonal statistics failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
+@app.command()
+def rasterize(
+    shapes: Path = typer.Argument(..., help="GeoJSON file of polygons, in the CRS of --like"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF (one band)"),
+    like: Path = typer.Option(..., "--like", help="Streaming FLAC file or GeoTIFF whose grid the output takes"),
+    attribute: Optional[str] = typer.Option(None, "--attribute", "-a", help="Burn this integer property of every feature "
+                                            "(default: feature i burns i + 1)"),
+    burn: Optional[int] = typer.Option(None, "--burn", help="Burn this value for every feature"),
+    fill: int = typer.Option(0, "--fill", help="What a pixel outside every polygon gets; the output's nodata tag"),
+    dtype: Optional[str] = typer.Option(None, "--dtype", help="uint8, int8, uint16, int16, uint32 or int32 (default: the "
+                                        "narrowest that holds the values)"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width'"),
+    cpu: bool = typer.Option(False, "--cpu", help="Rasterize with numpy on the host"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Polygons of a GeoJSON file burned onto the grid of a streaming FLAC file or a GeoTIFF -> GeoTIFF."""
+    from .streaming import rasterize_to_tiff
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        if attribute is not None and burn is not None:
+            console.print("[red]Error: give at most one of --attribute and --burn[/red]")
+            raise typer.Exit(1)
+        for p in (shapes, like):
+            if not p.exists():
+                console.print(f"[red]File not found: {p}[/red]")
+                raise typer.Exit(1)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        got, burned, dt = rasterize_to_tiff(like, shapes, output_path, attribute=attribute, burn=burn, window=win, bbox=box,
+                                            fill=fill, dtype=dtype, device=dev)
+        console.print(f"[green]{output_path}[/green]: {dt}, rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
+                      f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
+        console.print(f"burned: {burned} pixels, {100.0 * burned / (got[2] * got[3]):.2f}% of the window")
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Rasterizing failed")
         console.print(f"[red]Error: {e}[/red]")
         raise typer.Exit(1)
 

@@ -847,6 +847,172 @@ def zonal_with_tiff(source: Path, zones_tiff: Path, window: Optional[Sequence[in
     return _container_zonal(meta, win, blob, items, crop[0], nodata, ignore, device, semantics), win, meta
 
 
+# ------------------------------------------------------------------------------------------ polygons
+def _is_tiff(path: Path) -> bool:
+    with open(path, "rb") as f:
+        return f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
+
+
+def _label_dtype(values, fill) -> np.dtype:
+    """The narrowest of the six label dtypes that holds every burn value and the fill."""
+    lo, hi = min([int(fill)] + [int(v) for v in values]), max([int(fill)] + [int(v) for v in values])
+    for t in ((np.uint8, np.uint16, np.uint32) if lo >= 0 else (np.int8, np.int16, np.int32)):
+        if np.iinfo(t).min <= lo and hi <= np.iinfo(t).max:
+            return np.dtype(t)
+    raise ValueError(f"burn values {lo} .. {hi} do not fit an integer dtype of 32 bits")
+
+
+def _pixel_features(geojson, attribute, transform):
+    """The polygons of a GeoJSON file in pixel coordinates of a grid, and their values."""
+    from .rasterize import read_geojson, to_pixel
+
+    if not transform:
+        raise ValueError("the source has no transform: polygons cannot be placed on its grid")
+    features, values = read_geojson(geojson, attribute)
+    return to_pixel(features, Affine(*list(transform)[:6])), values
+
+
+def _burn(pix, win, values, fill, dt, device):
+    """``(raster, burned)`` of the window on the host (``device=None``) or on a GPU."""
+    from . import _native
+    from .rasterize import rasterize_arrays
+
+    if device is None:
+        return rasterize_arrays(pix, win, values, fill, dt)
+    return _native.default_context(int(device)).rasterize(pix, win, values, fill, dt)
+
+
+def _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype, device):
+    """:func:`rasterize_like` with ``burn`` (one value for every feature, or ``None``) and the burned count."""
+    source = Path(source)
+    if burn is not None and attribute is not None:
+        raise ValueError("give at most one of an attribute and a burn value")
+    if _is_tiff(source):
+        g = GeoTIFF(source)
+        try:
+            info = g.info
+            t, shape = (list(info.transform) if info.transform is not None else None), (info.height, info.width)
+            crs = str(info.crs) if info.crs is not None and str(info.crs) else None
+        finally:
+            g.close()
+    elif is_streaming_container(source):
+        index = open_streaming(source).index
+        t, shape, crs = index.get("transform"), (int(index["height"]), int(index["width"])), index.get("crs")
+        crs = crs if crs and crs != "None" else None
+    else:
+        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    pix, values = _pixel_features(geojson, attribute, t)
+    if burn is not None:
+        values = [int(burn)] * len(pix)
+    win = (0, 0) + shape if window is None and bbox is None else resolve_window(
+        {"height": shape[0], "width": shape[1], "transform": t}, window, bbox)
+    dt = _label_dtype(values, fill) if dtype is None else np.dtype(dtype)
+    raster, burned = _burn(pix, win, values, fill, dt, device)
+    return raster, win, tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]), crs, burned
+
+
+def rasterize_like(source, geojson, attribute: Optional[str] = None, window: Optional[Sequence[int]] = None,
+                   bbox: Optional[Sequence[float]] = None, fill: int = 0, dtype=None, device: Optional[int] = None):
+    """The polygons of a GeoJSON file (a path or the parsed object; its coordinates are taken to be in the source's
+    CRS) burned onto the grid of ``source`` -- a streaming container or a GeoTIFF -- or onto a window of it ->
+    ``(raster (h, w), window, transform of the window, crs)``.
+
+    Feature ``i`` burns ``i + 1``, or its integer property ``attribute``; ``fill`` elsewhere.  ``dtype=None`` picks the
+    narrowest of the six label dtypes that holds them.  ``device=None`` applies ``rasterize.rasterize_arrays``, an
+    integer makes one ``fra_rasterize`` call on that GPU; both are given the same pixel coordinates."""
+    return _rasterize_like(source, geojson, attribute, None, window, bbox, fill, dtype, device)[:4]
+
+
+def rasterize_to_tiff(source, geojson, tiff_path: Path, attribute: Optional[str] = None, burn: Optional[int] = None,
+                      window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None, fill: int = 0,
+                      dtype=None, device: Optional[int] = None):
+    """:func:`rasterize_like` into a single-band GeoTIFF on the source's grid with the fill as its nodata tag; ``burn``:
+    one value for every feature instead of ``i + 1`` or an attribute.  Returns ``(window, burned, dtype)``."""
+    from .tiff import write_geotiff
+
+    raster, win, transform, crs, burned = _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype,
+                                                          device)
+    write_geotiff(Path(tiff_path), raster[None], transform=transform, crs=crs, nodata=int(fill))
+    return win, burned, raster.dtype
+
+
+def zonal_with_polygons(source, geojson, attribute: Optional[str] = None, window: Optional[Sequence[int]] = None,
+                        bbox: Optional[Sequence[float]] = None, nodata: Optional[float] = None,
+                        device: Optional[int] = None, semantics: str = "pcm16"):
+    """Zonal statistics of ``source`` -- a streaming container or a GeoTIFF -- over the polygons of a GeoJSON file ->
+    ``(report, window, index or info)``.  Feature ``i`` is zone ``i + 1``, or the zone of its integer property
+    ``attribute`` (features may share one); 0 is the fill and no zone, so a label of 0 is refused.
+
+    The labels are burned for the window only.  ``device=None``: ``zonal.zonal_arrays`` over
+    ``rasterize.rasterize_arrays``.  On a GPU ``fra_rasterize`` burns them into a device buffer that goes to
+    ``fra_decode_device_zonal`` / ``fra_zonal`` as it is: the label raster never visits the host.  Labels spread over
+    more than 65536 values are burned as dense ids (``zonal.dense_zones``) and the report carries the labels."""
+    from . import _native
+    from .zonal import dense_zones, report_from_recs, zonal_arrays
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    source = Path(source)
+    a = blob = items = None
+    if _is_tiff(source):
+        g = GeoTIFF(source)
+        try:
+            meta = g.info
+            t = list(meta.transform) if meta.transform is not None else None
+            win = _tiff_window(g, window, bbox)
+            if nodata is None and meta.nodata is not None:
+                nodata = float(meta.nodata)
+            a = np.zeros((meta.count, win[2], win[3]), dtype=np.dtype(meta.dtype))
+            g.read_window_into(a, *win)
+        finally:
+            g.close()
+        src_dt, B = a.dtype, a.shape[0]
+    else:
+        if window is None and bbox is None:
+            window = _whole_window(source)
+        meta, win, blob, items = _window_items(source, window, bbox)
+        t = meta.get("transform")
+        src_dt, B = np.dtype(meta["dtype"]), int(meta["bands"])
+    pix, values = _pixel_features(geojson, attribute, t)
+    if any(int(v) == 0 for v in values):
+        raise ValueError("a zone label of 0 is not possible: 0 is what the pixels outside every polygon get")
+    if values:
+        _, zone_lo, nzones, labels = dense_zones(np.asarray(values, dtype=np.int64))
+    else:
+        zone_lo, nzones, labels = 1, 1, None
+    if labels is None and values and not -2**31 <= min(values) <= max(values) <= 2**31 - 1:
+        labels = np.unique(np.asarray(values, dtype=np.int64))  # close together, but past 32 bits
+    if labels is not None:  # dense ids 1 ... n stand for the labels
+        values, zone_lo, nzones = (np.searchsorted(labels, np.asarray(values, dtype=np.int64)) + 1).tolist(), 1, labels.size
+    zdt = _label_dtype(values, 0)
+    h, w = win[2], win[3]
+    if device is None:
+        zones, _ = _burn(pix, win, values, 0, zdt, None)
+        if a is None:
+            a = np.zeros((B, h, w), dtype=src_dt)
+            _decode_window_on_host(blob, items, win, a, semantics)
+        rep = zonal_arrays(a, zones, zone_lo, nzones, nodata=nodata, ignore=0)
+        if labels is not None:
+            for band in rep:
+                for rec in band["zones"]:
+                    rec["zone"] = int(labels[rec["zone"] - 1])
+        return rep, win, meta
+    ctx = _native.default_context(int(device))
+    d_zones = ctx.alloc(h * w * zdt.itemsize)
+    try:
+        ctx.rasterize(pix, win, values, 0, zdt, dst=d_zones)
+        if a is not None:
+            recs, outside = ctx.zonal(a, d_zones, zone_lo, nzones, nodata, 0, zone_dtype=zdt, zone_strides=(w, 1))
+        else:
+            denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+            recs, outside, _ = ctx.decode_device_zonal(np.frombuffer(blob, dtype=np.uint8), items, d_zones, src_dt, B, win,
+                                                       denorm, zone_lo, nzones, nodata, 0, zone_dtype=zdt,
+                                                       zone_strides=(w, 1))
+    finally:
+        ctx.free(d_zones)
+    return report_from_recs(recs, outside, src_dt, zone_lo, labels), win, meta
+
+
 # ------------------------------------------------------------------------------------------ band math
 def _calc_fill(fill, out_dtype):
     from .calc import default_fill

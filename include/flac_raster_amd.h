@@ -964,6 +964,61 @@ FRA_API int fra_warp_timing(float *ms);
  * built) and that gathered them from global memory (counts[1]: all of them) */
 FRA_API int fra_warp_paths(uint64_t counts[2]);
 
+/* Rasterizing polygons: vector features burned into an integer raster -- zones and masks for the units above -- by a rule
+ * that flac_raster/rasterize.py restates in numpy (rasterize_arrays).  All arithmetic is IEEE f64, every operation
+ * rounded on its own, nothing contracted.
+ *   Input: nfeatures features in order.  Feature f is the rings feature_ring_start[f] .. feature_ring_start[f + 1] - 1,
+ *     ring r the vertices ring_start[r] .. ring_start[r + 1] - 1 of xy (x, y interleaved), at least 3 of them, in PIXEL
+ *     coordinates of the raster the output window belongs to (x along columns, y along rows).  Exterior rings, holes
+ *     and the parts of a multipolygon are not told apart.  values[f] is the feature's burn value.  All of these arrays
+ *     are host memory.
+ *   Output: the window (row_off, col_off, height, width).  Pixel (r, c) has the centre
+ *     xc = (double)(col_off + c) + 0.5, yc = (double)(row_off + r) + 0.5.
+ *   Edges: a ring is closed implicitly (last -> first; a repeated closing vertex gives an edge of no length, dropped
+ *     next).  An edge with y0 == y1 is dropped.  Every other edge is oriented so that y0 < y1, its endpoints swapped if
+ *     need be before any arithmetic: two features that share an edge compute the same numbers for it.
+ *   Crossing: an edge crosses the scanline of yc when y0 <= yc && yc < y1.  Then t = (yc - y0) / (y1 - y0) and
+ *     xi = x0 + t * (x1 - x0); the edge counts for the pixel when xi > xc.
+ *   Coverage: a feature covers the pixel when an odd number of its edges count, over all its rings (even-odd).
+ *   Burn: the pixel's value is the burn value of the covering feature with the highest index (painter's order, as GDAL
+ *     burns); `fill` without one.  *burned: the pixels of the window covered by at least one feature.
+ *   Output dtype: FRA_U8, FRA_I8, FRA_U16, FRA_I16, FRA_U32 or FRA_I32 (the zone dtypes of fra_zonal).
+ * So the square [2.5, 10.5] x [2.5, 8.5] covers columns 2..9 and rows 2..7 (half-open on both axes), two features
+ * that share an edge never both cover a pixel nor both miss one between them, and the result does not depend on a
+ * ring's orientation, on its first vertex or on any binning.
+ *   FRA_E_INVALID before any GPU work, in this order: a null argument (ctx, job, dst; a geometry array that its count
+ *   makes needed); a dtype outside the six; height or width outside 1 .. 65536; a negative stride; negative counts,
+ *   feature_ring_start not ascending from 0 to nrings, ring_start not ascending from 0 or past nverts; a ring of fewer
+ *   than 3 vertices; a coordinate that is not finite or above 2^52 in magnitude; a burn value, then a fill, the dtype
+ *   does not hold; more than 2^24 features; more than 2^28 vertices.  nfeatures == 0 is valid: the fill everywhere,
+ *   *burned = 0.  FRA_E_NOMEM when the band lists below would pass 2^31 - 1 entries.
+ * The host builds the edge table and one list of edges per band of 16 output rows (an edge is in the list of every band
+ * one of whose row centres its [y0, y1) contains; feature order, and edge order within a feature, are kept).
+ * k_rasterize: one 256-thread workgroup per 16 x 64 output tile walks its band's list in chunks, computes xi once per
+ * (edge, row) into LDS and lets every thread toggle the parity of its 4 pixels (fra_rasterize.hip). */
+typedef struct {
+  const double *xy;                     /* nverts x (x, y) */
+  int64_t nverts;
+  const int64_t *ring_start;            /* nrings + 1 */
+  int64_t nrings;
+  const int64_t *feature_ring_start;    /* nfeatures + 1 */
+  int32_t nfeatures;
+  const int64_t *values;                /* nfeatures */
+  int32_t dtype;                        /* of the output */
+  int64_t row_off, col_off;
+  int32_t height, width;
+  int64_t fill;
+  void *dst;
+  int32_t dst_on_device;
+  int64_t row_stride, col_stride;       /* in elements, non-negative */
+} fra_rasterize_job;                    /* 128 bytes */
+/* Synchronous.  A host dst is staged whole, from its element 0 to the last one addressed, and copied back whole (as
+ * fra_warp stages it): the elements between the outputs keep the caller's values.  Every device allocation is per call
+ * and released on every path. */
+FRA_API int fra_rasterize(fra_ctx *ctx, const fra_rasterize_job *job, uint64_t *burned /* may be NULL */);
+/* HIP-event time (ms) of the calling thread's last k_rasterize and its fold */
+FRA_API int fra_rasterize_timing(float *ms);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -119,6 +119,18 @@ its values reach (the launches of the other windows leave without reading).  It 
 
     python tools/bench_decode.py --stats --steps 5 --warmup 2
 
+``--rasterize KIND`` times the polygon rasterizer (``fra_rasterize``: the edge table and band lists on the host, then
+``k_rasterize`` and its fold) over the scene's grid into a device-resident uint16 raster, ``--rasterize`` may be repeated.
+``blocks:N`` burns the N x N squares of ``--zonal blocks:N`` as four-edge polygons (feature i burns zone i) and exits
+non-zero unless the result equals that pattern's block raster exactly; ``circle:V`` burns one V-gon inscribed in the scene
+-- every band then holds edges of one feature, over several chunks of the kernel -- and is checked on three 64 x 512
+rectangles against ``rasterize.rasterize_arrays``.  Per leg ``k_rasterize_ms`` (``fra_rasterize_timing``), the call's wall
+time (host binning and uploads included), the features, the edges of the band lists and the longest list.  Beside them,
+in the same session, the plain read, ``k_calc``'s one-band uint16 copy and, with ``--zonal blocks:N``, ``k_zonal_ms`` of
+``fra_decode_device_zonal`` over the labels just burned, which never leave the device.
+
+    python tools/bench_decode.py --rasterize blocks:256 --zonal blocks:256 --rasterize circle:100000 --steps 5 --warmup 2
+
 ``--zonal PATTERN`` times the zonal statistics of the same container (``fra_decode_device_zonal``: the whole raster
 decoded to uint16 and reduced per zone there, only the records come back) over a uint16 zone raster synthesised on the
 host and resident on the device: ``blocks:N`` (squares of N x N pixels, ``blocks:256`` = 43 x 43 = 1849 zones),
@@ -284,6 +296,10 @@ def main():
                     help="time the band statistics and histograms of the container against the plain read")
     ap.add_argument("--zonal", default=None, metavar="PATTERN",
                     help="time fra_decode_device_zonal over a synthetic zone raster: blocks:N, const or random:N")
+    ap.add_argument("--rasterize", action="append", default=None, metavar="KIND",
+                    help="time fra_rasterize over the scene's grid into a resident uint16 raster: blocks:N (the squares of "
+                         "--zonal blocks:N as polygons) or circle:V (one V-gon inscribed in the scene); with --zonal "
+                         "blocks:N the zonal statistics then run over the burned labels")
     ap.add_argument("--calc", action="append", default=None, metavar="EXPR",
                     help="time band math over the container against the plain read: one expression per output band, "
                          "separated by ';', optionally followed by ':dtype'; repeat for further legs of the same run")
@@ -562,6 +578,113 @@ def main():
         res["all_ms"] = {"plain": [round(v, 3) for v in plain_ms], "plain_wall": [round(v, 3) for v in plain_wall]}
         print(json.dumps(res), flush=True)
         plan.close()
+        ctx.free(dev_out)
+        ctx.free(dev_raster)
+        return
+
+    if args.rasterize:
+        import math
+
+        from flac_raster.calc import compile_exprs, default_fill
+        from flac_raster.rasterize import edge_table, rasterize_arrays
+
+        if len(wins) != len(calculate_tiles(H, W, TILE)):
+            raise SystemExit("--rasterize needs every tile: the grid is the whole raster's")
+        roi = (0, 0, H, W)
+        citems = [dict(it, data_min=inf.data_min, data_max=inf.data_max) for it, inf in zip(items, infos)]
+        med = statistics.median
+        zdt = np.dtype(np.uint16)
+        dev_zones = ctx.alloc(H * W * zdt.itemsize)
+        plain_ms, kcopy = [], []
+        copy = compile_exprs(["b1"], B)
+        for s in range(args.warmup + args.steps):
+            ctx.decode_device_window((frames_ptr, total), citems, dev_out, dt, B, (H * W, W, 1), roi, N.DENORM_PCM16)
+            if s >= args.warmup:
+                plain_ms.append(ctx.decode_timing()[3])
+            ctx.decode_device_calc((frames_ptr, total), citems, dt, B, roi, copy, zdt, dst=dev_zones, denorm=N.DENORM_PCM16,
+                                   nodata=None, fill=default_fill(zdt))
+            if s >= args.warmup:
+                kcopy.append(ctx.calc_timing())
+        res = {
+            "workload": f"rasterize onto the C4-like grid {W}x{H}, uint16 labels resident on the device",
+            "steps": args.steps, "warmup": args.warmup, "plain_ms": round(med(plain_ms), 3),
+            "k_calc_copy_one_band_ms": round(med(kcopy), 4), "label_raster_bytes": H * W * zdt.itemsize, "legs": [],
+        }
+        got = np.empty((H, W), zdt)
+        for spec in args.rasterize:
+            kind, _, arg = spec.partition(":")
+            if kind == "blocks":
+                n = int(arg or 256)
+                per_row = -(-W // n)
+                feats = [[[(c0, r0), (min(c0 + n, W), r0), (min(c0 + n, W), min(r0 + n, H)), (c0, min(r0 + n, H))]]
+                         for r0 in range(0, H, n) for c0 in range(0, W, n)]
+                values, fill = list(range(len(feats))), 65535
+                if len(feats) > 65535:
+                    raise SystemExit(f"--rasterize {spec}: {len(feats)} squares do not fit uint16 labels beside the fill")
+            elif kind == "circle":
+                v = int(arg or 100000)
+                rad = 0.5 * min(H, W) - 1.0
+                feats = [[[(0.5 * W + rad * math.cos(2.0 * math.pi * k / v), 0.5 * H + rad * math.sin(2.0 * math.pi * k / v))
+                           for k in range(v)]]]
+                values, fill = [1], 0
+            else:
+                raise SystemExit("--rasterize takes blocks:N or circle:V")
+            wall, kr = [], []
+            for s in range(args.warmup + args.steps):
+                t0 = time.perf_counter()
+                _, burned = ctx.rasterize(feats, roi, values, fill, zdt, dst=dev_zones)
+                t1 = time.perf_counter()
+                if s >= args.warmup:
+                    wall.append((t1 - t0) * 1e3)
+                    kr.append(ctx.rasterize_timing())
+            ctx.d2h(got, dev_zones)
+            _, y0, _, y1, _ = edge_table(feats)
+            first = np.clip(np.ceil(y0 - 0.5), 0, H).astype(np.int64)       # the rows whose centres an edge holds
+            last = np.clip(np.ceil(y1 - 0.5) - 1, -1, H - 1).astype(np.int64)
+            ok = first <= last
+            lists = np.zeros(-(-H // 16) + 1, np.int64)
+            np.add.at(lists, first[ok] // 16, 1)
+            np.add.at(lists, last[ok] // 16 + 1, -1)
+            lists = np.cumsum(lists)[:-1]
+            leg = {"rasterize": spec, "features": len(feats), "edges": int(y0.size), "band_list_entries": int(lists.sum()),
+                   "longest_band_list": int(lists.max()), "burned": burned, "rasterize_wall_ms": round(med(wall), 3),
+                   "k_rasterize_ms": round(med(kr), 4), "k_rasterize_over_calc_copy": round(med(kr) / med(kcopy), 3),
+                   "all_ms": {"k_rasterize": [round(x, 4) for x in kr], "rasterize_wall": [round(x, 3) for x in wall]}}
+            if kind == "blocks":
+                zones = ((np.arange(H, dtype=np.uint32)[:, None] // n) * per_row
+                         + np.arange(W, dtype=np.uint32)[None, :] // n).astype(zdt)
+                if burned != H * W or got.tobytes() != zones.tobytes():
+                    raise SystemExit(f"rasterize {spec}: the result differs from the block raster")
+                leg["equals_block_raster"] = True
+                if args.zonal == spec:
+                    nzones = len(feats)
+                    zwall, inner, kz = [], [], []
+                    for s in range(args.warmup + args.steps):
+                        t0 = time.perf_counter()
+                        recs, outside, _ = ctx.decode_device_zonal((frames_ptr, total), citems, dev_zones, dt, B, roi,
+                                                                   N.DENORM_PCM16, 0, nzones, zone_dtype=zdt,
+                                                                   zone_strides=(W, 1))
+                        t1 = time.perf_counter()
+                        if s >= args.warmup:
+                            zwall.append((t1 - t0) * 1e3)
+                            inner.append(ctx.decode_timing()[3])
+                            kz.append(ctx.zonal_timing())
+                    counts = np.bincount(zones.ravel(), minlength=nzones)
+                    if outside != 0 or not np.array_equal(recs["count"][0], counts.astype(np.uint64)):
+                        raise SystemExit(f"zonal over the burned {spec}: the zone counts differ from np.bincount")
+                    leg.update({"nzones": nzones, "zonal_wall_ms": round(med(zwall), 3), "inner_read_ms": round(med(inner), 3),
+                                "k_zonal_ms": round(med(kz), 4), "k_rasterize_over_k_zonal": round(med(kr) / med(kz), 3)})
+                    leg["all_ms"]["k_zonal"] = [round(x, 4) for x in kz]
+            else:
+                for r0, c0 in ((0, W // 2 - 256), (H // 2 - 32, 0), (H - 64 - int(0.146 * H), W - 512 - int(0.146 * W) + 200)):
+                    want, _ = rasterize_arrays(feats, (r0, c0, 64, 512), values, fill, zdt)
+                    if got[r0:r0 + 64, c0:c0 + 512].tobytes() != want.tobytes():
+                        raise SystemExit(f"rasterize {spec}: rows {r0} ..., columns {c0} ... differ from rasterize_arrays")
+                leg["checked_rectangles_equal_rasterize_arrays"] = 3
+            res["legs"].append(leg)
+        print(json.dumps(res), flush=True)
+        plan.close()
+        ctx.free(dev_zones)
         ctx.free(dev_out)
         ctx.free(dev_raster)
         return

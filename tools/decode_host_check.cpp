@@ -14,9 +14,12 @@
 //     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats),
 //     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
 //     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
-//     fra_focal_check), the zonal statistics (fra_zonal, fra_decode_device_zonal) and the warped reads (fra_warp,
-//     fra_decode_device_warped, fra_warp_source_window), which returns before any GPU work, and the order of these
-//     refusals (inputs that break two rules at once);
+//     fra_focal_check), the zonal statistics (fra_zonal, fra_decode_device_zonal), the warped reads (fra_warp,
+//     fra_decode_device_warped, fra_warp_source_window) and the polygon rasterizer (fra_rasterize), which returns
+//     before any GPU work, and the order of these refusals (inputs that break two rules at once);
+//   * the rasterizer's edge table, x-extents and band lists (fra_rasterize.h): closed rings, dropped and oriented
+//     edges, an empty band, a feature spanning all bands, a ring with a repeated closing vertex, and that every
+//     (edge, row) crossing of the rule is in the row's band list, in the edges' order;
 //   * the source-window arithmetic of the warped reads (fra_warp.h source_window): pinned windows, footprints that
 //     miss the raster, non-finite grid nodes, and that every tap of every inside pixel lies in the window;
 //   * the chunk arithmetic of the row-chunk scan (fra_scan.h plan_chunks): invariants and pinned values.
@@ -31,6 +34,7 @@
 #include "../flac-raster_amd/csrc/fra_decode.cpp"  // the host decoder's frame validation (internal linkage)
 #include "../flac-raster_amd/csrc/fra_decode_host.h"
 #include "../flac-raster_amd/csrc/fra_scan.h"
+#include "../flac-raster_amd/csrc/fra_rasterize.h"
 #include "../flac-raster_amd/csrc/fra_warp.h"
 
 static std::string g_msg;
@@ -1025,6 +1029,129 @@ int main(int argc, char** argv) {
           }
         EXPECT(ok, "source window: rotation %d, scale %g: a tap lies outside (%d, %d, %d x %d)", deg, scale, x.row_off, x.col_off, x.height, x.width);
       }
+  }
+  // ... and of the polygon rasterizer (fra_rasterize.hip): refused before any GPU work, in the order the header gives
+  {
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    // feature 0: a square with a repeated closing vertex; feature 1: a triangle and a second ring
+    const double xy[] = {1, 1, 9, 1, 9, 9, 1, 9, 1, 1, /**/ 2, 20, 30, 22, 4, 40, /**/ 10, 3, 12, 3, 11, 5};
+    const int64_t ring_start[] = {0, 5, 8, 11}, feat_start[] = {0, 1, 3}, values[] = {7, -2};
+    int16_t rout[48 * 40];
+    uint64_t burned = 99;
+    fra_rasterize_job rj{};
+    rj.xy = xy; rj.nverts = 11; rj.ring_start = ring_start; rj.nrings = 3; rj.feature_ring_start = feat_start; rj.nfeatures = 2;
+    rj.values = values; rj.dtype = FRA_I16; rj.height = 48; rj.width = 40; rj.fill = -1;
+    rj.dst = rout; rj.row_stride = 40; rj.col_stride = 1;
+    EXPECT(fra_rasterize(nullptr, &rj, &burned) == FRA_E_INVALID, "rasterize: null ctx accepted");
+    EXPECT(fra_rasterize(ctx, nullptr, &burned) == FRA_E_INVALID, "rasterize: null job accepted");
+    { auto j = rj; j.dst = nullptr; EXPECT(says(fra_rasterize(ctx, &j, &burned), "null argument"), "rasterize: null dst: %s", g_msg.c_str()); }
+    { auto j = rj; j.xy = nullptr; EXPECT(says(fra_rasterize(ctx, &j, &burned), "null argument"), "rasterize: null xy: %s", g_msg.c_str()); }
+    { auto j = rj; j.ring_start = nullptr; EXPECT(says(fra_rasterize(ctx, &j, &burned), "null argument"), "rasterize: null ring_start: %s", g_msg.c_str()); }
+    { auto j = rj; j.feature_ring_start = nullptr; EXPECT(says(fra_rasterize(ctx, &j, &burned), "null argument"), "rasterize: null feature_ring_start: %s", g_msg.c_str()); }
+    { auto j = rj; j.values = nullptr; EXPECT(says(fra_rasterize(ctx, &j, &burned), "null argument"), "rasterize: null values: %s", g_msg.c_str()); }
+    for (int d : {-1, (int)FRA_F32, (int)FRA_F64, 8}) { auto j = rj; j.dtype = d; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad output dtype"), "rasterize: dtype %d: %s", d, g_msg.c_str()); }
+    for (int n : {0, -3, 65537}) {
+      { auto j = rj; j.height = n; EXPECT(says(fra_rasterize(ctx, &j, &burned), "output size"), "rasterize: height %d: %s", n, g_msg.c_str()); }
+      { auto j = rj; j.width = n; EXPECT(says(fra_rasterize(ctx, &j, &burned), "output size"), "rasterize: width %d: %s", n, g_msg.c_str()); }
+    }
+    { auto j = rj; j.row_stride = -40; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad output layout"), "rasterize: negative row stride: %s", g_msg.c_str()); }
+    { auto j = rj; j.col_stride = -1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad output layout"), "rasterize: negative column stride: %s", g_msg.c_str()); }
+    { auto j = rj; j.nfeatures = -1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad geometry tables"), "rasterize: -1 features: %s", g_msg.c_str()); }
+    { auto j = rj; j.nrings = -1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad geometry tables"), "rasterize: -1 rings: %s", g_msg.c_str()); }
+    { auto j = rj; j.nverts = -1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad geometry tables"), "rasterize: -1 vertices: %s", g_msg.c_str()); }
+    { auto j = rj; j.nfeatures = 0; EXPECT(says(fra_rasterize(ctx, &j, &burned), "rings of no feature"), "rasterize: rings without features: %s", g_msg.c_str()); }
+    { const int64_t fs[] = {0, 2, 1}; auto j = rj; j.feature_ring_start = fs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "feature_ring_start"), "rasterize: descending feature table: %s", g_msg.c_str()); }
+    { const int64_t fs[] = {1, 1, 3}; auto j = rj; j.feature_ring_start = fs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "feature_ring_start"), "rasterize: feature table from 1: %s", g_msg.c_str()); }
+    { const int64_t fs[] = {0, 1, 2}; auto j = rj; j.feature_ring_start = fs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "feature_ring_start"), "rasterize: feature table short of the rings: %s", g_msg.c_str()); }
+    { const int64_t rs[] = {0, 8, 5, 11}; auto j = rj; j.ring_start = rs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "ring_start"), "rasterize: descending ring table: %s", g_msg.c_str()); }
+    { const int64_t rs[] = {0, 5, 8, 12}; auto j = rj; j.ring_start = rs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "ring_start"), "rasterize: rings past the vertices: %s", g_msg.c_str()); }
+    { const int64_t rs[] = {0, 5, 9, 11}; auto j = rj; j.ring_start = rs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "ring 2 has 2 vertices"), "rasterize: a ring of 2: %s", g_msg.c_str()); }
+    { const int64_t rs[] = {0, 5, 5, 11}; auto j = rj; j.ring_start = rs; EXPECT(says(fra_rasterize(ctx, &j, &burned), "ring 1 has 0 vertices"), "rasterize: an empty ring: %s", g_msg.c_str()); }
+    for (double bad : {(double)NAN, (double)INFINITY, -(double)INFINITY, 9007199254740992.0, -4503599627370497.0}) {
+      double v[22]; memcpy(v, xy, sizeof(v)); v[13] = bad;
+      auto j = rj; j.xy = v; EXPECT(says(fra_rasterize(ctx, &j, &burned), "coordinate 13"), "rasterize: coordinate %g: %s", bad, g_msg.c_str());
+    }
+    { const int64_t v[] = {7, 32768}; auto j = rj; j.values = v; EXPECT(says(fra_rasterize(ctx, &j, &burned), "burn value 32768 of feature 1"), "rasterize: burn 32768 in int16: %s", g_msg.c_str()); }
+    { auto j = rj; j.dtype = FRA_U8; EXPECT(says(fra_rasterize(ctx, &j, &burned), "burn value -2"), "rasterize: burn -2 in uint8: %s", g_msg.c_str()); }
+    { auto j = rj; j.fill = -32769; EXPECT(says(fra_rasterize(ctx, &j, &burned), "fill -32769"), "rasterize: fill -32769 in int16: %s", g_msg.c_str()); }
+    { auto j = rj; j.dtype = FRA_U32; j.fill = (int64_t)1 << 32; const int64_t v[] = {7, 4294967295ll}; j.values = v; EXPECT(says(fra_rasterize(ctx, &j, &burned), "fill 4294967296"), "rasterize: fill 2^32 in uint32: %s", g_msg.c_str()); }
+    {  // more than 2^24 features: empty ones, the tables are still walked
+      std::vector<int64_t> fs((size_t)(1 << 24) + 2, 0), vs((size_t)(1 << 24) + 1, 1);
+      auto j = rj; j.nfeatures = (1 << 24) + 1; j.nrings = 0; j.nverts = 0; j.feature_ring_start = fs.data(); j.values = vs.data();
+      EXPECT(says(fra_rasterize(ctx, &j, &burned), "2^24"), "rasterize: 2^24 + 1 features: %s", g_msg.c_str());
+    }
+    { auto j = rj; j.nverts = ((int64_t)1 << 28) + 1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "2^28"), "rasterize: 2^28 + 1 vertices: %s", g_msg.c_str()); }
+    // the order: an input that breaks two rules gets the message of the first
+    { auto j = rj; j.dtype = 8; j.height = 0; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad output dtype"), "rasterize: dtype 8 and height 0: %s", g_msg.c_str()); }
+    { auto j = rj; j.width = 0; j.col_stride = -1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "output size"), "rasterize: width 0 and a negative stride: %s", g_msg.c_str()); }
+    { auto j = rj; j.row_stride = -1; j.nrings = -1; EXPECT(says(fra_rasterize(ctx, &j, &burned), "bad output layout"), "rasterize: a negative stride and -1 rings: %s", g_msg.c_str()); }
+    { const int64_t rs[] = {0, 5, 9, 11}; double v[22]; memcpy(v, xy, sizeof(v)); v[0] = NAN; auto j = rj; j.ring_start = rs; j.xy = v; EXPECT(says(fra_rasterize(ctx, &j, &burned), "ring 2 has 2"), "rasterize: a ring of 2 and a NaN: %s", g_msg.c_str()); }
+    { double v[22]; memcpy(v, xy, sizeof(v)); v[3] = NAN; auto j = rj; j.xy = v; j.fill = 1 << 20; EXPECT(says(fra_rasterize(ctx, &j, &burned), "coordinate 3"), "rasterize: a NaN and a fill out of range: %s", g_msg.c_str()); }
+    { const int64_t v[] = {70000, 1}; auto j = rj; j.values = v; j.fill = 1 << 20; EXPECT(says(fra_rasterize(ctx, &j, &burned), "burn value 70000"), "rasterize: a burn value and a fill out of range: %s", g_msg.c_str()); }
+    EXPECT(burned == 99, "rasterize: a refusal wrote the burned count");
+    EXPECT(fra_rasterize_timing(nullptr) == FRA_E_INVALID, "rasterize timing: null accepted");
+    // the edge table: rings closed on their first vertex, level edges and the one of no length dropped, y0 < y1
+    EXPECT(fra_rz::check_job(&rj) == FRA_OK, "rasterize: the sample job is refused: %s", g_msg.c_str());
+    std::vector<fra_rz::Edge> edges;
+    std::vector<int32_t> feat;
+    fra_rz::build_edges(&rj, &edges, &feat);
+    // the square: 2 level edges and the closing one dropped -> 2; the triangle 3; the small ring: 1 level -> 2
+    EXPECT(edges.size() == 7 && feat == std::vector<int32_t>({0, 0, 1, 1, 1, 1, 1}), "rasterize: %zu edges", edges.size());
+    bool oriented = true;
+    for (const auto& e : edges) oriented = oriented && e.y0 < e.y1;
+    EXPECT(oriented, "rasterize: an edge is not oriented");
+    EXPECT(edges.size() == 7 && edges[0].x0 == 9 && edges[0].y0 == 1 && edges[0].y1 == 9 && edges[1].x0 == 1 && edges[1].y0 == 1 && edges[1].x1 == 1 && edges[1].y1 == 9,
+           "rasterize: the square's edges");  // (9,1)->(9,9) as it is, (1,9)->(1,1) turned
+    EXPECT(edges.size() == 7 && edges[2].x0 == 2 && edges[2].y1 == 22 && edges[4].x0 == 2 && edges[4].y0 == 20 && edges[4].x1 == 4 && edges[4].y1 == 40,
+           "rasterize: the triangle's edges");  // (2,20)->(30,22) as it is, (4,40)->(2,20) turned
+    std::vector<fra_rz::Extent> ext;
+    fra_rz::extents(edges, feat, 2, &ext);
+    EXPECT(ext.size() == 2 && ext[0].lo <= 1 && ext[0].lo > 0.999 && ext[0].hi >= 9 && ext[0].hi < 9.001 && ext[1].lo <= 2 && ext[1].hi >= 30,
+           "rasterize: extents");
+    { std::vector<fra_rz::Extent> none; fra_rz::extents({}, {}, 1, &none); EXPECT(none.size() == 1 && none[0].lo > none[0].hi, "rasterize: the extent of a feature without edges"); }
+    // the band lists of a 48-row window: band 0 (rows 0..15) the square and the small ring, band 1 the triangle,
+    // band 2 the triangle's lower part; from row 16 on a window of 16 rows holds the triangle alone
+    fra_rz::Bins bins;
+    EXPECT(fra_rz::bin_edges(edges, feat, 0, 48, &bins) == FRA_OK && bins.band_start.size() == 4, "rasterize: bins");
+    EXPECT(bins.band_start == std::vector<uint32_t>({0, 4, 7, 9}), "rasterize: band starts %u %u %u %u", bins.band_start[0], bins.band_start[1], bins.band_start[2], bins.band_start[3]);
+    EXPECT(bins.feat == std::vector<int32_t>({0, 0, 1, 1, 1, 1, 1, 1, 1}), "rasterize: the features of the band lists");
+    fra_rz::Bins empty;  // below every edge: bands without an edge
+    EXPECT(fra_rz::bin_edges(edges, feat, 48, 40, &empty) == FRA_OK && empty.band_start == std::vector<uint32_t>({0, 0, 0, 0}), "rasterize: empty bands");
+    {  // a feature that spans all the bands of a tall window is in every list once per edge, and keeps its place
+      const double tall[] = {5, -10, 8, 5000, 2, 4000, /**/ 3, 100, 6, 100, 4, 120};
+      const int64_t rs[] = {0, 3, 6}, fs[] = {0, 1, 2}, vs[] = {1, 2};
+      fra_rasterize_job tj = rj;
+      tj.xy = tall; tj.nverts = 6; tj.ring_start = rs; tj.nrings = 2; tj.feature_ring_start = fs; tj.values = vs; tj.height = 330;
+      fra_rz::Prepared p;
+      EXPECT(fra_rz::check_job(&tj) == FRA_OK && fra_rz::prepare(&tj, &p) == FRA_OK, "rasterize: the tall job: %s", g_msg.c_str());
+      const size_t nb = (330 + 15) / 16;
+      bool ok = p.bins.band_start.size() == nb + 1 && p.values == std::vector<uint32_t>({1, 2});
+      for (size_t b = 0; b < nb && ok; b++) {
+        const uint32_t a = p.bins.band_start[b], z = p.bins.band_start[b + 1];
+        // (5,-10)-(8,5000) and (5,-10)-(2,4000) cross every row of the window; the small triangle rows 100 .. 119
+        const uint32_t want = 2 + ((b == 6 || b == 7) ? 2 : 0);
+        ok = z - a == want && p.bins.feat[a] == 0 && p.bins.feat[a + 1] == 0 && (want == 2 || (p.bins.feat[a + 2] == 1 && p.bins.feat[a + 3] == 1));
+      }
+      EXPECT(ok, "rasterize: the lists of a feature that spans all bands");
+    }
+    {  // every crossing of the rule is in its row's band list, for windows at several offsets
+      bool ok = true;
+      for (int64_t off : {(int64_t)0, (int64_t)3, (int64_t)17, (int64_t)-5})
+        for (int32_t hh : {1, 16, 17, 45}) {
+          fra_rz::Bins b;
+          ok = ok && fra_rz::bin_edges(edges, feat, off, hh, &b) == FRA_OK;
+          for (int32_t r = 0; r < hh && ok; r++) {
+            const double yc = (double)(off + r) + 0.5;
+            std::vector<int> want, got;
+            for (size_t k = 0; k < edges.size(); k++) if (edges[k].y0 <= yc && yc < edges[k].y1) want.push_back((int)k);
+            for (uint32_t k = b.band_start[(size_t)r / 16]; k < b.band_start[(size_t)r / 16 + 1]; k++)
+              if (b.edges[k].y0 <= yc && yc < b.edges[k].y1)
+                for (size_t q = 0; q < edges.size(); q++) if (!memcmp(&edges[q], &b.edges[k], sizeof(fra_rz::Edge)) && feat[q] == b.feat[k]) { got.push_back((int)q); break; }
+            ok = want == got;
+          }
+        }
+      EXPECT(ok, "rasterize: a crossing is missing from its band list, or out of order");
+    }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
   {
