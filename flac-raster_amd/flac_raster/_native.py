@@ -254,6 +254,28 @@ class RasterizeJob(C.Structure):
 
 assert C.sizeof(RasterizeJob) == 128
 
+
+class ProximityOpts(C.Structure):
+    """``fra_proximity_opts`` (280 bytes; the rule: ``proximity.py``)."""
+
+    _fields_ = [
+        ("nvalues", C.c_int32), ("has_max_dist", C.c_int32), ("has_fixed", C.c_int32), ("out_row_off", C.c_int32),
+        ("out_col_off", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32), ("reserved", C.c_int32),
+        ("values", C.c_double * 16), ("scale", C.c_double), ("max_dist", C.c_double), ("fixed", C.c_double),
+        ("fill", C.c_double), ("alloc_fill", C.c_double), ("dist", CalcDst), ("alloc", CalcDst),
+    ]
+
+
+class ProximityJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("band_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64), ("opts", ProximityOpts),
+    ]
+
+
+assert C.sizeof(ProximityOpts) == 280 and C.sizeof(ProximityJob) == 336
+
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 ZONAL_NODATA, ZONAL_IGNORE = 1, 2
 CALC_NODATA = 1
@@ -318,6 +340,7 @@ EXPORTS = [
     "fra_zonal", "fra_decode_device_zonal", "fra_zonal_timing",
     "fra_warp", "fra_decode_device_warped", "fra_warp_source_window", "fra_warp_timing", "fra_warp_paths",
     "fra_rasterize", "fra_rasterize_timing",
+    "fra_proximity", "fra_decode_device_proximity", "fra_proximity_timing",
 ]
 
 
@@ -441,6 +464,11 @@ def load():
         if hasattr(L, "fra_rasterize"):
             L.fra_rasterize.argtypes = [vp, C.POINTER(RasterizeJob), C.POINTER(u64)]
             L.fra_rasterize_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_proximity"):
+            L.fra_proximity.argtypes = [vp, C.POINTER(ProximityJob), C.POINTER(u64)]
+            L.fra_decode_device_proximity.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(ProximityOpts),
+                                                      C.POINTER(Decoded), C.POINTER(u64)]
+            L.fra_proximity_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -584,6 +612,32 @@ def _calc_dst(dst, dst_strides, out_dtype, shape) -> Tuple[CalcDst, object]:
         o.dst, o.dst_on_device = C.c_void_p(int(dst)), 1
     o.band_stride, o.row_stride, o.col_stride = st
     return o, ret
+
+
+def proximity_opts(opts, out_window, src_dtype, shape, dist, alloc, dist_dtype, dist_strides, alloc_strides):
+    """The ``fra_proximity_opts`` of a ``proximity.Options`` over a ``(B, h, w)`` region, and what the caller returns
+    as ``(dist, alloc)``.  ``dist`` / ``alloc``: ``False`` (not wanted), ``None`` (a new array), a numpy array view
+    ``(B, oh, ow)`` or a device pointer with element strides (default band-planar)."""
+    from .proximity import default_fill
+
+    B, h, w = shape
+    win = (0, 0, h, w) if out_window is None else tuple(int(v) for v in out_window)
+    o = ProximityOpts()
+    vals = [float(v) for v in opts.values]
+    o.nvalues = len(vals)
+    for i, v in enumerate(vals[:16]):
+        o.values[i] = v
+    o.has_max_dist, o.max_dist = (0, 0.0) if opts.max_dist is None else (1, float(opts.max_dist))
+    o.has_fixed, o.fixed = (0, 0.0) if opts.fixed is None else (1, float(opts.fixed))
+    o.out_row_off, o.out_col_off, o.out_height, o.out_width = win
+    o.scale, o.alloc_fill = float(opts.scale), float(opts.alloc_fill)
+    ret_d = ret_a = None
+    if dist is not False:
+        o.fill = default_fill(dist_dtype) if opts.fill is None else float(opts.fill)
+        o.dist, ret_d = _calc_dst(dist, dist_strides, dist_dtype, (B, win[2], win[3]))
+    if alloc is not False:
+        o.alloc, ret_a = _calc_dst(alloc, alloc_strides, src_dtype, (B, win[2], win[3]))
+    return o, ret_d, ret_a
 
 
 def _window_ref(w):
@@ -1382,6 +1436,54 @@ class Context:
         ms = C.c_float()
         _check(load().fra_rasterize_timing(C.byref(ms)))
         return ms.value
+
+    def proximity(self, src, opts=None, dist_dtype="float32", dist=None, alloc=None, *, out_window=None, dtype=None,
+                  shape=None, strides=None, dist_strides=None, alloc_strides=None):
+        """Distance to the nearest target pixel and nearest-target allocation over a raster on this context's GPU
+        (``fra_proximity``, the rule of ``flac_raster.proximity.proximity_arrays``): ``(dist, alloc, counts)``.
+
+        ``src``: as :meth:`stats`.  ``opts``: a ``proximity.Options``.  ``dist`` / ``alloc``: ``None`` (a new array is
+        returned), ``False`` (not wanted), a numpy array view ``(B, oh, ow)`` -- of ``dist_dtype`` and of the source's
+        dtype -- whose elements between the outputs keep their values, or a device pointer with element
+        ``dist_strides`` / ``alloc_strides`` (default band-planar).  ``out_window`` = (row_off, col_off, oh, ow) inside
+        the source, default all of it: targets outside it count.  ``counts``: targets, output pixels within reach,
+        output pixels filled, over all bands."""
+        from .proximity import Options
+
+        job = ProximityJob()
+        dt, (B, h, w), st = _raster_source(job, src, dtype, shape, strides)
+        job.band_stride, job.row_stride, job.col_stride = st
+        job.opts, ret_d, ret_a = proximity_opts(opts or Options(), out_window, dt, (B, h, w), dist, alloc, dist_dtype,
+                                                dist_strides, alloc_strides)
+        counts = np.zeros(3, np.uint64)
+        _check(load().fra_proximity(self.h, C.byref(job), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return ret_d, ret_a, counts
+
+    def decode_device_proximity(self, data, items, dst_dtype, channels: int, roi, opts=None, dist_dtype="float32",
+                                dist=None, alloc=None, *, out_window=None, denorm: int = DENORM_NONE,
+                                dist_strides=None, alloc_strides=None):
+        """:meth:`proximity` over ``roi`` of the tile streams (``fra_decode_device_proximity``): ``roi`` is the region
+        -- the wanted window grown by the halo of ``max_dist`` and clipped to the raster -- and ``out_window`` the wanted
+        window relative to it.  The decoded region never leaves the GPU.  ``data``, ``items``, ``roi``, ``denorm`` as
+        :meth:`decode_device_window`; the items must cover ``roi``.  Returns ``(dist, alloc, counts, infos)``."""
+        from .proximity import Options
+
+        if roi is None:
+            raise ValueError("roi is required")
+        o, ret_d, ret_a = proximity_opts(opts or Options(), out_window, np.dtype(dst_dtype),
+                                         (int(channels), int(roi[2]), int(roi[3])), dist, alloc, dist_dtype,
+                                         dist_strides, alloc_strides)
+        counts = np.zeros(3, np.uint64)
+        job, infos, keep = self._decode_job(data, items, None, np.dtype(dst_dtype), denorm, channels, (0, 0, 0))
+        infos = self._decode_run("fra_decode_device_proximity", job, infos, keep, _window_ref(roi), C.byref(o), infos,
+                                 counts.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return ret_d, ret_a, counts, infos
+
+    def proximity_timing(self) -> Tuple[float, float]:
+        """HIP-event ms of the two phases (columns, rows) of this thread's last proximity call."""
+        ms = (C.c_float * 2)()
+        _check(load().fra_proximity_timing(ms))
+        return float(ms[0]), float(ms[1])
 
     def decode_timing(self) -> List[float]:
         """HIP-event ms of this thread's last ``decode_device`` / ``decode_device_window``: parse, restore, scatter,

@@ -577,6 +577,78 @@ def rasterize(
 
 
 @app.command()
+def proximity(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file, GeoTIFF, or (with --like) a GeoJSON file of polygons"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF of the distances"),
+    values: Optional[str] = typer.Option(None, "--values", help="Target pixel values, e.g. '1,2' (default: every pixel "
+                                         "that is non-zero and not NaN)"),
+    max_dist: Optional[float] = typer.Option(None, "--max-dist", help="Pixels farther than this get the fill, in --units"),
+    units: str = typer.Option("pixel", "--units", help="pixel, or geo: the map units of the source's transform"),
+    fixed: Optional[float] = typer.Option(None, "--fixed", help="Write this value instead of the distance to every pixel "
+                                          "within reach, the targets included (a buffer)"),
+    fill: Optional[float] = typer.Option(None, "--fill", help="What a pixel out of reach gets, and the nodata tag "
+                                         "(default: NaN for float outputs, the maximum for integer ones)"),
+    dtype: str = typer.Option("float32", "--dtype", help="Output dtype of the distances"),
+    alloc: Optional[Path] = typer.Option(None, "--alloc", help="Also write the value of the nearest target to this GeoTIFF"),
+    alloc_fill: float = typer.Option(0.0, "--alloc-fill", help="What a pixel out of reach gets in --alloc"),
+    like: Optional[Path] = typer.Option(None, "--like", help="With a GeoJSON source: the streaming FLAC file or GeoTIFF "
+                                        "whose grid the polygons are burned on"),
+    attribute: Optional[str] = typer.Option(None, "--attribute", "-a", help="With --like: this integer property is a "
+                                            "polygon's label (default: feature i has i + 1)"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width' "
+                                         "(targets outside it still count)"),
+    cpu: bool = typer.Option(False, "--cpu", help="Evaluate with numpy on the host"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Distance of every pixel to the nearest target pixel (or polygon), and the nearest target's value -> GeoTIFF."""
+    import numpy as np
+
+    from .proximity import Options, default_fill
+    from .streaming import _fill_tag, proximity_of_polygons, proximity_to_tiff
+    from .tiff import write_geotiff
+
+    try:
+        if bbox is not None and pixels is not None:
+            console.print("[red]Error: give at most one of --bbox and --window[/red]")
+            raise typer.Exit(1)
+        if attribute is not None and like is None:
+            console.print("[red]Error: --attribute goes with a GeoJSON source and --like[/red]")
+            raise typer.Exit(1)
+        path = _local(file_path)
+        for p in (path,) + ((like,) if like is not None else ()):
+            if not p.exists():
+                console.print(f"[red]File not found: {p}[/red]")
+                raise typer.Exit(1)
+        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        vals = tuple(float(x.strip()) for x in values.split(",")) if values else ()
+        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        odt = np.dtype(dtype)
+        opts = Options(values=vals, max_dist=max_dist, fixed=fixed, fill=fill, alloc_fill=alloc_fill)
+        if like is not None:
+            dist, labels, counts, got, transform, crs = proximity_of_polygons(like, path, attribute, opts, window=win,
+                                                                              bbox=box, units=units, dist_dtype=odt, device=dev)
+            write_geotiff(output_path, dist, transform=transform, crs=crs,
+                          nodata=_fill_tag(default_fill(odt) if fill is None else fill, odt))
+            if alloc is not None:
+                write_geotiff(alloc, labels, transform=transform, crs=crs, nodata=_fill_tag(alloc_fill, labels.dtype))
+        else:
+            got, counts = proximity_to_tiff(path, output_path, opts, window=win, bbox=box, units=units, dist_dtype=odt,
+                                            alloc_path=alloc, device=dev)
+        n = int(counts[1]) + int(counts[2])
+        console.print(f"[green]{output_path}[/green]: {odt}, rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
+                      f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
+        console.print(f"targets: {int(counts[0])}; within reach: {100.0 * int(counts[1]) / max(1, n):.2f}% of the pixels")
+    except typer.Exit:
+        raise
+    except Exception as e:
+        logger.exception("Proximity failed")
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
+@app.command()
 def calc(
     file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
     output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF"),

@@ -882,11 +882,9 @@ def _burn(pix, win, values, fill, dt, device):
     return _native.default_context(int(device)).rasterize(pix, win, values, fill, dt)
 
 
-def _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype, device):
-    """:func:`rasterize_like` with ``burn`` (one value for every feature, or ``None``) and the burned count."""
+def _grid_of(source):
+    """``(transform, (height, width), crs)`` of a streaming container or a GeoTIFF."""
     source = Path(source)
-    if burn is not None and attribute is not None:
-        raise ValueError("give at most one of an attribute and a burn value")
     if _is_tiff(source):
         g = GeoTIFF(source)
         try:
@@ -901,6 +899,14 @@ def _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype,
         crs = crs if crs and crs != "None" else None
     else:
         raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    return t, shape, crs
+
+
+def _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype, device):
+    """:func:`rasterize_like` with ``burn`` (one value for every feature, or ``None``) and the burned count."""
+    if burn is not None and attribute is not None:
+        raise ValueError("give at most one of an attribute and a burn value")
+    t, shape, crs = _grid_of(source)
     pix, values = _pixel_features(geojson, attribute, t)
     if burn is not None:
         values = [int(burn)] * len(pix)
@@ -1011,6 +1017,173 @@ def zonal_with_polygons(source, geojson, attribute: Optional[str] = None, window
     finally:
         ctx.free(d_zones)
     return report_from_recs(recs, outside, src_dt, zone_lo, labels), win, meta
+
+
+# ------------------------------------------------------------------------------------------ proximity
+def _proximity_opts(opts, transform, units: str):
+    """``opts`` (default: none) with the scale of ``units``: 1 for pixels, the pixel size for map units."""
+    import dataclasses
+
+    from .proximity import Options, scale_of, validate
+
+    opts = dataclasses.replace(opts or Options(), scale=scale_of(transform, units))
+    validate(opts)
+    return opts
+
+
+def _proximity_region(win, opts, H: int, W: int):
+    """The region a window's result needs, and the window relative to it: the window grown by the halo of ``max_dist``
+    and clipped to the ``H x W`` raster; the whole raster without a ``max_dist``, when any target may be the nearest."""
+    from .proximity import halo
+
+    k = halo(opts)
+    if k is None:
+        return (0, 0, H, W), tuple(win)
+    r, c, h, w = win
+    r0, c0, r1, c1 = max(r - k, 0), max(c - k, 0), min(r + h + k, H), min(c + w + k, W)
+    return (r0, c0, r1 - r0, c1 - c0), (r - r0, c - c0, h, w)
+
+
+def proximity_window(src, opts=None, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                     units: str = "pixel", dist_dtype="float32", want_alloc: bool = False, device: Optional[int] = None,
+                     semantics: str = "pcm16"):
+    """The distance of every pixel of a streaming container (path or bytes), or of a window of it, to the nearest
+    target pixel -> ``(dist (B, h, w) in dist_dtype, alloc (B, h, w) in the container's dtype or None, counts, window,
+    index)``: the crop of ``proximity.proximity_arrays`` over the whole raster.
+
+    ``opts``: a ``proximity.Options`` whose ``max_dist`` is in ``units`` -- ``'pixel'``, or ``'geo'`` for the map units
+    of the container's transform (square, axis-aligned pixels; anything else is refused).  With a ``window`` / ``bbox``
+    and a ``max_dist`` the decoded region is the window grown by ``ceil(max_dist / scale)`` pixels and clipped to the
+    raster; without a ``max_dist`` it is the whole raster.  ``device=None`` reads the region on the host and applies the
+    numpy rule; an integer makes one ``fra_decode_device_proximity`` call on that GPU: the decoded pixels never leave
+    the device."""
+    from . import _native
+    from .proximity import proximity_arrays
+
+    if semantics not in ("pcm16", "int"):
+        raise ValueError("semantics must be 'pcm16' or 'int'")
+    index = _index_of(src)
+    H, W = int(index["height"]), int(index["width"])
+    opts = _proximity_opts(opts, index.get("transform"), units)
+    win = (0, 0, H, W) if window is None and bbox is None else resolve_window(index, window, bbox)
+    region, inner = _proximity_region(win, opts, H, W)
+    index, gwin, blob, items = _window_items(src, region, None)
+    dt, B, odt = np.dtype(index["dtype"]), int(index["bands"]), np.dtype(dist_dtype)
+    if device is None:
+        a = np.zeros((B, gwin[2], gwin[3]), dtype=dt)
+        _decode_window_on_host(blob, items, gwin, a, semantics)
+        dist, alloc, counts = proximity_arrays(a, opts, inner, odt)
+        return dist, alloc if want_alloc else None, counts, win, index
+    ctx = _native.default_context(int(device))
+    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
+    dist, alloc, counts, _ = ctx.decode_device_proximity(np.frombuffer(blob, dtype=np.uint8), items, dt, B, gwin, opts, odt,
+                                                         alloc=None if want_alloc else False, out_window=inner,
+                                                         denorm=denorm)
+    return dist, alloc, counts, win, index
+
+
+def proximity_tiff(path: Path, opts=None, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                   units: str = "pixel", dist_dtype="float32", want_alloc: bool = False, device: Optional[int] = None):
+    """:func:`proximity_window` for a GeoTIFF source -> ``(dist, alloc, counts, window, info, the options used)``.  The
+    region is read with the in-package reader; an integer ``device`` hands it to ``fra_proximity`` on that GPU, ``None``
+    to the numpy rule."""
+    from . import _native
+    from .proximity import proximity_arrays
+
+    g = GeoTIFF(Path(path))
+    try:
+        info = g.info
+        t = list(info.transform) if info.transform is not None else None
+        opts = _proximity_opts(opts, t, units)
+        win = _tiff_window(g, window, bbox)
+        region, inner = _proximity_region(win, opts, info.height, info.width)
+        a = np.zeros((info.count, region[2], region[3]), dtype=np.dtype(info.dtype))
+        g.read_window_into(a, *region)
+    finally:
+        g.close()
+    odt = np.dtype(dist_dtype)
+    if device is None:
+        dist, alloc, counts = proximity_arrays(a, opts, inner, odt)
+        alloc = alloc if want_alloc else None
+    else:
+        dist, alloc, counts = _native.default_context(int(device)).proximity(
+            a, opts, odt, alloc=None if want_alloc else False, out_window=inner)
+    return dist, alloc, counts, win, info, opts
+
+
+def _fill_tag(fill, dtype):
+    """A fill as a GeoTIFF nodata tag of ``dtype``."""
+    from .calc import convert
+
+    v = convert(np.array([float(fill)]), dtype)[0]
+    return float(v) if np.dtype(dtype).kind == "f" else int(v)
+
+
+def proximity_to_tiff(path: Path, tiff_path: Path, opts=None, window: Optional[Sequence[int]] = None,
+                      bbox: Optional[Sequence[float]] = None, units: str = "pixel", dist_dtype="float32",
+                      alloc_path: Optional[Path] = None, device: Optional[int] = None, semantics: str = "pcm16"):
+    """Proximity over a streaming container or a GeoTIFF (told apart by their first bytes) -> a GeoTIFF of the distances
+    with the source's CRS, the transform shifted to the window's origin and the fill as its nodata tag; ``alloc_path``:
+    a second GeoTIFF of the nearest targets' values, ``alloc_fill`` as its nodata tag.  Returns ``(window, counts)``."""
+    from .proximity import default_fill
+    from .tiff import write_geotiff
+
+    path = Path(path)
+    want = alloc_path is not None
+    if _is_tiff(path):
+        dist, alloc, counts, win, info, opts = proximity_tiff(path, opts, window, bbox, units, dist_dtype, want, device)
+        t, crs = list(info.transform) if info.transform is not None else None, str(info.crs) if info.crs is not None else None
+    elif is_streaming_container(path):
+        dist, alloc, counts, win, index = proximity_window(path, opts, window, bbox, units, dist_dtype, want, device, semantics)
+        t, crs = index.get("transform"), index.get("crs")
+    else:
+        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
+    crs = crs if crs and crs != "None" else None
+    fill = default_fill(dist.dtype) if opts is None or opts.fill is None else opts.fill
+    write_geotiff(Path(tiff_path), dist, transform=transform, crs=crs, nodata=_fill_tag(fill, dist.dtype))
+    if want:
+        write_geotiff(Path(alloc_path), alloc, transform=transform, crs=crs,
+                      nodata=_fill_tag(0.0 if opts is None else opts.alloc_fill, alloc.dtype))
+    return win, counts
+
+
+def proximity_of_polygons(source, geojson, attribute: Optional[str] = None, opts=None,
+                          window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                          units: str = "pixel", dist_dtype="float32", device: Optional[int] = None):
+    """The distance of every pixel of the grid of ``source`` -- a streaming container or a GeoTIFF, whose pixels are not
+    read -- to the nearest polygon of a GeoJSON file, and that polygon's label -> ``(dist (1, h, w), alloc (1, h, w),
+    counts, window, transform of the window, crs)``.  Feature ``i`` has the label ``i + 1``, or its integer property
+    ``attribute``; 0 is what a pixel outside every polygon is burned with, so a label of 0 is refused.
+
+    ``device=None``: ``proximity.proximity_arrays`` over ``rasterize.rasterize_arrays``.  On a GPU ``fra_rasterize``
+    burns the labels of the region into a device buffer that goes to ``fra_proximity`` as it is: the label raster never
+    visits the host."""
+    from . import _native
+    from .proximity import proximity_arrays
+
+    t, (H, W), crs = _grid_of(source)
+    pix, values = _pixel_features(geojson, attribute, t)
+    if any(int(v) == 0 for v in values):
+        raise ValueError("a label of 0 is not possible: 0 is what the pixels outside every polygon get")
+    opts = _proximity_opts(opts, t, units)
+    win = (0, 0, H, W) if window is None and bbox is None else resolve_window(
+        {"height": H, "width": W, "transform": t}, window, bbox)
+    region, inner = _proximity_region(win, opts, H, W)
+    zdt, odt = _label_dtype(values, 0), np.dtype(dist_dtype)
+    if device is None:
+        labels, _ = _burn(pix, region, values, 0, zdt, None)
+        dist, alloc, counts = proximity_arrays(labels, opts, inner, odt)
+    else:
+        ctx = _native.default_context(int(device))
+        d_labels = ctx.alloc(region[2] * region[3] * zdt.itemsize)
+        try:
+            ctx.rasterize(pix, region, values, 0, zdt, dst=d_labels)
+            dist, alloc, counts = ctx.proximity(d_labels, opts, odt, out_window=inner, dtype=zdt,
+                                                shape=(1, region[2], region[3]))
+        finally:
+            ctx.free(d_labels)
+    return dist, alloc, counts, win, tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]), crs
 
 
 # ------------------------------------------------------------------------------------------ band math

@@ -1019,6 +1019,78 @@ FRA_API int fra_rasterize(fra_ctx *ctx, const fra_rasterize_job *job, uint64_t *
 /* HIP-event time (ms) of the calling thread's last k_rasterize and its fold */
 FRA_API int fra_rasterize_timing(float *ms);
 
+/* Proximity: for every pixel of a region the exact Euclidean distance to the nearest target pixel, and the source
+ * value at that target (nearest-target allocation) -- buffers around burned features, distance to water, a mask grown by
+ * a radius.  flac_raster/proximity.py restates the rule in numpy (proximity_direct: all pairs; proximity_arrays: the
+ * separable form).  Squared pixel distances are integers, so everything up to the one f64 square root is exact.
+ *   Region: a (channels, h, w) raster of any fra_dtype, 1 <= h, w <= 32768 (every squared distance is below 2^31).  Each
+ *     band is handled on its own.  Targets outside the region do not exist.
+ *   Targets: with nvalues == 0 a pixel is a target when its value is non-zero and not NaN (-0.0 is zero); with
+ *     1 <= nvalues <= 16 when (double)v == values[i] for some i (so NaN never is).
+ *   Squared distance of pixel (r, c): d2 = min over the band's targets (r', c') of (r - r')^2 + (c - c')^2, in integers.
+ *     A band without a target has no d2.
+ *   Nearest target: among the targets at that minimum the one with the smallest column, among those the one with the
+ *     smallest row.
+ *   Distance: d = sqrt((double)d2) * scale in f64, each operation rounded on its own; scale is finite and > 0 (1: pixel
+ *     units; the pixel size: map units).
+ *   Reach: a pixel is within reach when it has a d2 and either has_max_dist is 0 or d <= max_dist in f64.  (d is
+ *     monotone in d2, so the host turns this into the greatest d2 within reach, exactly.)
+ *   dist output (optional, any fra_dtype; dist.dst == NULL: not wanted): a pixel within reach gets d, or `fixed` when
+ *     has_fixed is set -- a target included: a buffer contains its core; every other pixel gets `fill`.  All three are
+ *     converted as the band math converts a result (Output, above).
+ *   alloc output (optional, the source's dtype; alloc.dst == NULL: not wanted; alloc.dtype is ignored): a pixel within
+ *     reach gets the source value at its nearest target, bits copied; every other pixel gets alloc_fill, converted as
+ *     above.
+ *   Output window: only the pixels (out_row_off, out_col_off, out_height, out_width) of the region are written, at
+ *     dst[band, r - out_row_off, c - out_col_off] through the output's strides; targets anywhere in the region count.
+ *     So a window of a large raster is exact under a max_dist: the caller passes the window grown by
+ *     ceil(max_dist / scale) pixels, clipped to the raster, as the region.
+ *   counts[0]: the targets in the region; counts[1]: the output-window pixels within reach; counts[2]: the
+ *     output-window pixels that got the fill; each summed over the bands.
+ * Two phases.  Columns (k_prox_mask, k_prox_carry, k_prox_cols): per pixel of the output window's rows the vertical
+ * distance g to the nearest target of its own column and whether it lies above or below (above wins a tie; g beyond the
+ * reach is "none"), 16 bits per pixel, from one 64-bit target mask per 64 rows of a column.  Rows (k_prox_rows): per
+ * output row d2[c] = min over c' of g[c']^2 + (c - c')^2, the leftmost c' winning a tie; that argmin does not decrease
+ * with c, so the row is solved by divide and conquer in LDS, every level in parallel (fra_proximity.hip). */
+typedef struct {
+  int32_t nvalues;                          /* 0 .. 16 */
+  int32_t has_max_dist, has_fixed;
+  int32_t out_row_off, out_col_off, out_height, out_width;  /* the output window, inside the region */
+  int32_t reserved;
+  double values[16];
+  double scale, max_dist, fixed, fill, alloc_fill;
+  fra_calc_dst dist;                        /* (channels, out_height, out_width) of dist.dtype; dst NULL: none */
+  fra_calc_dst alloc;                       /* (channels, out_height, out_width) of the source's dtype; dst NULL: none */
+} fra_proximity_opts;                       /* 280 bytes */
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype of the source */
+  int32_t channels, height, width;          /* channels 1 .. 255; height, width 1 .. 32768 */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+  fra_proximity_opts opts;
+} fra_proximity_job;
+/* Over a host or device raster of any layout into host or device rasters of any layout.  Synchronous.  Host buffers are
+ * staged as fra_calc stages them (the elements of an output that are not outputs keep the caller's values).  The
+ * scratch (the masks, the carries and one band's 16-bit intermediate at a time) is per call and released on every path.
+ * counts (host memory, 3 words) may be NULL.
+ * FRA_E_INVALID, before any GPU work and in this order: a null argument (ctx, job, src); a bad source dtype or layout
+ * (more than 255 bands), a bad dtype or a negative stride of an output that is given; height or width outside
+ * 1 .. 32768; nvalues outside 0 .. 16 or a value that is not finite; a scale that is not finite and positive; with
+ * has_max_dist a max_dist that is NaN or negative (+inf is no limit); an output window that is empty or leaves the
+ * region; neither output given. */
+FRA_API int fra_proximity(fra_ctx *ctx, const fra_proximity_job *job, uint64_t *counts /* 3, may be NULL */);
+/* The same over what fra_decode_device_window would have written for `roi`, in job->dst_dtype: roi is the region
+ * (opts' output window is relative to it), job->dst and the job's strides are ignored, and the decoded region never
+ * leaves the device.  Every refusal and message of the windowed read is this call's as well; items that do not cover
+ * roi are refused as by fra_decode_device_compare; the options and outputs as by fra_proximity.  Afterwards
+ * fra_decode_device_timing reports the inner windowed read and fra_proximity_timing the transform. */
+FRA_API int fra_decode_device_proximity(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                        const fra_proximity_opts *opts, fra_decoded *infos /* nitems */,
+                                        uint64_t *counts /* 3, may be NULL */);
+/* HIP-event times (ms) of the calling thread's last proximity call: ms[0] the column phase, ms[1] the row phase, each
+ * summed over the bands */
+FRA_API int fra_proximity_timing(float ms[2]);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -131,6 +131,16 @@ in the same session, the plain read, ``k_calc``'s one-band uint16 copy and, with
 
     python tools/bench_decode.py --rasterize blocks:256 --zonal blocks:256 --rasterize circle:100000 --steps 5 --warmup 2
 
+``--proximity KIND[:MAXDIST]`` times the proximity unit (``fra_proximity``) over the scene's grid, from a device-resident
+uint16 target raster into a device-resident float32 ``dist``, and may be repeated: ``blocks:N`` (the outlines of the N x N
+squares the rasterize benchmark burns), ``single`` (one target pixel in the centre), ``random:P`` (a share P of the pixels),
+``all`` and ``none``; a further ``:MAXDIST`` limits the reach in pixels.  Per leg the two phase times (``cols_ms``,
+``rows_ms``: ``fra_proximity_timing``), their sum against the floor of 10 bytes per pixel (``floor_gb_per_s``) and against
+``k_calc``'s one-band uint16 -> float32 copy of the same run.  It exits non-zero unless a 64 x 512 rectangle through the
+centre equals ``proximity.proximity_arrays`` wherever the nearest target lies within 160 pixels.  No container is built.
+
+    python tools/bench_decode.py --proximity blocks:256 --proximity single --proximity random:0.01 --proximity all --proximity none --steps 5 --warmup 2
+
 ``--zonal PATTERN`` times the zonal statistics of the same container (``fra_decode_device_zonal``: the whole raster
 decoded to uint16 and reduced per zone there, only the records come back) over a uint16 zone raster synthesised on the
 host and resident on the device: ``blocks:N`` (squares of N x N pixels, ``blocks:256`` = 43 x 43 = 1849 zones),
@@ -241,6 +251,83 @@ def focal_over_dem(ctx, args):
     ctx.free(dem)
 
 
+def proximity_source(kind, arg):
+    """The uint16 target raster of a ``--proximity`` kind over the scene's grid."""
+    a = np.zeros((H, W), np.uint16)
+    if kind == "blocks":
+        n = int(arg or 256)
+        a[::n, :] = 1 + (np.arange(W) // n % 60000).astype(np.uint16)[None, :]
+        a[:, ::n] = 1 + (np.arange(H) // n % 60000).astype(np.uint16)[:, None]
+    elif kind == "single":
+        a[H // 2, W // 2] = 7
+    elif kind == "random":
+        rng = np.random.default_rng(SEED)
+        m = rng.random((H, W)) < float(arg or 0.01)
+        a[m] = rng.integers(1, 65536, int(m.sum()))
+    elif kind == "all":
+        a[:] = 1 + (np.arange(W) % 60000).astype(np.uint16)[None, :]
+    elif kind != "none":
+        raise SystemExit("--proximity takes blocks:N, single, random:P, all or none")
+    return a
+
+
+def proximity_over_grid(ctx, args):
+    """``--proximity``: the two phases of ``fra_proximity`` per kind, against the 10 B/pixel floor (a uint16 source, the
+    16-bit intermediate written and read, a float32 dist) and against a one-band ``k_calc`` copy uint16 -> float32."""
+    from flac_raster.calc import compile_exprs
+    from flac_raster.proximity import Options, proximity_arrays
+
+    med = statistics.median
+    d_src, d_dist = ctx.alloc(H * W * 2), ctx.alloc(H * W * 4)
+    copy = compile_exprs(["b1"], 1)
+    res = {"workload": f"proximity over the C4-like grid {W}x{H}: uint16 source and float32 dist resident on the device",
+           "steps": args.steps, "warmup": args.warmup, "floor_bytes_per_pixel": 10, "legs": []}
+    kcopy = []
+    for spec in args.proximity:
+        parts = spec.split(":")
+        kind = parts[0]
+        arg = parts[1] if len(parts) > 1 and kind in ("blocks", "random") else None
+        rest = parts[2:] if kind in ("blocks", "random") else parts[1:]
+        opts = Options(max_dist=float(rest[0])) if rest else Options()
+        src = proximity_source(kind, arg)
+        ctx.h2d(d_src, src)
+        if not kcopy:
+            for s in range(args.warmup + args.steps):
+                ctx.calc(d_src, copy, np.float32, d_dist, dtype=np.uint16, shape=(1, H, W))
+                if s >= args.warmup:
+                    kcopy.append(ctx.calc_timing())
+            res["k_calc_copy_uint16_to_float32_ms"] = round(med(kcopy), 4)
+        wall, cols, rows = [], [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            _, _, counts = ctx.proximity(d_src, opts, np.float32, d_dist, False, dtype=np.uint16, shape=(1, H, W))
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                ms = ctx.proximity_timing()
+                wall.append((t1 - t0) * 1e3), cols.append(ms[0]), rows.append(ms[1])
+        # a band of rows through the centre against the numpy rule over the band grown by 160 pixels: wherever the rule finds
+        # a target within 160 pixels, that target is the nearest of the whole grid too
+        r0, c0, hh, ww, grow = H // 2 - 32, W // 2 - 256, 64, 512, 160
+        got = np.empty((hh, W), np.float32)
+        ctx.d2h(got, d_dist + r0 * W * 4)
+        want = proximity_arrays(src[r0 - grow:r0 + hh + grow, c0 - grow:c0 + ww + grow], opts, (grow, grow, hh, ww))[0][0]
+        near = want <= grow
+        if not np.array_equal(got[:, c0:c0 + ww][near], want[near]) or (kind != "none" and not near.any()):
+            raise SystemExit(f"proximity {spec}: rows {r0} ..., columns {c0} ... differ from proximity_arrays")
+        if kind == "none" and not (np.isnan(got).all() and int(counts[0]) == 0):
+            raise SystemExit("proximity none: a pixel within reach")
+        total = med(cols) + med(rows)
+        res["legs"].append({
+            "proximity": spec, "targets": int(counts[0]), "within_reach": int(counts[1]),
+            "cols_ms": round(med(cols), 4), "rows_ms": round(med(rows), 4), "total_ms": round(total, 4),
+            "wall_ms": round(med(wall), 3), "floor_gb_per_s": round(10 * H * W / total / 1e6, 1),
+            "total_over_calc_copy": round(total / med(kcopy), 2), "checked_pixels_equal_proximity_arrays": int(near.sum()),
+            "all_ms": {"cols": [round(x, 4) for x in cols], "rows": [round(x, 4) for x in rows]}})
+    print(json.dumps(res), flush=True)
+    ctx.free(d_src)
+    ctx.free(d_dist)
+
+
 def warp_map_of(text):
     """The ``warp.Map`` of a ``--warp`` leg over the scene at its own size, and a word about it."""
     import math
@@ -300,6 +387,10 @@ def main():
                     help="time fra_rasterize over the scene's grid into a resident uint16 raster: blocks:N (the squares of "
                          "--zonal blocks:N as polygons) or circle:V (one V-gon inscribed in the scene); with --zonal "
                          "blocks:N the zonal statistics then run over the burned labels")
+    ap.add_argument("--proximity", action="append", default=None, metavar="KIND[:MAXDIST]",
+                    help="time fra_proximity over the scene's grid, a resident uint16 source into a resident float32 dist: "
+                         "blocks:N (the outlines of the N x N squares), single (one target pixel), random:P (a share P of "
+                         "the pixels), all, none; KIND:...:MAXDIST limits the reach, e.g. blocks:256:64 (repeatable)")
     ap.add_argument("--calc", action="append", default=None, metavar="EXPR",
                     help="time band math over the container against the plain read: one expression per output band, "
                          "separated by ';', optionally followed by ':dtype'; repeat for further legs of the same run")
@@ -328,6 +419,9 @@ def main():
     ctx = N.Context(0)
     if args.dem:
         focal_over_dem(ctx, args)
+        return
+    if args.proximity:
+        proximity_over_grid(ctx, args)
         return
     dt = np.dtype(np.uint16)
     dev_raster = ctx.alloc(B * H * W * dt.itemsize)

@@ -15,8 +15,11 @@
 //     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
 //     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
 //     fra_focal_check), the zonal statistics (fra_zonal, fra_decode_device_zonal), the warped reads (fra_warp,
-//     fra_decode_device_warped, fra_warp_source_window) and the polygon rasterizer (fra_rasterize), which returns
-//     before any GPU work, and the order of these refusals (inputs that break two rules at once);
+//     fra_decode_device_warped, fra_warp_source_window), the polygon rasterizer (fra_rasterize) and the proximity unit
+//     (fra_proximity, fra_decode_device_proximity), which return before any GPU work, and the order of these refusals
+//     (inputs that break two rules at once);
+//   * the proximity unit's reach threshold against the f64 predicate at and around perfect squares, the conversion of
+//     its fills and the arithmetic of its launch plan (fra_proximity.h);
 //   * the rasterizer's edge table, x-extents and band lists (fra_rasterize.h): closed rings, dropped and oriented
 //     edges, an empty band, a feature spanning all bands, a ring with a repeated closing vertex, and that every
 //     (edge, row) crossing of the rule is in the row's band list, in the edges' order;
@@ -34,6 +37,7 @@
 #include "../flac-raster_amd/csrc/fra_decode.cpp"  // the host decoder's frame validation (internal linkage)
 #include "../flac-raster_amd/csrc/fra_decode_host.h"
 #include "../flac-raster_amd/csrc/fra_scan.h"
+#include "../flac-raster_amd/csrc/fra_proximity.h"
 #include "../flac-raster_amd/csrc/fra_rasterize.h"
 #include "../flac-raster_amd/csrc/fra_warp.h"
 
@@ -1151,6 +1155,131 @@ int main(int argc, char** argv) {
           }
         }
       EXPECT(ok, "rasterize: a crossing is missing from its band list, or out of order");
+    }
+  }
+  // ... and of the proximity unit (fra_proximity.hip): refused before any GPU work, in the order the header gives
+  {
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    static uint8_t psrc[3 * 40 * 50];
+    static float pdist[3 * 40 * 50];
+    static uint8_t palloc[3 * 40 * 50];
+    uint64_t counts[3] = {9, 9, 9};
+    fra_proximity_job pj{};
+    pj.src = psrc; pj.dtype = FRA_U8; pj.channels = 3; pj.height = 40; pj.width = 50;
+    pj.band_stride = 2000; pj.row_stride = 50; pj.col_stride = 1;
+    pj.opts.scale = 1.0; pj.opts.out_height = 40; pj.opts.out_width = 50;
+    pj.opts.dist.dst = pdist; pj.opts.dist.dtype = FRA_F32; pj.opts.dist.band_stride = 2000; pj.opts.dist.row_stride = 50; pj.opts.dist.col_stride = 1;
+    pj.opts.alloc.dst = palloc; pj.opts.alloc.band_stride = 2000; pj.opts.alloc.row_stride = 50; pj.opts.alloc.col_stride = 1;
+    const fra_region::Strides pss{2000, 50, 1};
+    EXPECT(fra_px::check_job(FRA_U8, 3, 40, 50, pss, &pj.opts) == FRA_OK, "proximity: the sample job is refused: %s", g_msg.c_str());
+    EXPECT(fra_proximity(nullptr, &pj, counts) == FRA_E_INVALID, "proximity: null ctx accepted");
+    EXPECT(fra_proximity(ctx, nullptr, counts) == FRA_E_INVALID, "proximity: null job accepted");
+    { auto j = pj; j.src = nullptr; EXPECT(says(fra_proximity(ctx, &j, counts), "null argument"), "proximity: null src: %s", g_msg.c_str()); }
+    for (int d : {-1, 8}) { auto j = pj; j.dtype = d; EXPECT(says(fra_proximity(ctx, &j, counts), "bad dtype"), "proximity: dtype %d: %s", d, g_msg.c_str()); }
+    { auto j = pj; j.channels = 0; EXPECT(says(fra_proximity(ctx, &j, counts), "bad raster layout"), "proximity: no band: %s", g_msg.c_str()); }
+    { auto j = pj; j.channels = 256; EXPECT(says(fra_proximity(ctx, &j, counts), "more than 255"), "proximity: 256 bands: %s", g_msg.c_str()); }
+    { auto j = pj; j.row_stride = -50; EXPECT(says(fra_proximity(ctx, &j, counts), "bad raster layout"), "proximity: negative source stride: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.dist.dtype = 8; EXPECT(says(fra_proximity(ctx, &j, counts), "bad dist dtype"), "proximity: dist dtype 8: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.dist.col_stride = -1; EXPECT(says(fra_proximity(ctx, &j, counts), "bad dist layout"), "proximity: negative dist stride: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.alloc.band_stride = -1; EXPECT(says(fra_proximity(ctx, &j, counts), "bad alloc layout"), "proximity: negative alloc stride: %s", g_msg.c_str()); }
+    for (int n : {0, -3, 32769}) {
+      { auto j = pj; j.height = n; EXPECT(says(fra_proximity(ctx, &j, counts), "1 .. 32768"), "proximity: height %d: %s", n, g_msg.c_str()); }
+      { auto j = pj; j.width = n; EXPECT(says(fra_proximity(ctx, &j, counts), "1 .. 32768"), "proximity: width %d: %s", n, g_msg.c_str()); }
+    }
+    for (int n : {-1, 17}) { auto j = pj; j.opts.nvalues = n; EXPECT(says(fra_proximity(ctx, &j, counts), "nvalues"), "proximity: %d values: %s", n, g_msg.c_str()); }
+    for (double v : {(double)NAN, (double)INFINITY}) { auto j = pj; j.opts.nvalues = 2; j.opts.values[1] = v; EXPECT(says(fra_proximity(ctx, &j, counts), "target value 1 is not finite"), "proximity: value %g: %s", v, g_msg.c_str()); }
+    for (double v : {0.0, -1.0, (double)NAN, (double)INFINITY}) { auto j = pj; j.opts.scale = v; EXPECT(says(fra_proximity(ctx, &j, counts), "scale"), "proximity: scale %g: %s", v, g_msg.c_str()); }
+    for (double v : {-0.5, (double)NAN}) { auto j = pj; j.opts.has_max_dist = 1; j.opts.max_dist = v; EXPECT(says(fra_proximity(ctx, &j, counts), "max_dist"), "proximity: max_dist %g: %s", v, g_msg.c_str()); }
+    { auto o = pj.opts; o.max_dist = NAN; EXPECT(fra_px::check_job(FRA_U8, 3, 40, 50, pss, &o) == FRA_OK, "proximity: max_dist looked at without has_max_dist"); }
+    { auto o = pj.opts; o.has_max_dist = 1; o.max_dist = INFINITY; EXPECT(fra_px::check_job(FRA_U8, 3, 40, 50, pss, &o) == FRA_OK, "proximity: an infinite max_dist refused"); }
+    { auto j = pj; j.opts.out_height = 0; EXPECT(says(fra_proximity(ctx, &j, counts), "output window"), "proximity: empty window: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.out_col_off = 1; EXPECT(says(fra_proximity(ctx, &j, counts), "output window"), "proximity: window past the right edge: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.out_row_off = -1; EXPECT(says(fra_proximity(ctx, &j, counts), "output window"), "proximity: negative window offset: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.dist.dst = nullptr; j.opts.alloc.dst = nullptr; EXPECT(says(fra_proximity(ctx, &j, counts), "neither dist nor alloc"), "proximity: no output: %s", g_msg.c_str()); }
+    // two rules broken at once: the message of the first
+    { auto j = pj; j.dtype = 8; j.height = 0; EXPECT(says(fra_proximity(ctx, &j, counts), "bad dtype"), "proximity: dtype 8 and height 0: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.dist.dtype = -1; j.width = 40000; EXPECT(says(fra_proximity(ctx, &j, counts), "bad dist dtype"), "proximity: dist dtype and width: %s", g_msg.c_str()); }
+    { auto j = pj; j.height = 0; j.opts.nvalues = 17; EXPECT(says(fra_proximity(ctx, &j, counts), "1 .. 32768"), "proximity: height 0 and 17 values: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.nvalues = 17; j.opts.scale = 0.0; EXPECT(says(fra_proximity(ctx, &j, counts), "nvalues"), "proximity: 17 values and scale 0: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.scale = 0.0; j.opts.has_max_dist = 1; j.opts.max_dist = -1.0; EXPECT(says(fra_proximity(ctx, &j, counts), "scale"), "proximity: scale 0 and max_dist -1: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.has_max_dist = 1; j.opts.max_dist = -1.0; j.opts.out_width = 0; EXPECT(says(fra_proximity(ctx, &j, counts), "max_dist"), "proximity: max_dist -1 and an empty window: %s", g_msg.c_str()); }
+    { auto j = pj; j.opts.out_width = 0; j.opts.dist.dst = nullptr; j.opts.alloc.dst = nullptr; EXPECT(says(fra_proximity(ctx, &j, counts), "output window"), "proximity: an empty window and no output: %s", g_msg.c_str()); }
+    EXPECT(counts[0] == 9 && counts[1] == 9 && counts[2] == 9, "proximity: a refusal wrote the counts");
+    EXPECT(fra_proximity_timing(nullptr) == FRA_E_INVALID, "proximity timing: null accepted");
+    // the read over a region: what the windowed read refuses is referred to it; the options as above
+    {
+      fra_decode_item di = it;
+      di.window = {0, 0, 4, 8};
+      fra_decode_job dj = job;
+      dj.items = &di;
+      const fra_window r48{0, 0, 4, 8};
+      fra_window r40 = r48;
+      r40.width = 0;
+      auto o = pj.opts;
+      o.out_height = 4; o.out_width = 8;
+      EXPECT(fra_decode_device_proximity(ctx, &dj, &r48, nullptr, inf, counts) == FRA_E_INVALID && g_msg == "null argument", "proximity read: null options: %s", g_msg.c_str());
+      EXPECT(fra_decode_device_proximity(ctx, &dj, nullptr, &o, inf, counts) == FRA_E_INVALID, "proximity read: null roi accepted");
+      EXPECT(says(fra_decode_device_proximity(ctx, &dj, &r40, &o, inf, counts), "region of interest"), "proximity read: zero-width roi: %s", g_msg.c_str());
+      { auto q = o; q.scale = 0.0; EXPECT(says(fra_decode_device_proximity(ctx, &dj, &r40, &q, inf, counts), "region of interest"), "proximity read: zero-width roi and scale 0: %s", g_msg.c_str()); }
+      { auto q = o; q.scale = 0.0; EXPECT(says(fra_decode_device_proximity(ctx, &dj, &r48, &q, inf, counts), "scale"), "proximity read: scale 0: %s", g_msg.c_str()); }
+      { auto q = o; q.out_width = 9; EXPECT(says(fra_decode_device_proximity(ctx, &dj, &r48, &q, inf, counts), "output window"), "proximity read: window past the region: %s", g_msg.c_str()); }
+      { fra_window r = r48; r.height = 5; auto q = o; q.out_height = 5; EXPECT(says(fra_decode_device_proximity(ctx, &dj, &r, &q, inf, counts), "do not cover"), "proximity read: uncovered row: %s", g_msg.c_str()); }
+    }
+    // the reach threshold against the f64 predicate, at and around perfect squares
+    for (double scale : {1.0, 0.1, 10.0, 30.0}) {
+      bool ok = true;
+      for (int64_t k : {0, 1, 2, 3, 7, 100, 1000, 12345, 32767, 46339})
+        for (int64_t off : {-2, -1, 0, 1, 2}) {
+          const int64_t d2 = k * k + off;
+          if (d2 < 0 || d2 > fra_px::kMaxD2) continue;
+          const double md = std::sqrt((double)d2) * scale;  // exactly the distance of d2: d2 is within reach, d2 + 1 is not
+          const int64_t t = fra_px::reach_threshold(true, scale, md);
+          ok = ok && t == d2 && fra_px::within(t, scale, md) && (t == fra_px::kMaxD2 || !fra_px::within(t + 1, scale, md));
+          const double below = std::nextafter(md, 0.0);
+          if (d2 > 0) ok = ok && fra_px::reach_threshold(true, scale, below) == d2 - 1;
+          const int64_t ta = fra_px::reach_threshold(true, scale, (double)k * scale);  // a radius of k pixels
+          ok = ok && fra_px::within(ta, scale, (double)k * scale) && (ta == fra_px::kMaxD2 || !fra_px::within(ta + 1, scale, (double)k * scale));
+        }
+      EXPECT(ok, "proximity: the reach threshold disagrees with the predicate at scale %g", scale);
+    }
+    EXPECT(fra_px::reach_threshold(false, 1.0, 0.0) == fra_px::kMaxD2 && fra_px::reach_threshold(true, 1.0, INFINITY) == fra_px::kMaxD2, "proximity: no limit");
+    EXPECT(fra_px::reach_threshold(true, 1.0, 0.0) == 0 && fra_px::reach_threshold(true, 30.0, 29.0) == 0 && fra_px::reach_threshold(true, 1.0, 5.0) == 25, "proximity: pinned thresholds");
+    EXPECT(fra_px::isqrt(0) == 0 && fra_px::isqrt(24) == 4 && fra_px::isqrt(25) == 5 && fra_px::isqrt(fra_px::kMaxD2) == 46339, "proximity: isqrt");
+    // the fills as the output holds them
+    EXPECT(fra_px::out_bits(FRA_F32, NAN) == 0x7fc00000u && fra_px::out_bits(FRA_F64, -NAN) == 0x7ff8000000000000ull, "proximity: a NaN fill");
+    EXPECT(fra_px::out_bits(FRA_U8, 300.0) == 255 && fra_px::out_bits(FRA_U8, -3.0) == 0 && fra_px::out_bits(FRA_I8, -7.0) == 0xf9 && fra_px::out_bits(FRA_U16, 2.5) == 2 &&
+               fra_px::out_bits(FRA_U16, 3.5) == 4 && fra_px::out_bits(FRA_I32, NAN) == 0 && fra_px::out_bits(FRA_I16, -1e9) == 0x8000, "proximity: integer fills");
+    // the launch plan
+    {
+      struct Case { int32_t h, w, r0, c0, oh, ow; };
+      const Case cases[] = {{1, 1, 0, 0, 1, 1}, {7, 19, 0, 0, 7, 19}, {200, 70, 60, 3, 75, 60}, {130, 517, 17, 29, 90, 333}, {9, 512, 0, 0, 9, 512},
+                            {9, 513, 0, 0, 9, 513}, {3, 32768, 0, 0, 3, 32768}, {32768, 3, 0, 0, 32768, 3}, {10980, 10980, 0, 0, 10980, 10980}};
+      for (const Case& c : cases) {
+        fra_proximity_opts o{};
+        o.out_row_off = c.r0; o.out_col_off = c.c0; o.out_height = c.oh; o.out_width = c.ow;
+        const fra_px::Plan p = fra_px::make_plan(c.h, c.w, o);
+        bool ok = (int64_t)p.nchunks * 64 >= c.h && (int64_t)(p.nchunks - 1) * 64 < c.h && p.k0 * 64 <= c.r0 && c.r0 < (p.k0 + 1) * 64 &&
+                  p.k1 * 64 <= c.r0 + c.oh - 1 && c.r0 + c.oh - 1 < (p.k1 + 1) * 64 && p.k1 < p.nchunks &&
+                  (int64_t)p.col_blocks * 256 >= c.w && (int64_t)(p.col_blocks - 1) * 256 < c.w;
+        ok = ok && p.rows_per_wg * p.team_threads == 256 && p.team_threads % 64 == 0 && (p.rows_per_wg == 4) == (c.w <= 512) &&
+             (int64_t)p.row_wgs * p.rows_per_wg >= c.oh && (int64_t)(p.row_wgs - 1) * p.rows_per_wg < c.oh;
+        ok = ok && (1 << (p.levels - 1)) <= c.ow && c.ow < (1ll << p.levels);
+        // every output pixel belongs to exactly one level
+        int64_t pixels = 0;
+        for (int L = 0; L < p.levels; L++) pixels += (c.ow / (1 << (p.levels - 1 - L)) + 1) / 2;
+        ok = ok && pixels == c.ow;
+        ok = ok && p.opt_off >= 2u * (uint32_t)c.w && p.queue_off >= p.opt_off + 2u * (uint32_t)c.ow && p.count_off >= p.queue_off + 2u * p.queue_cap &&
+             p.opt_off % 4 == 0 && p.count_off % 4 == 0 && p.team_bytes == p.count_off + 8 && p.lds_bytes == p.team_bytes * (uint32_t)p.rows_per_wg &&
+             (int64_t)p.queue_cap * 64 > c.w + c.ow && p.lds_bytes + 64 <= 160 * 1024;
+        EXPECT(ok, "proximity: the plan of %d x %d, window (%d, %d, %d x %d)", c.h, c.w, c.r0, c.c0, c.oh, c.ow);
+      }
+      fra_proximity_opts o{};
+      o.out_height = 3; o.out_width = 32768;
+      const fra_px::Plan wide = fra_px::make_plan(3, 32768, o);
+      EXPECT(wide.levels == 16 && wide.rows_per_wg == 1 && wide.queue_cap == 1025 && wide.lds_bytes == 133132 && wide.row_wgs == 3 && wide.col_blocks == 128, "proximity: the widest plan: %d levels, %u bytes", wide.levels, wide.lds_bytes);
+      o.out_row_off = 60; o.out_col_off = 3; o.out_height = 75; o.out_width = 60;
+      const fra_px::Plan seam = fra_px::make_plan(200, 70, o);
+      EXPECT(seam.nchunks == 4 && seam.k0 == 0 && seam.k1 == 2 && seam.rows_per_wg == 4 && seam.row_wgs == 19 && seam.levels == 6, "proximity: the plan of the seam shape");
     }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
