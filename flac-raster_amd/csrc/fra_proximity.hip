@@ -58,15 +58,10 @@ __device__ inline bool is_target(T v, const ProxArgs& a) {
   return hit;
 }
 
-// the workgroup's sum of `v` into out[its index] (256 threads)
+// the workgroup's sum of `v` into out[its index]: a word of its own
 __device__ inline void wg_sum_to(uint32_t v, uint32_t* out, uint32_t index) {
-  __shared__ uint32_t s_part[4];
-  const uint32_t tid = threadIdx.x;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-  if ((tid & 63u) == 0) s_part[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) out[index] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+  const uint32_t total = wg_sum(v);
+  if (threadIdx.x == 0) out[index] = total;
 }
 
 // grid (col_blocks, nchunks): the target mask of 64 rows of a column per thread
@@ -235,16 +230,12 @@ __global__ void __launch_bounds__(256) k_prox_rows(ProxArgs a) {
 
 // out[x] = the sum of the n words of list x (one workgroup each)
 __global__ void __launch_bounds__(256) k_prox_fold(const uint32_t* a, uint32_t na, const uint32_t* b, uint32_t nb, unsigned long long* out) {
-  __shared__ unsigned long long s_sum[4];
   const uint32_t tid = threadIdx.x, n = blockIdx.x ? nb : na;
   const uint32_t* const p = blockIdx.x ? b : a;
   unsigned long long s = 0;
   for (uint32_t i = tid; i < n; i += 256u) s += p[i];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += (unsigned long long)__shfl_xor((long long)s, m, 64);
-  if ((tid & 63u) == 0) s_sum[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) out[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+  const unsigned long long total = wg_sum(s);
+  if (tid == 0) out[blockIdx.x] = total;
 }
 
 thread_local float g_prox_ms[2] = {0.f, 0.f};

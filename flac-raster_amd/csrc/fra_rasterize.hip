@@ -75,7 +75,6 @@ template <typename T>
 __global__ void __launch_bounds__(256) k_rasterize(RzArgs a) {
   __shared__ alignas(16) double s_xi[kTH * kRowStride];
   __shared__ alignas(16) int32_t s_feat[kChunk];
-  __shared__ uint32_t s_cnt[4];
   const uint32_t tid = threadIdx.x;
   const int32_t trow = (int32_t)(tid >> 4), r0 = (int32_t)blockIdx.y * kTH, c0 = (int32_t)blockIdx.x * kTW;
   const int32_t R = r0 + trow, C = c0 + (int32_t)(tid & 15u) * kPix;
@@ -166,24 +165,17 @@ __global__ void __launch_bounds__(256) k_rasterize(RzArgs a) {
     }
   }
   // the workgroup's covered pixels into its own word
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, m, 64);
-  if ((tid & 63u) == 0) s_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) a.partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+  const uint32_t total = wg_sum(cnt);
+  if (tid == 0) a.partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
 // out[workgroup] = the sum of its kFold partial counts
 __global__ void __launch_bounds__(256) k_rasterize_fold(const uint32_t* __restrict__ partial, uint32_t n, unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long s_sum[4];
   const uint32_t tid = threadIdx.x, base = blockIdx.x * (uint32_t)kFold;
   unsigned long long s = 0;
   for (uint32_t i = tid; i < (uint32_t)kFold && base + i < n; i += 256u) s += partial[base + i];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += (unsigned long long)__shfl_xor((long long)s, m, 64);
-  if ((tid & 63u) == 0) s_sum[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) out[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+  const unsigned long long total = wg_sum(s);
+  if (tid == 0) out[blockIdx.x] = total;
 }
 
 thread_local float g_rasterize_ms = 0.f;

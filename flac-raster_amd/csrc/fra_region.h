@@ -1,5 +1,5 @@
-// fra_region.h -- the host scaffold of the units over a raster or a decoded region on the device: six reduce it
-// (fra_decimate.hip, fra_resample.hip, fra_resample_masked.hip, fra_compare.hip, fra_stats.hip, fra_zonal.hip), two map it
+// fra_region.h -- the host scaffold of the units over a raster or a decoded region on the device: five reduce it
+// (fra_decimate.hip, fra_resample.hip with its nodata-aware reads, fra_compare.hip, fra_stats.hip, fra_zonal.hip), two map it
 // (fra_calc.hip and fra_focal.hip, whose output has a dtype, a size or a band count of its own: Dst, run_raster_to,
 // run_region_to) and one transforms it as a whole (fra_proximity.hip, with two outputs of its own: stage_in, stage_out,
 // run_region_src); fra_warp.hip and fra_rasterize.hip use its staging.  Once each:
@@ -13,6 +13,8 @@
 //     frames around a unit's kernels: a raster job (run_raster) and a region decoded by the windowed read
 //     (fra_decode_device_window, called as any caller would: same kernels, refusals and messages) into a per-call
 //     device buffer (decode; run_region_src without a destination, run_region_to and run_region with one).
+//   * device code: the vector access and the conversion of a result the mapping units share (VecOf, to_out), and the
+//     workgroup's sum of a count (wg_sum: the resampling, the warp, the proximity, the rasterizer).
 // The scan of a raster in chunks of rows and slots, which four of the units share, is in fra_scan.h.
 // Every function is inline: the units are separate translation units of one library and of one check program.
 #pragma once
@@ -309,6 +311,21 @@ __device__ inline D to_out(double x) {
   } else {
     return (D)sat(rint(x), (double)std::numeric_limits<D>::lowest(), (double)std::numeric_limits<D>::max());
   }
+}
+
+// Device code every unit that counts per workgroup shares: the sum of `v` (a 32- or 64-bit unsigned) over the 256
+// threads of a workgroup, to thread 0 alone (the others get 0).  Lane exchanges within each wave, four words of LDS,
+// one barrier: every thread of the workgroup calls it, once per kernel.  What becomes of the total is the caller's.
+template <typename S>
+__device__ inline S wg_sum(S v) {
+  static_assert(std::is_unsigned<S>::value && (sizeof(S) == 4 || sizeof(S) == 8), "a 32- or 64-bit count");
+  using X = std::conditional_t<sizeof(S) == 4, int, long long>;  // what the lane exchange takes
+  __shared__ S s_part[4];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += (S)__shfl_xor((X)v, m, 64);
+  if ((threadIdx.x & 63u) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return threadIdx.x == 0 ? (S)(s_part[0] + s_part[1] + s_part[2] + s_part[3]) : (S)0;
 }
 #endif
 

@@ -1,8 +1,10 @@
-// fra_resample.h -- what the resampling kernels and their hosts share (fra_resample.hip, fra_resample_masked.hip;
-// fra_decimate.hip takes AccOf, log2_factor and check_factor): the kernels' arguments, the device helpers of the rule
-// (include/flac_raster_amd.h: centres, tap weights, the conversion of a result), the refusals of an output size, a
-// resampling code, an average the rule's exact arithmetic does not hold, a decimation factor and a nodata value
-// (check_nodata; fra_warp.hip takes it too), and the grid of a launch.  The host scaffold around the kernels is fra_region.h.
+// fra_resample.h -- what the units that sample a raster share (fra_resample.hip with its nodata-aware reads and
+// fra_warp.hip; fra_decimate.hip takes AccOf, log2_factor and check_factor): the resampling kernel's arguments, the
+// device helpers of the rule (include/flac_raster_amd.h: centres, tap weights, the conversion of a result, what an
+// invalid pixel is, and the value of a bilinear or cubic pixel from its taps: combine_taps, the one place that holds
+// "all taps valid: the unmasked formula; else the masked bilinear of the same centre"), the refusals of an output size,
+// a resampling code, an average the rule's exact arithmetic does not hold, a decimation factor and a nodata value, and
+// the grid of a launch.  The host scaffold around the kernels is fra_region.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,12 +33,10 @@ struct ResampleArgs {
   int32_t vec;  // average: 16-byte row loads are aligned (scs == 1; base, row and band strides multiples of 16 bytes)
   int32_t narrow;  // average of 8- and 16-bit integers: a column's sum fits 32 bits (h' 2^(8 itemsize) <= 2^31); masked:
                    // and its valid weight 16
+  double nodata;               // the masked instantiations only
+  unsigned long long* filled;  // ... one word per band, zeroed by the host; null: not counted
 };
-struct MaskedArgs : ResampleArgs {
-  double nodata;
-  unsigned long long* filled;  // one word per band, zeroed by the host; null: not counted
-};
-static_assert(sizeof(ResampleArgs) == 128 && sizeof(MaskedArgs) == 144, "the kernels' arguments, without padding");
+static_assert(sizeof(ResampleArgs) == 144, "the kernel's arguments, without padding");
 
 template <typename T>
 struct AccOf { using type = std::conditional_t<std::is_floating_point<T>::value, double, long long>; };
@@ -76,6 +76,78 @@ __device__ inline T from_f64(double v) {
     constexpr double hi = (double)((1ull << (8 * sizeof(T) - (std::is_signed<T>::value ? 1 : 0))) - 1);
     return (T)(long long)fmin(fmax(rint(v), lo), hi);
   }
+}
+
+// (double)x == nd (nd = (T)nodata is exact, says the host; a NaN nd equals nothing), or a NaN pixel
+template <typename T>
+__device__ inline bool invalid(T x, T nd) {
+  if constexpr (std::is_floating_point<T>::value) return x == nd || x != x;
+  else return x == nd;
+}
+
+// taps per axis of a mode that interpolates
+template <int MODE>
+constexpr int kTaps = MODE == FRA_RESAMPLE_BILINEAR ? 2 : 4;
+
+// The value of a bilinear or cubic pixel from its taps x[j][i] (tap row j, tap column i, already fetched and clamped)
+// and the fractions ty, tx of its centre: the rule's formula, vertically (top to bottom) then left to right, converted
+// by CONV.  MASKED: that formula when every tap is valid, else the masked bilinear of the same centre over the valid
+// ones of its four taps; a pixel none of them reaches gets `fillv` and raises *nfill.
+template <typename T, int MODE, bool MASKED, T (*CONV)(double)>
+__device__ inline T combine_taps(const T (&x)[kTaps<MODE>][kTaps<MODE>], double ty, double tx, T nd, T fillv,
+                                 uint32_t* nfill) {
+  constexpr int NT = kTaps<MODE>;
+  if constexpr (MASKED) {
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < NT; j++)
+#pragma unroll
+      for (int i = 0; i < NT; i++) all = all && !invalid(x[j][i], nd);
+    if (!all) {
+      constexpr int M = MODE == FRA_RESAMPLE_CUBIC ? 1 : 0;  // where the bilinear taps i0, i0 + 1 lie among the NT
+      const double wy[2] = {1.0 - ty, ty}, wx[2] = {1.0 - tx, tx};
+      double v = 0.0, wt = 0.0;
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        double c = 0.0, u = 0.0;
+        bool have = false;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const T xv = x[M + j][M + i];
+          if (!invalid(xv, nd)) {
+            const double term = (double)xv * wy[j];
+            c = have ? c + term : term;
+            u = have ? u + wy[j] : wy[j];
+            have = true;
+          }
+        }
+        if (have) {
+          const double cv = c * wx[i], cu = u * wx[i];
+          v = any ? v + cv : cv;
+          wt = any ? wt + cu : cu;
+          any = true;
+        }
+      }
+      if (!any || wt <= 0.0) {
+        *nfill += 1u;
+        return fillv;
+      }
+      return CONV(v / wt);
+    }
+  }
+  double wy[NT], wx[NT];
+  tap_weights<MODE>(ty, wy);
+  tap_weights<MODE>(tx, wx);
+  double v = 0.0;
+#pragma unroll
+  for (int i = 0; i < NT; i++) {
+    double c = (double)x[0][i] * wy[0];  // vertically, top to bottom
+#pragma unroll
+    for (int j = 1; j < NT; j++) c = c + (double)x[j][i] * wy[j];
+    v = i == 0 ? c * wx[0] : v + c * wx[i];  // then left to right
+  }
+  return CONV(v);
 }
 
 // the sizes of a resampling into `a`; FRA_E_INVALID for an output size, a code or an average the rule refuses
@@ -140,7 +212,7 @@ inline int check_nodata(double nd, int dtype, const char* what = "nodata") {
   return FRA_OK;
 }
 
-// The launch of k_resample / k_resample_masked over `io` into `a` (its sizes are set), *mode and *grid.
+// The launch of k_resample over `io` into `a` (its sizes are set), *mode and *grid.
 // `same_size_copies`: an output of the input's size is the input, in every mode (the resampling's rule; the decimation
 // has no such case).  `masked`: the kernel keeps a column's valid weight in 16 bits beside its NARROW sum.
 inline int plan_grid(ResampleArgs* a, const fra_region::Io& io, int dtype, int channels, int* mode, bool same_size_copies,

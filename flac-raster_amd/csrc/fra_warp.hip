@@ -7,7 +7,8 @@
 // checked against bit for bit): u = C + 0.5, v = R + 0.5; AFFINE x = (a u + b v) + c, y = (d u + e v) + f; GRID the
 // bilinear patch of the cell (min(C / step, gw - 2), min(R / step, gh - 2)); inside when 0 <= x < W and 0 <= y < H, else
 // fill; nearest in[floor(y)][floor(x)]; bilinear and cubic about px = x - 0.5 with the resampling rule's taps, weights,
-// clamping, order and conversion; with a nodata value the nodata-aware rule's masked bilinear.
+// clamping, order and conversion; with a nodata value the nodata-aware rule's masked bilinear (fra_resample.h:
+// combine_taps, which the resampling kernel calls too; the conversion of a NaN and the fill are the warp's own).
 //
 // k_warp<T, MODE, MASKED>: a workgroup owns a tile of kTH x kTW = 16 x 64 output pixels of one band; wave w owns the tile
 // rows w, w + 4, w + 8, w + 12 and a lane one column, so a wave stores 64 neighbouring pixels and, under a map close to a
@@ -17,8 +18,8 @@
 // coalesced 16-byte row loads and read every tap from there was built, measured and deleted -- over the 4 x 10980^2
 // uint16 scene it took 2.22 ms against 1.94 ms for a 10 degree rotation (bilinear), and lost for a shift, for the
 // Mercator grid and for the nearest as well (DESIGN 6c has the table).
-//   The counters.  The fill count as k_resample_masked's: summed within the wave, one atomicAdd per workgroup that has
-//   any into the band's word.  One 64-bit vector atomic add per workgroup into the gathered counter, which is kept in
+//   The counters.  The fill count as k_resample_masked's: summed over the workgroup (fra_region.h: wg_sum), one
+//   atomicAdd per workgroup that has any into the band's word.  One 64-bit vector atomic add per workgroup into the gathered counter, which is kept in
 //   kShards words on lines of their own and summed by the host: with one word the 472,656 adds of that scene took 3.8 of
 //   the kernel's 6.0 ms (a word takes about 88 adds per microsecond).  fra_warp_paths reports 0 staged workgroups.
 // Memory safety does not rest on the host's window arithmetic: a tap index is clamped to the region after it is
@@ -68,13 +69,6 @@ struct WarpArgs {
   int32_t kind, step, gh, gw;
   uint32_t tiles_x, ntiles;    // tiles across the output, and in all
 };
-
-// (double)x == nd (nd = (T)nodata is exact, says the host; a NaN nd equals nothing), or a NaN pixel
-template <typename T>
-__device__ inline bool invalid(T x, T nd) {
-  if constexpr (std::is_floating_point<T>::value) return x == nd || x != x;
-  else return x == nd;
-}
 
 // tap i along an axis of n raster pixels as an index into the region [off, off + len) of it: clamped to the raster (the
 // rule), then to the region (which holds every tap when the host's window is right; memory safety when it is not)
@@ -131,8 +125,6 @@ __device__ inline int32_t first_tap(double x, double* t) {
 // to be counted (it got the fill, or the nearest picked an invalid pixel).
 template <typename T, int MODE, bool MASKED, typename Fetch>
 __device__ inline T sample(const WarpArgs& a, double x, double y, T nd, T fillv, Fetch&& fetch, uint32_t* nfill) {
-  constexpr int NT = MODE == FRA_RESAMPLE_NEAREST ? 1 : (MODE == FRA_RESAMPLE_BILINEAR ? 2 : 4);
-  constexpr int M = MODE == FRA_RESAMPLE_CUBIC ? 1 : 0;  // where the bilinear taps i0, i0 + 1 lie among the NT
   double ty, tx;
   const int32_t fy = first_tap<MODE>(y, &ty), fx = first_tap<MODE>(x, &tx);
   if constexpr (MODE == FRA_RESAMPLE_NEAREST) {
@@ -140,8 +132,8 @@ __device__ inline T sample(const WarpArgs& a, double x, double y, T nd, T fillv,
     if constexpr (MASKED) *nfill += invalid(v, nd) ? 1u : 0u;
     return v;
   } else {
+    constexpr int NT = kTaps<MODE>;
     T xv[NT][NT];  // [j][i]: tap row j, tap column i
-    bool all = true;
     int32_t cols[NT];
 #pragma unroll
     for (int i = 0; i < NT; i++) cols[i] = tap_at(fx + i, a.W, a.col0, a.rw);
@@ -149,61 +141,14 @@ __device__ inline T sample(const WarpArgs& a, double x, double y, T nd, T fillv,
     for (int j = 0; j < NT; j++) {
       const int32_t r = tap_at(fy + j, a.H, a.row0, a.rh);
 #pragma unroll
-      for (int i = 0; i < NT; i++) {
-        xv[j][i] = fetch(r, cols[i]);
-        if constexpr (MASKED) all = all && !invalid(xv[j][i], nd);
-      }
+      for (int i = 0; i < NT; i++) xv[j][i] = fetch(r, cols[i]);
     }
-    if (all) {  // the unmasked formula
-      double wy[NT], wx[NT];
-      tap_weights<MODE>(ty, wy);
-      tap_weights<MODE>(tx, wx);
-      double v = 0.0;
-#pragma unroll
-      for (int i = 0; i < NT; i++) {
-        double c = (double)xv[0][i] * wy[0];  // vertically, top to bottom
-#pragma unroll
-        for (int j = 1; j < NT; j++) c = c + (double)xv[j][i] * wy[j];
-        v = i == 0 ? c * wx[0] : v + c * wx[i];  // then left to right
-      }
-      return result_of<T>(v);
-    }
-    // the masked bilinear of the same centre
-    const double wy[2] = {1.0 - ty, ty}, wx[2] = {1.0 - tx, tx};
-    double v = 0.0, wt = 0.0;
-    bool any = false;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      double c = 0.0, u = 0.0;
-      bool have = false;
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        const T t = xv[M + j][M + i];
-        if (!invalid(t, nd)) {
-          const double term = (double)t * wy[j];
-          c = have ? c + term : term;
-          u = have ? u + wy[j] : wy[j];
-          have = true;
-        }
-      }
-      if (have) {
-        const double cv = c * wx[i], cu = u * wx[i];
-        v = any ? v + cv : cv;
-        wt = any ? wt + cu : cu;
-        any = true;
-      }
-    }
-    if (!any || wt <= 0.0) {
-      *nfill += 1u;
-      return fillv;
-    }
-    return result_of<T>(v / wt);
+    return combine_taps<T, MODE, MASKED, result_of<T>>(xv, ty, tx, nd, fillv, nfill);
   }
 }
 
 template <typename T, int MODE, bool MASKED>
 __global__ void __launch_bounds__(256) k_warp(WarpArgs a) {
-  __shared__ uint32_t s_fill[4];
   const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
   const uint32_t band = blockIdx.y;
   const uint32_t tile_id = blockIdx.z * gridDim.x + blockIdx.x;
@@ -229,14 +174,9 @@ __global__ void __launch_bounds__(256) k_warp(WarpArgs a) {
     }
   }
   // the counters: the workgroup's fill count into its band's word, and the workgroup itself into its shard
-  uint32_t s = nfill;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += (uint32_t)__shfl_xor((int)s, m, 64);
-  if (lane == 0) s_fill[wave] = s;
-  __syncthreads();
+  const uint32_t total = wg_sum(nfill);
   if (tid == 0) {
-    const unsigned long long total = (unsigned long long)s_fill[0] + s_fill[1] + s_fill[2] + s_fill[3];
-    if (total) atomicAdd(&a.filled[band], total);
+    if (total) atomicAdd(&a.filled[band], (unsigned long long)total);
     atomicAdd(&a.gathered[((tile_id + band) % (uint32_t)kShards) * kShardStride], 1ull);
   }
 }

@@ -206,6 +206,31 @@ def test_kernel_nearest_no_invalid_and_wide_spans(dt):
             assert _same(ctx.resample(tall, (1, 2), "average", nodata=nd), resample(tall, (1, 2), "average", nodata=nd)), h
 
 
+@pytest.mark.parametrize("h", (65535, 65536, 65539))
+@pytest.mark.parametrize("dt", (np.uint8, np.int8), ids=("uint8", "int8"))
+def test_kernel_wide_masked_average_of_8_bit(dt, h):
+    """The masked average of an 8-bit dtype keeps a column's valid weight in 16 bits while h' < 65536 and takes the wide
+    instance from there on: h rows into one row are h' = h (narrow, wide, wide), into two h' = 65535, 32768, 65539
+    (narrow, narrow, wide).  65536 valid pixels of a column are the sharp case: a weight of 16 bits wraps to 0 and the
+    output becomes the fill."""
+    dt = np.dtype(dt)
+    rng = np.random.default_rng(970 + dt.num + h)
+    ctx = _ctx()
+    info = np.iinfo(dt)
+    a = np.full((1, h, 3), info.max, dt)
+    a[0, rng.random(h) < 0.3, 0] = 7
+    vals = rng.integers(info.min, int(info.max), size=len(a[0, ::7, 1]), dtype=np.int64)  # the range without one value ...
+    a[0, ::7, 1] = (vals + (vals >= 7)).astype(dt)  # ... which is 7: the column is valid throughout
+    a[0, ::5, 2] = 7
+    assert (a[0, :, 1] != 7).all() and (a[0, :, 0] == 7).any()  # u_i = h in column 1: 65536 does not fit 16 bits
+    for out_shape in ((1, 2), (2, 2)):
+        want = resample(a, out_shape, "average", nodata=7.0)
+        filled = np.full(1, 99, np.uint64)
+        got = ctx.resample(a, out_shape, "average", nodata=7.0, filled=filled)
+        assert _same(got, want), (h, out_shape, got.tolist(), want.tolist())
+        assert np.array_equal(filled, _count_fill(want, 7.0)), (h, out_shape, filled)
+
+
 # ------------------------------------------------------------------------------- 2. the decimate geometry
 @pytest.mark.parametrize("dt", DTYPES, ids=IDS)
 def test_decimate_geometry_equals_the_numpy_rule(dt):

@@ -103,7 +103,8 @@ same run, beside the plain read and the ``--calc`` legs, once per mode of ``--wa
 centre, ``shift:DX,DY``, or ``mercator`` (UTM 33 N to EPSG:3857 through ``warp.fit_grid``).  Per leg ``k_warp_ms`` (HIP
 events), the bytes read and written, the ``staged`` / ``gathered`` workgroups and, with ``--calc b1:uint16``,
 ``over_calc_copy_per_band``.  It exits non-zero unless three 64 x 512 rectangles of the result equal ``warp.warp_arrays``
-of the plain read byte for byte.  ``FRA_LIB_PATH`` set to the ``warpgather`` diagnostic build times the kernel without its
+of the plain read byte for byte.  With ``--nodata X`` (a value of the scene's uint16, or ``corner``) the legs run the
+masked ``k_warp`` and are checked against ``warp_arrays`` with that value.  ``FRA_LIB_PATH`` set to the ``warpgather`` diagnostic build times the kernel without its
 staged path.
 
     python tools/bench_decode.py --warp shift:0.5,0.5 --warp rotate:10 --warp mercator --calc b1:uint16 --steps 5 --warmup 2
@@ -376,7 +377,7 @@ def main():
     ap.add_argument("--region", default=None, metavar="r,c,h,w", help="with --resample: the region (default: all)")
     ap.add_argument("--nodata", default=None, metavar="X",
                     help="with --decimate or --resample: the nodata-aware read with this value of the decoded int16 "
-                         "('corner': what pixel (0, 0) decodes to)")
+                         "('corner': what pixel (0, 0) decodes to); with --calc, --focal or --warp: of the scene's uint16")
     ap.add_argument("--compare", action="store_true",
                     help="time the comparison of the container with its source raster against the plain read")
     ap.add_argument("--stats", action="store_true",
@@ -409,8 +410,8 @@ def main():
     args = ap.parse_args()
     if args.decimate and args.resampling not in RESAMPLING:
         ap.error("--decimate takes --resampling nearest or average")
-    if args.nodata is not None and not (args.decimate or args.resample or args.calc or args.focal):
-        ap.error("--nodata goes with --decimate, --resample, --calc or --focal")
+    if args.nodata is not None and not (args.decimate or args.resample or args.calc or args.focal or args.warp):
+        ap.error("--nodata goes with --decimate, --resample, --calc, --focal or --warp")
     if args.dem and not args.focal:
         ap.error("--dem goes with --focal")
     if args.nodata not in (None, "corner"):
@@ -989,7 +990,7 @@ def main():
                 for s in range(args.warmup + args.steps):
                     t0 = time.perf_counter()
                     _, filled = ctx.decode_device_warped((frames_ptr, total), citems, dev_res, dt, B, (H * W, W, 1), (H, W), (H, W),
-                                                         m, mode, denorm=N.DENORM_PCM16)
+                                                         m, mode, denorm=N.DENORM_PCM16, nodata=nodata)
                     t1 = time.perf_counter()
                     if s >= args.warmup:
                         wall.append((t1 - t0) * 1e3)
@@ -1006,7 +1007,7 @@ def main():
                         for r in range(ow_[2]):
                             ctx.d2h(got[k, r], dev_res + ((k * H + ow_[0] + r) * W + ow_[1]) * dt.itemsize)
                     if not ok.any():
-                        if (got != 0).any():
+                        if (got != (0 if nodata is None else nodata)).any():
                             raise SystemExit(f"warp {text} {mode}: a rectangle outside the source is not all fill")
                         continue
                     r0, r1 = max(int(np.floor(y[ok].min())) - 3, 0), min(int(np.floor(y[ok].max())) + 3, H - 1)
@@ -1015,12 +1016,13 @@ def main():
                     for k in range(B):
                         for r in range(part.shape[1]):
                             ctx.d2h(part[k, r], dev_out + ((k * H + r0 + r) * W + c0) * dt.itemsize)
-                    want, _ = WP.warp_arrays(part, (H, W), m, mode, origin=(r0, c0), raster_shape=(H, W), out_window=ow_)
+                    want, _ = WP.warp_arrays(part, (H, W), m, mode, nodata=nodata, origin=(r0, c0), raster_shape=(H, W),
+                                             out_window=ow_)
                     if got.tobytes() != want.tobytes():
                         raise SystemExit(f"warp {text} {mode}: the rectangle at {ow_[:2]} differs from warp_arrays")
                 rd = wr = B * H * W * dt.itemsize
                 res["legs"].append({
-                    "warp": text, "map": what, "resampling": mode, "filled": [int(v) for v in filled],
+                    "warp": text, "map": what, "resampling": mode, "nodata": nodata, "filled": [int(v) for v in filled],
                     "source_window": WP.source_window(m, (H, W), (H, W)), "staged": staged, "gathered": gathered,
                     "warp_wall_ms": round(med(wall), 3), "inner_read_ms": round(med(inner), 3),
                     "k_warp_ms": round(med(kw), 4), "bytes_read": rd, "bytes_written": wr,

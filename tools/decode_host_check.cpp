@@ -10,7 +10,7 @@
 //     exactly when the flipped byte lies in a selected frame;
 //   * the argument validation of fra_decode_device, fra_decode_device_window, the verify entry behind
 //     fra_plan_verify (fra_internal_verify_device: null arguments, a first frame past the stream), the decimated and resampled reads,
-//     their nodata-aware entries (fra_resample_masked.hip: a nodata value the dtype does not admit included),
+//     their nodata-aware entries (fra_resample.hip: a nodata value the dtype does not admit included),
 //     the comparison (fra_compare, fra_decode_device_compare), the statistics (fra_stats, fra_decode_device_stats),
 //     the band math (fra_calc, fra_decode_device_calc, and every refusal of its program validator, fra_calc_check),
 //     the focal operations (fra_focal, fra_decode_device_focal, and every refusal of their spec validator,
@@ -452,7 +452,7 @@ int main(int argc, char** argv) {
     { auto j = mj; j.dtype = FRA_F64; j.height = (1 << 27) + 1; j.width = (1 << 26) + 1; j.out_height = 2; j.out_width = 2; EXPECT(fra_resample(ctx, &j) == FRA_E_INVALID && g_msg.find("average") != std::string::npos, "resample: f64 average of 2^53 weights accepted"); }
     EXPECT(fra_resample_timing(nullptr) == FRA_E_INVALID, "resample timing: null accepted");
   }
-  // ... and of the nodata-aware reads (fra_resample_masked.hip): the unmasked refusals, and a nodata value the dtype
+  // ... and of the nodata-aware reads (fra_resample.hip): the unmasked refusals, and a nodata value the dtype
   // does not admit, before any GPU work
   {
     fra_decode_item di = it;
