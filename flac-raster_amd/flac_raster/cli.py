@@ -10,6 +10,7 @@ from __future__ import annotations
 import json
 import logging
 import tempfile
+from contextlib import contextmanager
 from pathlib import Path
 from typing import List, Optional
 
@@ -54,6 +55,48 @@ def _gpu_present() -> bool:
         return False
 
 
+def _pick_device(device: Optional[int], cpu: bool = False) -> Optional[int]:
+    """The given device, else device 0 when a GPU is present, else the host path; ``cpu``: the host path."""
+    if cpu:
+        return None
+    return device if device is not None else (0 if _gpu_present() else None)
+
+
+def _request_window(bbox: Optional[str], pixels: Optional[str]):
+    """``(window, bbox)`` of ``--window`` and ``--bbox``, of which at most one may be given."""
+    if bbox is not None and pixels is not None:
+        console.print("[red]Error: give at most one of --bbox and --window[/red]")
+        raise typer.Exit(1)
+    box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
+    win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+    return win, box
+
+
+def _existing(*paths: Path):
+    for p in paths:
+        if not p.exists():
+            console.print(f"[red]File not found: {p}[/red]")
+            raise typer.Exit(1)
+
+
+@contextmanager
+def _failing(what: str):
+    """The frame of a command: an exit passes; anything else is logged as ``what``, printed, and exits with 1."""
+    try:
+        yield
+    except typer.Exit:
+        raise
+    except VerifyMismatch as e:  # convert --verify: reported by its first differing sample, without a traceback
+        console.print(f"[red]Verify failed: tile {e.tile}, pixel row {e.pixel[0]} col {e.pixel[1]} band {e.pixel[2]}: "
+                      f"expected sample {e.expected}, decoded {e.got} ({e.mismatches} samples differ in this tile, "
+                      f"{e.bad_tiles} tile(s) differ)[/red]")
+        raise typer.Exit(1)
+    except Exception as e:
+        logger.exception(what)
+        console.print(f"[red]Error: {e}[/red]")
+        raise typer.Exit(1)
+
+
 @app.command()
 def convert(
     input_file: str = typer.Argument(..., help="Input file (TIFF or FLAC)"),
@@ -71,7 +114,7 @@ def convert(
     """Convert between TIFF and FLAC formats."""
     if verbose:
         logging.getLogger("flac_raster").setLevel(logging.DEBUG)
-    try:
+    with _failing("Conversion failed"):
         src = _local(input_file)
         if not src.exists():
             console.print(f"[red]Error: Input file does not exist: {src}[/red]")
@@ -105,8 +148,7 @@ def convert(
             from .streaming import is_streaming_container, streaming_to_tiff
 
             if is_streaming_container(src):
-                # first of --devices, else device 0 when a GPU is present, else the host decoder
-                dev = devs[0] if devs else (0 if _gpu_present() else None)
+                dev = _pick_device(devs[0] if devs else None)  # the first of --devices
                 idx = streaming_to_tiff(src, output_file, device=dev)
                 console.print(f"[green]SUCCESS: Converted {len(idx['frames'])} tiles to TIFF: {output_file}[/green]")
                 return
@@ -117,23 +159,12 @@ def convert(
                 console.print(f"[green]Created {len(res.frames)} spatial tiles[/green]")
         else:
             conv.flac_to_tiff(src, output_file)
-    except typer.Exit:
-        raise
-    except VerifyMismatch as e:
-        console.print(f"[red]Verify failed: tile {e.tile}, pixel row {e.pixel[0]} col {e.pixel[1]} band {e.pixel[2]}: "
-                      f"expected sample {e.expected}, decoded {e.got} ({e.mismatches} samples differ in this tile, "
-                      f"{e.bad_tiles} tile(s) differ)[/red]")
-        raise typer.Exit(1)
-    except Exception as e:
-        logger.exception("Conversion failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
 def info(file_path: str = typer.Argument(..., help="File to inspect")):
     """Display information about a FLAC or TIFF file."""
-    try:
+    with _failing("Info failed"):
         p = _local(file_path)
         if not p.exists():
             console.print(f"[red]Error: File not found: {p}[/red]")
@@ -146,12 +177,6 @@ def info(file_path: str = typer.Argument(..., help="File to inspect")):
         else:
             console.print(f"[red]Unsupported format: {s}[/red]")
             raise typer.Exit(1)
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Info failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -166,7 +191,7 @@ def extract(
     """Extract one tile of a streaming FLAC file to GeoTIFF."""
     from .streaming import open_streaming, read_tile_bytes, select_frame
 
-    try:
+    with _failing("Extraction failed"):
         path = _local(flac_file)
         sf = open_streaming(path)
         frames = sf.index["frames"]
@@ -185,12 +210,6 @@ def extract(
         console.print(f"[green]Saved to: {output}[/green]")
         console.print(f"[blue]Bandwidth: {fr['byte_size'] / 1024:.1f} KB "
                       f"(saved {(1 - fr['byte_size'] / total) * 100:.1f}%)[/blue]")
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Extraction failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 def _print_nodata_shares(nodata, shares):
@@ -216,15 +235,13 @@ def window(
     """Read a pixel window of a streaming FLAC file to GeoTIFF (only the tiles and frames it needs)."""
     from .streaming import window_to_tiff
 
-    try:
+    with _failing("Window read failed"):
         if (bbox is None) == (pixels is None):
             console.print("[red]Error: give exactly one of --bbox and --window[/red]")
             raise typer.Exit(1)
+        win, box = _request_window(bbox, pixels)
         path = _local(flac_file)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
-        # the given device, else device 0 when a GPU is present, else the host decoder (as convert)
-        dev = device if device is not None else (0 if _gpu_present() else None)
+        dev = _pick_device(device)
         shape = tuple(int(x.strip()) for x in out_shape.split(",")) if out_shape else None
         shares: list = []
         got, idx = window_to_tiff(path, output, window=win, bbox=box, device=dev, decimate=decimate,
@@ -235,12 +252,6 @@ def window(
         console.print(f"[green]Saved rows {got[0]}..{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]} of "
                       f"{idx['height']} x {idx['width']}{scale} to: {output}[/green]")
         _print_nodata_shares(nodata, shares)
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Window read failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -259,9 +270,9 @@ def overview(
     """Write a reduced-resolution preview of a whole streaming FLAC file to GeoTIFF."""
     from .streaming import overview_to_tiff
 
-    try:
+    with _failing("Overview failed"):
         path = _local(flac_file)
-        dev = device if device is not None else (0 if _gpu_present() else None)
+        dev = _pick_device(device)
         if (factor is None) == (size is None):
             console.print("[red]Error: give exactly one of --factor and --size[/red]")
             raise typer.Exit(1)
@@ -272,12 +283,6 @@ def overview(
         console.print(f"[green]Saved {idx['height']} x {idx['width']} {how} ({resampling}) as "
                       f"{shape[1]} x {shape[2]} to: {output}[/green]")
         _print_nodata_shares(nodata, shares)
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Overview failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -289,7 +294,7 @@ def query(
     """Byte ranges of the tiles of a spatial FLAC file that intersect a bbox."""
     from .spatial_encoder import SpatialFLACStreamer
 
-    try:
+    with _failing("Query failed"):
         coords = tuple(float(x.strip()) for x in bbox.split(","))
         if len(coords) != 4:
             console.print("[red]Bbox must have 4 coordinates[/red]")
@@ -307,12 +312,6 @@ def query(
         if output:
             output.write_text(json.dumps({"bbox": list(coords), "ranges": [{"start": s, "end": e} for s, e in ranges],
                                           "total_bytes": total}, indent=2))
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Query failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -351,17 +350,11 @@ def check(
     from .compare import display_first_differences
     from .streaming import check_against_tiff
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
-        if not source.exists():
-            console.print(f"[red]File not found: {source}[/red]")
-            raise typer.Exit(1)
+    with _failing("Check failed"):
+        win, box = _request_window(bbox, pixels)
+        _existing(source)
         path = _local(flac_file)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
-        dev = device if device is not None else (0 if _gpu_present() else None)
+        dev = _pick_device(device)
         res, got, _ = check_against_tiff(path, source, window=win, bbox=box, device=dev, semantics=semantics,
                                          count_one_sided_nans=max_diff is not None)
         display_comparison_table(res)
@@ -382,12 +375,6 @@ def check(
             console.print(f"[red]{path.name} differs from {source.name} in {res['differing']} pixel values ({where}, "
                           f"{semantics}, largest difference {res['max_difference']:g})[/red]")
             raise typer.Exit(1)
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Check failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -406,37 +393,21 @@ def stats(
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
 ):
     """Band statistics, histogram and percentiles of a streaming FLAC file or a GeoTIFF."""
-    import numpy as np
-
     from .stats import display_stats_table, exact_range, percentile
-    from .streaming import container_stats, is_streaming_container, open_streaming, tiff_stats
-    from .tiff import GeoTIFF
+    from .source import open_source
+    from .streaming import container_stats, tiff_stats
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
+    with _failing("Statistics failed"):
+        win, box = _request_window(bbox, pixels)
         path = _local(file_path)
-        if not path.exists():
-            console.print(f"[red]File not found: {path}[/red]")
-            raise typer.Exit(1)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        _existing(path)
         qs = [float(x.strip()) for x in percentiles.split(",") if x.strip()]
-        with open(path, "rb") as f:
-            is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-        is_container = not is_tiff and is_streaming_container(path)
-        if not is_tiff and not is_container:
-            console.print("[red]Error: a streaming FLAC file (convert --streaming) or a GeoTIFF is needed[/red]")
+        try:
+            src = open_source(path)
+        except ValueError as e:  # neither a container nor a GeoTIFF: a refusal, not a failure to log
+            console.print(f"[red]Error: {e}[/red]")
             raise typer.Exit(1)
-        if is_container:
-            dt = np.dtype(open_streaming(path).index["dtype"])
-        else:
-            g = GeoTIFF(path)
-            try:
-                dt = np.dtype(g.info.dtype)
-            finally:
-                g.close()
+        dt = src.dtype
         rng = tuple(float(x.strip()) for x in hist_range.split(",")) if hist_range else None
         if rng is not None and len(rng) != 2:
             console.print("[red]Error: --range takes 'lo,hi'[/red]")
@@ -446,8 +417,8 @@ def stats(
             rng = (lo, hi)
         elif bins is None:
             bins = 256
-        dev = device if device is not None else (0 if _gpu_present() else None)
-        if is_container:
+        dev = _pick_device(device)
+        if src.encoded:
             bands, got, _ = container_stats(path, window=win, bbox=box, bins=bins, hist_range=rng, nodata=nodata,
                                             device=dev, semantics=semantics)
         else:
@@ -458,14 +429,8 @@ def stats(
             for b in bands:
                 b["percentiles"] = {f"{q:g}": percentile(b, q) for q in qs}
             export_json.write_text(json.dumps({"file": path.name, "dtype": str(dt), "window": list(got),
-                                               "semantics": semantics if is_container else None,
+                                               "semantics": semantics if src.encoded else None,
                                                "device": dev, "bands": bands}, indent=2))
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Statistics failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -490,21 +455,14 @@ def zonal(
     from .streaming import zonal_with_polygons, zonal_with_tiff
     from .zonal import display_zonal_table, export_report
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
+    with _failing("Zonal statistics failed"):
+        win, box = _request_window(bbox, pixels)
         path = _local(file_path)
-        for p in (path, zones):
-            if not p.exists():
-                console.print(f"[red]File not found: {p}[/red]")
-                raise typer.Exit(1)
+        _existing(path, zones)
         if export is not None and export.suffix.lower() not in (".json", ".csv"):
             console.print("[red]Error: --export takes a .json or a .csv file[/red]")
             raise typer.Exit(1)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
-        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        dev = _pick_device(device, cpu)
         if zones.suffix.lower() in (".geojson", ".json"):
             if ignore is not None:
                 console.print("[red]Error: --ignore goes with a zones GeoTIFF: polygons leave the pixels outside them "
@@ -522,12 +480,6 @@ def zonal(
                                           f"{got[1]}..{got[1] + got[3]}")
         if export is not None:
             export_report(export, report, {"file": path.name, "zones": zones.name, "window": list(got), "device": dev})
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Zonal statistics failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -549,31 +501,18 @@ def rasterize(
     """Polygons of a GeoJSON file burned onto the grid of a streaming FLAC file or a GeoTIFF -> GeoTIFF."""
     from .streaming import rasterize_to_tiff
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
+    with _failing("Rasterizing failed"):
+        win, box = _request_window(bbox, pixels)
         if attribute is not None and burn is not None:
             console.print("[red]Error: give at most one of --attribute and --burn[/red]")
             raise typer.Exit(1)
-        for p in (shapes, like):
-            if not p.exists():
-                console.print(f"[red]File not found: {p}[/red]")
-                raise typer.Exit(1)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
-        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        _existing(shapes, like)
+        dev = _pick_device(device, cpu)
         got, burned, dt = rasterize_to_tiff(like, shapes, output_path, attribute=attribute, burn=burn, window=win, bbox=box,
                                             fill=fill, dtype=dtype, device=dev)
         console.print(f"[green]{output_path}[/green]: {dt}, rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
                       f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
         console.print(f"burned: {burned} pixels, {100.0 * burned / (got[2] * got[3]):.2f}% of the window")
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Rasterizing failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -604,35 +543,25 @@ def proximity(
     """Distance of every pixel to the nearest target pixel (or polygon), and the nearest target's value -> GeoTIFF."""
     import numpy as np
 
-    from .proximity import Options, default_fill
-    from .streaming import _fill_tag, proximity_of_polygons, proximity_to_tiff
-    from .tiff import write_geotiff
+    from .proximity import Options
+    from .streaming import proximity_of_polygons_to_tiff, proximity_to_tiff
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
+    with _failing("Proximity failed"):
+        win, box = _request_window(bbox, pixels)
         if attribute is not None and like is None:
             console.print("[red]Error: --attribute goes with a GeoJSON source and --like[/red]")
             raise typer.Exit(1)
         path = _local(file_path)
-        for p in (path,) + ((like,) if like is not None else ()):
-            if not p.exists():
-                console.print(f"[red]File not found: {p}[/red]")
-                raise typer.Exit(1)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
+        _existing(path)
+        if like is not None:
+            _existing(like)
         vals = tuple(float(x.strip()) for x in values.split(",")) if values else ()
-        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        dev = _pick_device(device, cpu)
         odt = np.dtype(dtype)
         opts = Options(values=vals, max_dist=max_dist, fixed=fixed, fill=fill, alloc_fill=alloc_fill)
         if like is not None:
-            dist, labels, counts, got, transform, crs = proximity_of_polygons(like, path, attribute, opts, window=win,
-                                                                              bbox=box, units=units, dist_dtype=odt, device=dev)
-            write_geotiff(output_path, dist, transform=transform, crs=crs,
-                          nodata=_fill_tag(default_fill(odt) if fill is None else fill, odt))
-            if alloc is not None:
-                write_geotiff(alloc, labels, transform=transform, crs=crs, nodata=_fill_tag(alloc_fill, labels.dtype))
+            got, counts = proximity_of_polygons_to_tiff(like, path, output_path, attribute, opts, window=win, bbox=box,
+                                                        units=units, dist_dtype=odt, alloc_path=alloc, device=dev)
         else:
             got, counts = proximity_to_tiff(path, output_path, opts, window=win, bbox=box, units=units, dist_dtype=odt,
                                             alloc_path=alloc, device=dev)
@@ -640,12 +569,6 @@ def proximity(
         console.print(f"[green]{output_path}[/green]: {odt}, rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
                       f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
         console.print(f"targets: {int(counts[0])}; within reach: {100.0 * int(counts[1]) / max(1, n):.2f}% of the pixels")
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Proximity failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 @app.command()
@@ -669,17 +592,11 @@ def calc(
 
     from .streaming import calc_to_tiff
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
+    with _failing("Band math failed"):
+        win, box = _request_window(bbox, pixels)
         path = _local(file_path)
-        if not path.exists():
-            console.print(f"[red]File not found: {path}[/red]")
-            raise typer.Exit(1)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
-        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        _existing(path)
+        dev = _pick_device(device, cpu)
         got, left, n = calc_to_tiff(path, output_path, list(expr), window=win, bbox=box, out_dtype=np.dtype(dtype),
                                     nodata=nodata, fill=fill, device=dev)
         console.print(f"[green]{output_path}[/green]: {len(expr)} band(s) of {np.dtype(dtype)}, rows {got[0]}.."
@@ -688,12 +605,6 @@ def calc(
         if nodata is not None or int(left[0]):
             console.print("left out: " + ", ".join(f"band {k + 1}: {100.0 * int(v) / max(1, n):.2f}%"
                                                    for k, v in enumerate(left)))
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Band math failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 def _run_focal(what: str, file_path: str, output_path: Path, spec, bbox, pixels, dtype: str, cpu: bool, device):
@@ -702,29 +613,17 @@ def _run_focal(what: str, file_path: str, output_path: Path, spec, bbox, pixels,
 
     from .streaming import focal_to_tiff
 
-    try:
-        if bbox is not None and pixels is not None:
-            console.print("[red]Error: give at most one of --bbox and --window[/red]")
-            raise typer.Exit(1)
+    with _failing("Focal operation failed"):
+        win, box = _request_window(bbox, pixels)
         path = _local(file_path)
-        if not path.exists():
-            console.print(f"[red]File not found: {path}[/red]")
-            raise typer.Exit(1)
-        box = [float(x.strip()) for x in bbox.split(",")] if bbox else None
-        win = [int(x.strip()) for x in pixels.split(",")] if pixels else None
-        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        _existing(path)
+        dev = _pick_device(device, cpu)
         got, left, n = focal_to_tiff(path, output_path, spec(), window=win, bbox=box, out_dtype=np.dtype(dtype), device=dev)
         console.print(f"[green]{output_path}[/green]: {what}, {len(left)} band(s) of {np.dtype(dtype)}, rows {got[0]}.."
                       f"{got[0] + got[2]}, columns {got[1]}..{got[1] + got[3]}"
                       + (f" (GPU {dev})" if dev is not None else " (host)"))
         console.print("left out: " + ", ".join(f"band {k + 1}: {100.0 * int(v) / max(1, n):.2f}%"
                                                for k, v in enumerate(left)))
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Focal operation failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 _F_BBOX = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'")
@@ -822,29 +721,6 @@ def slope(
     _run_focal("slope", file_path, output_path, spec, bbox, pixels, dtype, cpu, device)
 
 
-def _source_grid(path: Path):
-    """``(transform, (H, W), crs)`` of a streaming container or a GeoTIFF."""
-    from .streaming import is_streaming_container, open_streaming
-    from .tiff import GeoTIFF
-
-    with open(path, "rb") as f:
-        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-    if is_tiff:
-        g = GeoTIFF(path)
-        try:
-            i = g.info
-            return (list(i.transform)[:6] if i.transform is not None else None, (i.height, i.width),
-                    str(i.crs) if i.crs is not None and str(i.crs) else None)
-        finally:
-            g.close()
-    if not is_streaming_container(path):
-        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
-    index = open_streaming(path).index
-    crs = index.get("crs")
-    t = index.get("transform")
-    return (list(t)[:6] if t else None), (int(index["height"]), int(index["width"])), (crs if crs and crs != "None" else None)
-
-
 def _numbers(text: str, n: int, what: str, kind=float):
     try:
         vals = [kind(x.strip()) for x in text.split(",")]
@@ -880,9 +756,10 @@ def warp(
     """A streaming FLAC file or a GeoTIFF onto another grid (another CRS, another raster's grid, any transform) -> GeoTIFF."""
     from .crs import suggested_grid, transformer
     from .geo import Affine
+    from .source import open_source
     from .streaming import warp_to_tiff
 
-    try:
+    with _failing("Warp failed"):
         if sum(x is not None for x in (dst_crs, like, transform)) != 1:
             console.print("[red]Error: give exactly one of --dst-crs, --like and --transform[/red]")
             raise typer.Exit(1)
@@ -896,17 +773,17 @@ def warp(
             console.print("[red]Error: give at most one of --res and --size[/red]")
             raise typer.Exit(1)
         path = _local(file_path)
-        if not path.exists():
-            console.print(f"[red]File not found: {path}[/red]")
-            raise typer.Exit(1)
+        _existing(path)
         if like is not None:
-            t, shape, crs = _source_grid(like)
+            grid = open_source(like)
+            t, shape, crs = grid.transform, (grid.height, grid.width), grid.crs
             if t is None:
                 raise ValueError(f"{like} has no transform")
         elif transform is not None:
             t, shape, crs = _numbers(transform, 6, "--transform"), tuple(_numbers(out_shape, 2, "--out-shape", int)), None
         else:
-            st, sshape, scrs = _source_grid(path)
+            grid = open_source(path)
+            st, sshape, scrs = grid.transform, (grid.height, grid.width), grid.crs
             if st is None or scrs is None:
                 raise ValueError("--dst-crs needs a source with a transform and a CRS")
             crs = dst_crs
@@ -925,7 +802,7 @@ def warp(
                     t = Affine((xmax - xmin) / shape[1], 0.0, xmin, 0.0, -(ymax - ymin) / shape[0], ymax)
                 else:
                     t = Affine(r, 0.0, xmin, 0.0, -r, ymax)
-        dev = None if cpu else (device if device is not None else (0 if _gpu_present() else None))
+        dev = _pick_device(device, cpu)
         info = warp_to_tiff(path, output_path, tuple(t)[:6], shape, crs, None, resampling, nodata, fill, dev, cpu,
                             grid_step=grid_step)
         console.print(f"[green]{output_path}[/green]: {len(info['filled'])} band(s) of {shape[0]} x {shape[1]}, {resampling}"
@@ -936,12 +813,6 @@ def warp(
         console.print("source window: " + (f"rows {w[0]}..{w[0] + w[2]}, columns {w[1]}..{w[1] + w[3]}" if w else
                                            "none (the grid misses the source)"))
         console.print("filled: " + ", ".join(f"band {k + 1}: {100.0 * v:.2f}%" for k, v in enumerate(info["shares"])))
-    except typer.Exit:
-        raise
-    except Exception as e:
-        logger.exception("Warp failed")
-        console.print(f"[red]Error: {e}[/red]")
-        raise typer.Exit(1)
 
 
 def _show_tiff_info(path: Path):

@@ -12,6 +12,9 @@ the whole container, ``read_window`` a pixel window of it (only the byte ranges 
 and on the GPU only the frames that hold its rows are decoded), at full resolution, decimated by 2 .. 64
 (``decimate=``) or resampled to any size (``out_shape=``), and ``read_overview`` the whole raster decimated or resampled
 (``resample`` states the rules).
+
+Every windowed operation below is written once over a source (``source``: a container or a GeoTIFF behind one surface);
+the public ``X_window`` / ``X_tiff`` / ``X_to_tiff`` functions pick the source and shape the return tuple.
 """
 
 from __future__ import annotations
@@ -28,6 +31,7 @@ import numpy as np
 from . import flac_meta, resample
 from .converter import raster_metadata, raster_tags
 from .geo import Affine, window_transform
+from .source import ContainerSource, TiffSource, _decode_window_on_host, denorm_code, normal_crs, open_source
 from .tiff import GeoTIFF
 from .tiles import TileStream, calculate_tiles, encode_tiles, encode_tiles_ring
 
@@ -250,10 +254,6 @@ def read_tile_bytes(path: Path, frame: Dict, header_size: int) -> bytes:
 
 
 # ------------------------------------------------------------------------------------------ container -> raster
-def _container_bytes(src) -> bytes:
-    return bytes(src) if isinstance(src, (bytes, bytearray, memoryview)) else Path(src).read_bytes()
-
-
 def is_streaming_container(path: Path) -> bool:
     """A ``.flac`` file that starts with neither ``fLaC`` nor an ID3v2 tag: the ``--streaming`` container."""
     with open(path, "rb") as f:
@@ -263,18 +263,24 @@ def is_streaming_container(path: Path) -> bool:
 
 def _tile_items(data: bytes):
     """The index and, per tile, the ``decode_device`` item: byte range, window and the tile's own min / max tags."""
-    index, hs = read_index_bytes(data)
-    items = []
-    for fr in index["frames"]:
-        a = hs + fr["byte_offset"]
-        b = a + fr["byte_size"]
-        if b > len(data):
-            raise ValueError(f"tile {fr['frame_id']} runs past the end of the container")
-        tags = flac_meta.FLACFile(data[a:b]).tags
-        w = fr["window"]
-        items.append({"offset": a, "bytes": b - a, "window": (w["row_off"], w["col_off"], w["height"], w["width"]),
-                      "data_min": float(tags["GEOSPATIAL_DATA_MIN"][0]), "data_max": float(tags["GEOSPATIAL_DATA_MAX"][0])})
-    return index, items
+    s = ContainerSource(data)
+    return s.meta, s.whole()[1]
+
+
+def _to_raster(s: ContainerSource, device: Optional[int], semantics: str):
+    """:func:`streaming_to_raster` of a source."""
+    from . import _native
+
+    denorm = denorm_code(semantics)
+    data, items = s.whole()  # to the device as they are
+    H, W = s.height, s.width
+    out = np.zeros((s.bands, H, W), dtype=s.dtype)
+    if device is not None:
+        ctx = _native.default_context(int(device))
+        ctx.decode_device(np.frombuffer(data, dtype=np.uint8), items, out, s.dtype, s.bands, (H * W, W, 1), denorm)
+    else:
+        _decode_window_on_host(data, items, s.window(), out, semantics)
+    return out, s.meta
 
 
 def streaming_to_raster(src, device: Optional[int] = None, semantics: str = "pcm16"):
@@ -285,44 +291,38 @@ def streaming_to_raster(src, device: Optional[int] = None, semantics: str = "pcm
     ``"int"`` denormalises the exact integer samples.  ``device=None`` is the host implementation (``fra_decode`` per
     tile + ``denormalize_from_audio``, no GPU needed); an integer runs one ``fra_decode_device`` call over all tiles
     on that GPU."""
-    from . import _native
-    from .decoder import decode_flac, pcm16_float
-    from .normalization import NormalizationParams, denormalize_from_audio
+    return _to_raster(ContainerSource(src), device, semantics)
 
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    data = _container_bytes(src)
-    index, items = _tile_items(data)
-    dt = np.dtype(index["dtype"])
-    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
-    out = np.zeros((B, H, W), dtype=dt)
-    if device is not None:
-        ctx = _native.default_context(int(device))
-        ctx.decode_device(np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (H * W, W, 1),
-                          _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
-        return out, index
-    for it in items:
-        r, c, h, w = it["window"]
-        samples, _, bps = decode_flac(data[it["offset"]:it["offset"] + it["bytes"]])
-        if samples.shape != (h * w, B):
-            raise ValueError(f"tile at ({r}, {c}) decodes to {samples.shape}, expected {(h * w, B)}")
-        params = NormalizationParams(it["data_min"], it["data_max"], str(dt), 16 if bps <= 16 else 24,
-                                     32767 if bps <= 16 else 8388607)
-        audio = pcm16_float(samples) if semantics == "pcm16" else samples
-        out[:, r:r + h, c:c + w] = denormalize_from_audio(audio, params).reshape(h, w, B).transpose(2, 0, 1)
-    return out, index
+
+def _to_tiff(tiff_path: Path, raster: np.ndarray, s, win=None, transform=None, crs=None, nodata=None):
+    """A result raster of the source ``s`` -> GeoTIFF with the source's CRS (``crs``: the grid's, after a warp), the
+    transform at the origin of the window ``win`` (``transform``: the one of a read that resampled or warped) and
+    ``nodata`` as its nodata tag."""
+    from .tiff import write_geotiff
+
+    write_geotiff(Path(tiff_path), raster, transform=s.window_transform(win) if transform is None else transform,
+                  crs=s.crs if crs is None else normal_crs(crs), nodata=nodata)
+
+
+def _fill_tag(fill, dtype):
+    """A fill as the output dtype holds it (``calc.convert``), as a GeoTIFF nodata tag."""
+    from .calc import convert
+
+    v = convert(np.array([float(fill)]), dtype)[0]
+    return float(v) if np.dtype(dtype).kind == "f" else int(v)
+
+
+def _nodata(s, nodata):
+    """``nodata=None`` takes the source's own nodata tag, when it has one."""
+    return s.nodata if nodata is None else nodata
 
 
 def streaming_to_tiff(path: Path, tiff_path: Path, device: Optional[int] = None) -> Dict:
     """Streaming container -> GeoTIFF with the index's transform and CRS (``flac_to_tiff`` semantics per tile);
     returns the index."""
-    from .tiff import write_geotiff
-
-    raster, index = streaming_to_raster(Path(path), device=device)
-    t = index.get("transform")
-    crs = index.get("crs")
-    write_geotiff(Path(tiff_path), raster, transform=tuple(t[:6]) if t else None,
-                  crs=crs if crs and crs != "None" else None)
+    s = ContainerSource(Path(path))
+    raster, index = _to_raster(s, device, "pcm16")
+    _to_tiff(tiff_path, raster, s, transform=s.transform)
     return index
 
 
@@ -361,6 +361,52 @@ def resolve_window(index: Dict, window: Optional[Sequence[int]] = None,
     return r0, c0, r1 - r0, c1 - c0
 
 
+def _read_window(s: ContainerSource, window, bbox, device, semantics, decimate, resampling, out_shape, nodata):
+    """:func:`read_window` of a source."""
+    from . import _native
+
+    k = 1
+    if out_shape is not None:
+        if decimate != 1:
+            raise ValueError("give decimate or out_shape, not both")
+        out_shape = resample.check_out_shape(out_shape)
+        resample.resampling_any_code(resampling)
+    elif decimate != 1:
+        k = resample.check_factor(decimate)
+        resample.resampling_code(resampling)
+    win = resolve_window(s.meta, window, bbox)  # a read names its window: no whole-raster default here
+    reg = s.region(win, semantics)
+    index, dt, B = s.meta, s.dtype, s.bands
+    h, w = win[2], win[3]
+    if nodata is not None:
+        if out_shape is None and k == 1:
+            raise ValueError("nodata needs decimate or out_shape")
+        nodata = resample.check_nodata(nodata, dt)
+    if device is None:
+        out = reg.host()
+        if out_shape is not None:
+            out = resample.resample(out, out_shape, resampling, nodata)
+        elif k > 1:
+            out = resample.decimate(out, k, resampling, nodata)
+        return out, win, index
+    ctx = _native.default_context(int(device))
+    data, items = reg.decode_args()[:2]
+    if out_shape is not None:
+        oh, ow = out_shape
+        out = np.zeros((B, oh, ow), dtype=dt)
+        ctx.decode_device_resampled(data, items, out, dt, B, (oh * ow, ow, 1), win, out_shape, resampling, reg.denorm,
+                                    nodata=nodata)
+    elif k > 1:
+        oh, ow = resample.decimated_shape(h, w, k)
+        out = np.zeros((B, oh, ow), dtype=dt)
+        ctx.decode_device_decimated(data, items, out, dt, B, (oh * ow, ow, 1), win, k, resampling, reg.denorm,
+                                    nodata=nodata)
+    else:
+        out = np.zeros((B, h, w), dtype=dt)
+        ctx.decode_device_window(data, items, out, dt, B, (h * w, w, 1), win, reg.denorm)
+    return out, win, index
+
+
 def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
                 device: Optional[int] = None, semantics: str = "pcm16", decimate: int = 1,
                 resampling: str = "nearest", out_shape: Optional[Sequence[int]] = None, nodata=None):
@@ -386,144 +432,35 @@ def read_window(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequ
     the returned window is the clipped one.  Of a file only the index and the byte ranges of the intersecting tiles
     are read (seek + read).  ``device=None`` decodes those tiles on the host and crops; an integer makes one
     ``fra_decode_device_window`` call on that GPU, which decodes only the frames that hold the window's rows."""
-    from . import _native
-
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    k = 1
-    if out_shape is not None:
-        if decimate != 1:
-            raise ValueError("give decimate or out_shape, not both")
-        out_shape = resample.check_out_shape(out_shape)
-        resample.resampling_any_code(resampling)
-    elif decimate != 1:
-        k = resample.check_factor(decimate)
-        resample.resampling_code(resampling)
-    index, win, blob, items = _window_items(src, window, bbox)
-    R, C_, h, w = win
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
-    if nodata is not None:
-        if out_shape is None and k == 1:
-            raise ValueError("nodata needs decimate or out_shape")
-        nodata = resample.check_nodata(nodata, dt)
-    if out_shape is not None:
-        if device is None:
-            out = np.zeros((B, h, w), dtype=dt)
-            _decode_window_on_host(blob, items, win, out, semantics)
-            return resample.resample(out, out_shape, resampling, nodata), win, index
-        oh, ow = out_shape
-        out = np.zeros((B, oh, ow), dtype=dt)
-        ctx = _native.default_context(int(device))
-        ctx.decode_device_resampled(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win,
-                                    out_shape, resampling,
-                                    _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT, nodata=nodata)
-        return out, win, index
-    if device is not None and k > 1:
-        oh, ow = resample.decimated_shape(h, w, k)
-        out = np.zeros((B, oh, ow), dtype=dt)
-        ctx = _native.default_context(int(device))
-        ctx.decode_device_decimated(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), win, k,
-                                    resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT,
-                                    nodata=nodata)
-        return out, win, index
-    out = np.zeros((B, h, w), dtype=dt)
-    if device is not None:
-        ctx = _native.default_context(int(device))
-        ctx.decode_device_window(np.frombuffer(blob, dtype=np.uint8), items, out, dt, B, (h * w, w, 1), win,
-                                 _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT)
-        return out, win, index
-    _decode_window_on_host(blob, items, win, out, semantics)
-    if k > 1:
-        out = resample.decimate(out, k, resampling, nodata)
-    return out, win, index
+    return _read_window(ContainerSource(src), window, bbox, device, semantics, decimate, resampling, out_shape, nodata)
 
 
 def _window_items(src, window, bbox):
     """The index of a container (path or bytes), the clipped window of a request, and the bytes and ``decode_device``
     items of the tiles that intersect it (of a file only the index and those byte ranges are read)."""
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        data = memoryview(src)
-        index, hs = read_index_bytes(bytes(data[:4 + struct.unpack(">I", data[:4])[0]]))
-        size, fh = len(data), None
-    else:
-        sf = open_streaming(Path(src))
-        index, hs = sf.index, sf.header_size
-        size, fh = Path(src).stat().st_size, open(src, "rb")
-    try:
-        R, C_, h, w = win = resolve_window(index, window, bbox)
-        blob, items = bytearray(), []
-        for fr in index["frames"]:
-            fw = fr["window"]
-            if (fw["row_off"] >= R + h or fw["row_off"] + fw["height"] <= R or fw["col_off"] >= C_ + w
-                    or fw["col_off"] + fw["width"] <= C_):
-                continue
-            a = hs + fr["byte_offset"]
-            b = a + fr["byte_size"]
-            if b > size:
-                raise ValueError(f"tile {fr['frame_id']} runs past the end of the container")
-            if fh is None:
-                tile = bytes(data[a:b])
-            else:
-                fh.seek(a)
-                tile = fh.read(b - a)
-            tags = flac_meta.FLACFile(tile).tags  # the tile's own min / max, as _tile_items
-            items.append({"offset": len(blob), "bytes": b - a,
-                          "window": (fw["row_off"], fw["col_off"], fw["height"], fw["width"]),
-                          "data_min": float(tags["GEOSPATIAL_DATA_MIN"][0]),
-                          "data_max": float(tags["GEOSPATIAL_DATA_MAX"][0])})
-            blob += tile
-    finally:
-        if fh is not None:
-            fh.close()
-    if not items:
-        raise LookupError("No tiles intersect the window")
-    return index, win, blob, items
-
-
-def _decode_window_on_host(blob, items, win, out: np.ndarray, semantics: str):
-    """The tiles of ``_window_items`` decoded on the host, denormalised and cropped into ``out`` (B, h, w)."""
-    from .decoder import decode_flac, pcm16_float
-    from .normalization import NormalizationParams, denormalize_from_audio
-
-    R, C_, h, w = win
-    B, dt = out.shape[0], out.dtype
-    for it in items:
-        r, c, th, tw = it["window"]
-        samples, _, bps = decode_flac(bytes(blob[it["offset"]:it["offset"] + it["bytes"]]))
-        if samples.shape != (th * tw, B):
-            raise ValueError(f"tile at ({r}, {c}) decodes to {samples.shape}, expected {(th * tw, B)}")
-        params = NormalizationParams(it["data_min"], it["data_max"], str(dt), 16 if bps <= 16 else 24,
-                                     32767 if bps <= 16 else 8388607)
-        audio = pcm16_float(samples) if semantics == "pcm16" else samples
-        tile = denormalize_from_audio(audio, params).reshape(th, tw, B).transpose(2, 0, 1)
-        ra, rb, ca, cb = max(r, R), min(r + th, R + h), max(c, C_), min(c + tw, C_ + w)
-        out[:, ra - R:rb - R, ca - C_:cb - C_] = tile[:, ra - r:rb - r, ca - c:cb - c]
+    s = ContainerSource(src)
+    reg = s.region(resolve_window(s.meta, window, bbox))
+    return s.meta, reg.win, reg.blob, reg.items
 
 
 # ------------------------------------------------------------------------------------------ container against raster
-def _compare_window(win, blob, items, ref: np.ndarray, device: Optional[int], semantics: str,
-                    count_one_sided_nans: bool = False) -> Dict:
-    """The window ``win`` of the tiles of ``_window_items`` against ``ref`` (B, h, w): on the host the window is
-    decoded and compared with numpy; on a GPU one ``fra_decode_device_compare`` call returns the reports."""
+def _compare_window(reg, ref: np.ndarray, device: Optional[int], count_one_sided_nans: bool = False) -> Dict:
+    """The region ``reg`` of a container against ``ref`` (B, h, w): on the host the window is decoded and compared with
+    numpy; on a GPU one ``fra_decode_device_compare`` call returns the reports."""
     from . import _native
     from .compare import compare_arrays, report_from_bands
 
-    B, dt = ref.shape[0], ref.dtype
-    r, c, h, w = win
+    r, c, h, w = reg.win
     if device is None:
-        out = np.zeros((B, h, w), dtype=dt)
-        _decode_window_on_host(blob, items, win, out, semantics)
-        report = compare_arrays(out, ref)
+        report = compare_arrays(reg.host(), ref)
     else:
         ctx = _native.default_context(int(device))
-        data = np.frombuffer(blob, dtype=np.uint8)
-        denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-        bands, _ = ctx.decode_device_compare(data, items, ref, dt, B, win, denorm)
+        data, items, dt, B, win = reg.decode_args()
+        bands, _ = ctx.decode_device_compare(data, items, ref, dt, B, win, reg.denorm)
         report = report_from_bands(bands, dt)
         if count_one_sided_nans and report["one_sided_nan"] is None:
             out = np.zeros((B, h, w), dtype=dt)
-            ctx.decode_device_window(data, items, out, dt, B, (h * w, w, 1), win, denorm)
+            ctx.decode_device_window(data, items, out, dt, B, (h * w, w, 1), win, reg.denorm)
             for i, band in enumerate(report["bands"]):
                 band["one_sided_nan"] = int(np.count_nonzero(np.isnan(out[i]) != np.isnan(ref[i])))
             report["one_sided_nan"] = sum(band["one_sided_nan"] for band in report["bands"])
@@ -545,27 +482,19 @@ def compare_with_raster(src, raster: np.ndarray, window: Optional[Sequence[int]]
     ``fra_decode_device_compare`` call on that GPU: the decoded pixels never leave the device, the raster's window goes
     there, and only the reports come back (``one_sided_nan`` is then ``None`` where a band has both unordered and
     differing pixels, see ``compare.report_from_bands``)."""
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    if window is None and bbox is None:
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            mv = memoryview(src)
-            index, _ = read_index_bytes(bytes(mv[:4 + struct.unpack(">I", mv[:4])[0]]))
-        else:
-            index = open_streaming(Path(src)).index
-        window = (0, 0, int(index["height"]), int(index["width"]))
-    index, win, blob, items = _window_items(src, window, bbox)
-    dt = np.dtype(index["dtype"])
-    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
+    s = ContainerSource(src)
+    win = s.window(window, bbox)
+    reg = s.region(win, semantics)
+    shape, dt = (s.bands, s.height, s.width), s.dtype
     raster = np.asarray(raster)
-    if raster.shape != (B, H, W) or raster.dtype != dt:
-        raise ValueError(f"the raster must be {(B, H, W)} of {dt} as the container's index says, got {raster.shape} of "
+    if raster.shape != shape or raster.dtype != dt:
+        raise ValueError(f"the raster must be {shape} of {dt} as the container's index says, got {raster.shape} of "
                          f"{raster.dtype}")
     r, c, h, w = win
     ref = raster[:, r:r + h, c:c + w]
     if any(st < 0 or st % dt.itemsize for st in ref.strides) or not ref.dtype.isnative:
         ref = np.ascontiguousarray(ref, dtype=dt.newbyteorder("="))
-    return _compare_window(win, blob, items, ref, device, semantics), win, index
+    return _compare_window(reg, ref, device), win, s.meta
 
 
 def check_against_tiff(container: Path, tiff: Path, window: Optional[Sequence[int]] = None,
@@ -579,37 +508,44 @@ def check_against_tiff(container: Path, tiff: Path, window: Optional[Sequence[in
     ``count_one_sided_nans``: a GPU report leaves ``one_sided_nan`` open (``None``) when a band has both unordered and
     differing pixels; the window is then read once more (``fra_decode_device_window``) and the pixels with a NaN on
     one side only are counted on the host.  The host path always counts them."""
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
     container, tiff = Path(container), Path(tiff)
-    index = open_streaming(container).index
-    dt = np.dtype(index["dtype"])
-    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
-    g = GeoTIFF(tiff)
-    try:
-        info = g.info
-        shape, tdt = (info.count, info.height, info.width), np.dtype(info.dtype)
-        if shape != (B, H, W) or tdt != dt:
-            raise ValueError(f"{tiff.name} is {shape} of {tdt}, the container holds {(B, H, W)} of {dt}")
-        if window is None and bbox is None:
-            window = (0, 0, H, W)
-        index, win, blob, items = _window_items(container, window, bbox)
-        ref = np.zeros((B, win[2], win[3]), dtype=dt)
-        g.read_window_into(ref, *win)
-        crs = str(info.crs)
-    finally:
-        g.close()
-    report = _compare_window(win, blob, items, ref, device, semantics, count_one_sided_nans)
+    s, t = ContainerSource(container), TiffSource(tiff)
+    shape, tshape = (s.bands, s.height, s.width), (t.bands, t.height, t.width)
+    if tshape != shape or t.dtype != s.dtype:
+        raise ValueError(f"{tiff.name} is {tshape} of {t.dtype}, the container holds {shape} of {s.dtype}")
+    win = s.window(window, bbox)
+    reg = s.region(win, semantics)
+    report = _compare_window(reg, t.region(win).host(), device, count_one_sided_nans)
+    crs, tcrs = str(s.meta.get("crs")), str(t.meta.crs)  # as they are stored, "None" for none
     report.update({
         "file1": container.name, "file2": tiff.name, "shape_match": True, "dtype_match": True,
-        "crs_match": str(index.get("crs")) == crs, "file1_shape": (B, H, W), "file2_shape": shape,
-        "file1_dtype": str(dt), "file2_dtype": str(tdt), "file1_crs": str(index.get("crs")), "file2_crs": crs,
+        "crs_match": crs == tcrs, "file1_shape": shape, "file2_shape": tshape,
+        "file1_dtype": str(s.dtype), "file2_dtype": str(t.dtype), "file1_crs": crs, "file2_crs": tcrs,
         "window": list(win), "semantics": semantics,
     })
-    return report, win, index
+    return report, win, s.meta
 
 
 # ------------------------------------------------------------------------------------------ statistics
+def _stats(s, window, bbox, bins, hist_range, nodata, device, semantics=None):
+    """Band statistics of a source -> ``(report, window)``."""
+    from . import _native
+    from .stats import check_options, report_from_bands, stats_arrays
+
+    check_options(bins, hist_range, nodata)
+    win = s.window(window, bbox)
+    nodata = _nodata(s, nodata)
+    reg = s.region(win, semantics)
+    if device is None:
+        return stats_arrays(reg.host(), bins, hist_range, nodata), win
+    ctx = _native.default_context(int(device))
+    if reg.encoded:
+        bands, hist, _ = ctx.decode_device_stats(*reg.decode_args(), reg.denorm, bins, hist_range, nodata)
+    else:
+        bands, hist = ctx.stats(reg.host(), bins, hist_range, nodata)
+    return report_from_bands(bands, hist, s.dtype), win
+
+
 def container_stats(src, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
                     bins: int = 0, hist_range=None, nodata: Optional[float] = None, device: Optional[int] = None,
                     semantics: str = "pcm16"):
@@ -620,31 +556,8 @@ def container_stats(src, window: Optional[Sequence[int]] = None, bbox: Optional[
     ``"auto"`` / ``None``) and ``nodata`` as ``stats.stats_arrays``.  ``device=None`` reads the window on the host and
     applies the numpy rule; an integer makes one ``fra_decode_device_stats`` call on that GPU: the decoded pixels never
     leave the device and only the reports and the histogram come back."""
-    from . import _native
-    from .stats import check_options, report_from_bands, stats_arrays
-
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    check_options(bins, hist_range, nodata)
-    if window is None and bbox is None:
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            mv = memoryview(src)
-            index, _ = read_index_bytes(bytes(mv[:4 + struct.unpack(">I", mv[:4])[0]]))
-        else:
-            index = open_streaming(Path(src)).index
-        window = (0, 0, int(index["height"]), int(index["width"]))
-    index, win, blob, items = _window_items(src, window, bbox)
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
-    if device is None:
-        out = np.zeros((B, win[2], win[3]), dtype=dt)
-        _decode_window_on_host(blob, items, win, out, semantics)
-        return stats_arrays(out, bins, hist_range, nodata), win, index
-    ctx = _native.default_context(int(device))
-    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-    bands, hist, _ = ctx.decode_device_stats(np.frombuffer(blob, dtype=np.uint8), items, dt, B, win, denorm, bins,
-                                             hist_range, nodata)
-    return report_from_bands(bands, hist, dt), win, index
+    s = ContainerSource(src)
+    return _stats(s, window, bbox, bins, hist_range, nodata, device, semantics) + (s.meta,)
 
 
 def tiff_stats(path: Path, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -652,28 +565,8 @@ def tiff_stats(path: Path, window: Optional[Sequence[int]] = None, bbox: Optiona
     """Band statistics and histograms of a GeoTIFF, or of a window of it -> ``(report, window, info)``.  The window is
     read with the in-package reader; an integer ``device`` hands it to ``fra_stats`` on that GPU, ``None`` to the numpy
     rule.  ``nodata=None`` takes the TIFF's own nodata tag, when it has one."""
-    from . import _native
-    from .stats import report_from_bands, stats_arrays
-
-    g = GeoTIFF(Path(path))
-    try:
-        info = g.info
-        dt = np.dtype(info.dtype)
-        if window is None and bbox is None:
-            win = (0, 0, info.height, info.width)
-        else:
-            win = resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)},
-                                 window, bbox)
-        if nodata is None and info.nodata is not None:
-            nodata = float(info.nodata)
-        a = np.zeros((info.count, win[2], win[3]), dtype=dt)
-        g.read_window_into(a, *win)
-    finally:
-        g.close()
-    if device is None:
-        return stats_arrays(a, bins, hist_range, nodata), win, info
-    bands, hist = _native.default_context(int(device)).stats(a, bins, hist_range, nodata)
-    return report_from_bands(bands, hist, dt), win, info
+    s = TiffSource(path)
+    return _stats(s, window, bbox, bins, hist_range, nodata, device) + (s.meta,)
 
 
 # ------------------------------------------------------------------------------------------ zonal statistics
@@ -709,36 +602,36 @@ def _zonal_on_device(run, crop: np.ndarray, dt, nodata, ignore):
     return report_from_recs(recs, outside, dt, first, labels)
 
 
-def _whole_window(src):
-    """The window of the whole raster of a container (path or bytes)."""
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        mv = memoryview(src)
-        index, _ = read_index_bytes(bytes(mv[:4 + struct.unpack(">I", mv[:4])[0]]))
-    else:
-        index = open_streaming(Path(src)).index
-    return 0, 0, int(index["height"]), int(index["width"])
-
-
-def _container_zonal(index, win, blob, items, crop: np.ndarray, nodata, ignore, device, semantics: str):
-    """The report of the window ``win`` of the tiles of ``_window_items`` over ``crop``, the zones of that window."""
+def _zonal(s, win, crop: np.ndarray, nodata, ignore, device, semantics):
+    """The report of the window ``win`` of a source over ``crop``, the zones of that window."""
     from . import _native
     from .zonal import zonal_arrays
 
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
+    nodata = _nodata(s, nodata)
+    reg = s.region(win, semantics)
     if device is None:
-        out = np.zeros((B, win[2], win[3]), dtype=dt)
-        _decode_window_on_host(blob, items, win, out, semantics)
-        return zonal_arrays(out, crop, nodata=nodata, ignore=ignore)
+        return zonal_arrays(reg.host(), crop, nodata=nodata, ignore=ignore)
     ctx = _native.default_context(int(device))
-    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-    data = np.frombuffer(blob, dtype=np.uint8)
+    if reg.encoded:
+        data, items, dt, B, _ = reg.decode_args()
 
-    def run(z, zone_lo, nzones, ign):
-        recs, outside, _ = ctx.decode_device_zonal(data, items, z, dt, B, win, denorm, zone_lo, nzones, nodata, ign)
-        return recs, outside
+        def run(z, zone_lo, nzones, ign):
+            recs, outside, _ = ctx.decode_device_zonal(data, items, z, dt, B, win, reg.denorm, zone_lo, nzones, nodata, ign)
+            return recs, outside
+    else:
+        a = reg.host()
 
-    return _zonal_on_device(run, crop, dt, nodata, ignore)
+        def run(z, zone_lo, nzones, ign):
+            return ctx.zonal(a, z, zone_lo, nzones, nodata, ign)
+
+    return _zonal_on_device(run, crop, s.dtype, nodata, ignore)
+
+
+def _zonal_over_array(s, zones, window, bbox, nodata, ignore, device, semantics=None):
+    """Zonal statistics of a source over the whole ``(H, W)`` zone raster ``zones`` -> ``(report, window, meta)``."""
+    win = s.window(window, bbox)
+    crop = _zone_crop(zones, (s.height, s.width), win)
+    return _zonal(s, win, crop, nodata, ignore, device, semantics), win, s.meta
 
 
 def container_zonal(src, zones, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -751,31 +644,7 @@ def container_zonal(src, zones, window: Optional[Sequence[int]] = None, bbox: Op
     dtype; ``window`` / ``bbox`` as in :func:`read_window` (default: the whole raster).  ``device=None`` reads the
     window on the host and applies the numpy rule; an integer makes one ``fra_decode_device_zonal`` call on that GPU:
     the decoded pixels never leave the device, the cropped zone raster goes there, and only the records come back."""
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    if window is None and bbox is None:
-        window = _whole_window(src)
-    index, win, blob, items = _window_items(src, window, bbox)
-    crop = _zone_crop(zones, (int(index["height"]), int(index["width"])), win)
-    return _container_zonal(index, win, blob, items, crop, nodata, ignore, device, semantics), win, index
-
-
-def _tiff_window(g: GeoTIFF, window, bbox):
-    info = g.info
-    if window is None and bbox is None:
-        return 0, 0, info.height, info.width
-    return resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)}, window, bbox)
-
-
-def _array_zonal(a: np.ndarray, crop: np.ndarray, nodata, ignore, device):
-    """The report of a raster in host memory over its zones: the numpy rule, or ``fra_zonal`` on a GPU."""
-    from . import _native
-    from .zonal import zonal_arrays
-
-    if device is None:
-        return zonal_arrays(a, crop, nodata=nodata, ignore=ignore)
-    ctx = _native.default_context(int(device))
-    return _zonal_on_device(lambda z, lo, n, ign: ctx.zonal(a, z, lo, n, nodata, ign), crop, a.dtype, nodata, ignore)
+    return _zonal_over_array(ContainerSource(src), zones, window, bbox, nodata, ignore, device, semantics)
 
 
 def tiff_zonal(path: Path, zones, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -784,18 +653,7 @@ def tiff_zonal(path: Path, zones, window: Optional[Sequence[int]] = None, bbox: 
     ``(report, window, info)``.  The window is read with the in-package reader; an integer ``device`` hands it to
     ``fra_zonal`` on that GPU, ``None`` to the numpy rule.  ``nodata=None`` takes the TIFF's own nodata tag, when it
     has one."""
-    g = GeoTIFF(Path(path))
-    try:
-        info = g.info
-        win = _tiff_window(g, window, bbox)
-        if nodata is None and info.nodata is not None:
-            nodata = float(info.nodata)
-        crop = _zone_crop(zones, (info.height, info.width), win)
-        a = np.zeros((info.count, win[2], win[3]), dtype=np.dtype(info.dtype))
-        g.read_window_into(a, *win)
-    finally:
-        g.close()
-    return _array_zonal(a, crop, nodata, ignore, device), win, info
+    return _zonal_over_array(TiffSource(path), zones, window, bbox, nodata, ignore, device)
 
 
 def zonal_with_tiff(source: Path, zones_tiff: Path, window: Optional[Sequence[int]] = None,
@@ -805,54 +663,21 @@ def zonal_with_tiff(source: Path, zones_tiff: Path, window: Optional[Sequence[in
     GeoTIFF of the same shape -> ``(report, window, index or info)``.  Only the window of the zones TIFF is read
     (in-package reader).  ``ignore=None`` takes the zones TIFF's nodata tag, when it has one; ``nodata=None`` a source
     TIFF's."""
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
     source, zones_tiff = Path(source), Path(zones_tiff)
-    with open(source, "rb") as f:
-        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-    a = blob = items = None
-    if is_tiff:
-        g = GeoTIFF(source)
-        try:
-            meta = g.info
-            shape = (meta.height, meta.width)
-            win = _tiff_window(g, window, bbox)
-            if nodata is None and meta.nodata is not None:
-                nodata = float(meta.nodata)
-            a = np.zeros((meta.count, win[2], win[3]), dtype=np.dtype(meta.dtype))
-            g.read_window_into(a, *win)
-        finally:
-            g.close()
-    else:
-        if window is None and bbox is None:
-            window = _whole_window(source)
-        meta, win, blob, items = _window_items(source, window, bbox)
-        shape = (int(meta["height"]), int(meta["width"]))
-    z = GeoTIFF(zones_tiff)
-    try:
-        zi = z.info
-        zdt = np.dtype(zi.dtype)
-        if zi.count != 1 or zdt.kind not in "iu":
-            raise ValueError(f"{zones_tiff.name} must be a single-band integer raster, it has {zi.count} band(s) of {zdt}")
-        if (zi.height, zi.width) != shape:
-            raise ValueError(f"{zones_tiff.name} is {(zi.height, zi.width)}, {source.name} is {shape}")
-        if ignore is None and zi.nodata is not None and float(zi.nodata) == int(float(zi.nodata)):
-            ignore = int(float(zi.nodata))
-        crop = np.zeros((1, win[2], win[3]), dtype=zdt)
-        z.read_window_into(crop, *win)
-    finally:
-        z.close()
-    if is_tiff:
-        return _array_zonal(a, crop[0], nodata, ignore, device), win, meta
-    return _container_zonal(meta, win, blob, items, crop[0], nodata, ignore, device, semantics), win, meta
+    s = open_source(source)
+    win = s.window(window, bbox)
+    z = TiffSource(zones_tiff)
+    if z.bands != 1 or z.dtype.kind not in "iu":
+        raise ValueError(f"{zones_tiff.name} must be a single-band integer raster, it has {z.bands} band(s) of {z.dtype}")
+    if (z.height, z.width) != (s.height, s.width):
+        raise ValueError(f"{zones_tiff.name} is {(z.height, z.width)}, {source.name} is {(s.height, s.width)}")
+    if ignore is None and z.nodata is not None and z.nodata == int(z.nodata):
+        ignore = int(z.nodata)
+    crop = z.region(win).host()[0]
+    return _zonal(s, win, crop, nodata, ignore, device, semantics), win, s.meta
 
 
 # ------------------------------------------------------------------------------------------ polygons
-def _is_tiff(path: Path) -> bool:
-    with open(path, "rb") as f:
-        return f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-
-
 def _label_dtype(values, fill) -> np.dtype:
     """The narrowest of the six label dtypes that holds every burn value and the fill."""
     lo, hi = min([int(fill)] + [int(v) for v in values]), max([int(fill)] + [int(v) for v in values])
@@ -882,39 +707,19 @@ def _burn(pix, win, values, fill, dt, device):
     return _native.default_context(int(device)).rasterize(pix, win, values, fill, dt)
 
 
-def _grid_of(source):
-    """``(transform, (height, width), crs)`` of a streaming container or a GeoTIFF."""
-    source = Path(source)
-    if _is_tiff(source):
-        g = GeoTIFF(source)
-        try:
-            info = g.info
-            t, shape = (list(info.transform) if info.transform is not None else None), (info.height, info.width)
-            crs = str(info.crs) if info.crs is not None and str(info.crs) else None
-        finally:
-            g.close()
-    elif is_streaming_container(source):
-        index = open_streaming(source).index
-        t, shape, crs = index.get("transform"), (int(index["height"]), int(index["width"])), index.get("crs")
-        crs = crs if crs and crs != "None" else None
-    else:
-        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
-    return t, shape, crs
-
-
 def _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype, device):
-    """:func:`rasterize_like` with ``burn`` (one value for every feature, or ``None``) and the burned count."""
+    """:func:`rasterize_like` with ``burn`` (one value for every feature, or ``None``) -> ``(raster, window, burned
+    count, the source)``."""
     if burn is not None and attribute is not None:
         raise ValueError("give at most one of an attribute and a burn value")
-    t, shape, crs = _grid_of(source)
-    pix, values = _pixel_features(geojson, attribute, t)
+    s = open_source(source)
+    pix, values = _pixel_features(geojson, attribute, s.transform)
     if burn is not None:
         values = [int(burn)] * len(pix)
-    win = (0, 0) + shape if window is None and bbox is None else resolve_window(
-        {"height": shape[0], "width": shape[1], "transform": t}, window, bbox)
+    win = s.window(window, bbox)
     dt = _label_dtype(values, fill) if dtype is None else np.dtype(dtype)
     raster, burned = _burn(pix, win, values, fill, dt, device)
-    return raster, win, tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]), crs, burned
+    return raster, win, burned, s
 
 
 def rasterize_like(source, geojson, attribute: Optional[str] = None, window: Optional[Sequence[int]] = None,
@@ -926,7 +731,8 @@ def rasterize_like(source, geojson, attribute: Optional[str] = None, window: Opt
     Feature ``i`` burns ``i + 1``, or its integer property ``attribute``; ``fill`` elsewhere.  ``dtype=None`` picks the
     narrowest of the six label dtypes that holds them.  ``device=None`` applies ``rasterize.rasterize_arrays``, an
     integer makes one ``fra_rasterize`` call on that GPU; both are given the same pixel coordinates."""
-    return _rasterize_like(source, geojson, attribute, None, window, bbox, fill, dtype, device)[:4]
+    raster, win, _, s = _rasterize_like(source, geojson, attribute, None, window, bbox, fill, dtype, device)
+    return raster, win, s.window_transform(win), s.crs
 
 
 def rasterize_to_tiff(source, geojson, tiff_path: Path, attribute: Optional[str] = None, burn: Optional[int] = None,
@@ -934,11 +740,8 @@ def rasterize_to_tiff(source, geojson, tiff_path: Path, attribute: Optional[str]
                       dtype=None, device: Optional[int] = None):
     """:func:`rasterize_like` into a single-band GeoTIFF on the source's grid with the fill as its nodata tag; ``burn``:
     one value for every feature instead of ``i + 1`` or an attribute.  Returns ``(window, burned, dtype)``."""
-    from .tiff import write_geotiff
-
-    raster, win, transform, crs, burned = _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype,
-                                                          device)
-    write_geotiff(Path(tiff_path), raster[None], transform=transform, crs=crs, nodata=int(fill))
+    raster, win, burned, s = _rasterize_like(source, geojson, attribute, burn, window, bbox, fill, dtype, device)
+    _to_tiff(tiff_path, raster[None], s, win, nodata=int(fill))
     return win, burned, raster.dtype
 
 
@@ -956,30 +759,11 @@ def zonal_with_polygons(source, geojson, attribute: Optional[str] = None, window
     from . import _native
     from .zonal import dense_zones, report_from_recs, zonal_arrays
 
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    source = Path(source)
-    a = blob = items = None
-    if _is_tiff(source):
-        g = GeoTIFF(source)
-        try:
-            meta = g.info
-            t = list(meta.transform) if meta.transform is not None else None
-            win = _tiff_window(g, window, bbox)
-            if nodata is None and meta.nodata is not None:
-                nodata = float(meta.nodata)
-            a = np.zeros((meta.count, win[2], win[3]), dtype=np.dtype(meta.dtype))
-            g.read_window_into(a, *win)
-        finally:
-            g.close()
-        src_dt, B = a.dtype, a.shape[0]
-    else:
-        if window is None and bbox is None:
-            window = _whole_window(source)
-        meta, win, blob, items = _window_items(source, window, bbox)
-        t = meta.get("transform")
-        src_dt, B = np.dtype(meta["dtype"]), int(meta["bands"])
-    pix, values = _pixel_features(geojson, attribute, t)
+    s = open_source(Path(source))
+    win = s.window(window, bbox)
+    nodata = _nodata(s, nodata)
+    reg = s.region(win, semantics)
+    pix, values = _pixel_features(geojson, attribute, s.transform)
     if any(int(v) == 0 for v in values):
         raise ValueError("a zone label of 0 is not possible: 0 is what the pixels outside every polygon get")
     if values:
@@ -994,29 +778,25 @@ def zonal_with_polygons(source, geojson, attribute: Optional[str] = None, window
     h, w = win[2], win[3]
     if device is None:
         zones, _ = _burn(pix, win, values, 0, zdt, None)
-        if a is None:
-            a = np.zeros((B, h, w), dtype=src_dt)
-            _decode_window_on_host(blob, items, win, a, semantics)
-        rep = zonal_arrays(a, zones, zone_lo, nzones, nodata=nodata, ignore=0)
+        rep = zonal_arrays(reg.host(), zones, zone_lo, nzones, nodata=nodata, ignore=0)
         if labels is not None:
             for band in rep:
                 for rec in band["zones"]:
                     rec["zone"] = int(labels[rec["zone"] - 1])
-        return rep, win, meta
+        return rep, win, s.meta
     ctx = _native.default_context(int(device))
     d_zones = ctx.alloc(h * w * zdt.itemsize)
     try:
         ctx.rasterize(pix, win, values, 0, zdt, dst=d_zones)
-        if a is not None:
-            recs, outside = ctx.zonal(a, d_zones, zone_lo, nzones, nodata, 0, zone_dtype=zdt, zone_strides=(w, 1))
+        if reg.encoded:
+            data, items, dt, B, _ = reg.decode_args()
+            recs, outside, _ = ctx.decode_device_zonal(data, items, d_zones, dt, B, win, reg.denorm, zone_lo, nzones,
+                                                       nodata, 0, zone_dtype=zdt, zone_strides=(w, 1))
         else:
-            denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-            recs, outside, _ = ctx.decode_device_zonal(np.frombuffer(blob, dtype=np.uint8), items, d_zones, src_dt, B, win,
-                                                       denorm, zone_lo, nzones, nodata, 0, zone_dtype=zdt,
-                                                       zone_strides=(w, 1))
+            recs, outside = ctx.zonal(reg.host(), d_zones, zone_lo, nzones, nodata, 0, zone_dtype=zdt, zone_strides=(w, 1))
     finally:
         ctx.free(d_zones)
-    return report_from_recs(recs, outside, src_dt, zone_lo, labels), win, meta
+    return report_from_recs(recs, outside, s.dtype, zone_lo, labels), win, s.meta
 
 
 # ------------------------------------------------------------------------------------------ proximity
@@ -1044,6 +824,29 @@ def _proximity_region(win, opts, H: int, W: int):
     return (r0, c0, r1 - r0, c1 - c0), (r - r0, c - c0, h, w)
 
 
+def _proximity(s, opts, window, bbox, units, dist_dtype, want_alloc, device, semantics=None):
+    """Proximity over a source -> ``(dist, alloc or None, counts, window, the options used)``."""
+    from . import _native
+    from .proximity import proximity_arrays
+
+    opts = _proximity_opts(opts, s.transform, units)
+    win = s.window(window, bbox)
+    region, inner = _proximity_region(win, opts, s.height, s.width)
+    reg = s.region(region, semantics)
+    odt = np.dtype(dist_dtype)
+    if device is None:
+        dist, alloc, counts = proximity_arrays(reg.host(), opts, inner, odt)
+        return dist, alloc if want_alloc else None, counts, win, opts
+    ctx = _native.default_context(int(device))
+    if reg.encoded:
+        dist, alloc, counts, _ = ctx.decode_device_proximity(*reg.decode_args(), opts, odt,
+                                                             alloc=None if want_alloc else False, out_window=inner,
+                                                             denorm=reg.denorm)
+    else:
+        dist, alloc, counts = ctx.proximity(reg.host(), opts, odt, alloc=None if want_alloc else False, out_window=inner)
+    return dist, alloc, counts, win, opts
+
+
 def proximity_window(src, opts=None, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
                      units: str = "pixel", dist_dtype="float32", want_alloc: bool = False, device: Optional[int] = None,
                      semantics: str = "pcm16"):
@@ -1057,29 +860,8 @@ def proximity_window(src, opts=None, window: Optional[Sequence[int]] = None, bbo
     raster; without a ``max_dist`` it is the whole raster.  ``device=None`` reads the region on the host and applies the
     numpy rule; an integer makes one ``fra_decode_device_proximity`` call on that GPU: the decoded pixels never leave
     the device."""
-    from . import _native
-    from .proximity import proximity_arrays
-
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    index = _index_of(src)
-    H, W = int(index["height"]), int(index["width"])
-    opts = _proximity_opts(opts, index.get("transform"), units)
-    win = (0, 0, H, W) if window is None and bbox is None else resolve_window(index, window, bbox)
-    region, inner = _proximity_region(win, opts, H, W)
-    index, gwin, blob, items = _window_items(src, region, None)
-    dt, B, odt = np.dtype(index["dtype"]), int(index["bands"]), np.dtype(dist_dtype)
-    if device is None:
-        a = np.zeros((B, gwin[2], gwin[3]), dtype=dt)
-        _decode_window_on_host(blob, items, gwin, a, semantics)
-        dist, alloc, counts = proximity_arrays(a, opts, inner, odt)
-        return dist, alloc if want_alloc else None, counts, win, index
-    ctx = _native.default_context(int(device))
-    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-    dist, alloc, counts, _ = ctx.decode_device_proximity(np.frombuffer(blob, dtype=np.uint8), items, dt, B, gwin, opts, odt,
-                                                         alloc=None if want_alloc else False, out_window=inner,
-                                                         denorm=denorm)
-    return dist, alloc, counts, win, index
+    s = ContainerSource(src)
+    return _proximity(s, opts, window, bbox, units, dist_dtype, want_alloc, device, semantics)[:4] + (s.meta,)
 
 
 def proximity_tiff(path: Path, opts=None, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -1087,36 +869,20 @@ def proximity_tiff(path: Path, opts=None, window: Optional[Sequence[int]] = None
     """:func:`proximity_window` for a GeoTIFF source -> ``(dist, alloc, counts, window, info, the options used)``.  The
     region is read with the in-package reader; an integer ``device`` hands it to ``fra_proximity`` on that GPU, ``None``
     to the numpy rule."""
-    from . import _native
-    from .proximity import proximity_arrays
-
-    g = GeoTIFF(Path(path))
-    try:
-        info = g.info
-        t = list(info.transform) if info.transform is not None else None
-        opts = _proximity_opts(opts, t, units)
-        win = _tiff_window(g, window, bbox)
-        region, inner = _proximity_region(win, opts, info.height, info.width)
-        a = np.zeros((info.count, region[2], region[3]), dtype=np.dtype(info.dtype))
-        g.read_window_into(a, *region)
-    finally:
-        g.close()
-    odt = np.dtype(dist_dtype)
-    if device is None:
-        dist, alloc, counts = proximity_arrays(a, opts, inner, odt)
-        alloc = alloc if want_alloc else None
-    else:
-        dist, alloc, counts = _native.default_context(int(device)).proximity(
-            a, opts, odt, alloc=None if want_alloc else False, out_window=inner)
-    return dist, alloc, counts, win, info, opts
+    s = TiffSource(path)
+    dist, alloc, counts, win, opts = _proximity(s, opts, window, bbox, units, dist_dtype, want_alloc, device)
+    return dist, alloc, counts, win, s.meta, opts
 
 
-def _fill_tag(fill, dtype):
-    """A fill as a GeoTIFF nodata tag of ``dtype``."""
-    from .calc import convert
+def _proximity_to_tiff(s, win, opts, tiff_path, dist, alloc_path, alloc):
+    """The distances, and with ``alloc_path`` the nearest targets' values, as GeoTIFFs on the window's grid with the
+    fills of ``opts`` as their nodata tags."""
+    from .proximity import default_fill
 
-    v = convert(np.array([float(fill)]), dtype)[0]
-    return float(v) if np.dtype(dtype).kind == "f" else int(v)
+    fill = default_fill(dist.dtype) if opts.fill is None else opts.fill
+    _to_tiff(tiff_path, dist, s, win, nodata=_fill_tag(fill, dist.dtype))
+    if alloc_path is not None:
+        _to_tiff(alloc_path, alloc, s, win, nodata=_fill_tag(opts.alloc_fill, alloc.dtype))
 
 
 def proximity_to_tiff(path: Path, tiff_path: Path, opts=None, window: Optional[Sequence[int]] = None,
@@ -1125,51 +891,24 @@ def proximity_to_tiff(path: Path, tiff_path: Path, opts=None, window: Optional[S
     """Proximity over a streaming container or a GeoTIFF (told apart by their first bytes) -> a GeoTIFF of the distances
     with the source's CRS, the transform shifted to the window's origin and the fill as its nodata tag; ``alloc_path``:
     a second GeoTIFF of the nearest targets' values, ``alloc_fill`` as its nodata tag.  Returns ``(window, counts)``."""
-    from .proximity import default_fill
-    from .tiff import write_geotiff
-
-    path = Path(path)
-    want = alloc_path is not None
-    if _is_tiff(path):
-        dist, alloc, counts, win, info, opts = proximity_tiff(path, opts, window, bbox, units, dist_dtype, want, device)
-        t, crs = list(info.transform) if info.transform is not None else None, str(info.crs) if info.crs is not None else None
-    elif is_streaming_container(path):
-        dist, alloc, counts, win, index = proximity_window(path, opts, window, bbox, units, dist_dtype, want, device, semantics)
-        t, crs = index.get("transform"), index.get("crs")
-    else:
-        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
-    transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
-    crs = crs if crs and crs != "None" else None
-    fill = default_fill(dist.dtype) if opts is None or opts.fill is None else opts.fill
-    write_geotiff(Path(tiff_path), dist, transform=transform, crs=crs, nodata=_fill_tag(fill, dist.dtype))
-    if want:
-        write_geotiff(Path(alloc_path), alloc, transform=transform, crs=crs,
-                      nodata=_fill_tag(0.0 if opts is None else opts.alloc_fill, alloc.dtype))
+    s = open_source(Path(path))
+    dist, alloc, counts, win, opts = _proximity(s, opts, window, bbox, units, dist_dtype, alloc_path is not None, device,
+                                                semantics)
+    _proximity_to_tiff(s, win, opts, tiff_path, dist, alloc_path, alloc)
     return win, counts
 
 
-def proximity_of_polygons(source, geojson, attribute: Optional[str] = None, opts=None,
-                          window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
-                          units: str = "pixel", dist_dtype="float32", device: Optional[int] = None):
-    """The distance of every pixel of the grid of ``source`` -- a streaming container or a GeoTIFF, whose pixels are not
-    read -- to the nearest polygon of a GeoJSON file, and that polygon's label -> ``(dist (1, h, w), alloc (1, h, w),
-    counts, window, transform of the window, crs)``.  Feature ``i`` has the label ``i + 1``, or its integer property
-    ``attribute``; 0 is what a pixel outside every polygon is burned with, so a label of 0 is refused.
-
-    ``device=None``: ``proximity.proximity_arrays`` over ``rasterize.rasterize_arrays``.  On a GPU ``fra_rasterize``
-    burns the labels of the region into a device buffer that goes to ``fra_proximity`` as it is: the label raster never
-    visits the host."""
+def _proximity_of_polygons(s, geojson, attribute, opts, window, bbox, units, dist_dtype, device):
+    """:func:`proximity_of_polygons` over the grid of a source -> ``(dist, alloc, counts, window, the options used)``."""
     from . import _native
     from .proximity import proximity_arrays
 
-    t, (H, W), crs = _grid_of(source)
-    pix, values = _pixel_features(geojson, attribute, t)
+    pix, values = _pixel_features(geojson, attribute, s.transform)
     if any(int(v) == 0 for v in values):
         raise ValueError("a label of 0 is not possible: 0 is what the pixels outside every polygon get")
-    opts = _proximity_opts(opts, t, units)
-    win = (0, 0, H, W) if window is None and bbox is None else resolve_window(
-        {"height": H, "width": W, "transform": t}, window, bbox)
-    region, inner = _proximity_region(win, opts, H, W)
+    opts = _proximity_opts(opts, s.transform, units)
+    win = s.window(window, bbox)
+    region, inner = _proximity_region(win, opts, s.height, s.width)
     zdt, odt = _label_dtype(values, 0), np.dtype(dist_dtype)
     if device is None:
         labels, _ = _burn(pix, region, values, 0, zdt, None)
@@ -1183,7 +922,37 @@ def proximity_of_polygons(source, geojson, attribute: Optional[str] = None, opts
                                                 shape=(1, region[2], region[3]))
         finally:
             ctx.free(d_labels)
-    return dist, alloc, counts, win, tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]), crs
+    return dist, alloc, counts, win, opts
+
+
+def proximity_of_polygons(source, geojson, attribute: Optional[str] = None, opts=None,
+                          window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                          units: str = "pixel", dist_dtype="float32", device: Optional[int] = None):
+    """The distance of every pixel of the grid of ``source`` -- a streaming container or a GeoTIFF, whose pixels are not
+    read -- to the nearest polygon of a GeoJSON file, and that polygon's label -> ``(dist (1, h, w), alloc (1, h, w),
+    counts, window, transform of the window, crs)``.  Feature ``i`` has the label ``i + 1``, or its integer property
+    ``attribute``; 0 is what a pixel outside every polygon is burned with, so a label of 0 is refused.
+
+    ``device=None``: ``proximity.proximity_arrays`` over ``rasterize.rasterize_arrays``.  On a GPU ``fra_rasterize``
+    burns the labels of the region into a device buffer that goes to ``fra_proximity`` as it is: the label raster never
+    visits the host."""
+    s = open_source(source)
+    dist, alloc, counts, win, _ = _proximity_of_polygons(s, geojson, attribute, opts, window, bbox, units, dist_dtype,
+                                                         device)
+    return dist, alloc, counts, win, s.window_transform(win), s.crs
+
+
+def proximity_of_polygons_to_tiff(source, geojson, tiff_path: Path, attribute: Optional[str] = None, opts=None,
+                                  window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                                  units: str = "pixel", dist_dtype="float32", alloc_path: Optional[Path] = None,
+                                  device: Optional[int] = None):
+    """:func:`proximity_of_polygons` into GeoTIFFs as :func:`proximity_to_tiff` writes them: the distances, and with
+    ``alloc_path`` the nearest polygons' labels.  Returns ``(window, counts)``."""
+    s = open_source(source)
+    dist, alloc, counts, win, opts = _proximity_of_polygons(s, geojson, attribute, opts, window, bbox, units, dist_dtype,
+                                                            device)
+    _proximity_to_tiff(s, win, opts, tiff_path, dist, alloc_path, alloc)
+    return win, counts
 
 
 # ------------------------------------------------------------------------------------------ band math
@@ -1191,6 +960,27 @@ def _calc_fill(fill, out_dtype):
     from .calc import default_fill
 
     return default_fill(out_dtype) if fill is None else float(fill)
+
+
+def _calc(s, exprs, window, bbox, out_dtype, nodata, fill, device, semantics=None):
+    """Band math over a source -> ``(raster, left-out pixels, window, the nodata used)``."""
+    from . import _native
+    from .calc import calc_arrays, compile_exprs
+
+    program = compile_exprs(exprs, s.bands)
+    win = s.window(window, bbox)
+    nodata = _nodata(s, nodata)
+    odt = np.dtype(out_dtype)
+    fill = _calc_fill(fill, odt)
+    reg = s.region(win, semantics)
+    if device is None:
+        res, left = calc_arrays(reg.host(), program, odt, nodata, fill)
+    elif reg.encoded:
+        res, left, _ = _native.default_context(int(device)).decode_device_calc(
+            *reg.decode_args(), program, odt, denorm=reg.denorm, nodata=nodata, fill=fill)
+    else:
+        res, left = _native.default_context(int(device)).calc(reg.host(), program, odt, nodata=nodata, fill=fill)
+    return res, left, win, nodata
 
 
 def calc_window(src, exprs, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -1205,30 +995,8 @@ def calc_window(src, exprs, window: Optional[Sequence[int]] = None, bbox: Option
     being NaN for float outputs and 0 for integer ones.  ``device=None`` reads the window on the host and applies the
     numpy rule; an integer makes one ``fra_decode_device_calc`` call on that GPU: the decoded pixels never leave the
     device and only the result comes back."""
-    from . import _native
-    from .calc import calc_arrays, compile_exprs
-
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    if window is None and bbox is None:
-        index = _index_of(src)
-        window = (0, 0, int(index["height"]), int(index["width"]))
-    index, win, blob, items = _window_items(src, window, bbox)
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
-    program = compile_exprs(exprs, B)
-    odt = np.dtype(out_dtype)
-    fill = _calc_fill(fill, odt)
-    if device is None:
-        out = np.zeros((B, win[2], win[3]), dtype=dt)
-        _decode_window_on_host(blob, items, win, out, semantics)
-        res, left = calc_arrays(out, program, odt, nodata, fill)
-        return res, left, win, index
-    ctx = _native.default_context(int(device))
-    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-    res, left, _ = ctx.decode_device_calc(np.frombuffer(blob, dtype=np.uint8), items, dt, B, win, program, odt,
-                                          denorm=denorm, nodata=nodata, fill=fill)
-    return res, left, win, index
+    s = ContainerSource(src)
+    return _calc(s, exprs, window, bbox, out_dtype, nodata, fill, device, semantics)[:3] + (s.meta,)
 
 
 def calc_tiff(path: Path, exprs, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -1237,31 +1005,9 @@ def calc_tiff(path: Path, exprs, window: Optional[Sequence[int]] = None, bbox: O
     """:func:`calc_window` for a GeoTIFF source -> ``(raster, left-out pixels, window, info, the nodata used)``.  The
     window is read with the in-package reader; an integer ``device`` hands it to ``fra_calc`` on that GPU, ``None`` to
     the numpy rule.  ``nodata=None`` takes the TIFF's own nodata tag, when it has one."""
-    from . import _native
-    from .calc import calc_arrays, compile_exprs
-
-    g = GeoTIFF(Path(path))
-    try:
-        info = g.info
-        program = compile_exprs(exprs, int(info.count))
-        if window is None and bbox is None:
-            win = (0, 0, info.height, info.width)
-        else:
-            win = resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)},
-                                 window, bbox)
-        if nodata is None and info.nodata is not None:
-            nodata = float(info.nodata)
-        a = np.zeros((info.count, win[2], win[3]), dtype=np.dtype(info.dtype))
-        g.read_window_into(a, *win)
-    finally:
-        g.close()
-    odt = np.dtype(out_dtype)
-    fill = _calc_fill(fill, odt)
-    if device is None:
-        res, left = calc_arrays(a, program, odt, nodata, fill)
-    else:
-        res, left = _native.default_context(int(device)).calc(a, program, odt, nodata=nodata, fill=fill)
-    return res, left, win, info, nodata
+    s = TiffSource(path)
+    res, left, win, nodata = _calc(s, exprs, window, bbox, out_dtype, nodata, fill, device)
+    return res, left, win, s.meta, nodata
 
 
 def calc_to_tiff(path: Path, tiff_path: Path, exprs, window: Optional[Sequence[int]] = None,
@@ -1271,27 +1017,10 @@ def calc_to_tiff(path: Path, tiff_path: Path, exprs, window: Optional[Sequence[i
     source's CRS and the transform shifted to the window's origin.  When a nodata value was given (or the source TIFF
     carries one) the result's nodata tag is ``fill`` as the output dtype holds it.  Returns ``(window, left-out pixels
     per output band, pixels per band)``."""
-    from .tiff import write_geotiff
-
-    path = Path(path)
-    with open(path, "rb") as f:
-        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-    if is_tiff:
-        res, left, win, info, nodata = calc_tiff(path, exprs, window, bbox, out_dtype, nodata, fill, device)
-        t, crs = list(info.transform), str(info.crs) if info.crs is not None else None
-    elif is_streaming_container(path):
-        res, left, win, index = calc_window(path, exprs, window, bbox, out_dtype, nodata, fill, device, semantics)
-        t, crs = index.get("transform"), index.get("crs")
-    else:
-        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
-    transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
-    tag = None
-    if nodata is not None:
-        from .calc import convert
-
-        v = convert(np.array([_calc_fill(fill, res.dtype)]), res.dtype)[0]
-        tag = float(v) if res.dtype.kind == "f" else int(v)
-    write_geotiff(Path(tiff_path), res, transform=transform, crs=crs if crs and crs != "None" else None, nodata=tag)
+    s = open_source(Path(path))
+    res, left, win, nodata = _calc(s, exprs, window, bbox, out_dtype, nodata, fill, device, semantics)
+    tag = _fill_tag(_calc_fill(fill, res.dtype), res.dtype) if nodata is not None else None
+    _to_tiff(tiff_path, res, s, win, nodata=tag)
     return win, left, int(win[2]) * int(win[3])
 
 
@@ -1319,6 +1048,31 @@ def _grown(win, spec, H: int, W: int):
     return (r0, c0, r1 - r0, c1 - c0), (r - r0, c - c0, h, w)
 
 
+def _focal(s, spec, window, bbox, out_dtype, device, semantics=None):
+    """A focal operation over a source -> ``(raster, pixels that got fill, window, the spec used)``."""
+    import dataclasses
+
+    from . import _native
+    from .focal import focal_arrays, validate
+
+    spec = _focal_spec(spec, s.transform)
+    if spec.nodata is None and s.nodata is not None:
+        spec = dataclasses.replace(spec, nodata=s.nodata)
+    validate(spec)
+    win = s.window(window, bbox)
+    grown, inner = _grown(win, spec, s.height, s.width)
+    reg = s.region(grown, semantics)
+    odt = np.dtype(out_dtype)
+    if device is None:
+        res, left = focal_arrays(reg.host(), spec, odt, inner)
+    elif reg.encoded:
+        res, left, _ = _native.default_context(int(device)).decode_device_focal(*reg.decode_args(), spec, inner, odt,
+                                                                                denorm=reg.denorm)
+    else:
+        res, left = _native.default_context(int(device)).focal(reg.host(), spec, odt, out_window=inner)
+    return res, left, win, spec
+
+
 def focal_window(src, spec, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
                  out_dtype="float32", device: Optional[int] = None, semantics: str = "pcm16"):
     """A focal operation over a streaming container (path or bytes), or over a window of it -> ``(raster (B, h, w) in
@@ -1331,31 +1085,8 @@ def focal_window(src, spec, window: Optional[Sequence[int]] = None, bbox: Option
     clipped to the raster, and the tiles of the grown window are selected: ``device=None`` reads it on the host and
     applies the numpy rule; an integer makes one ``fra_decode_device_focal`` call on that GPU: the decoded pixels never
     leave the device and only the result comes back."""
-    from . import _native
-    from .focal import focal_arrays, validate
-
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    index = _index_of(src)
-    H, W = int(index["height"]), int(index["width"])
-    spec = _focal_spec(spec, index.get("transform"))
-    validate(spec)
-    win = (0, 0, H, W) if window is None and bbox is None else resolve_window(index, window, bbox)
-    grown, inner = _grown(win, spec, H, W)
-    index, gwin, blob, items = _window_items(src, grown, None)
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
-    odt = np.dtype(out_dtype)
-    if device is None:
-        out = np.zeros((B, gwin[2], gwin[3]), dtype=dt)
-        _decode_window_on_host(blob, items, gwin, out, semantics)
-        res, left = focal_arrays(out, spec, odt, inner)
-        return res, left, win, index
-    ctx = _native.default_context(int(device))
-    denorm = _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT
-    res, left, _ = ctx.decode_device_focal(np.frombuffer(blob, dtype=np.uint8), items, dt, B, gwin, spec, inner, odt,
-                                           denorm=denorm)
-    return res, left, win, index
+    s = ContainerSource(src)
+    return _focal(s, spec, window, bbox, out_dtype, device, semantics)[:3] + (s.meta,)
 
 
 def focal_tiff(path: Path, spec, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
@@ -1363,34 +1094,9 @@ def focal_tiff(path: Path, spec, window: Optional[Sequence[int]] = None, bbox: O
     """:func:`focal_window` for a GeoTIFF source -> ``(raster, pixels that got fill, window, info, the spec used)``.
     The grown window is read with the in-package reader; an integer ``device`` hands it to ``fra_focal`` on that GPU,
     ``None`` to the numpy rule.  A spec without a nodata value takes the TIFF's own nodata tag, when it has one."""
-    import dataclasses
-
-    from . import _native
-    from .focal import focal_arrays, validate
-
-    g = GeoTIFF(Path(path))
-    try:
-        info = g.info
-        spec = _focal_spec(spec, list(info.transform) if info.transform is not None else None)
-        if spec.nodata is None and info.nodata is not None:
-            spec = dataclasses.replace(spec, nodata=float(info.nodata))
-        validate(spec)
-        if window is None and bbox is None:
-            win = (0, 0, info.height, info.width)
-        else:
-            win = resolve_window({"height": info.height, "width": info.width, "transform": list(info.transform)},
-                                 window, bbox)
-        grown, inner = _grown(win, spec, info.height, info.width)
-        a = np.zeros((info.count, grown[2], grown[3]), dtype=np.dtype(info.dtype))
-        g.read_window_into(a, *grown)
-    finally:
-        g.close()
-    odt = np.dtype(out_dtype)
-    if device is None:
-        res, left = focal_arrays(a, spec, odt, inner)
-    else:
-        res, left = _native.default_context(int(device)).focal(a, spec, odt, out_window=inner)
-    return res, left, win, info, spec
+    s = TiffSource(path)
+    res, left, win, spec = _focal(s, spec, window, bbox, out_dtype, device)
+    return res, left, win, s.meta, spec
 
 
 def focal_to_tiff(path: Path, tiff_path: Path, spec, window: Optional[Sequence[int]] = None,
@@ -1400,29 +1106,10 @@ def focal_to_tiff(path: Path, tiff_path: Path, spec, window: Optional[Sequence[i
     source's CRS and the transform shifted to the window's origin.  When the spec used has a nodata value (its own or
     the source TIFF's) the result's nodata tag is ``fill`` as the output dtype holds it.  Returns ``(window, pixels that
     got fill per band, pixels per band)``."""
-    from .tiff import write_geotiff
-
-    path = Path(path)
-    with open(path, "rb") as f:
-        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-    if is_tiff:
-        res, left, win, info, spec = focal_tiff(path, spec, window, bbox, out_dtype, device)
-        t, crs = list(info.transform), str(info.crs) if info.crs is not None else None
-    elif is_streaming_container(path):
-        t = open_streaming(path).index.get("transform")
-        spec = _focal_spec(spec, t)
-        res, left, win, index = focal_window(path, spec, window, bbox, out_dtype, device, semantics)
-        crs = index.get("crs")
-    else:
-        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
-    transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
-    tag = None
-    if spec.nodata is not None:
-        from .calc import convert
-
-        v = convert(np.array([_calc_fill(spec.fill, res.dtype)]), res.dtype)[0]
-        tag = float(v) if res.dtype.kind == "f" else int(v)
-    write_geotiff(Path(tiff_path), res, transform=transform, crs=crs if crs and crs != "None" else None, nodata=tag)
+    s = open_source(Path(path))
+    res, left, win, spec = _focal(s, spec, window, bbox, out_dtype, device, semantics)
+    tag = _fill_tag(_calc_fill(spec.fill, res.dtype), res.dtype) if spec.nodata is not None else None
+    _to_tiff(tiff_path, res, s, win, nodata=tag)
     return win, left, int(win[2]) * int(win[3])
 
 
@@ -1455,10 +1142,38 @@ def _warp_map(src_transform, src_crs, dst_transform, out_shape, dst_crs, coords,
     return m, m.step, err
 
 
-def _warp_info(m, step, err, window, filled, out_shape, index=None):
-    n = int(out_shape[0]) * int(out_shape[1])
-    return {"map": m, "grid_step": step, "grid_error": err, "source_window": window, "filled": filled,
-            "shares": [int(v) / n for v in filled], "index": index}
+def _warp(s, dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device, cpu, grid_step, max_error,
+          semantics="pcm16"):
+    """A source read onto another grid -> ``(raster, output transform, output CRS, info, the nodata used)``."""
+    from . import _native, warp
+
+    denorm = denorm_code(semantics)
+    oh, ow = resample.check_out_shape(out_shape)
+    warp.resampling_code(resampling)
+    nodata = _nodata(s, nodata)
+    H, W, B, dt = s.height, s.width, s.bands, s.dtype
+    m, step, err = _warp_map(s.transform, s.crs, dst_transform, (oh, ow), dst_crs, coords, grid_step, max_error)
+    warp.check_values(dt, nodata, fill)
+    win = warp.source_window(m, (H, W), (oh, ow))
+    # of a container only the window the map touches is decoded (none when the map misses the raster); a GeoTIFF is read
+    # whole, as fra_warp takes it
+    read = win if s.encoded else s.window()
+    reg = s.region(read, semantics) if read is not None else None
+    if cpu or device is None:
+        region, origin = (np.zeros((B, 1, 1), dt), (0, 0)) if reg is None else (reg.host(), read[:2])
+        out, filled = warp.warp_arrays(region, (oh, ow), m, resampling, nodata, fill, origin=origin, raster_shape=(H, W))
+    elif s.encoded:
+        data, items = (np.zeros(0, np.uint8), []) if reg is None else reg.decode_args()[:2]
+        out = np.zeros((B, oh, ow), dtype=dt)
+        _, filled = _native.default_context(int(device)).decode_device_warped(
+            data, items, out, dt, B, (oh * ow, ow, 1), (H, W), (oh, ow), m, resampling, denorm, nodata=nodata, fill=fill)
+    else:
+        out, filled = _native.default_context(int(device)).warp(reg.host(), (oh, ow), m, resampling, nodata=nodata,
+                                                                fill=fill)
+    n = oh * ow
+    info = {"map": m, "grid_step": step, "grid_error": err, "source_window": win, "filled": filled,
+            "shares": [int(v) / n for v in filled], "index": s.meta if s.encoded else None}
+    return out, tuple(float(v) for v in tuple(dst_transform)[:6]), (dst_crs or s.crs), info, nodata
 
 
 def warp_window(src, dst_transform, out_shape, dst_crs=None, coords=None, resampling: str = "bilinear", nodata=None,
@@ -1475,40 +1190,8 @@ def warp_window(src, dst_transform, out_shape, dst_crs=None, coords=None, resamp
     GPU: the decoded window never leaves it and only the output comes back; ``cpu=True`` (or ``device=None``) decodes the
     window on the host and applies the numpy rule.  ``info``: the map, the grid step and the error reached, the source
     window (``None``: the map misses the raster), the pixels written as fill per band and their shares."""
-    from . import _native, warp
-
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    oh, ow = resample.check_out_shape(out_shape)
-    warp.resampling_code(resampling)
-    index = _index_of(src)
-    H, W = int(index["height"]), int(index["width"])
-    dt = np.dtype(index["dtype"])
-    B = int(index["bands"])
-    src_crs = index.get("crs")
-    src_crs = src_crs if src_crs and src_crs != "None" else None
-    m, step, err = _warp_map(index.get("transform"), src_crs, dst_transform, (oh, ow), dst_crs, coords, grid_step, max_error)
-    warp.check_values(dt, nodata, fill)
-    win = warp.source_window(m, (H, W), (oh, ow))
-    blob, items = bytearray(), []
-    if win is not None:
-        index, win, blob, items = _window_items(src, win, None)
-    if cpu or device is None:
-        if win is None:
-            region, origin = np.zeros((B, 1, 1), dt), (0, 0)
-        else:
-            region, origin = np.zeros((B, win[2], win[3]), dtype=dt), (win[0], win[1])
-            _decode_window_on_host(blob, items, win, region, semantics)
-        out, filled = warp.warp_arrays(region, (oh, ow), m, resampling, nodata, fill, origin=origin, raster_shape=(H, W))
-    else:
-        out = np.zeros((B, oh, ow), dtype=dt)
-        ctx = _native.default_context(int(device))
-        _, filled = ctx.decode_device_warped(np.frombuffer(bytes(blob), dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1),
-                                             (H, W), (oh, ow), m, resampling,
-                                             _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT,
-                                             nodata=nodata, fill=fill)
-    return out, tuple(float(v) for v in tuple(dst_transform)[:6]), (dst_crs or src_crs), \
-        _warp_info(m, step, err, win, filled, (oh, ow), index)
+    return _warp(ContainerSource(src), dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device, cpu,
+                 grid_step, max_error, semantics)[:4]
 
 
 def warp_tiff(path: Path, dst_transform, out_shape, dst_crs=None, coords=None, resampling: str = "bilinear", nodata=None,
@@ -1516,31 +1199,10 @@ def warp_tiff(path: Path, dst_transform, out_shape, dst_crs=None, coords=None, r
               max_error: float = 0.125):
     """:func:`warp_window` for a GeoTIFF source, read whole with the in-package reader: ``fra_warp`` on the GPU
     ``device``, the numpy rule with ``cpu=True`` (or ``device=None``).  Without ``nodata`` the TIFF's own tag is used."""
-    from . import _native, warp
-
-    oh, ow = resample.check_out_shape(out_shape)
-    warp.resampling_code(resampling)
-    g = GeoTIFF(Path(path))
-    try:
-        info = g.info
-        if nodata is None and info.nodata is not None:
-            nodata = float(info.nodata)
-        src_crs = str(info.crs) if info.crs is not None and str(info.crs) else None
-        m, step, err = _warp_map(list(info.transform) if info.transform is not None else None, src_crs, dst_transform,
-                                 (oh, ow), dst_crs, coords, grid_step, max_error)
-        warp.check_values(np.dtype(info.dtype), nodata, fill)
-        a = np.zeros((info.count, info.height, info.width), dtype=np.dtype(info.dtype))
-        g.read_window_into(a, 0, 0, info.height, info.width)
-    finally:
-        g.close()
-    win = warp.source_window(m, a.shape[1:], (oh, ow))
-    if cpu or device is None:
-        out, filled = warp.warp_arrays(a, (oh, ow), m, resampling, nodata, fill)
-    else:
-        out, filled = _native.default_context(int(device)).warp(a, (oh, ow), m, resampling, nodata=nodata, fill=fill)
-    res = _warp_info(m, step, err, win, filled, (oh, ow))
-    res["nodata"] = nodata
-    return out, tuple(float(v) for v in tuple(dst_transform)[:6]), (dst_crs or src_crs), res
+    out, t, crs, info, nodata = _warp(TiffSource(path), dst_transform, out_shape, dst_crs, coords, resampling, nodata,
+                                      fill, device, cpu, grid_step, max_error)
+    info["nodata"] = nodata
+    return out, t, crs, info
 
 
 def warp_to_tiff(path: Path, tiff_path: Path, dst_transform, out_shape, dst_crs=None, coords=None,
@@ -1550,32 +1212,50 @@ def warp_to_tiff(path: Path, tiff_path: Path, dst_transform, out_shape, dst_crs=
     grid's transform and CRS; with a nodata value (the caller's or the source TIFF's) the nodata tag is the fill.
     Returns the ``info`` of :func:`warp_window`."""
     from . import warp
-    from .tiff import write_geotiff
 
-    path = Path(path)
-    with open(path, "rb") as f:
-        is_tiff = f.read(4) in (b"II*\x00", b"MM\x00*", b"II+\x00", b"MM\x00+")
-    if is_tiff:
-        out, t, crs, info = warp_tiff(path, dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device, cpu,
-                                      grid_step, max_error)
-        nodata = info["nodata"]
-    elif is_streaming_container(path):
-        out, t, crs, info = warp_window(path, dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device,
-                                        cpu, semantics, grid_step, max_error)
-    else:
-        raise ValueError("a streaming FLAC file (convert --streaming) or a GeoTIFF is needed")
+    s = open_source(Path(path))
+    out, t, crs, info, nodata = _warp(s, dst_transform, out_shape, dst_crs, coords, resampling, nodata, fill, device,
+                                      cpu, grid_step, max_error, semantics)
+    if not s.encoded:
+        info["nodata"] = nodata
     tag = None
-    if nodata is not None:
+    if nodata is not None:  # not _fill_tag: the warp's fill defaults to the nodata value (warp.check_values)
         v = warp.check_values(out.dtype, nodata, fill)[1]
         tag = float(v) if out.dtype.kind == "f" else int(v)
-    write_geotiff(Path(tiff_path), out, transform=t, crs=str(crs) if crs and str(crs) != "None" else None, nodata=tag)
+    _to_tiff(tiff_path, out, s, transform=t, crs=crs, nodata=tag)
     return info
 
 
-def _index_of(src):
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        return read_index_bytes(bytes(memoryview(src)[:4 + struct.unpack(">I", memoryview(src)[:4])[0]]))[0]
-    return open_streaming(Path(src)).index
+def _read_overview(s: ContainerSource, factor, resampling, device, semantics, out_shape, max_size, nodata):
+    """:func:`read_overview` of a source."""
+    from . import _native
+
+    if (factor is not None) + (out_shape is not None) + (max_size is not None) != 1:
+        raise ValueError("give exactly one of factor, out_shape and max_size")
+    H, W = s.height, s.width
+    if max_size is not None:
+        out_shape = resample.max_size_shape(H, W, max_size)
+    if device is None:
+        out, _, index = _read_window(s, s.window(), None, None, semantics,
+                                     1 if factor is None else resample.check_factor(factor), resampling, out_shape, nodata)
+        return out, index
+    denorm = denorm_code(semantics)
+    if factor is None:
+        oh, ow = resample.check_out_shape(out_shape)
+        resample.resampling_any_code(resampling)
+    else:
+        k = resample.check_factor(factor)
+        resample.resampling_code(resampling)
+        oh, ow = resample.decimated_shape(H, W, k)
+    data, items = s.whole()  # to the device as they are
+    out = np.zeros((s.bands, oh, ow), dtype=s.dtype)
+    ctx = _native.default_context(int(device))
+    args = np.frombuffer(data, dtype=np.uint8), items, out, s.dtype, s.bands, (oh * ow, ow, 1), s.window()
+    if factor is None:
+        ctx.decode_device_resampled(*args, (oh, ow), resampling, denorm, nodata=nodata)
+    else:
+        ctx.decode_device_decimated(*args, k, resampling, denorm, nodata=nodata)
+    return out, s.meta
 
 
 def read_overview(src, factor: Optional[int] = None, resampling: str = "average", device: Optional[int] = None,
@@ -1592,53 +1272,7 @@ def read_overview(src, factor: Optional[int] = None, resampling: str = "average"
     (``resample.resample``, ``resampling`` any of its four; on a GPU one ``fra_decode_device_resampled`` call), or
     ``max_size`` = N, the output shape whose longest side is N (``resample.max_size_shape``).  ``nodata``: as
     :func:`read_window`."""
-    from . import _native
-
-    if out_shape is not None or max_size is not None:
-        if factor is not None or (out_shape is not None and max_size is not None):
-            raise ValueError("give exactly one of factor, out_shape and max_size")
-        index = _index_of(src)
-        H, W = int(index["height"]), int(index["width"])
-        if max_size is not None:
-            out_shape = resample.max_size_shape(H, W, max_size)
-        if device is None:
-            out, _, index = read_window(src, window=(0, 0, H, W), device=None, semantics=semantics,
-                                        resampling=resampling, out_shape=out_shape, nodata=nodata)
-            return out, index
-        if semantics not in ("pcm16", "int"):
-            raise ValueError("semantics must be 'pcm16' or 'int'")
-        oh, ow = resample.check_out_shape(out_shape)
-        resample.resampling_any_code(resampling)
-        data = _container_bytes(src)  # as they are, as below
-        index, items = _tile_items(data)
-        dt, B = np.dtype(index["dtype"]), int(index["bands"])
-        out = np.zeros((B, oh, ow), dtype=dt)
-        _native.default_context(int(device)).decode_device_resampled(
-            np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), (0, 0, H, W), (oh, ow), resampling,
-            _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT, nodata=nodata)
-        return out, index
-    if factor is None:
-        raise ValueError("give exactly one of factor, out_shape and max_size")
-    k = resample.check_factor(factor)
-    resample.resampling_code(resampling)
-    if semantics not in ("pcm16", "int"):
-        raise ValueError("semantics must be 'pcm16' or 'int'")
-    if device is None:
-        index = _index_of(src)
-        out, _, index = read_window(src, window=(0, 0, int(index["height"]), int(index["width"])), device=None,
-                                    semantics=semantics, decimate=k, resampling=resampling, nodata=nodata)
-        return out, index
-    data = _container_bytes(src)
-    index, items = _tile_items(data)
-    dt = np.dtype(index["dtype"])
-    B, H, W = int(index["bands"]), int(index["height"]), int(index["width"])
-    oh, ow = resample.decimated_shape(H, W, k)
-    out = np.zeros((B, oh, ow), dtype=dt)
-    ctx = _native.default_context(int(device))
-    ctx.decode_device_decimated(np.frombuffer(data, dtype=np.uint8), items, out, dt, B, (oh * ow, ow, 1), (0, 0, H, W),
-                                k, resampling, _native.DENORM_PCM16 if semantics == "pcm16" else _native.DENORM_INT,
-                                nodata=nodata)
-    return out, index
+    return _read_overview(ContainerSource(src), factor, resampling, device, semantics, out_shape, max_size, nodata)
 
 
 def _tiff_nodata(nodata, dtype):
@@ -1664,20 +1298,14 @@ def window_to_tiff(path: Path, tiff_path: Path, window: Optional[Sequence[int]] 
     resampled to that size; pixel size scaled to match; ``nodata``: as :func:`read_window`, and the TIFF carries the
     value in its nodata tag; ``shares``, a list, then receives :func:`nodata_share` of what was written); returns
     ``(window, index)``."""
-    from .tiff import write_geotiff
-
-    raster, win, index = read_window(Path(path), window=window, bbox=bbox, device=device, decimate=decimate,
-                                     resampling=resampling, out_shape=out_shape, nodata=nodata)
-    t = index.get("transform")
-    crs = index.get("crs")
-    if t and out_shape is not None:
-        transform = resample.resampled_transform(t, win, out_shape)
-    elif t and decimate != 1:
-        transform = resample.decimated_transform(t, win, decimate)
-    else:
-        transform = tuple(window_transform(Affine(*t[:6]), win[1], win[0])[:6]) if t else None
-    write_geotiff(Path(tiff_path), raster, transform=transform, crs=crs if crs and crs != "None" else None,
-                  nodata=_tiff_nodata(nodata, raster.dtype))
+    s = ContainerSource(Path(path))
+    raster, win, index = _read_window(s, window, bbox, device, "pcm16", decimate, resampling, out_shape, nodata)
+    transform = None  # the window's own
+    if s.transform and out_shape is not None:
+        transform = resample.resampled_transform(s.transform, win, out_shape)
+    elif s.transform and decimate != 1:
+        transform = resample.decimated_transform(s.transform, win, decimate)
+    _to_tiff(tiff_path, raster, s, win, transform, nodata=_tiff_nodata(nodata, raster.dtype))
     if nodata is not None and shares is not None:
         shares.extend(nodata_share(raster, nodata))
     return win, index
@@ -1690,17 +1318,14 @@ def overview_to_tiff(path: Path, tiff_path: Path, factor: Optional[int] = None, 
     pixels -> GeoTIFF with the index's CRS and the pixel size scaled to match (``nodata``: as :func:`read_window`, and
     the TIFF carries the value in its nodata tag; ``shares`` as :func:`window_to_tiff`); returns ``(raster shape,
     index)``."""
-    from .tiff import write_geotiff
-
-    raster, index = read_overview(Path(path), factor, resampling, device=device, max_size=max_size, nodata=nodata)
-    t = index.get("transform")
-    crs = index.get("crs")
-    if t and max_size is not None:
-        transform = resample.resampled_transform(t, (0, 0, int(index["height"]), int(index["width"])), raster.shape[1:])
-    else:
-        transform = resample.decimated_transform(t, (0, 0), factor) if t else None
-    write_geotiff(Path(tiff_path), raster, transform=transform,
-                  crs=crs if crs and crs != "None" else None, nodata=_tiff_nodata(nodata, raster.dtype))
+    s = ContainerSource(Path(path))
+    raster, index = _read_overview(s, factor, resampling, device, "pcm16", None, max_size, nodata)
+    transform = None
+    if s.transform and max_size is not None:
+        transform = resample.resampled_transform(s.transform, s.window(), raster.shape[1:])
+    elif s.transform:
+        transform = resample.decimated_transform(s.transform, (0, 0), factor)
+    _to_tiff(tiff_path, raster, s, transform=transform, nodata=_tiff_nodata(nodata, raster.dtype))
     if nodata is not None and shares is not None:
         shares.extend(nodata_share(raster, nodata))
     return raster.shape, index
