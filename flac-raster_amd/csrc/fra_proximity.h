@@ -70,6 +70,18 @@ inline uint64_t out_bits(int dtype, double x) {
   return bits;
 }
 
+#ifdef __HIPCC__
+// the rule's target predicate (the regions unit's foreground is the same one): nvalues == 0: non-zero and not NaN
+template <typename T>
+__device__ inline bool is_target(T v, int32_t nvalues, const double* values) {
+  if (nvalues == 0) return v != (T)0 && v == v;
+  const double x = (double)v;
+  bool hit = false;
+  for (int i = 0; i < nvalues; i++) hit |= x == values[i];
+  return hit;
+}
+#endif
+
 // FRA_E_INVALID for what the rule refuses, in the header's order (after the null arguments): a (channels, h, w) source
 // of `dtype` with the strides ss, and the options
 inline int check_job(int dtype, int32_t channels, int32_t h, int32_t w, const fra_region::Strides& ss, const fra_proximity_opts* o) {

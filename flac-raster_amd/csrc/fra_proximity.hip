@@ -49,15 +49,6 @@ struct ProxArgs {
   Plan plan;
 };
 
-template <typename T>
-__device__ inline bool is_target(T v, const ProxArgs& a) {
-  if (a.nvalues == 0) return v != (T)0 && v == v;
-  const double x = (double)v;
-  bool hit = false;
-  for (int i = 0; i < a.nvalues; i++) hit |= x == a.values[i];
-  return hit;
-}
-
 // the workgroup's sum of `v` into out[its index]: a word of its own
 __device__ inline void wg_sum_to(uint32_t v, uint32_t* out, uint32_t index) {
   const uint32_t total = wg_sum(v);
@@ -72,7 +63,7 @@ __global__ void __launch_bounds__(256) k_prox_mask(ProxArgs a) {
   if (c < a.w) {
     const int32_t ra = k * kChunkRows, n = min(kChunkRows, a.h - ra);
     const T* p = (const T*)a.src + (int64_t)ra * a.srs + (int64_t)c * a.scs;
-    for (int32_t i = 0; i < n; i++) m |= (unsigned long long)is_target(p[(int64_t)i * a.srs], a) << i;
+    for (int32_t i = 0; i < n; i++) m |= (unsigned long long)is_target(p[(int64_t)i * a.srs], a.nvalues, a.values) << i;
     a.mask[(int64_t)k * a.w + c] = m;
   }
   wg_sum_to((uint32_t)__popcll(m), a.targets, blockIdx.y * gridDim.x + blockIdx.x);

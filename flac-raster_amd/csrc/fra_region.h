@@ -2,7 +2,8 @@
 // (fra_decimate.hip, fra_resample.hip with its nodata-aware reads, fra_compare.hip, fra_stats.hip, fra_zonal.hip), two map it
 // (fra_calc.hip and fra_focal.hip, whose output has a dtype, a size or a band count of its own: Dst, run_raster_to,
 // run_region_to) and one transforms it as a whole (fra_proximity.hip, with two outputs of its own: stage_in, stage_out,
-// run_region_src); fra_warp.hip and fra_rasterize.hip use its staging.  Once each:
+// run_region_src), as does the one that labels its connected components (fra_regions.hip, three outputs and a table);
+// fra_warp.hip and fra_rasterize.hip use its staging.  Once each:
 //   * the refusals they share: a bad dtype or raster layout (check_raster), items that do not cover the region
 //     (check_cover), and what is left to the windowed read, which refuses it with its own message
 //     (left_to_window_read, left_to_window_read_no_dst, refer_to_window_read);

@@ -41,6 +41,16 @@ class OutputTooSmall(NativeError):
         self.needed = needed
 
 
+class RegionsNoSpace(NativeError):
+    """A band of a regions call has more kept components than the labels dtype or the table holds (``FRA_E_SPACE``).
+    ``counts``: the complete ``(B, 4)`` counts, ``counts[:, 2]`` the N of every band; nothing has been written."""
+
+    def __init__(self, message: str, counts):
+        super().__init__(message)
+        self.code = E_SPACE
+        self.counts = counts
+
+
 class VerifyMismatch(NativeError):
     """Verify found decoded samples that differ from the normalised input (``Plan.verify``, ``verify=True``).
 
@@ -276,6 +286,28 @@ class ProximityJob(C.Structure):
 
 assert C.sizeof(ProximityOpts) == 280 and C.sizeof(ProximityJob) == 336
 
+
+class RegionsOpts(C.Structure):
+    """``fra_regions_opts`` (296 bytes; the rule: ``regions.py``)."""
+
+    _fields_ = [
+        ("nvalues", C.c_int32), ("invert", C.c_int32), ("by_value", C.c_int32), ("connectivity", C.c_int32),
+        ("min_size", C.c_int32), ("table_cap", C.c_int32), ("table_on_device", C.c_int32), ("reserved", C.c_int32),
+        ("values", C.c_double * 16), ("sieve_fill", C.c_double), ("table", C.c_void_p),
+        ("labels", CalcDst), ("area", CalcDst), ("sieved", CalcDst),
+    ]
+
+
+class RegionsJob(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_on_device", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32),
+        ("height", C.c_int32), ("width", C.c_int32), ("band_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("col_stride", C.c_int64), ("opts", RegionsOpts),
+    ]
+
+
+assert C.sizeof(RegionsOpts) == 296 and C.sizeof(RegionsJob) == 352
+
 STATS_AUTO_RANGE, STATS_NODATA = 1, 2
 ZONAL_NODATA, ZONAL_IGNORE = 1, 2
 CALC_NODATA = 1
@@ -341,6 +373,7 @@ EXPORTS = [
     "fra_warp", "fra_decode_device_warped", "fra_warp_source_window", "fra_warp_timing", "fra_warp_paths",
     "fra_rasterize", "fra_rasterize_timing",
     "fra_proximity", "fra_decode_device_proximity", "fra_proximity_timing",
+    "fra_regions", "fra_decode_device_regions", "fra_regions_timing",
 ]
 
 
@@ -469,6 +502,11 @@ def load():
             L.fra_decode_device_proximity.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(ProximityOpts),
                                                       C.POINTER(Decoded), C.POINTER(u64)]
             L.fra_proximity_timing.argtypes = [C.POINTER(C.c_float)]
+        if hasattr(L, "fra_regions"):
+            L.fra_regions.argtypes = [vp, C.POINTER(RegionsJob), C.POINTER(u64)]
+            L.fra_decode_device_regions.argtypes = [vp, C.POINTER(DecodeJob), C.POINTER(Window), C.POINTER(RegionsOpts),
+                                                    C.POINTER(Decoded), C.POINTER(u64)]
+            L.fra_regions_timing.argtypes = [C.POINTER(C.c_float)]
         L.fra_tiff_compress_bound.argtypes = [i32, u64]
         L.fra_tiff_compress_bound.restype = u64
         L.fra_tiff_compress.argtypes = [i32, i32, vp, u64, i32, vp, u64, C.POINTER(u64), i32]
@@ -480,6 +518,13 @@ def _check(rc: int):
     if rc != 0:
         msg = load().fra_last_error()
         raise NativeError(f"flac_raster_amd error {rc}: {msg.decode() if msg else ''}")
+
+
+def _check_regions(rc: int, counts):
+    if rc == E_SPACE:
+        msg = load().fra_last_error()
+        raise RegionsNoSpace(f"flac_raster_amd error {rc}: {msg.decode() if msg else ''}", counts)
+    _check(rc)
 
 
 def _masked_args(nodata, filled, dtype, channels: int):
@@ -638,6 +683,49 @@ def proximity_opts(opts, out_window, src_dtype, shape, dist, alloc, dist_dtype, 
     if alloc is not False:
         o.alloc, ret_a = _calc_dst(alloc, alloc_strides, src_dtype, (B, win[2], win[3]))
     return o, ret_d, ret_a
+
+
+def regions_opts(opts, src_dtype, shape, labels, area, sieved, table, label_dtype, area_dtype, strides):
+    """The ``fra_regions_opts`` of a ``regions.Options`` over a ``(B, h, w)`` region, and what the caller returns as
+    ``(labels, area, sieved, table)``.  ``labels`` / ``area`` / ``sieved``: ``False`` (not wanted), ``None`` (a new
+    array), a numpy array view ``(B, h, w)`` or a device pointer with the element strides ``strides[name]`` (default
+    band-planar).  ``table``: ``False`` / ``None`` (none), a number of records per band (a new ``(B, cap)`` array of
+    ``regions.REC``), such an array, or ``(device pointer, records per band)``."""
+    from .regions import REC
+
+    B, h, w = shape
+    o = RegionsOpts()
+    vals = [float(v) for v in opts.values]
+    o.nvalues = len(vals)
+    for i, v in enumerate(vals[:16]):
+        o.values[i] = v
+    o.invert, o.by_value = int(bool(opts.invert)), int(bool(opts.by_value))
+    o.connectivity, o.min_size, o.sieve_fill = int(opts.connectivity), int(opts.min_size), float(opts.sieve_fill)
+    strides = strides or {}
+    ret_l = ret_a = ret_s = ret_t = None
+    if labels is not False:
+        o.labels, ret_l = _calc_dst(labels, strides.get("labels"), label_dtype, (B, h, w))
+    if area is not False:
+        o.area, ret_a = _calc_dst(area, strides.get("area"), area_dtype, (B, h, w))
+    if sieved is not False:
+        o.sieved, ret_s = _calc_dst(sieved, strides.get("sieved"), src_dtype, (B, h, w))
+    if table is not None and table is not False:
+        if isinstance(table, tuple):
+            o.table, o.table_cap, o.table_on_device = C.c_void_p(int(table[0])), int(table[1]), 1
+        else:
+            if not isinstance(table, np.ndarray):
+                table = np.zeros((B, max(int(table), 0)), REC) if int(table) >= 0 else int(table)
+            if isinstance(table, np.ndarray):
+                if table.dtype != REC or table.ndim != 2 or table.shape[0] != B or not table.flags.c_contiguous:
+                    raise ValueError(f"table must be a C-contiguous ({B}, cap) array of regions.REC")
+                ret_t = table
+                o.table, o.table_cap = C.c_void_p(table.ctypes.data if table.size else _EMPTY_TABLE.ctypes.data), table.shape[1]
+            else:
+                o.table, o.table_cap = C.c_void_p(_EMPTY_TABLE.ctypes.data), table  # (a negative cap: the library refuses)
+    return o, ret_l, ret_a, ret_s, ret_t
+
+
+_EMPTY_TABLE = np.zeros(24, np.uint8)  # what a table of no records points at: the pointer says "wanted"
 
 
 def _window_ref(w):
@@ -1484,6 +1572,57 @@ class Context:
         ms = (C.c_float * 2)()
         _check(load().fra_proximity_timing(ms))
         return float(ms[0]), float(ms[1])
+
+    def regions(self, src, opts=None, label_dtype="int32", area_dtype="uint32", labels=None, area=False, sieved=False,
+                table=None, *, dtype=None, shape=None, strides=None, out_strides=None):
+        """Connected components, their areas and the sieve over a raster on this context's GPU (``fra_regions``, the
+        rule of ``flac_raster.regions.regions_arrays``): ``(labels, area, sieved, table, counts)``.
+
+        ``src``: as :meth:`stats`.  ``opts``: a ``regions.Options``.  ``labels`` / ``area`` / ``sieved``: ``None`` (a new
+        array is returned), ``False`` (not wanted), a numpy array view ``(B, h, w)`` -- of ``label_dtype``, ``area_dtype``
+        and the source's dtype -- whose elements between the outputs keep their values, or a device pointer with the
+        element strides ``out_strides[name]`` (default band-planar).  ``table``: ``None`` (none), a number of records
+        per band, a ``(B, cap)`` array of ``regions.REC`` or ``(device pointer, cap)``.  ``counts``: ``(B, 4)``:
+        foreground pixels, components, kept components N, their pixels.  A band whose N does not fit ``label_dtype`` or
+        the table raises :class:`RegionsNoSpace` with the complete ``counts`` as ``.counts``; nothing has been
+        written then."""
+        from .regions import Options
+
+        job = RegionsJob()
+        dt, (B, h, w), st = _raster_source(job, src, dtype, shape, strides)
+        job.band_stride, job.row_stride, job.col_stride = st
+        job.opts, ret_l, ret_a, ret_s, ret_t = regions_opts(opts or Options(), dt, (B, h, w), labels, area, sieved, table,
+                                                            label_dtype, area_dtype, out_strides)
+        counts = np.zeros((max(B, 0), 4), np.uint64)
+        _check_regions(load().fra_regions(self.h, C.byref(job), counts.ctypes.data_as(C.POINTER(C.c_uint64))), counts)
+        return ret_l, ret_a, ret_s, ret_t, counts
+
+    def decode_device_regions(self, data, items, dst_dtype, channels: int, roi, opts=None, label_dtype="int32",
+                              area_dtype="uint32", labels=None, area=False, sieved=False, table=None, *,
+                              denorm: int = DENORM_NONE, out_strides=None):
+        """:meth:`regions` over ``roi`` of the tile streams (``fra_decode_device_regions``): the decoded region never
+        leaves the GPU.  ``data``, ``items``, ``roi``, ``denorm`` as :meth:`decode_device_window`; the items must cover
+        ``roi``.  Returns ``(labels, area, sieved, table, counts, infos)``."""
+        from .regions import Options
+
+        if roi is None:
+            raise ValueError("roi is required")
+        B = int(channels)
+        o, ret_l, ret_a, ret_s, ret_t = regions_opts(opts or Options(), np.dtype(dst_dtype), (B, int(roi[2]), int(roi[3])),
+                                                     labels, area, sieved, table, label_dtype, area_dtype, out_strides)
+        counts = np.zeros((max(B, 0), 4), np.uint64)
+        job, infos, keep = self._decode_job(data, items, None, np.dtype(dst_dtype), denorm, channels, (0, 0, 0))
+        rc = load().fra_decode_device_regions(self.h, C.byref(job), _window_ref(roi), C.byref(o), infos,
+                                              counts.ctypes.data_as(C.POINTER(C.c_uint64)))
+        del keep
+        _check_regions(rc, counts)
+        return ret_l, ret_a, ret_s, ret_t, counts, list(infos)[: job.nitems]
+
+    def regions_timing(self) -> Tuple[float, float, float, float]:
+        """HIP-event ms of the four phases (links, tiles, seams, the rest) of this thread's last regions call."""
+        ms = (C.c_float * 4)()
+        _check(load().fra_regions_timing(ms))
+        return tuple(float(v) for v in ms)
 
     def decode_timing(self) -> List[float]:
         """HIP-event ms of this thread's last ``decode_device`` / ``decode_device_window``: parse, restore, scatter,

@@ -445,14 +445,22 @@ def zonal(
     nodata: Optional[float] = typer.Option(None, "--nodata", help="Nodata value (default: a source TIFF's own tag)"),
     ignore: Optional[int] = typer.Option(None, "--ignore", help="Zone label to leave out (default: the zones TIFF's "
                                          "nodata tag)"),
+    zones_regions: bool = typer.Option(False, "--zones-regions", help="The zones are the connected components of --zones, "
+                                       "a single-band raster on the same grid (a streaming FLAC file or a GeoTIFF)"),
+    connectivity: int = typer.Option(4, "--connectivity", help="With --zones-regions: 4 or 8"),
+    min_size: int = typer.Option(1, "--min-size", help="With --zones-regions: drop components of fewer pixels"),
+    values: Optional[str] = typer.Option(None, "--values", help="With --zones-regions: the foreground values, e.g. '1,2' "
+                                         "(default: every pixel that is non-zero and not NaN)"),
+    invert: bool = typer.Option(False, "--invert", help="With --zones-regions: swap foreground and background"),
+    by_value: bool = typer.Option(False, "--by-value", help="With --zones-regions: link only neighbours of equal value"),
     semantics: str = typer.Option("pcm16", "--semantics", help="Container pixels: pcm16 (what convert back gives) or int"),
     export: Optional[Path] = typer.Option(None, "--export", "-e", help="Export the full report to .json or .csv"),
     cpu: bool = typer.Option(False, "--cpu", help="Decode and reduce on the host (numpy)"),
     device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
 ):
-    """Per-zone band statistics of a streaming FLAC file or a GeoTIFF over the zones of a GeoTIFF or the polygons of a
-    GeoJSON file."""
-    from .streaming import zonal_with_polygons, zonal_with_tiff
+    """Per-zone band statistics of a streaming FLAC file or a GeoTIFF over the zones of a GeoTIFF, the polygons of a
+    GeoJSON file or the connected components of a mask."""
+    from .streaming import zonal_of_regions, zonal_with_polygons, zonal_with_tiff
     from .zonal import display_zonal_table, export_report
 
     with _failing("Zonal statistics failed"):
@@ -463,7 +471,17 @@ def zonal(
             console.print("[red]Error: --export takes a .json or a .csv file[/red]")
             raise typer.Exit(1)
         dev = _pick_device(device, cpu)
-        if zones.suffix.lower() in (".geojson", ".json"):
+        if zones_regions:
+            from .regions import Options as RegionOptions
+
+            if ignore is not None or attribute is not None:
+                console.print("[red]Error: --ignore and --attribute do not go with --zones-regions[/red]")
+                raise typer.Exit(1)
+            ropts = RegionOptions(_float_list(values), invert, by_value, connectivity, min_size)
+            report, got, _, rcounts = zonal_of_regions(path, zones, ropts, window=win, bbox=box, nodata=nodata, device=dev,
+                                                       semantics=semantics)
+            console.print(f"zones: {int(rcounts[0, 2])} components of {zones.name} ({int(rcounts[0, 1])} before the sieve)")
+        elif zones.suffix.lower() in (".geojson", ".json"):
             if ignore is not None:
                 console.print("[red]Error: --ignore goes with a zones GeoTIFF: polygons leave the pixels outside them "
                               "out already[/red]")
@@ -569,6 +587,89 @@ def proximity(
         console.print(f"[green]{output_path}[/green]: {odt}, rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
                       f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
         console.print(f"targets: {int(counts[0])}; within reach: {100.0 * int(counts[1]) / max(1, n):.2f}% of the pixels")
+
+
+def _float_list(values: Optional[str]):
+    return tuple(float(x.strip()) for x in values.split(",")) if values else ()
+
+
+def _print_region_counts(counts):
+    for b, (fg, ncomp, kept, px) in enumerate(counts.tolist()):
+        console.print(f"band {b + 1}: {fg} foreground pixels, {ncomp} components, {kept} kept with {px} pixels")
+
+
+@app.command()
+def regions(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF of the labels (nodata 0)"),
+    values: Optional[str] = typer.Option(None, "--values", help="Foreground pixel values, e.g. '1,2' (default: every "
+                                         "pixel that is non-zero and not NaN)"),
+    invert: bool = typer.Option(False, "--invert", help="Swap foreground and background (a NaN stays background)"),
+    by_value: bool = typer.Option(False, "--by-value", help="Link only neighbours of equal value: regions of one class"),
+    connectivity: int = typer.Option(4, "--connectivity", help="4 or 8"),
+    min_size: int = typer.Option(1, "--min-size", help="Drop components of fewer pixels"),
+    area: Optional[Path] = typer.Option(None, "--area", help="Also write every pixel's component area to this GeoTIFF"),
+    export: Optional[Path] = typer.Option(None, "--export", "-e", help="Export a row per band and component (label, "
+                                          "value, area, box, first pixel) to .json or .csv"),
+    dtype: str = typer.Option("int32", "--dtype", help="Dtype of the labels: uint8, int8, uint16, int16, uint32 or int32"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width' "
+                                         "(a component is cut at the window's edge)"),
+    semantics: str = typer.Option("pcm16", "--semantics", help="Container pixels: pcm16 (what convert back gives) or int"),
+    cpu: bool = typer.Option(False, "--cpu", help="Label with numpy on the host"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Connected components of a streaming FLAC file or a GeoTIFF -> a GeoTIFF of labels, numbered in the order of the
+    components' first pixels."""
+    from .regions import Options
+    from .streaming import regions_to_tiff
+
+    with _failing("Regions failed"):
+        win, box = _request_window(bbox, pixels)
+        path = _local(file_path)
+        _existing(path)
+        if export is not None and export.suffix.lower() not in (".json", ".csv"):
+            console.print("[red]Error: --export takes a .json or a .csv file[/red]")
+            raise typer.Exit(1)
+        dev = _pick_device(device, cpu)
+        opts = Options(_float_list(values), invert, by_value, connectivity, min_size)
+        got, counts = regions_to_tiff(path, output_path, opts, window=win, bbox=box, label_dtype=dtype, area_path=area,
+                                      export_path=export, device=dev, semantics=semantics)
+        console.print(f"[green]{output_path}[/green]: {dtype}, rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
+                      f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
+        _print_region_counts(counts)
+
+
+@app.command()
+def sieve(
+    file_path: str = typer.Argument(..., help="Streaming FLAC file or GeoTIFF"),
+    output_path: Path = typer.Option(..., "--output", "-o", help="Output GeoTIFF: the source without its small components"),
+    min_size: int = typer.Option(..., "--min-size", help="Components of fewer pixels are replaced by --fill"),
+    connectivity: int = typer.Option(4, "--connectivity", help="4 or 8"),
+    any_value: bool = typer.Option(False, "--any-value", help="Link neighbouring foreground pixels whatever their values "
+                                   "(default: only equal values, regions of one class)"),
+    values: Optional[str] = typer.Option(None, "--values", help="Foreground pixel values (default: non-zero, not NaN)"),
+    invert: bool = typer.Option(False, "--invert", help="Swap foreground and background"),
+    fill: float = typer.Option(0.0, "--fill", help="What the pixels of removed components get; the output's nodata tag"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="This bounding box only: 'xmin,ymin,xmax,ymax'"),
+    pixels: Optional[str] = typer.Option(None, "--window", "-w", help="This pixel window only: 'row,col,height,width'"),
+    semantics: str = typer.Option("pcm16", "--semantics", help="Container pixels: pcm16 (what convert back gives) or int"),
+    cpu: bool = typer.Option(False, "--cpu", help="Label with numpy on the host"),
+    device: Optional[int] = typer.Option(None, "--device", help="GPU id (default: 0 when a GPU is present)"),
+):
+    """Remove the connected components of fewer than --min-size pixels (filled, not merged into a neighbour)."""
+    from .streaming import sieve_to_tiff
+
+    with _failing("Sieve failed"):
+        win, box = _request_window(bbox, pixels)
+        path = _local(file_path)
+        _existing(path)
+        dev = _pick_device(device, cpu)
+        got, counts = sieve_to_tiff(path, output_path, min_size, connectivity, not any_value, _float_list(values), invert,
+                                    fill, window=win, bbox=box, device=dev, semantics=semantics)
+        console.print(f"[green]{output_path}[/green]: rows {got[0]}..{got[0] + got[2]}, columns {got[1]}.."
+                      f"{got[1] + got[3]}" + (f" (GPU {dev})" if dev is not None else " (host)"))
+        _print_region_counts(counts)
 
 
 @app.command()

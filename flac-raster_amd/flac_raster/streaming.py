@@ -955,6 +955,182 @@ def proximity_of_polygons_to_tiff(source, geojson, tiff_path: Path, attribute: O
     return win, counts
 
 
+# ------------------------------------------------------------------------------------------ regions
+_TABLE_GUESS = 4096  # records per band the first GPU call has room for; the library says how many it takes
+
+
+def _regions_on_device(ctx, reg, opts, label_dtype, area_dtype, labels, area, sieved, want_table, out_strides=None):
+    """One regions call over a region on a GPU, repeated once with the table the library asked for ->
+    ``(labels, area, sieved, tables or None, counts)``."""
+    from . import _native
+
+    def call(cap):
+        kw = dict(label_dtype=label_dtype, area_dtype=area_dtype, labels=labels, area=area, sieved=sieved,
+                  table=cap if want_table else None, out_strides=out_strides)
+        if reg.encoded:
+            return ctx.decode_device_regions(*reg.decode_args(), opts, denorm=reg.denorm, **kw)[:5]
+        return ctx.regions(reg.host(), opts, **kw)
+
+    try:
+        got = call(_TABLE_GUESS)
+    except _native.RegionsNoSpace as e:
+        n = int(e.counts[:, 2].max())
+        if not want_table or n <= _TABLE_GUESS:
+            raise  # the labels dtype is what does not hold them
+        got = call(n)
+    lab, ar, sv, table, counts = got
+    tables = None if table is None else [table[b, :int(counts[b, 2])].copy() for b in range(table.shape[0])]
+    return lab, ar, sv, tables, counts
+
+
+def _regions(s, opts, window, bbox, label_dtype, area_dtype, want_area, want_sieved, device, semantics=None):
+    """Regions over a source -> ``(labels, area or None, sieved or None, tables, counts, window)``."""
+    from . import _native
+    from .regions import Options, check_label_dtype, regions_arrays, validate
+
+    opts = opts or Options()
+    validate(opts)
+    ldt = check_label_dtype(label_dtype)
+    win = s.window(window, bbox)
+    reg = s.region(win, semantics)
+    if device is None:
+        lab, ar, sv, tables, counts = regions_arrays(reg.host(), opts, ldt, area_dtype if want_area else None)
+        return lab, ar, sv if want_sieved else None, tables, counts, win
+    ctx = _native.default_context(int(device))
+    return _regions_on_device(ctx, reg, opts, ldt, area_dtype, None, None if want_area else False,
+                              None if want_sieved else False, True) + (win,)
+
+
+def regions_window(src, opts=None, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                   label_dtype="int32", area_dtype="uint32", want_area: bool = False, want_sieved: bool = False,
+                   device: Optional[int] = None, semantics: str = "pcm16"):
+    """The connected components of a streaming container (path or bytes), or of a window of it -> ``(labels (B, h, w),
+    area or None, sieved or None, tables (a list of B arrays of regions.REC), counts (B, 4), window, index)``:
+    ``regions.regions_arrays(read_window(src, ...)[0], opts)``.  A window of a raster labels the window: a component is
+    cut at its edge.  ``device=None`` reads the window on the host and applies the numpy rule; an integer makes one
+    ``fra_decode_device_regions`` call on that GPU -- the decoded pixels never leave the device -- and a second one when
+    a band has more components than the first table holds."""
+    s = ContainerSource(src)
+    return _regions(s, opts, window, bbox, label_dtype, area_dtype, want_area, want_sieved, device, semantics) + (s.meta,)
+
+
+def regions_tiff(path: Path, opts=None, window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                 label_dtype="int32", area_dtype="uint32", want_area: bool = False, want_sieved: bool = False,
+                 device: Optional[int] = None):
+    """:func:`regions_window` for a GeoTIFF source (``fra_regions`` on a GPU); the last element is its info."""
+    s = TiffSource(path)
+    return _regions(s, opts, window, bbox, label_dtype, area_dtype, want_area, want_sieved, device) + (s.meta,)
+
+
+def export_components(path: Path, rows: List[dict]):
+    """The rows of ``regions.export_rows`` as JSON (``.json``) or CSV (anything else)."""
+    path = Path(path)
+    if path.suffix.lower() == ".json":
+        path.write_text(json.dumps({"components": rows}, indent=1))
+        return
+    import csv
+
+    with open(path, "w", newline="") as f:
+        wr = csv.DictWriter(f, fieldnames=list(rows[0].keys()) if rows else ["band", "label"])
+        wr.writeheader()
+        wr.writerows(rows)
+
+
+def regions_to_tiff(path: Path, tiff_path: Path, opts=None, window: Optional[Sequence[int]] = None,
+                    bbox: Optional[Sequence[float]] = None, label_dtype="int32", area_path: Optional[Path] = None,
+                    sieved_path: Optional[Path] = None, export_path: Optional[Path] = None, area_dtype="uint32",
+                    device: Optional[int] = None, semantics: str = "pcm16"):
+    """Regions over a streaming container or a GeoTIFF (told apart by their first bytes) -> a GeoTIFF of the labels on
+    the window's grid with nodata 0; ``area_path``: a GeoTIFF of the areas (nodata 0); ``sieved_path``: the source with
+    the removed components filled (``sieve_fill`` as its nodata tag); ``export_path``: a ``.json`` or ``.csv`` with a row
+    per band and component (``regions.export_rows``).  Returns ``(window, counts)``."""
+    from .regions import Options, export_rows
+
+    opts = opts or Options()
+    s = open_source(Path(path))
+    # a kept component's pixels keep the source's bits in `sieved`: the export takes the components' values from it
+    want_sieved = sieved_path is not None or export_path is not None
+    lab, ar, sv, tables, counts, win = _regions(s, opts, window, bbox, label_dtype, area_dtype, area_path is not None,
+                                                want_sieved, device, semantics)
+    _to_tiff(tiff_path, lab, s, win, nodata=0)
+    if area_path is not None:
+        _to_tiff(area_path, ar, s, win, nodata=0)
+    if sieved_path is not None:
+        _to_tiff(sieved_path, sv, s, win, nodata=_fill_tag(opts.sieve_fill, sv.dtype))
+    if export_path is not None:
+        export_components(export_path, export_rows(sv, tables, s.window_transform(win)))
+    return win, counts
+
+
+def sieve_to_tiff(path: Path, tiff_path: Path, min_size: int, connectivity: int = 4, by_value: bool = True,
+                  values: Sequence[float] = (), invert: bool = False, fill: float = 0.0,
+                  window: Optional[Sequence[int]] = None, bbox: Optional[Sequence[float]] = None,
+                  device: Optional[int] = None, semantics: str = "pcm16"):
+    """The source with every component of fewer than ``min_size`` pixels replaced by ``fill`` -> a GeoTIFF with ``fill`` as
+    its nodata tag.  Components are regions of one value by default (``by_value``), as ``gdal_sieve`` sees them; the
+    removed ones are filled and not merged into a neighbour.  Returns ``(window, counts)``."""
+    from .regions import Options
+
+    opts = Options(tuple(values), invert, by_value, connectivity, min_size, fill)
+    s = open_source(Path(path))
+    _, _, sv, _, counts, win = _regions(s, opts, window, bbox, "int32", "uint32", False, True, device, semantics)
+    _to_tiff(tiff_path, sv, s, win, nodata=_fill_tag(fill, sv.dtype))
+    return win, counts
+
+
+def zonal_of_regions(source, mask_source, opts=None, window: Optional[Sequence[int]] = None,
+                     bbox: Optional[Sequence[float]] = None, nodata: Optional[float] = None,
+                     device: Optional[int] = None, semantics: str = "pcm16"):
+    """Zonal statistics of ``source`` over the connected components of ``mask_source``, a single-band raster on the same
+    grid (each a streaming container or a GeoTIFF) -> ``(report, window, index or info of the source, counts of the
+    components)``.  Component ``i`` of the window is zone ``i``.
+
+    ``device=None``: ``zonal.zonal_arrays`` over the labels of ``regions.regions_arrays``.  On a GPU the labels are born
+    in a device buffer that goes to ``fra_decode_device_zonal`` / ``fra_zonal`` as it is: the label raster never visits
+    the host.  More than 65536 kept components are refused: raise ``min_size``."""
+    from . import _native
+    from .regions import MAX_ZONES, Options, regions_arrays, validate
+    from .zonal import report_from_recs, zonal_arrays
+
+    opts = opts or Options()
+    validate(opts)
+    s, m = open_source(source), open_source(mask_source)
+    if m.bands != 1:
+        raise ValueError(f"the mask must be a single-band raster, it has {m.bands} bands")
+    if (m.height, m.width) != (s.height, s.width):
+        raise ValueError(f"the mask is {(m.height, m.width)}, the source is {(s.height, s.width)}")
+    win = s.window(window, bbox)
+    nodata = _nodata(s, nodata)
+    reg, mreg = s.region(win, semantics), m.region(win, semantics)
+    h, w = win[2], win[3]
+
+    def check(n):
+        if n > MAX_ZONES:
+            raise ValueError(f"{n} components are more than the {MAX_ZONES} zones of one call: drop the small ones with "
+                             f"min_size (it is {opts.min_size})")
+        return max(n, 1)
+
+    if device is None:
+        lab, _, _, _, counts = regions_arrays(mreg.host(), opts, np.int32, None)
+        nzones = check(int(counts[0, 2]))
+        return zonal_arrays(reg.host(), lab[0], 1, nzones, nodata=nodata, ignore=0), win, s.meta, counts
+    ctx = _native.default_context(int(device))
+    zdt = np.dtype(np.int32)
+    d_zones = ctx.alloc(h * w * zdt.itemsize)
+    try:
+        counts = _regions_on_device(ctx, mreg, opts, zdt, "uint32", d_zones, False, False, False)[4]
+        nzones = check(int(counts[0, 2]))
+        if reg.encoded:
+            data, items, dt, B, _ = reg.decode_args()
+            recs, outside, _ = ctx.decode_device_zonal(data, items, d_zones, dt, B, win, reg.denorm, 1, nzones, nodata, 0,
+                                                       zone_dtype=zdt, zone_strides=(w, 1))
+        else:
+            recs, outside = ctx.zonal(reg.host(), d_zones, 1, nzones, nodata, 0, zone_dtype=zdt, zone_strides=(w, 1))
+    finally:
+        ctx.free(d_zones)
+    return report_from_recs(recs, outside, s.dtype, 1), win, s.meta, counts
+
+
 # ------------------------------------------------------------------------------------------ band math
 def _calc_fill(fill, out_dtype):
     from .calc import default_fill

@@ -1091,6 +1091,95 @@ FRA_API int fra_decode_device_proximity(fra_ctx *ctx, const fra_decode_job *job,
  * summed over the bands */
 FRA_API int fra_proximity_timing(float ms[2]);
 
+/* Regions: the connected components of a raster's foreground, their areas and boxes, and a sieve that removes the small
+ * ones -- "how many water bodies, how big, where", "drop the specks below 20 pixels", "a zone per field".
+ * flac_raster/regions.py restates the rule in numpy (regions_direct: a flood fill; regions_arrays: run-based union-find).
+ * Everything is integer work, so the GPU result equals the rule byte for byte, and is the same from run to run.
+ *   Region: a (channels, h, w) raster of any fra_dtype, 1 <= h, w <= 32768 (every pixel index and every area is below
+ *     2^31).  Each band is handled on its own.  Pixels outside the region do not exist: a component is cut at the
+ *     region's edge, so a window of a raster labels the window.  There is no output window.
+ *   Foreground: the targets of the proximity rule (above): with nvalues == 0 a pixel whose value is non-zero and not NaN,
+ *     with 1 <= nvalues <= 16 one with (double)v == values[i] for some i.  invert (0 / 1) swaps foreground and
+ *     background after that test; a NaN stays background.  values = {nodata}, invert = 1 is "everything but nodata".
+ *   Links: connectivity is 4 (W, E, N, S) or 8 (the diagonals too).  Two neighbouring foreground pixels are linked when
+ *     by_value == 0; with by_value == 1 only if their values are also equal under == in the source dtype (-0.0 == 0.0).
+ *     A component is a class of the transitive closure of the links.
+ *   First pixel, area, box: a component's first pixel is its pixel with the smallest r * w + c; its area is its pixel
+ *     count; its box is the minimum and maximum of its rows and of its columns.
+ *   Sieve: min_size >= 1.  A component is kept when area >= min_size and removed otherwise (1 keeps everything).
+ *   Numbering: the kept components of a band are numbered 1 .. N in the order of their first pixels.  Background pixels
+ *     and the pixels of removed components have label 0.
+ *   Outputs, each optional (dst == NULL: not wanted), at least one of the three rasters or the table:
+ *     labels (an integer fra_dtype): the number of the pixel's kept component, 0 elsewhere;
+ *     area (any fra_dtype): the area of the pixel's kept component, 0 elsewhere, converted as the band math converts a
+ *       result (Output, above);
+ *     sieved (the source's dtype; sieved.dtype is ignored): the source bits, except that the pixels of removed components
+ *       get sieve_fill, converted as the proximity rule converts its fills;
+ *     table: table_cap records per band, in host memory or (table_on_device) device memory; record i - 1 of a band
+ *       describes its kept component i.  The value of a component is the source at `first`.
+ *   counts[4 * band + k]: k = 0 the foreground pixels, 1 the components before the sieve, 2 the kept components N, 3 the
+ *     pixels of kept components.
+ *   Refused after the counts are known, FRA_E_SPACE: N of some band exceeds the maximum of the labels dtype, or
+ *     table_cap.  The message names the band, N and the limit; counts is complete and no element of any output has been
+ *     written.
+ * Four phases (fra_regions.hip): k_reg_links turns the source into one byte per pixel (foreground and the links towards
+ * W, N, NW, NE) -- every later kernel reads only these; k_reg_tile labels tiles of 64 x 64 pixels by union-find in LDS
+ * and writes every pixel's parent as a pixel index; k_reg_seam unites across the tile borders on that array with
+ * atomicMin; then every pixel finds its root (the component's first pixel), the roots are numbered in raster order by
+ * a prefix sum, areas and boxes are accumulated with integer atomics (merged per thread run and per workgroup first),
+ * the kept components are numbered by a second prefix sum and a last pass writes the outputs.  No kernel waits for
+ * another workgroup. */
+typedef struct {
+  uint32_t first;                           /* r * w + c of the component's first pixel */
+  uint32_t area;
+  int32_t rmin, cmin, rmax, cmax;
+} fra_region_rec;                           /* 24 bytes */
+typedef struct {
+  int32_t nvalues;                          /* 0 .. 16 */
+  int32_t invert, by_value;                 /* 0 / 1 (non-zero: 1) */
+  int32_t connectivity;                     /* 4 or 8 */
+  int32_t min_size;                         /* >= 1 */
+  int32_t table_cap;                        /* records per band that `table` holds, >= 0 */
+  int32_t table_on_device, reserved;
+  double values[16];
+  double sieve_fill;
+  fra_region_rec *table;                    /* channels x table_cap records; NULL: none */
+  fra_calc_dst labels;                      /* (channels, h, w) of labels.dtype, an integer one; dst NULL: none */
+  fra_calc_dst area;                        /* (channels, h, w) of area.dtype; dst NULL: none */
+  fra_calc_dst sieved;                      /* (channels, h, w) of the source's dtype; dst NULL: none */
+} fra_regions_opts;                         /* 296 bytes */
+typedef struct {
+  const void *src; int32_t src_on_device;   /* element (band 0, row 0, col 0); host memory is copied to the device */
+  int32_t dtype;                            /* fra_dtype of the source */
+  int32_t channels, height, width;          /* channels 1 .. 255; height, width 1 .. 32768 */
+  int64_t band_stride, row_stride, col_stride;  /* elements, >= 0 */
+  fra_regions_opts opts;
+} fra_regions_job;
+/* Over a host or device raster of any layout into host or device rasters of any layout.  Synchronous.  Host buffers are
+ * staged as fra_proximity stages them (the elements of an output that are not outputs keep the caller's values; a host
+ * table is written record by record up to N per band).  The scratch -- one band at a time: a link byte and a 4-byte
+ * parent per pixel, and 28 bytes per component before the sieve -- is per call and released on every path.  With more
+ * than one band and a possible FRA_E_SPACE (a table, or a labels dtype narrower than 31 bits) every band is counted
+ * before any is written, so the bands are labelled twice.  counts (host memory, 4 words per band) may be NULL.
+ * FRA_E_INVALID, before any GPU work and in this order: a null argument (ctx, job, src); a bad source dtype or layout
+ * (more than 255 bands); a labels dtype that is not an integer one; a bad dtype or a negative stride of an output that
+ * is given; height or width outside 1 .. 32768; nvalues outside 0 .. 16 or a value that is not finite; a connectivity
+ * other than 4 or 8; min_size < 1; table_cap < 0; no output given. */
+FRA_API int fra_regions(fra_ctx *ctx, const fra_regions_job *job, uint64_t *counts /* 4 per band, may be NULL */);
+/* The same over what fra_decode_device_window would have written for `roi`, in job->dst_dtype: roi is the region,
+ * job->dst and the job's strides are ignored, and the decoded region never leaves the device.  Every refusal and message
+ * of the windowed read is this call's as well; items that do not cover roi are refused as by fra_decode_device_compare;
+ * the options and outputs as by fra_regions.  Afterwards fra_decode_device_timing reports the inner windowed read and
+ * fra_regions_timing the labelling. */
+FRA_API int fra_decode_device_regions(fra_ctx *ctx, const fra_decode_job *job, const fra_window *roi,
+                                      const fra_regions_opts *opts, fra_decoded *infos /* nitems */,
+                                      uint64_t *counts /* 4 per band, may be NULL */);
+/* HIP-event times (ms) of the calling thread's last regions call, each summed over the bands and over both rounds when
+ * the bands are labelled twice: ms[0] the links, ms[1] the tile labelling, ms[2] the seams, ms[3] the kernels after them
+ * (flatten, count, number, write; the waits for the two counts the host reads back lie between its three stretches of
+ * kernels and are not in it). */
+FRA_API int fra_regions_timing(float ms[4]);
+
 /* Verify (libFLAC's verify mode for a plan): after an execute (or fra_plan_encode_host / _progress / _ring) has
  * completed, decode the plan's own frames on its GPU through its frame offsets -- k_dec_parse with every CRC-16,
  * k_dec_restore -- and compare every decoded sample with the plan's current raster (the caller's device raster, or the

@@ -142,6 +142,14 @@ centre equals ``proximity.proximity_arrays`` wherever the nearest target lies wi
 
     python tools/bench_decode.py --proximity blocks:256 --proximity single --proximity random:0.01 --proximity all --proximity none --steps 5 --warmup 2
 
+``--regions KIND`` times the regions unit (``fra_regions``) over the scene's grid, from a device-resident uint16 mask
+into device-resident uint32 labels: ``none``, ``all``, ``blocks:N``, ``checker``, ``random:P[:4|8]`` or ``spiral``.  Per
+kind: the four phase times (``fra_regions_timing``: links, tiles, seams, and everything after them), their sum against
+the floor of 16 bytes per pixel and against a one-band ``k_calc`` copy uint16 -> uint16 of the same run.  The counts are
+checked where the kind fixes them, the labels against the mask, and a corner crop against ``regions.regions_arrays``.
+
+    python tools/bench_decode.py --regions none --regions all --regions blocks:256 --regions checker --regions random:0.59:4 --regions spiral --steps 5 --warmup 2
+
 ``--zonal PATTERN`` times the zonal statistics of the same container (``fra_decode_device_zonal``: the whole raster
 decoded to uint16 and reduced per zone there, only the records come back) over a uint16 zone raster synthesised on the
 host and resident on the device: ``blocks:N`` (squares of N x N pixels, ``blocks:256`` = 43 x 43 = 1849 zones),
@@ -329,6 +337,106 @@ def proximity_over_grid(ctx, args):
     ctx.free(d_dist)
 
 
+def regions_source(kind, arg):
+    """The uint16 mask of a ``--regions`` kind over the scene's grid, and what its counts must be (``None``: unknown)."""
+    a = np.zeros((H, W), np.uint16)
+    expect = None
+    if kind == "all":
+        a[:] = 1
+        expect = [H * W, 1, 1, H * W]
+    elif kind == "blocks":
+        n = int(arg or 256)
+        a[:] = 1
+        a[n - 1::n, :] = 0
+        a[:, n - 1::n] = 0
+        fg = int(a.sum())
+        ncomp = ((H + n - 1) // n) * ((W + n - 1) // n) if n > 1 else 0
+        expect = [fg, ncomp, ncomp, fg]
+    elif kind == "checker":
+        a[:] = (np.add.outer(np.arange(H), np.arange(W)) % 2) == 0
+        fg = int(a.sum())
+        expect = [fg, fg, fg, fg]
+    elif kind == "random":
+        a[:] = np.random.default_rng(SEED).random((H, W)) < float(arg or 0.59)
+    elif kind == "spiral":  # one 4-connected path of one pixel's width: the frames at every second inset, each cut
+        k = 0               # below its top left corner and joined to the next one
+        while k < min(H, W) - k:
+            a[k, k:W - k] = a[H - 1 - k, k:W - k] = 1
+            a[k:H - k, k] = a[k:H - k, W - 1 - k] = 1
+            if k + 2 < min(H, W) - k - 2:
+                a[k + 1, k] = 0
+                a[k + 2, k + 1] = 1
+            k += 2
+        fg = int(a.sum())
+        expect = [fg, 1, 1, fg]
+    elif kind == "none":
+        expect = [0, 0, 0, 0]
+    else:
+        raise SystemExit("--regions takes none, all, blocks:N, checker, random:P[:4|8] or spiral")
+    return a, expect
+
+
+def regions_over_grid(ctx, args):
+    """``--regions``: the four phases of ``fra_regions`` per kind -- a resident uint16 mask into resident uint32 labels --
+    against the floor of 16 bytes per pixel (the source read, the link byte written and read, the parent written and
+    read, the labels written) and against a one-band ``k_calc`` copy uint16 -> uint16 of the same run."""
+    from flac_raster.calc import compile_exprs
+    from flac_raster.regions import Options, regions_arrays
+
+    med = statistics.median
+    d_src, d_lab, d_copy = ctx.alloc(H * W * 2), ctx.alloc(H * W * 4), ctx.alloc(H * W * 2)
+    copy = compile_exprs(["b1"], 1)
+    res = {"workload": f"regions over the C4-like grid {W}x{H}: uint16 mask and uint32 labels resident on the device",
+           "steps": args.steps, "warmup": args.warmup, "floor_bytes_per_pixel": 16, "legs": []}
+    kcopy = []
+    for spec in args.regions:
+        parts = spec.split(":")
+        kind = parts[0]
+        arg = parts[1] if len(parts) > 1 else None
+        conn = int(parts[2]) if len(parts) > 2 else 4
+        opts = Options(connectivity=conn)
+        src, expect = regions_source(kind, arg)
+        ctx.h2d(d_src, src)
+        if not kcopy:
+            for s in range(args.warmup + args.steps):
+                ctx.calc(d_src, copy, np.uint16, d_copy, dtype=np.uint16, shape=(1, H, W))
+                if s >= args.warmup:
+                    kcopy.append(ctx.calc_timing())
+            res["k_calc_copy_uint16_to_uint16_ms"] = round(med(kcopy), 4)
+        wall, phases = [], []
+        for s in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            counts = ctx.regions(d_src, opts, np.uint32, labels=d_lab, dtype=np.uint16, shape=(1, H, W))[4]
+            t1 = time.perf_counter()
+            if s >= args.warmup:
+                wall.append((t1 - t0) * 1e3), phases.append(ctx.regions_timing())
+        got = counts[0].tolist()
+        if expect is not None and got != expect:
+            raise SystemExit(f"regions {spec}: counts {got}, expected {expect}")
+        lab = np.empty((H, W), np.uint32)
+        ctx.d2h(lab, d_lab)
+        if not np.array_equal(lab > 0, src > 0) or int(lab.max()) != got[2] or got[3] != got[0]:
+            raise SystemExit(f"regions {spec}: the labels do not cover the mask with 1 .. N")
+        # a corner crop: the rule's components of the crop are pieces of the grid's, so each lies in exactly one label
+        crop = 512
+        piece = regions_arrays(src[None, :crop, :crop], opts, np.int32, None)[0][0]
+        pairs = np.unique(np.stack([piece[piece > 0], lab[:crop, :crop][piece > 0].astype(np.int64)], axis=1), axis=0)
+        if pairs.shape[0] != int(piece.max()):
+            raise SystemExit(f"regions {spec}: a component of the corner crop is split over several labels")
+        ph = [med([p[k] for p in phases]) for k in range(4)]
+        total = sum(ph)
+        worst = max(range(4), key=lambda k: ph[k])
+        res["legs"].append({
+            "regions": spec, "connectivity": conn, "counts": got,
+            "links_ms": round(ph[0], 4), "tiles_ms": round(ph[1], 4), "seams_ms": round(ph[2], 4), "rest_ms": round(ph[3], 4),
+            "total_ms": round(total, 4), "wall_ms": round(med(wall), 3), "floor_gb_per_s": round(16 * H * W / total / 1e6, 1),
+            "total_over_calc_copy": round(total / med(kcopy), 2), "longest_phase": ("links", "tiles", "seams", "rest")[worst],
+            "all_ms": [[round(x, 4) for x in p] for p in phases]})
+    print(json.dumps(res), flush=True)
+    for d in (d_src, d_lab, d_copy):
+        ctx.free(d)
+
+
 def warp_map_of(text):
     """The ``warp.Map`` of a ``--warp`` leg over the scene at its own size, and a word about it."""
     import math
@@ -392,6 +500,11 @@ def main():
                     help="time fra_proximity over the scene's grid, a resident uint16 source into a resident float32 dist: "
                          "blocks:N (the outlines of the N x N squares), single (one target pixel), random:P (a share P of "
                          "the pixels), all, none; KIND:...:MAXDIST limits the reach, e.g. blocks:256:64 (repeatable)")
+    ap.add_argument("--regions", action="append", default=None, metavar="KIND",
+                    help="time fra_regions over the scene's grid, a resident uint16 mask into resident uint32 labels: none, "
+                         "all, blocks:N (squares of N x N with a background line between them), checker, random:P[:4|8] (a "
+                         "share P of the pixels, 4- or 8-connected) or spiral (repeatable); the k_calc copy of the same run "
+                         "is timed beside them, so a --calc leg is not needed")
     ap.add_argument("--calc", action="append", default=None, metavar="EXPR",
                     help="time band math over the container against the plain read: one expression per output band, "
                          "separated by ';', optionally followed by ':dtype'; repeat for further legs of the same run")
@@ -423,6 +536,9 @@ def main():
         return
     if args.proximity:
         proximity_over_grid(ctx, args)
+        return
+    if args.regions:
+        regions_over_grid(ctx, args)
         return
     dt = np.dtype(np.uint16)
     dev_raster = ctx.alloc(B * H * W * dt.itemsize)

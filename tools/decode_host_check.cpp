@@ -20,6 +20,8 @@
 //     (inputs that break two rules at once);
 //   * the proximity unit's reach threshold against the f64 predicate at and around perfect squares, the conversion of
 //     its fills and the arithmetic of its launch plan (fra_proximity.h);
+//   * the regions unit's refusals in the header's order (fra_regions, fra_decode_device_regions), its FRA_E_SPACE
+//     decisions and the arithmetic of its tile, seam and scan plan (fra_regions.h);
 //   * the rasterizer's edge table, x-extents and band lists (fra_rasterize.h): closed rings, dropped and oriented
 //     edges, an empty band, a feature spanning all bands, a ring with a repeated closing vertex, and that every
 //     (edge, row) crossing of the rule is in the row's band list, in the edges' order;
@@ -38,6 +40,7 @@
 #include "../flac-raster_amd/csrc/fra_decode_host.h"
 #include "../flac-raster_amd/csrc/fra_scan.h"
 #include "../flac-raster_amd/csrc/fra_proximity.h"
+#include "../flac-raster_amd/csrc/fra_regions.h"
 #include "../flac-raster_amd/csrc/fra_rasterize.h"
 #include "../flac-raster_amd/csrc/fra_warp.h"
 
@@ -1280,6 +1283,131 @@ int main(int argc, char** argv) {
       o.out_row_off = 60; o.out_col_off = 3; o.out_height = 75; o.out_width = 60;
       const fra_px::Plan seam = fra_px::make_plan(200, 70, o);
       EXPECT(seam.nchunks == 4 && seam.k0 == 0 && seam.k1 == 2 && seam.rows_per_wg == 4 && seam.row_wgs == 19 && seam.levels == 6, "proximity: the plan of the seam shape");
+    }
+  }
+  // ... and of the regions unit (fra_regions.hip): refused before any GPU work, in the order the header gives
+  {
+    auto says = [&](int rc, const char* what) { return rc == FRA_E_INVALID && g_msg.find(what) != std::string::npos; };
+    static uint8_t rsrc[3 * 40 * 50];
+    static int32_t rlab[3 * 40 * 50];
+    static float rarea[3 * 40 * 50];
+    static uint8_t rsieved[3 * 40 * 50];
+    static fra_region_rec rtab[3 * 10];
+    uint64_t counts[12];
+    for (uint64_t& v : counts) v = 9;
+    fra_regions_job rj{};
+    rj.src = rsrc; rj.dtype = FRA_U8; rj.channels = 3; rj.height = 40; rj.width = 50;
+    rj.band_stride = 2000; rj.row_stride = 50; rj.col_stride = 1;
+    rj.opts.connectivity = 4; rj.opts.min_size = 1; rj.opts.table = rtab; rj.opts.table_cap = 10;
+    rj.opts.labels.dst = rlab; rj.opts.labels.dtype = FRA_I32; rj.opts.labels.band_stride = 2000; rj.opts.labels.row_stride = 50; rj.opts.labels.col_stride = 1;
+    rj.opts.area.dst = rarea; rj.opts.area.dtype = FRA_F32; rj.opts.area.band_stride = 2000; rj.opts.area.row_stride = 50; rj.opts.area.col_stride = 1;
+    rj.opts.sieved.dst = rsieved; rj.opts.sieved.band_stride = 2000; rj.opts.sieved.row_stride = 50; rj.opts.sieved.col_stride = 1;
+    const fra_region::Strides rss{2000, 50, 1};
+    EXPECT(fra_rg::check_job(FRA_U8, 3, 40, 50, rss, &rj.opts) == FRA_OK, "regions: the sample job is refused: %s", g_msg.c_str());
+    EXPECT(fra_regions(nullptr, &rj, counts) == FRA_E_INVALID, "regions: null ctx accepted");
+    EXPECT(fra_regions(ctx, nullptr, counts) == FRA_E_INVALID, "regions: null job accepted");
+    { auto j = rj; j.src = nullptr; EXPECT(says(fra_regions(ctx, &j, counts), "null argument"), "regions: null src: %s", g_msg.c_str()); }
+    for (int d : {-1, 8}) { auto j = rj; j.dtype = d; EXPECT(says(fra_regions(ctx, &j, counts), "bad dtype"), "regions: dtype %d: %s", d, g_msg.c_str()); }
+    { auto j = rj; j.channels = 0; EXPECT(says(fra_regions(ctx, &j, counts), "bad raster layout"), "regions: no band: %s", g_msg.c_str()); }
+    { auto j = rj; j.channels = 256; EXPECT(says(fra_regions(ctx, &j, counts), "more than 255"), "regions: 256 bands: %s", g_msg.c_str()); }
+    { auto j = rj; j.col_stride = -1; EXPECT(says(fra_regions(ctx, &j, counts), "bad raster layout"), "regions: negative source stride: %s", g_msg.c_str()); }
+    for (int d : {-1, (int)FRA_F32, (int)FRA_F64, 8}) { auto j = rj; j.opts.labels.dtype = d; EXPECT(says(fra_regions(ctx, &j, counts), "bad labels dtype"), "regions: labels dtype %d: %s", d, g_msg.c_str()); }
+    { auto j = rj; j.opts.labels.row_stride = -1; EXPECT(says(fra_regions(ctx, &j, counts), "bad labels layout"), "regions: negative labels stride: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.area.dtype = 8; EXPECT(says(fra_regions(ctx, &j, counts), "bad area dtype"), "regions: area dtype 8: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.area.band_stride = -1; EXPECT(says(fra_regions(ctx, &j, counts), "bad area layout"), "regions: negative area stride: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.sieved.col_stride = -1; EXPECT(says(fra_regions(ctx, &j, counts), "bad sieved layout"), "regions: negative sieved stride: %s", g_msg.c_str()); }
+    { auto o = rj.opts; o.labels.dst = nullptr; o.labels.dtype = FRA_F32; o.area.dst = nullptr; o.area.dtype = 8; o.sieved.dtype = 99;
+      EXPECT(fra_rg::check_job(FRA_U8, 3, 40, 50, rss, &o) == FRA_OK, "regions: the dtype of an output that is not given was looked at: %s", g_msg.c_str()); }
+    for (int n : {0, -3, 32769}) {
+      { auto j = rj; j.height = n; EXPECT(says(fra_regions(ctx, &j, counts), "1 .. 32768"), "regions: height %d: %s", n, g_msg.c_str()); }
+      { auto j = rj; j.width = n; EXPECT(says(fra_regions(ctx, &j, counts), "1 .. 32768"), "regions: width %d: %s", n, g_msg.c_str()); }
+    }
+    for (int n : {-1, 17}) { auto j = rj; j.opts.nvalues = n; EXPECT(says(fra_regions(ctx, &j, counts), "nvalues"), "regions: %d values: %s", n, g_msg.c_str()); }
+    for (double v : {(double)NAN, (double)INFINITY}) { auto j = rj; j.opts.nvalues = 2; j.opts.values[1] = v; EXPECT(says(fra_regions(ctx, &j, counts), "foreground value 1 is not finite"), "regions: value %g: %s", v, g_msg.c_str()); }
+    for (int n : {0, 6, -4, 16}) { auto j = rj; j.opts.connectivity = n; EXPECT(says(fra_regions(ctx, &j, counts), "connectivity"), "regions: connectivity %d: %s", n, g_msg.c_str()); }
+    for (int n : {0, -7}) { auto j = rj; j.opts.min_size = n; EXPECT(says(fra_regions(ctx, &j, counts), "min_size"), "regions: min_size %d: %s", n, g_msg.c_str()); }
+    { auto j = rj; j.opts.table_cap = -1; EXPECT(says(fra_regions(ctx, &j, counts), "table_cap"), "regions: table_cap -1: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.labels.dst = nullptr; j.opts.area.dst = nullptr; j.opts.sieved.dst = nullptr; j.opts.table = nullptr;
+      EXPECT(says(fra_regions(ctx, &j, counts), "none of labels, area, sieved and table"), "regions: no output: %s", g_msg.c_str()); }
+    { auto o = rj.opts; o.labels.dst = nullptr; o.area.dst = nullptr; o.sieved.dst = nullptr; o.table_cap = 0;
+      EXPECT(fra_rg::check_job(FRA_U8, 3, 40, 50, rss, &o) == FRA_OK, "regions: a table alone refused: %s", g_msg.c_str()); }
+    // the order: an input that breaks two rules gets the message of the first
+    { auto j = rj; j.dtype = 8; j.height = 0; EXPECT(says(fra_regions(ctx, &j, counts), "bad dtype"), "regions: dtype 8 and height 0: %s", g_msg.c_str()); }
+    { auto j = rj; j.channels = 256; j.opts.labels.dtype = FRA_F32; EXPECT(says(fra_regions(ctx, &j, counts), "more than 255"), "regions: 256 bands and float labels: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.labels.dtype = FRA_F64; j.opts.area.dtype = -1; EXPECT(says(fra_regions(ctx, &j, counts), "bad labels dtype"), "regions: labels and area dtypes: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.area.dtype = -1; j.width = 40000; EXPECT(says(fra_regions(ctx, &j, counts), "bad area dtype"), "regions: area dtype and width: %s", g_msg.c_str()); }
+    { auto j = rj; j.height = 0; j.opts.nvalues = 17; EXPECT(says(fra_regions(ctx, &j, counts), "1 .. 32768"), "regions: height 0 and 17 values: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.nvalues = 17; j.opts.connectivity = 5; EXPECT(says(fra_regions(ctx, &j, counts), "nvalues"), "regions: 17 values and connectivity 5: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.connectivity = 5; j.opts.min_size = 0; EXPECT(says(fra_regions(ctx, &j, counts), "connectivity"), "regions: connectivity 5 and min_size 0: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.min_size = 0; j.opts.table_cap = -1; EXPECT(says(fra_regions(ctx, &j, counts), "min_size"), "regions: min_size 0 and table_cap -1: %s", g_msg.c_str()); }
+    { auto j = rj; j.opts.table_cap = -1; j.opts.labels.dst = nullptr; j.opts.area.dst = nullptr; j.opts.sieved.dst = nullptr; j.opts.table = nullptr;
+      EXPECT(says(fra_regions(ctx, &j, counts), "table_cap"), "regions: table_cap -1 and no output: %s", g_msg.c_str()); }
+    bool untouched = true;
+    for (uint64_t v : counts) untouched = untouched && v == 9;
+    EXPECT(untouched, "regions: a refusal wrote the counts");
+    EXPECT(fra_regions_timing(nullptr) == FRA_E_INVALID, "regions timing: null accepted");
+    // the read over a region: what the windowed read refuses is referred to it; the options as above
+    {
+      fra_decode_item di = it;
+      di.window = {0, 0, 4, 8};
+      fra_decode_job dj = job;
+      dj.items = &di;
+      const fra_window r48{0, 0, 4, 8};
+      fra_window r40 = r48;
+      r40.width = 0;
+      auto o = rj.opts;
+      EXPECT(fra_decode_device_regions(ctx, &dj, &r48, nullptr, inf, counts) == FRA_E_INVALID && g_msg == "null argument", "regions read: null options: %s", g_msg.c_str());
+      EXPECT(fra_decode_device_regions(ctx, &dj, nullptr, &o, inf, counts) == FRA_E_INVALID, "regions read: null roi accepted");
+      EXPECT(says(fra_decode_device_regions(ctx, &dj, &r40, &o, inf, counts), "region of interest"), "regions read: zero-width roi: %s", g_msg.c_str());
+      { auto q = o; q.min_size = 0; EXPECT(says(fra_decode_device_regions(ctx, &dj, &r40, &q, inf, counts), "region of interest"), "regions read: zero-width roi and min_size 0: %s", g_msg.c_str()); }
+      { auto q = o; q.min_size = 0; EXPECT(says(fra_decode_device_regions(ctx, &dj, &r48, &q, inf, counts), "min_size"), "regions read: min_size 0: %s", g_msg.c_str()); }
+      { auto q = o; q.labels.dtype = FRA_F32; EXPECT(says(fra_decode_device_regions(ctx, &dj, &r48, &q, inf, counts), "bad labels dtype"), "regions read: float labels: %s", g_msg.c_str()); }
+      { fra_window r = r48; r.height = 5; EXPECT(says(fra_decode_device_regions(ctx, &dj, &r, &o, inf, counts), "do not cover"), "regions read: uncovered row: %s", g_msg.c_str()); }
+    }
+    // the FRA_E_SPACE decisions: N against the labels dtype, then against the table
+    {
+      auto space = [&](int rc, const char* what) { return rc == FRA_E_SPACE && g_msg.find(what) != std::string::npos; };
+      EXPECT(fra_rg::label_max(FRA_U8) == 255 && fra_rg::label_max(FRA_I8) == 127 && fra_rg::label_max(FRA_U16) == 65535 && fra_rg::label_max(FRA_I16) == 32767 &&
+                 fra_rg::label_max(FRA_U32) == 4294967295ll && fra_rg::label_max(FRA_I32) == 2147483647ll, "regions: the greatest label of a dtype");
+      auto o = rj.opts;
+      o.labels.dtype = FRA_U8; o.table_cap = 300;
+      EXPECT(fra_rg::check_space(1, 255, &o) == FRA_OK, "regions: 255 components refused for uint8 labels: %s", g_msg.c_str());
+      EXPECT(space(fra_rg::check_space(1, 256, &o), "band 1 has 256 components, more than the labels dtype holds (255)"), "regions: 256 components in uint8 labels: %s", g_msg.c_str());
+      o.labels.dtype = FRA_I8;
+      EXPECT(fra_rg::check_space(0, 127, &o) == FRA_OK && space(fra_rg::check_space(0, 128, &o), "labels dtype holds (127)"), "regions: int8 labels: %s", g_msg.c_str());
+      o.labels.dtype = FRA_I32;
+      EXPECT(fra_rg::check_space(2, 300, &o) == FRA_OK, "regions: a full table refused: %s", g_msg.c_str());
+      EXPECT(space(fra_rg::check_space(2, 301, &o), "band 2 has 301 components, more than the table holds (300)"), "regions: 301 components in a table of 300: %s", g_msg.c_str());
+      o.labels.dtype = FRA_U8;  // both: the labels dtype is named
+      EXPECT(space(fra_rg::check_space(2, 301, &o), "labels dtype"), "regions: both limits: %s", g_msg.c_str());
+      o.labels.dst = nullptr; o.table = nullptr; o.table_cap = 0;
+      EXPECT(fra_rg::check_space(0, 1 << 30, &o) == FRA_OK, "regions: limits of outputs that are not given: %s", g_msg.c_str());
+      o = rj.opts;  // int32 labels, a table of 10
+      EXPECT(fra_rg::may_lack_space(40, 50, &o), "regions: a table of 10 for 2000 pixels cannot lack space");
+      o.table_cap = 2000;
+      EXPECT(!fra_rg::may_lack_space(40, 50, &o), "regions: a table of a record per pixel can lack space");
+      o.table = nullptr; o.labels.dtype = FRA_U16;
+      EXPECT(!fra_rg::may_lack_space(40, 50, &o) && fra_rg::may_lack_space(256, 257, &o) && !fra_rg::may_lack_space(255, 257, &o), "regions: uint16 labels and the pixel count");
+      o.labels.dtype = FRA_I32;
+      EXPECT(!fra_rg::may_lack_space(32768, 32768, &o), "regions: int32 labels hold 2^30 components");
+    }
+    // the launch plan: tiles of 64, a seam thread per border pixel, scan blocks of 4096
+    {
+      EXPECT(fra_rg::kRun == 16 && fra_rg::kScanBlock == 4096 && (fra_rg::kRootBit & 0x40000000u) == 0 && (int64_t)fra_rg::kMaxSide * fra_rg::kMaxSide <= (int64_t)fra_rg::kRootBit >> 1, "regions: the constants");
+      const struct { int h, w, tx, ty; long long rows, cols; unsigned links, seams, blocks; } cases[] = {
+          {1, 1, 1, 1, 0, 0, 1, 0, 1},       {64, 64, 1, 1, 0, 0, 16, 0, 1},        {65, 65, 2, 2, 65, 65, 17, 1, 2},
+          {130, 191, 3, 3, 382, 260, 97, 3, 7}, {5, 1100, 18, 1, 0, 85, 22, 1, 2}, {520, 520, 9, 9, 4160, 4160, 1057, 33, 67},
+          {3, 32768, 512, 1, 0, 1533, 384, 6, 24}, {32768, 3, 1, 512, 1533, 0, 384, 6, 24}};
+      for (const auto& c : cases) {
+        const fra_rg::Plan p = fra_rg::make_plan(c.h, c.w);
+        EXPECT(p.tiles_x == c.tx && p.tiles_y == c.ty && p.npix == (int64_t)c.h * c.w && p.seam_row_threads == c.rows && p.seam_col_threads == c.cols &&
+                   p.link_wgs == c.links && p.seam_wgs == c.seams && p.pixel_scan_blocks == c.blocks,
+               "regions: the plan of %d x %d: %d x %d tiles, %lld + %lld seam threads, %u / %u / %u workgroups", c.h, c.w, p.tiles_x, p.tiles_y,
+               (long long)p.seam_row_threads, (long long)p.seam_col_threads, p.link_wgs, p.seam_wgs, p.pixel_scan_blocks);
+      }
+      const fra_rg::Plan big = fra_rg::make_plan(32768, 32768);
+      EXPECT(big.npix == (1ll << 30) && big.link_wgs == (1u << 22) && big.pixel_scan_blocks == (1u << 18) && big.seam_row_threads == 511ll * 32768 && big.seam_wgs == 130816u, "regions: the greatest plan");
+      EXPECT(fra_rg::scan_blocks(0) == 0 && fra_rg::scan_blocks(1) == 1 && fra_rg::scan_blocks(4096) == 1 && fra_rg::scan_blocks(4097) == 2, "regions: scan blocks");
     }
   }
   // ... and the order of the refusals of these five units: an input that breaks two rules gets the message of the first
